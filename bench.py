@@ -10,7 +10,10 @@ each step's per-shard match list is gathered to rank 0 by RCCL (frizbee_amd/dist
 buffers, asynchronous and double-buffered, so step i's gather overlaps step i+1's kernels; every gather has completed
 when the closing barrier + synchronize returns).
 
-Prints ONE JSON line on rank 0 (see the driver contract): `value` = haystacks scored per second, whole job.  Beside it:
+Prints ONE JSON line on rank 0 (see the driver contract): `value` = haystacks scored per second, whole job, `ms_per_step`, the workload
+(`config`) and `roofline_step` (arithmetic on ms_per_step: no run of its own).  A plain run does nothing else: set-up, W warm-up steps, the
+K timed steps, the line.  `--dump-outputs DIR` writes the last timed step's records (dump_outputs).  `--full` adds everything below, each
+from runs or checks of its own after the timed steps:
   roofline        the dominant kernel = the streaming filter k1_dfa, HBM-bound: achieved = algorithmic bytes per launch
                   (sum len + 1 decision bit per haystack; the list has uniform length, so no end offsets are read) / its average duration over the profiled steps, measured
                   with HIP events recorded on the launch stream by the library (fzb_last_stage_timings).  `traffic` = HBM bytes per launch from the
@@ -49,11 +52,26 @@ HAY_LEN = 32
 PER_GPU = 10_000_000
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 PUBLISHED_PER_THREAD = 1.15e8  # /root/reference BENCHMARKS.md:123 - match_list, len 32, partial match, one thread of a Ryzen 9950X3D
+DUMP_MAX_RECORDS = 2_000_000  # --dump-outputs: 16 bytes per record once dumped (f64 index + f32 score + f32 exact), at most 32 MB
 
 
 def _median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2]
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the Match records the timed path left in its last step (index order; N > 1: the runs gathered on rank 0, rank order
+    = index order) as one float array per field, so that two builds can be compared output for output on the same seeded list.  A list of
+    more than DUMP_MAX_RECORDS records is cut to a seeded sample of that many positions (the same positions for the same record count)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(records)
+    if n > DUMP_MAX_RECORDS:
+        records = records[np.sort(np.random.default_rng(12345).choice(n, DUMP_MAX_RECORDS, replace=False))]
+    np.save(os.path.join(out_dir, "match_count.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "match_index.npy"), records["index"].astype(np.float64))  # (float32 is exact only below 2^24)
+    np.save(os.path.join(out_dir, "match_score.npy"), records["score"].astype(np.float32))
+    np.save(os.path.join(out_dir, "match_exact.npy"), records["exact"].astype(np.float32))
 
 
 def cpu_baseline(rows_dev, n_sample, max_typos):
@@ -547,13 +565,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--per-gpu", type=int, default=PER_GPU)
     ap.add_argument("--max-typos", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the records of the last timed step to DIR/*.npy (float64 / float32, at most 32 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: stage timings and roofline, e2e, other configs, oracle check, CPU baseline, "
+                         "live counters, N > 1 exchange attribution / ordered mode / configs[3]; the --no-* options below select within it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the C3 / C4-shard / C5 block")
     ap.add_argument("--no-sharded", action="store_true", help="skip the sharded-on-one-device block (fzb_match_list_parallel_sharded vs fzb_match_list)")
     ap.add_argument("--no-check", action="store_true", help="skip the 1M-item oracle comparison")
     ap.add_argument("--no-two-in-flight", action="store_true", help="skip the two-streams throughput figure")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not spawn the two rocprofv3 --pmc child runs; report the stored traffic figure")
-    ap.add_argument("--fast", action="store_true", help="= --no-cpu-baseline --no-configs --no-check --no-two-in-flight (profiling runs)")
+    ap.add_argument("--fast", action="store_true", help="= --full --no-cpu-baseline --no-configs --no-check --no-two-in-flight --no-live-traffic --no-sharded (profiling runs)")
     ap.add_argument("--mix", choices=("partial", "all", "none"), default="partial",
                     help="haystack classes of the list (benches/lib.rs:60-64): partial = 5%% full / 20%% partial / 75%% none (the headline), all = All Match, none = No Match (profiling child runs)")
     ap.add_argument("--c4-total", type=int, default=-1,
@@ -564,17 +586,21 @@ def main():
     backend = os.environ.get("FZB_BENCH_BACKEND", "nccl")
     rehearsal = backend != "nccl"
     if args.fast:
+        args.full = True
         args.no_cpu_baseline = args.no_configs = args.no_check = args.no_two_in_flight = args.no_live_traffic = args.no_sharded = True
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback exists for the product path)")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if torch.cuda.device_count() < args.gpus and not rehearsal:
         raise SystemExit(f"bench.py --gpus {args.gpus}: only {torch.cuda.device_count()} GPU(s) visible on this node - refusing to run fewer ranks than asked for")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # invoked as plain `python bench.py --gpus N`: start the N ranks ourselves, exactly the way the driver would
-        # (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1), and hand over to them
+        # (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1), and wait for them.  A child process, not an exec:
+        # this process has initialised the HIP runtime above, and replacing the program of such a process is not safe
         import socket
 
         s_ = socket.socket()
@@ -583,8 +609,11 @@ def main():
         s_.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.abspath(__file__), *sys.argv[1:]]
+        import subprocess
+
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execvpe(cmd[0], cmd, os.environ)
+        rc = subprocess.run(cmd, env=os.environ).returncode
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner through C stdio on fd 1 (seen after the JSON line when stdout is a
     # file: it is flushed at exit), so the line gets its own duplicate of the original stdout and fd 1 itself is pointed at stderr.
     json_out = os.fdopen(os.dup(1), "w")
@@ -682,21 +711,36 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    # Kernel-level timing: the SAME K steps again, immediately after, with HIP events recorded by the library around the
-    # stages on the launch stream (kept out of the timed region above so the events cost nothing there;
-    # rocprofv3 --kernel-trace of this command covers both passes).
-    m.set_profiling(True)
-    for _ in range(args.steps):
-        step()
-    fence()
-    st = m.last_stage_timings_ms()
-    m.set_profiling(False)
-    counters = m.last_counters()  # (of a full step: the untimed checks further down query sub-ranges)
-    attribution = None
-    if use_dist:
+    # what the timed path left in its last step: this rank's records (N = 1), or every shard's run gathered on rank 0 (N > 1)
+    runs = None
+    if ex is None:
+        n_matches = int(cnt[0].item())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out[: n_matches * 8].cpu().numpy().view(F.MATCH_DTYPE))
+    else:
+        last = (step_no[0] - 1) & 1
+        runs = ex.collect(last)       # root: the per-shard runs of the last step; everyone: drains the exchange
+        ex.collect(last ^ 1)
+        n_matches = int(ex.send[last][:4].cpu().numpy().view(np.uint32)[0])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, np.concatenate(runs))
         t = torch.tensor([elapsed], dtype=torch.float64, device=ctl_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    counters = m.last_counters()  # (of a full step: the untimed checks further down query sub-ranges)
+    st = None
+    attribution = None
+    if args.full:
+        # Kernel-level timing: the SAME K steps again, immediately after, with HIP events recorded by the library around the
+        # stages on the launch stream (kept out of the timed region above so the events cost nothing there;
+        # rocprofv3 --kernel-trace of this command covers both passes).
+        m.set_profiling(True)
+        for _ in range(args.steps):
+            step()
+        fence()
+        st = m.last_stage_timings_ms()
+        m.set_profiling(False)
+    if use_dist and args.full:
         # ---- what the exchange costs, so that a scaling loss at N > 1 is attributable (untimed here; same K steps, same fences) -------------
         # (1) the loop WITHOUT the exchange: the pipeline still writes into the exchange buffers, nothing is posted
         ex.wait(0)
@@ -728,17 +772,14 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     gathered = None
     e2e_multi = None
-    if ex is None:
-        n_matches = int(cnt[0].item())
-    else:
-        last = (step_no[0] - 1) & 1
-        runs = ex.collect(last)       # root: the per-shard runs of the last step; everyone: drains the exchange
-        ex.collect(last ^ 1)
-        n_matches = int(ex.send[last][:4].cpu().numpy().view(np.uint32)[0])
+    c4_row = None
+    if ex is not None and rank == 0:
+        gathered = {"matches_all_shards": int(sum(len(r) for r in runs)), "exchange_capacity_records": ex.cap,
+                    "capacity_over_records": ex.cap / max(1, max(len(r) for r in runs))}
+    if ex is not None and args.full:
         if rank == 0:
             merged = merge_shard_runs(runs, F.SortStrategy.ScoreThenIndexAsc)  # host form of the combine (the device form is timed below)
-            gathered = {"matches_all_shards": int(sum(len(r) for r in runs)), "merged_len": int(len(merged)), "exchange_capacity_records": ex.cap,
-                        "capacity_over_records": ex.cap / max(1, max(len(r) for r in runs)), **(attribution or {})}
+            gathered.update({"merged_len": int(len(merged)), **(attribution or {})})
         # ---- the end-to-end mode (reported beside `value`, never instead of it): every step ends with the ORDERED list on rank 0's
         # host - what match_list_parallel returns (parallel.rs:66-87).  Each rank runs the pipeline unsorted with global indices, a
         # synchronous gather puts the runs into the root's HBM, and the root orders the whole list ONCE on the device (rank order is
@@ -793,20 +834,6 @@ def main():
         c4_row = c4_sharded_block(F, synth, dist, dev, rank, world, c4_total, max(3, min(10, args.steps)), stream) if c4_total else None
     if rank == 0:
         total = n * world
-        # algorithmic bytes of one filter launch (this rank's shard): payload once + 1 decision bit per haystack (no end offsets: uniform length)
-        filt_bytes = n * HAY_LEN + n / 8
-        achieved = filt_bytes / (st["filter"] * 1e-3) / 1e9
-        tr = stored_json("latest_traffic.json") or {}
-        sq = stored_json("latest_sq.json") or {}
-        scorer = {"kernel": sq.get("scorer_kernel"), "bound": "valu-issue", "avg_ms": st["scorers"]}
-        if sq.get("scorer_valu_wave_instructions_per_launch"):
-            clk = sq.get("shader_clock_GHz", 2.25)
-            simds = 4 * 256
-            scorer.update({"valu_wave_instructions_per_launch": sq["scorer_valu_wave_instructions_per_launch"],
-                           "all_wave_instructions_per_launch": sq.get("scorer_all_wave_instructions_per_launch"),
-                           "issue_frac": sq["scorer_valu_wave_instructions_per_launch"] * 4 / (simds * st["scorers"] * 1e-3 * clk * 1e9),
-                           "assumes": f"4 cycles per wave64 VALU instruction, {simds} SIMDs, {clk} GHz (in-kernel s_memtime / s_memrealtime, tools/exp_dp_timing.py)",
-                           "counters_source": sq.get("source")})
         res = {
             "metric": "haystacks scored/sec (whole node) + achieved HBM GB/s, 6-char needle vs 10M len-32 haystacks",
             "value": total / (elapsed / args.steps),
@@ -829,15 +856,30 @@ def main():
                        "backend": ((f"{backend} - REHEARSAL of the N > 1 path: {world} rank(s) share {torch.cuda.device_count()} GPU(s), the exchange moves CPU tensors; not a scaling measurement"
                                     if rehearsal else "nccl (RCCL)") if use_dist else "none (single process)"),
                        "matches_per_shard": n_matches, "filter_survivors": counters["filter_survivors"], "exchange": gathered},
-            "roofline": {"bound": "hbm", "kernel": "k1_dfa", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": tr.get("k1_filter_hbm_bytes_per_launch"),
-                         "traffic_source": "STORED, not measured in this run: profiles/latest_traffic.json (" + str(tr.get("source")) + ")",
-                         "traffic_stored": tr.get("k1_filter_hbm_bytes_per_launch"),
-                         "bytes_per_launch": filt_bytes, "avg_kernel_ms": st["filter"], "launches_averaged": st["calls"]},
             "roofline_step": step_roofline(n * HAY_LEN, n, n_matches, ms_per_step, ends_read=False),
-            "stages": {"filter_ms": st["filter"], "compaction_ms": st["compaction_and_window"], "scorer_ms": st["scorers"], "device_pipeline_ms": st["total"], "scorer": scorer,
-                       "what": "HIP events on the launch stream around each stage, averaged over the profiled steps (the K steps after the timed K)"},
         }
+    if rank == 0 and args.full:
+        # algorithmic bytes of one filter launch (this rank's shard): payload once + 1 decision bit per haystack (no end offsets: uniform length)
+        filt_bytes = n * HAY_LEN + n / 8
+        achieved = filt_bytes / (st["filter"] * 1e-3) / 1e9
+        tr = stored_json("latest_traffic.json") or {}
+        sq = stored_json("latest_sq.json") or {}
+        scorer = {"kernel": sq.get("scorer_kernel"), "bound": "valu-issue", "avg_ms": st["scorers"]}
+        if sq.get("scorer_valu_wave_instructions_per_launch"):
+            clk = sq.get("shader_clock_GHz", 2.25)
+            simds = 4 * 256
+            scorer.update({"valu_wave_instructions_per_launch": sq["scorer_valu_wave_instructions_per_launch"],
+                           "all_wave_instructions_per_launch": sq.get("scorer_all_wave_instructions_per_launch"),
+                           "issue_frac": sq["scorer_valu_wave_instructions_per_launch"] * 4 / (simds * st["scorers"] * 1e-3 * clk * 1e9),
+                           "assumes": f"4 cycles per wave64 VALU instruction, {simds} SIMDs, {clk} GHz (in-kernel s_memtime / s_memrealtime, tools/exp_dp_timing.py)",
+                           "counters_source": sq.get("source")})
+        res["roofline"] = {"bound": "hbm", "kernel": "k1_dfa", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": tr.get("k1_filter_hbm_bytes_per_launch"),
+                           "traffic_source": "STORED, not measured in this run: profiles/latest_traffic.json (" + str(tr.get("source")) + ")",
+                           "traffic_stored": tr.get("k1_filter_hbm_bytes_per_launch"),
+                           "bytes_per_launch": filt_bytes, "avg_kernel_ms": st["filter"], "launches_averaged": st["calls"]}
+        res["stages"] = {"filter_ms": st["filter"], "compaction_ms": st["compaction_and_window"], "scorer_ms": st["scorers"], "device_pipeline_ms": st["total"], "scorer": scorer,
+                         "what": "HIP events on the launch stream around each stage, averaged over the profiled steps (the K steps after the timed K)"}
         if e2e_multi:
             res["e2e_sorted_merge"] = e2e_multi
             if c4_row is not None:
@@ -945,7 +987,7 @@ def main():
                 bound = max(res["cpu_baseline"]["value"], res["cpu_baseline"]["linear_bound"]["haystacks_per_s"], res["cpu_baseline"]["published_bound"]["haystacks_per_s"])
                 res["gpu_over_cpu_bound"] = {"ratio": res["value"] / bound,
                                              "against": "the largest of: measured port, single-thread x physical cores, published per-thread x physical cores"}
-    if use_dist and not rehearsal and os.environ.get("FZB_BENCH_CABI_RCCL", "1") != "0":
+    if args.full and use_dist and not rehearsal and os.environ.get("FZB_BENCH_CABI_RCCL", "1") != "0":
         # ---- the ordered query through the C ABI ALONE (fzb_match_list_parallel_rccl, csrc/host_rccl.hip: RCCL opened by the library itself, what a
         # Rust host with one process per GPU binds) - untimed for `value`, reported beside e2e_sorted_merge.  It has never run on more than one GPU, so it
         # runs LAST, after everything else of the line exists, under a watchdog: if it has not come back in time every rank leaves and rank 0 prints the

@@ -192,7 +192,7 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 
 def test_two_rank_rehearsal_of_the_bench_on_one_gpu():
-    """`FZB_BENCH_BACKEND=gloo python bench.py --gpus 2`: the N > 1 path of the driver's bench with TWO real ranks on a box with one GPU -
+    """`FZB_BENCH_BACKEND=gloo python bench.py --gpus 2 --full`: the N > 1 path of the driver's bench with TWO real ranks on a box with one GPU -
     bench.py starts the ranks under torch.distributed.run itself, both score their shard on the visible GPU with a global index offset,
     the exchange moves CPU tensors (gloo), rank 0 combines.  Everything an RCCL run executes except the transport: the rank bookkeeping,
     the double-buffered exchange, ordered_query's grow-and-retry, the per-shard oracle check, and BASELINE configs[3] cut into
@@ -200,7 +200,7 @@ def test_two_rank_rehearsal_of_the_bench_on_one_gpu():
     import json
     env = dict(os.environ, FZB_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--per-gpu", "1000000", "--steps", "5", "--warmup", "2", "--c4-total", "2000000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--per-gpu", "1000000", "--steps", "5", "--warmup", "2", "--c4-total", "2000000", "--full"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

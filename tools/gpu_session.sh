@@ -13,7 +13,7 @@ for s in $STEPS; do
   case $s in
     test) timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/summary.txt; tail -5 $OUT/pytest.log;;
     testfull) timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/summary.txt; tail -15 $OUT/pytest.log;;
-    bench) timeout 600 python bench.py --steps 50 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench.json;;
+    bench) timeout 600 python bench.py --steps 50 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench.json;;
     benchfast) timeout 600 python bench.py --steps 50 --warmup 5 --fast > $OUT/bench_fast.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench_fast.json;;
     prof) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o p -- python $OLDPWD/bench.py --steps 20 --warmup 3 --fast > $OUT/prof.log 2>&1); f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); if [ -n "$f" ]; then python tools/prof_summary.py $f $OUT/kernel_stats.csv; cp $f $OUT/kernel_stats_raw.csv; else tail -20 $OUT/prof.log; fi; rm -rf $OUT/prof;;
     profcfg) (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profcfg -o p -- python $OLDPWD/tools/bench_configs.py C3 C4 C5 > $OUT/profcfg.log 2>&1); f=$(find $OUT/profcfg -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && python tools/prof_summary.py $f $OUT/cfg_kernel_stats.csv; rm -rf $OUT/profcfg;;
