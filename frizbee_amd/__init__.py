@@ -118,6 +118,8 @@ SYMBOLS = [
     "fzb_merge_shard_runs", "fzb_corpus_build_view", "fzb_debug_reload_knobs", "fzb_matcher_shard_report",
     "fzb_rccl_unique_id", "fzb_shard_comm_create", "fzb_shard_comm_free", "fzb_shard_comm_rank", "fzb_shard_comm_world", "fzb_match_list_parallel_rccl",
     "fzb_shard_comm_last_exchange",
+    "fzb_multi_matcher_set_patterns", "fzb_multi_matcher_set_config", "fzb_multi_matcher_reserve", "fzb_multi_matcher_clone", "fzb_multi_match_list_parallel",
+    "fzb_multi_match_list_parallel_sharded", "fzb_multi_match_list_parallel_rccl", "fzb_multi_matcher_shard_report", "fzb_debug_device_allocs",
 ]
 
 
@@ -193,6 +195,16 @@ def lib():
         l.fzb_shard_comm_last_exchange.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_debug_lcs_dfa_accepts.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
         l.fzb_debug_cdfa_state.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+        l.fzb_multi_matcher_set_patterns.argtypes = [C.c_void_p, C.POINTER(_CPattern), C.c_size_t]
+        l.fzb_multi_matcher_set_config.argtypes = [C.c_void_p, C.POINTER(_CConfig)]
+        l.fzb_multi_matcher_reserve.argtypes = [C.c_void_p, C.c_void_p]
+        l.fzb_multi_matcher_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        l.fzb_multi_match_list_parallel.argtypes = l.fzb_match_list_parallel.argtypes
+        l.fzb_multi_match_list_parallel_sharded.argtypes = l.fzb_match_list_parallel_sharded.argtypes
+        l.fzb_multi_match_list_parallel_rccl.argtypes = l.fzb_match_list_parallel_rccl.argtypes
+        l.fzb_multi_matcher_shard_report.argtypes = [C.c_void_p]
+        l.fzb_multi_matcher_shard_report.restype = C.c_char_p
+        l.fzb_debug_device_allocs.argtypes = [C.POINTER(C.c_uint64)]
         _lib = l
     return _lib
 
@@ -349,6 +361,31 @@ class Pattern:
     matching: "Matching | None" = None
 
 
+def device_allocs():
+    """fzb_debug_device_allocs: device allocations the library has made in this process so far (test hook)"""
+    n = C.c_uint64()
+    _check(lib().fzb_debug_device_allocs(C.byref(n)))
+    return n.value
+
+
+def _c_patterns(pats):
+    """list[Pattern] -> (the C array, the needle bytes it points into - keep them alive for the call)"""
+    arr = (_CPattern * max(len(pats), 1))()
+    keep = []
+    for i, p in enumerate(pats):
+        n = _b(p.needle)
+        keep.append(n)
+        arr[i].needle_utf8, arr[i].needle_len, arr[i].negated = C.cast(C.c_char_p(n), C.c_void_p), len(n), int(p.negated)
+        arr[i].has_max_typos, arr[i].max_typos = int(p.max_typos is not None), int(p.max_typos or 0)
+        arr[i].casing = -1 if p.casing is None else int(p.casing)
+        arr[i].unicode = -1 if p.unicode is None else int(p.unicode)
+        arr[i].has_scoring = int(p.scoring is not None)
+        arr[i].matching = -1 if p.matching is None else int(p.matching)
+        for name, v in zip([f[0] for f in _CScoring._fields_], (p.scoring or Scoring()).as_list()):
+            setattr(arr[i].scoring, name, v)
+    return arr, keep
+
+
 def parse_query(query):
     """`Pattern::parse_query` (src/pattern.rs:186-222) -> list[Pattern]"""
     q = _b(query)
@@ -399,25 +436,62 @@ class MultiMatcher(_IterApi):
     def __init__(self, patterns, config=None):
         self.config = config or Config()
         pats = [p if isinstance(p, Pattern) else Pattern(p) for p in patterns]
-        arr = (_CPattern * max(len(pats), 1))()
-        self._keep = []
-        for i, p in enumerate(pats):
-            n = _b(p.needle)
-            self._keep.append(n)
-            arr[i].needle_utf8, arr[i].needle_len, arr[i].negated = C.cast(C.c_char_p(n), C.c_void_p), len(n), int(p.negated)
-            arr[i].has_max_typos, arr[i].max_typos = int(p.max_typos is not None), int(p.max_typos or 0)
-            arr[i].casing = -1 if p.casing is None else int(p.casing)
-            arr[i].unicode = -1 if p.unicode is None else int(p.unicode)
-            arr[i].has_scoring = int(p.scoring is not None)
-            arr[i].matching = -1 if p.matching is None else int(p.matching)
-            for name, v in zip([f[0] for f in _CScoring._fields_], (p.scoring or Scoring()).as_list()):
-                setattr(arr[i].scoring, name, v)
+        arr, self._keep = _c_patterns(pats)
         c = _c_config(self.config)
         self.h = C.c_void_p()
         _check(lib().fzb_multi_matcher_create(C.byref(c), arr, len(pats), C.byref(self.h)))
+        self.patterns = pats  # `Matcher::patterns` / `Matcher::config` (src/matcher/mod.rs:144-150) are these two attributes
 
     def __len__(self):
         return lib().fzb_multi_matcher_len(self.h)
+
+    def set_patterns(self, patterns):
+        """`Matcher::set_patterns` (src/matcher/mod.rs:170-176): skipped when the patterns are the same; otherwise the sub-matchers are
+        rebuilt in place and their device buffers kept (a re-query per keystroke allocates nothing once `reserve` sized them).  `patterns`:
+        a list of `Pattern` / needles, or a query string, which is parsed with `parse_query` (`Matcher::from_query`'s syntax)."""
+        if isinstance(patterns, (str, bytes)):
+            patterns = parse_query(patterns)
+        pats = [p if isinstance(p, Pattern) else Pattern(p) for p in patterns]
+        arr, keep = _c_patterns(pats)
+        _check(lib().fzb_multi_matcher_set_patterns(self.h, arr, len(pats)))
+        self.patterns, self._keep = pats, keep
+
+    def set_config(self, config):
+        """`Matcher::set_config` (src/matcher/mod.rs:154-162); a change of `sort` alone rebuilds no sub-matcher"""
+        c = _c_config(config)
+        _check(lib().fzb_multi_matcher_set_config(self.h, C.byref(c)))
+        self.config = config
+
+    def reserve(self, corpus):
+        """Allocate every device buffer queries over `corpus` can need now: the composition, ordering and staging, and every sub-matcher
+        slot for any needle of up to 64 bytes in any matching form (later keystrokes that do not add a pattern allocate nothing)."""
+        _check(lib().fzb_multi_matcher_reserve(self.h, corpus.h))
+
+    def clone(self):
+        """`impl Clone for Matcher` (src/matcher/parallel.rs:46): an independent matcher with its own device buffers"""
+        out = MultiMatcher.__new__(MultiMatcher)
+        out.h = C.c_void_p()
+        _check(lib().fzb_multi_matcher_clone(self.h, C.byref(out.h)))
+        out.config, out.patterns, out._keep = self.config, list(self.patterns), list(self._keep)
+        return out
+
+    def match_list_parallel(self, haystacks, threads):
+        """`Matcher::match_list_parallel` (src/matcher/parallel.rs:18-89); identical result for every thread count."""
+        cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().fzb_multi_match_list_parallel(self.h, cp.h, threads, C.byref(out), C.byref(n)))
+        return _take(out, n)
+
+    def match_list_parallel_sharded(self, sharded, copy=True):
+        """`match_list_parallel` with one DEVICE per worker: the whole composition per shard on its device, the runs gathered and ordered
+        once on the root.  Equals `match_list` on the unsharded list."""
+        out, n = C.c_void_p(), C.c_size_t()
+        _check(lib().fzb_multi_match_list_parallel_sharded(self.h, sharded.h, C.byref(out), C.byref(n)))
+        return _take(out, n, copy)
+
+    def shard_report(self):
+        """How the runs of the last `match_list_parallel_sharded` reached the root (see `Matcher.shard_report`)."""
+        return lib().fzb_multi_matcher_shard_report(self.h).decode()
 
     def match_list(self, haystacks, copy=True):
         cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)

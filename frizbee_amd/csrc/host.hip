@@ -151,6 +151,8 @@ hipError_t dev_alloc(void** p, size_t bytes) { return fzb_dev_alloc(p, bytes); }
 
 }  // namespace
 
+std::atomic<uint64_t> g_fzb_dev_allocs{0};
+
 int fzb_fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
@@ -820,18 +822,22 @@ int fzb_matcher_set_pattern(fzb_matcher* m, const uint8_t* needle_utf8, size_t n
     return rebuild_matcher(m, &cfg, needle_utf8, needle_len);
 }
 
+}  // extern "C"
+// field by field: fzb_config / fzb_scoring have padding bytes a C caller need not have cleared
+static bool same_scoring(const fzb_scoring& a, const fzb_scoring& b) {
+    return a.match_score == b.match_score && a.mismatch_penalty == b.mismatch_penalty && a.gap_open_penalty == b.gap_open_penalty && a.gap_extend_penalty == b.gap_extend_penalty &&
+           a.prefix_bonus == b.prefix_bonus && a.capitalization_bonus == b.capitalization_bonus && a.matching_case_bonus == b.matching_case_bonus &&
+           a.exact_match_bonus == b.exact_match_bonus && a.delimiter_bonus == b.delimiter_bonus;
+}
+static bool same_config(const fzb_config& a, const fzb_config& b) {
+    return a.max_typos == b.max_typos && a.casing == b.casing && a.unicode == b.unicode && a.sort == b.sort && a.pf_lanes == b.pf_lanes && a.sw_lanes == b.sw_lanes &&
+           a.matching == b.matching && same_scoring(a.scoring, b.scoring);
+}
+extern "C" {
+
 int fzb_matcher_set_config(fzb_matcher* m, const fzb_config* config) {
     if (!m || !config) return fail(FZB_ERR_INVALID, "null argument");
-    {  // field by field: fzb_config has padding bytes a C caller need not have cleared
-        const fzb_config &a = m->config, &b = *config;
-        const bool same = a.max_typos == b.max_typos && a.casing == b.casing && a.unicode == b.unicode && a.sort == b.sort && a.pf_lanes == b.pf_lanes && a.sw_lanes == b.sw_lanes &&
-                          a.matching == b.matching && a.scoring.match_score == b.scoring.match_score && a.scoring.mismatch_penalty == b.scoring.mismatch_penalty &&
-                          a.scoring.gap_open_penalty == b.scoring.gap_open_penalty && a.scoring.gap_extend_penalty == b.scoring.gap_extend_penalty &&
-                          a.scoring.prefix_bonus == b.scoring.prefix_bonus && a.scoring.capitalization_bonus == b.scoring.capitalization_bonus &&
-                          a.scoring.matching_case_bonus == b.scoring.matching_case_bonus && a.scoring.exact_match_bonus == b.scoring.exact_match_bonus &&
-                          a.scoring.delimiter_bonus == b.scoring.delimiter_bonus;
-        if (same) return FZB_OK;
-    }
+    if (same_config(m->config, *config)) return FZB_OK;
     const std::string needle = m->needle;
     return rebuild_matcher(m, config, (const uint8_t*)needle.data(), needle.size());
 }
@@ -929,7 +935,7 @@ static int verify_promise(const fzb_corpus* c, u32 uniform_len, u32 max_len, con
     } guard{prev_dev, own_dev};
     if (own_dev != prev_dev) HIPCHK(hipSetDevice(own_dev));
     HIPCHK(hipDeviceSynchronize());  // the caller may have filled the buffers on any stream of that device
-    HIPCHK(hipMalloc((void**)&d, 16));
+    HIPCHK(dev_alloc((void**)&d, 16));
     const unsigned long long init[2] = {0ull, ~0ull};
     hipError_t e = hipMemcpy(d, init, 16, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -1042,11 +1048,12 @@ static bool typo_fast_path_configured(const fzb_matcher* m) {
     return !m->literal_mode && !m->empty && m->lc.filter_mode == 2 && !m->nd.unicode && m->lc.cf_ok && (m->lc.sw_lanes == 64 || m->lc.sw_lanes == 32);
 }
 
-static int ensure_workspace(fzb_matcher* m, size_t count, hipStream_t st = nullptr, bool have_stream = false) {
+// every_form: the buffers of every filter / scorer form, whatever this needle needs (a multi-pattern slot changes form between keystrokes)
+static int ensure_workspace(fzb_matcher* m, size_t count, hipStream_t st = nullptr, bool have_stream = false, bool every_form = false) {
     Workspace& w = m->ws;
-    const bool need_l2 = !m->lc.filter_exact;
-    const bool need_marg = typo_fast_path_configured(m);
-    const bool need_cls = !m->literal_mode && !m->empty && !m->nd.unicode && m->lc.cf_ok;  // classified scoring (fzb_launch_dp_classes)
+    const bool need_l2 = every_form || !m->lc.filter_exact;
+    const bool need_marg = every_form || typo_fast_path_configured(m);
+    const bool need_cls = every_form || (!m->literal_mode && !m->empty && !m->nd.unicode && m->lc.cf_ok);  // classified scoring (fzb_launch_dp_classes)
     // (cap_items >= count + FZB_UNICODE_FWD_CAP: run_pipeline anchors the queue's back at count + FZB_UNICODE_FWD_CAP entries - a workspace
     // allocated for a smaller range holds count0 + count0/8 + 4096 entries and must not be reused for a range within 4096 of that)
     if (w.cap_items >= count + FZB_UNICODE_FWD_CAP && (!need_l2 || w.cap_level2 >= count) && (!need_marg || w.cap_marg >= count) && (!need_cls || w.cap_cls >= count) && w.counters) {
@@ -1121,9 +1128,9 @@ static int ensure_aux_stream(fzb_matcher* m) {
     m->ev_join = ej;
     return FZB_OK;
 }
-static int ensure_dp_scratch(fzb_matcher* m, int mgrid) {  // parked rows of the multi-chunk scorer
+static size_t dp_scratch_words(int rows, int sw_lanes, int mgrid) { return (size_t)(rows + 1) * (size_t)(sw_lanes / 2) * (size_t)mgrid * 128; }
+static int ensure_dp_scratch_words(fzb_matcher* m, size_t words) {
     Workspace& w = m->ws;
-    const size_t words = (size_t)(m->nd.rows + 1) * (size_t)(m->lc.sw_lanes / 2) * (size_t)mgrid * 128;
     if (w.dp_scratch_words >= words) return FZB_OK;
     if (w.dp_scratch) HIPCHK(hipFree(w.dp_scratch));
     w.dp_scratch = nullptr;
@@ -1131,6 +1138,9 @@ static int ensure_dp_scratch(fzb_matcher* m, int mgrid) {  // parked rows of the
     HIPCHK(dev_alloc((void**)&w.dp_scratch, words * 4));
     w.dp_scratch_words = words;
     return FZB_OK;
+}
+static int ensure_dp_scratch(fzb_matcher* m, int mgrid) {  // parked rows of the multi-chunk scorer
+    return ensure_dp_scratch_words(m, dp_scratch_words(m->nd.rows, m->lc.sw_lanes, mgrid));
 }
 static int ensure_sort_buffers(fzb_matcher* m, size_t cap) {  // ping-pong buffer + tile histograms of the device radix sort
     Workspace& w = m->ws;
@@ -1752,6 +1762,31 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     return FZB_OK;
 }
 
+}  // extern "C"
+// fzb_matcher_reserve for a sub-matcher slot of a multi-pattern matcher, whose needle and matching form change with the keystrokes: the
+// workspace of EVERY form (level-2 windows, margin pass, classified scorer, whatever the current needle needs), and the parked rows of the
+// multi-chunk scorers for the largest short needle (1 .. FZB_MAX_ROWS rows, each at the lane width its score class gets under the slot's
+// scoring and lanes; ASCII grid, the unicode scorer's is half of it).  Only a long needle (beyond 64 bytes / 63 rows) or another scoring /
+// lane pair can make the slot grow later.  A slot never runs the synchronous entry points: no staging or sort buffers.
+static int reserve_slot_any_needle(fzb_matcher* m, const fzb_corpus* c) {
+    if (m->empty || c->dev.n == 0) return FZB_OK;
+    int rc = fzb_bind_device(m);
+    if (rc) return rc;
+    if ((rc = ensure_workspace(m, c->dev.n, nullptr, false, true))) return rc;
+    size_t words = 0;
+    for (int r = 1; r <= FZB_MAX_ROWS; r++) {
+        const bool u8 = fits_in_u8((size_t)r, m->config.scoring);  // (a unicode needle of r scalars has >= r bytes: never a wider class)
+        int pf = m->config.pf_lanes, sw = m->config.sw_lanes;
+        if (pf == 0 && sw == 0) detect_host_lanes(u8, pf, sw);
+        else if (sw == 0) sw = u8 ? pf : pf / 2;
+        const bool no_wide = c->dev.max_len != 0 && c->dev.max_len <= (u32)sw;  // (no window beyond one chunk: the scratch is never used)
+        if (!no_wide) words = std::max(words, dp_scratch_words(r, sw, m->lc.num_cus * 4));
+    }
+    if (words && (rc = ensure_dp_scratch_words(m, words))) return rc;
+    return ensure_aux_stream(m);
+}
+extern "C" {
+
 int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                           uint32_t* dev_count, void* stream) {
     return run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
@@ -1791,7 +1826,7 @@ int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPla
     p->reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;          // src/matcher/mod.rs:215-217
     p->by_score = sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;  // :218-220
     // one radix pass is enough when no score can reach 256 (Scoring::guard's bound on the matrix + the exact-match bonus added after it)
-    p->one_pass = !m->literal_mode && max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus < 256;
+    p->one_pass = !m->sum_scores && !m->literal_mode && max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus < 256;
     p->via_tmp = p->by_score && p->one_pass && cap != 0;
     p->in = dev_out;
     if (p->by_score) {
@@ -2206,29 +2241,8 @@ void fzb_patterns_free(fzb_pattern* patterns, size_t n) {
 }
 
 // ---- multi-pattern composition (src/matcher/multi.rs) ---------------------------------------------------
-struct fzb_multi_matcher {
-    fzb_config config{};
-    struct Compiled { bool negated; fzb_matcher* m; };
-    std::vector<Compiled> patterns;  // empty needles dropped (src/matcher/mod.rs:193-195)
-    int num_cus = 0;
-    // device buffers, grown on demand: two candidate lists (ping-pong), their lengths, the item list handed to the next pattern,
-    // and the bitmap / per-tile counts of the negation's compaction
-    size_t cap = 0;
-    fzb_match_rec* cand[2] = {nullptr, nullptr};
-    u32* counts = nullptr;  // [0],[4] = lengths of cand[0], cand[1]; [8] = hits of a negated pattern (each slot: count, untruncated total)
-    u32* items = nullptr;
-    u64* bitmap = nullptr;
-    u32* tile_counts = nullptr;
-    // ordering + staging for the synchronous API
-    fzb_match_rec* out_dev = nullptr;
-    size_t out_cap = 0;
-    u32* count_dev = nullptr;
-    fzb_match_rec* sort_tmp = nullptr;
-    u32* sort_hist = nullptr;
-    size_t sort_cap = 0;
-    FetchHint fetch;
-};
-
+// (struct fzb_multi_matcher: host_internal.h - the multi-device forms in host_shard.hip / host_rccl.hip use it too)
+}  // extern "C"
 static void multi_free_buffers(fzb_multi_matcher* mm) {
     void* ptrs[] = {mm->cand[0], mm->cand[1], mm->counts, mm->items, mm->bitmap, mm->tile_counts};
     for (void* p : ptrs)
@@ -2240,33 +2254,273 @@ static void multi_free_buffers(fzb_multi_matcher* mm) {
     mm->cap = 0;
 }
 
+// the composition's buffers for ranges of up to `count` haystacks
+static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
+    if (mm->cap >= count) return FZB_OK;
+    multi_free_buffers(mm);
+    const size_t cap = count + count / 8 + 4096;
+    HIPCHK(dev_alloc((void**)&mm->cand[0], (cap + 16) * sizeof(fzb_match_rec)));
+    HIPCHK(dev_alloc((void**)&mm->cand[1], (cap + 16) * sizeof(fzb_match_rec)));
+    HIPCHK(dev_alloc((void**)&mm->counts, 64));
+    HIPCHK(dev_alloc((void**)&mm->items, cap * 4));
+    HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
+    HIPCHK(dev_alloc((void**)&mm->tile_counts, ((cap + FZB_TILE - 1) / FZB_TILE + 2) * 4));
+    mm->cap = cap;
+    return FZB_OK;
+}
+
+// the device-side result of the synchronous entry points
+static int multi_ensure_out(fzb_multi_matcher* mm, size_t count) {
+    if (mm->out_cap >= count && mm->count_dev && mm->out_dev) return FZB_OK;
+    if (mm->out_dev) (void)hipFree(mm->out_dev);
+    mm->out_dev = nullptr;
+    mm->out_cap = 0;
+    HIPCHK(dev_alloc((void**)&mm->out_dev, (count + 16) * sizeof(fzb_match_rec)));
+    mm->out_cap = count;
+    if (!mm->count_dev) HIPCHK(dev_alloc((void**)&mm->count_dev, 64));
+    return FZB_OK;
+}
+
+// ping-pong buffer + tile histograms of the device radix sort (match_list's Score* strategies)
+static int multi_ensure_sort(fzb_multi_matcher* mm, size_t count) {
+    if (mm->sort_cap >= count && mm->sort_tmp) return FZB_OK;
+    if (mm->sort_tmp) (void)hipFree(mm->sort_tmp);
+    if (mm->sort_hist) (void)hipFree(mm->sort_hist);
+    mm->sort_tmp = nullptr; mm->sort_hist = nullptr; mm->sort_cap = 0;
+    HIPCHK(dev_alloc((void**)&mm->sort_tmp, (count + 16) * sizeof(fzb_match_rec)));
+    const size_t hist_words = (size_t)2 * 256 * (count / 2048 + 2);  // (+ the digit totals and the phase word: kernels_sort.hip)
+    HIPCHK(dev_alloc((void**)&mm->sort_hist, (hist_words + 1024) * 4));
+    HIPCHK(hipMemset(mm->sort_hist + hist_words, 0, 1024 * 4));
+    mm->sort_cap = count;
+    return FZB_OK;
+}
+
+// PatternConfig::resolve (src/pattern.rs:250-262); `sort` is the matcher's and applies to the combined list only
+static fzb_config resolve_pattern(const fzb_config& config, const fzb_pattern& p) {
+    fzb_config rc = config;
+    if (p.has_max_typos) rc.max_typos = p.max_typos;
+    if (p.casing >= 0) rc.casing = p.casing;
+    if (p.unicode >= 0) rc.unicode = p.unicode;
+    if (p.has_scoring) rc.scoring = p.scoring;
+    if (p.matching >= 0) rc.matching = p.matching;
+    rc.sort = FZB_SORT_INDEX_ASC;
+    return rc;
+}
+
+// A slot holds the needle under `rcfg` already: the same config, the lane pair compared as RESOLVED (a slot made by fzb_matcher_clone
+// stores the resolved pair, the caller's config may ask for 0 / 0 or a prefilter width alone - the same needle resolves them alike)
+static bool slot_unchanged(const fzb_matcher* m, const fzb_config& rcfg) {
+    fzb_config a = m->config;
+    a.pf_lanes = rcfg.pf_lanes;
+    a.sw_lanes = rcfg.sw_lanes;
+    if (!same_config(a, rcfg)) return false;
+    int pf = rcfg.pf_lanes, sw = rcfg.sw_lanes;
+    if (pf == 0 && sw == 0) detect_host_lanes(m->use_u8, pf, sw);
+    else if (sw == 0) sw = m->use_u8 ? pf : pf / 2;
+    return pf == m->lc.pf_lanes && sw == m->lc.sw_lanes;
+}
+
+static bool same_pattern(const fzb_multi_matcher::Raw& r, const fzb_pattern& p) {  // field by field: fzb_pattern has padding
+    const fzb_pattern& q = r.pattern;
+    return r.needle.size() == p.needle_len && (p.needle_len == 0 || memcmp(r.needle.data(), p.needle_utf8, p.needle_len) == 0) && q.negated == p.negated &&
+           q.has_max_typos == p.has_max_typos && (!p.has_max_typos || q.max_typos == p.max_typos) && q.casing == p.casing && q.unicode == p.unicode &&
+           q.has_scoring == p.has_scoring && (!p.has_scoring || same_scoring(q.scoring, p.scoring)) && q.matching == p.matching;
+}
+
+// Compiles `patterns` under `config` into the matcher's sub-matcher slots, in order: a slot whose needle and resolved config are unchanged
+// is left alone, any other is rebuilt in place (rebuild_matcher keeps its device workspace), and a sub-matcher is created only when the
+// compiled patterns outnumber the slots.  Slots beyond the compiled patterns become spares.  mm->config / mm->raw are the caller's to set.
+// On an error the slots before the failing pattern have been rebuilt already: multi_compile restores them.
+static int compile_into_slots(fzb_multi_matcher* mm, const fzb_config& config, const fzb_pattern* patterns, size_t n_patterns) {
+    std::vector<fzb_matcher*> slots;
+    slots.reserve(mm->patterns.size() + mm->spare.size());
+    for (auto& c : mm->patterns) slots.push_back(c.m);
+    slots.insert(slots.end(), mm->spare.begin(), mm->spare.end());
+    std::vector<fzb_multi_matcher::Compiled> compiled;
+    int rc = FZB_OK;
+    for (size_t i = 0; i < n_patterns && !rc; i++) {
+        const fzb_pattern& p = patterns[i];
+        if (p.needle_len == 0) continue;  // Matcher::compile returns None for an empty needle
+        const fzb_config rcfg = resolve_pattern(config, p);
+        const size_t k = compiled.size();
+        if (k < slots.size()) {
+            fzb_matcher* m = slots[k];
+            if (!(slot_unchanged(m, rcfg) && m->needle.size() == p.needle_len && memcmp(m->needle.data(), p.needle_utf8, p.needle_len) == 0))
+                rc = rebuild_matcher(m, &rcfg, p.needle_utf8, p.needle_len);
+        } else {
+            fzb_matcher* m = nullptr;
+            rc = fzb_matcher_create(&rcfg, p.needle_utf8, p.needle_len, &m);
+            if (!rc) slots.push_back(m);
+        }
+        if (!rc) compiled.push_back({p.negated != 0, slots[k]});
+    }
+    // (on an error the slots are kept in their order too: nothing is lost and the restore reuses them)
+    const size_t k = rc ? 0 : compiled.size();
+    if (rc) {
+        compiled.clear();
+        for (size_t i = 0; i < mm->patterns.size() && i < slots.size(); i++) compiled.push_back({mm->patterns[i].negated, slots[i]});
+    }
+    mm->patterns.assign(compiled.begin(), compiled.end());
+    mm->spare.assign(slots.begin() + (rc ? (std::ptrdiff_t)mm->patterns.size() : (std::ptrdiff_t)k), slots.end());
+    return rc;
+}
+
+static std::vector<fzb_pattern> raw_patterns(const fzb_multi_matcher* mm) {  // the stored patterns with their needles pointed at again
+    std::vector<fzb_pattern> v;
+    for (const auto& r : mm->raw) {
+        fzb_pattern p = r.pattern;
+        p.needle_utf8 = (const uint8_t*)r.needle.data();
+        v.push_back(p);
+    }
+    return v;
+}
+
+// set_patterns / set_config / create: compile, and on success record what was compiled; on an error the previous patterns are compiled
+// again (they were accepted before, so that cannot fail) and the matcher answers as it did
+static int multi_compile(fzb_multi_matcher* mm, const fzb_config& config, const fzb_pattern* patterns, size_t n_patterns) {
+    for (size_t i = 0; i < n_patterns; i++)
+        if (patterns[i].needle_len && !patterns[i].needle_utf8) return fail(FZB_ERR_INVALID, "null needle");
+    int rc = compile_into_slots(mm, config, patterns, n_patterns);
+    if (rc) {
+        const std::string msg = fzb_last_error();
+        const std::vector<fzb_pattern> old = raw_patterns(mm);
+        (void)compile_into_slots(mm, mm->config, old.data(), old.size());
+        return fail(rc, msg);
+    }
+    std::vector<fzb_multi_matcher::Raw> raw;
+    for (size_t i = 0; i < n_patterns; i++) {
+        fzb_multi_matcher::Raw r{patterns[i].needle_len ? std::string((const char*)patterns[i].needle_utf8, patterns[i].needle_len) : std::string(), patterns[i]};
+        r.pattern.needle_utf8 = nullptr;
+        raw.push_back(std::move(r));
+    }
+    mm->raw.swap(raw);
+    mm->config = config;
+    if (mm->order) mm->order->config.sort = config.sort;
+    return FZB_OK;
+}
+
+// the per-shard clones of the multi-device form follow their parent (their device state stays where it is)
+static void multi_follow(fzb_multi_matcher* mm) {
+    if (mm->shard_clones.empty()) return;
+    const std::vector<fzb_pattern> pats = raw_patterns(mm);
+    bool ok = true;
+    for (fzb_multi_matcher* cm : mm->shard_clones) ok = ok && multi_compile(cm, mm->config, pats.data(), pats.size()) == FZB_OK;
+    if (!ok) {  // cannot happen for patterns the parent accepted; drop the clones rather than keep stale ones (they are made again on the next query)
+        int cur = 0;
+        const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+        for (size_t g = 0; g < mm->shard_clones.size(); g++) {
+            if (mm->shard_devices[g] >= 0) (void)hipSetDevice(mm->shard_devices[g]);
+            fzb_multi_matcher_free(mm->shard_clones[g]);
+        }
+        if (have_cur) (void)hipSetDevice(cur);
+        mm->shard_clones.clear();
+        mm->shard_devices.clear();
+        fzb_clear_error();
+    }
+}
+
+int fzb_multi_order_host(fzb_multi_matcher* mm, fzb_matcher** out) {
+    if (!mm->order) {
+        int rc = fzb_matcher_create(&mm->config, nullptr, 0, &mm->order);
+        if (rc) return rc;
+        mm->order->sum_scores = true;
+    }
+    *out = mm->order;
+    return FZB_OK;
+}
+extern "C" {
+
 int fzb_multi_matcher_create(const fzb_config* config, const fzb_pattern* patterns, size_t n_patterns, fzb_multi_matcher** out) {
     if (!config || !out || (n_patterns && !patterns)) return fail(FZB_ERR_INVALID, "null argument");
     auto mm = new fzb_multi_matcher();
     mm->config = *config;
-    for (size_t i = 0; i < n_patterns; i++) {
-        const fzb_pattern& p = patterns[i];
-        if (p.needle_len == 0) continue;  // Matcher::compile returns None for an empty needle
-        if (!p.needle_utf8) { fzb_multi_matcher_free(mm); return fail(FZB_ERR_INVALID, "null needle"); }
-        fzb_config rc = *config;  // PatternConfig::resolve (src/pattern.rs:250-262); `sort` is the matcher's and applies to the combined list only
-        if (p.has_max_typos) rc.max_typos = p.max_typos;
-        if (p.casing >= 0) rc.casing = p.casing;
-        if (p.unicode >= 0) rc.unicode = p.unicode;
-        if (p.has_scoring) rc.scoring = p.scoring;
-        if (p.matching >= 0) rc.matching = p.matching;
-        rc.sort = FZB_SORT_INDEX_ASC;
-        fzb_matcher* m = nullptr;
-        int rc_create = fzb_matcher_create(&rc, p.needle_utf8, p.needle_len, &m);
-        if (rc_create) { fzb_multi_matcher_free(mm); return rc_create; }
-        mm->patterns.push_back({p.negated != 0, m});
+    int rc = multi_compile(mm, *config, patterns, n_patterns);
+    if (rc) {
+        const std::string msg = fzb_last_error();
+        fzb_multi_matcher_free(mm);
+        return fail(rc, msg);
     }
     *out = mm;
     return FZB_OK;
 }
 
+int fzb_multi_matcher_set_patterns(fzb_multi_matcher* mm, const fzb_pattern* patterns, size_t n_patterns) {
+    if (!mm || (n_patterns && !patterns)) return fail(FZB_ERR_INVALID, "null argument");
+    for (size_t i = 0; i < n_patterns; i++)
+        if (patterns[i].needle_len && !patterns[i].needle_utf8) return fail(FZB_ERR_INVALID, "null needle");
+    bool same = n_patterns == mm->raw.size();
+    for (size_t i = 0; same && i < n_patterns; i++) same = same_pattern(mm->raw[i], patterns[i]);
+    if (same) return FZB_OK;  // "Skipped if the patterns are the same" (src/matcher/mod.rs:170-176)
+    const fzb_config cfg = mm->config;
+    int rc = multi_compile(mm, cfg, patterns, n_patterns);
+    if (rc) return rc;
+    multi_follow(mm);
+    return FZB_OK;
+}
+
+int fzb_multi_matcher_set_config(fzb_multi_matcher* mm, const fzb_config* config) {
+    if (!mm || !config) return fail(FZB_ERR_INVALID, "null argument");
+    if (same_config(mm->config, *config)) return FZB_OK;
+    // every pattern is resolved again; a change of `sort` alone leaves every slot as it is (sub-matchers run IndexAsc)
+    const std::vector<fzb_pattern> pats = raw_patterns(mm);
+    int rc = multi_compile(mm, *config, pats.data(), pats.size());
+    if (rc) return rc;
+    multi_follow(mm);
+    return FZB_OK;
+}
+
+int fzb_multi_matcher_clone(const fzb_multi_matcher* src, fzb_multi_matcher** out) {
+    if (!src || !out) return fail(FZB_ERR_INVALID, "null argument");
+    auto mm = new fzb_multi_matcher();
+    mm->config = src->config;
+    mm->raw = src->raw;
+    for (const auto& c : src->patterns) {
+        fzb_matcher* m = nullptr;
+        int rc = fzb_matcher_clone(c.m, &m);  // keeps the resolved lane pair
+        if (rc) {
+            const std::string msg = fzb_last_error();
+            fzb_multi_matcher_free(mm);
+            return fail(rc, msg);
+        }
+        mm->patterns.push_back({c.negated, m});
+    }
+    *out = mm;
+    return FZB_OK;
+}
+
+int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
+    if (!mm || !c) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = c->dev.n;
+    int rc;
+    for (auto& p : mm->patterns)
+        if ((rc = reserve_slot_any_needle(p.m, c))) return rc;
+    for (fzb_matcher* m : mm->spare)
+        if ((rc = reserve_slot_any_needle(m, c))) return rc;
+    if ((rc = multi_ensure_buffers(mm, n)) || (rc = multi_ensure_out(mm, n)) || (rc = multi_ensure_sort(mm, n))) return rc;
+    if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
+    return FZB_OK;
+}
+
+int fzb_debug_device_allocs(uint64_t* out) {
+    if (!out) return fail(FZB_ERR_INVALID, "null argument");
+    *out = g_fzb_dev_allocs.load(std::memory_order_relaxed);
+    return FZB_OK;
+}
+
 void fzb_multi_matcher_free(fzb_multi_matcher* mm) {
     if (!mm) return;
+    fzb_matcher_free(mm->order);  // first: joins its shard workers before the per-shard clones they run go
+    if (!mm->shard_clones.empty()) {  // a shard clone's device state lives on its shard's device
+        int cur = 0;
+        const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+        for (size_t g = 0; g < mm->shard_clones.size(); g++) {
+            if (mm->shard_devices[g] >= 0) (void)hipSetDevice(mm->shard_devices[g]);
+            fzb_multi_matcher_free(mm->shard_clones[g]);
+        }
+        if (have_cur) (void)hipSetDevice(cur);
+    }
     for (auto& p : mm->patterns) fzb_matcher_free(p.m);
+    for (fzb_matcher* m : mm->spare) fzb_matcher_free(m);
     multi_free_buffers(mm);
     void* ptrs[] = {mm->out_dev, mm->count_dev, mm->sort_tmp, mm->sort_hist};
     for (void* p : ptrs)
@@ -2276,6 +2530,12 @@ void fzb_multi_matcher_free(fzb_multi_matcher* mm) {
 }
 
 size_t fzb_multi_matcher_len(const fzb_multi_matcher* mm) { return mm ? mm->patterns.size() : 0; }
+
+int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, size_t threads, fzb_match** out, size_t* out_len) {
+    if (!mm || !c) return fail(FZB_ERR_INVALID, "null argument");
+    if (threads == 0) return fail(FZB_ERR_PANIC, "threads must be positive");  // parallel.rs:24
+    return fzb_multi_match_list(mm, c, out, out_len);
+}
 
 int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                                 uint32_t* dev_count, void* stream) {
@@ -2306,17 +2566,7 @@ int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
         return FZB_OK;
     }
     if (ps.size() == 1 && !ps[0].negated) return fzb_match_list_device(ps[0].m, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
-    if (mm->cap < count) {
-        multi_free_buffers(mm);
-        const size_t cap = count + count / 8 + 4096;
-        HIPCHK(dev_alloc((void**)&mm->cand[0], (cap + 16) * sizeof(fzb_match_rec)));
-        HIPCHK(dev_alloc((void**)&mm->cand[1], (cap + 16) * sizeof(fzb_match_rec)));
-        HIPCHK(dev_alloc((void**)&mm->counts, 64));
-        HIPCHK(dev_alloc((void**)&mm->items, cap * 4));
-        HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
-        HIPCHK(dev_alloc((void**)&mm->tile_counts, ((cap + FZB_TILE - 1) / FZB_TILE + 2) * 4));
-        mm->cap = cap;
-    }
+    if (int rc_ = multi_ensure_buffers(mm, count)) return rc_;
     // match_list_multi_into (src/matcher/multi.rs:84-152)
     size_t base = ps.size();
     for (size_t i = 0; i < ps.size(); i++)
@@ -2359,14 +2609,7 @@ int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match**
     const size_t count = c->dev.n;
     *out = nullptr;
     *out_len = 0;
-    if (mm->out_cap < count || !mm->count_dev) {
-        if (mm->out_dev) (void)hipFree(mm->out_dev);
-        mm->out_dev = nullptr;
-        mm->out_cap = 0;
-        HIPCHK(dev_alloc((void**)&mm->out_dev, (count + 16) * sizeof(fzb_match_rec)));
-        mm->out_cap = count;
-        if (!mm->count_dev) HIPCHK(dev_alloc((void**)&mm->count_dev, 64));
-    }
+    if (int rc_ = multi_ensure_out(mm, count)) return rc_;
     int rc = fzb_multi_match_list_device(mm, c, 0, count, 0, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
     if (rc) return rc;
     // Matcher::match_list (src/matcher/mod.rs:212-222): reverse, then the stable radix sort unless there is no pattern at all
@@ -2374,16 +2617,8 @@ int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match**
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
     const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
     if ((reversed || by_score) && count) {
-        if (by_score && mm->sort_cap < count) {
-            if (mm->sort_tmp) (void)hipFree(mm->sort_tmp);
-            if (mm->sort_hist) (void)hipFree(mm->sort_hist);
-            mm->sort_tmp = nullptr; mm->sort_hist = nullptr; mm->sort_cap = 0;
-            HIPCHK(dev_alloc((void**)&mm->sort_tmp, (count + 16) * sizeof(fzb_match_rec)));
-            const size_t hist_words = (size_t)2 * 256 * (count / 2048 + 2);  // (+ the digit totals and the phase word: kernels_sort.hip)
-            HIPCHK(dev_alloc((void**)&mm->sort_hist, (hist_words + 1024) * 4));
-            HIPCHK(hipMemset(mm->sort_hist + hist_words, 0, 1024 * 4));
-            mm->sort_cap = count;
-        }
+        if (by_score)
+            if (int rc_ = multi_ensure_sort(mm, count)) return rc_;
         fzb_launch_sort(mm->out_dev, mm->sort_tmp, mm->count_dev, mm->sort_hist, (u32)(mm->sort_cap / 2048 + 2), reversed, by_score, mm->num_cus * 2, nullptr);
         HIPCHK(hipGetLastError());
     }
@@ -2478,14 +2713,7 @@ int fzb_multi_match_list_into(fzb_multi_matcher* mm, const fzb_corpus* c, size_t
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
     *out = nullptr;
     *out_len = 0;
-    if (mm->out_cap < count || !mm->count_dev) {
-        if (mm->out_dev) (void)hipFree(mm->out_dev);
-        mm->out_dev = nullptr;
-        mm->out_cap = 0;
-        HIPCHK(dev_alloc((void**)&mm->out_dev, (count + 16) * sizeof(fzb_match_rec)));
-        mm->out_cap = count;
-        if (!mm->count_dev) HIPCHK(dev_alloc((void**)&mm->count_dev, 64));
-    }
+    if (int rc_ = multi_ensure_out(mm, count)) return rc_;
     int rc = fzb_multi_match_list_device(mm, c, first, count, index_offset, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
     if (rc) return rc;
     return fetch_records(mm->fetch, mm->out_dev, mm->count_dev, mm->out_cap, out, out_len);

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <atomic>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -20,7 +22,12 @@ void fzb_clear_error();
         if (e_ != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-inline hipError_t fzb_dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 16); }
+// every device allocation of the library goes through here; the counter is fzb_debug_device_allocs (host.hip)
+extern std::atomic<uint64_t> g_fzb_dev_allocs;
+inline hipError_t fzb_dev_alloc(void** p, size_t bytes) {
+    g_fzb_dev_allocs.fetch_add(1, std::memory_order_relaxed);
+    return hipMalloc(p, bytes ? bytes : 16);
+}
 
 struct fzb_corpus {
     CorpusDev dev{};
@@ -102,6 +109,44 @@ struct fzb_matcher {
     // them through host memory), and the last query's report of how every shard's run reached the root (fzb_matcher_shard_report)
     std::vector<std::array<int, 3>> shard_peers;  // {root, device, state}
     std::string shard_report;
+    // an ordering host of summed multi-pattern scores (fzb_multi_matcher::order): the radix sort always takes both passes
+    bool sum_scores = false;
+};
+
+// ---- multi-pattern composition (src/matcher/multi.rs; host.hip) ----------------------------------------------------------
+struct fzb_multi_matcher {
+    fzb_config config{};
+    struct Compiled { bool negated; fzb_matcher* m; };
+    std::vector<Compiled> patterns;  // empty needles dropped (src/matcher/mod.rs:193-195)
+    // sub-matchers beyond the compiled patterns, kept by fzb_multi_matcher_set_patterns for a later query with more patterns (slot order:
+    // `patterns`, then these); released only by fzb_multi_matcher_free
+    std::vector<fzb_matcher*> spare;
+    // the patterns as the caller gave them (set_patterns: "skipped if the patterns are the same"); pattern.needle_utf8 is not kept
+    struct Raw { std::string needle; fzb_pattern pattern; };
+    std::vector<Raw> raw;
+    int num_cus = 0;
+    // device buffers, grown on demand: two candidate lists (ping-pong), their lengths, the item list handed to the next pattern,
+    // and the bitmap / per-tile counts of the negation's compaction
+    size_t cap = 0;
+    fzb_match_rec* cand[2] = {nullptr, nullptr};
+    u32* counts = nullptr;  // [0],[4] = lengths of cand[0], cand[1]; [8] = hits of a negated pattern (each slot: count, untruncated total)
+    u32* items = nullptr;
+    u64* bitmap = nullptr;
+    u32* tile_counts = nullptr;
+    // ordering + staging for the synchronous API
+    fzb_match_rec* out_dev = nullptr;
+    size_t out_cap = 0;
+    u32* count_dev = nullptr;
+    fzb_match_rec* sort_tmp = nullptr;
+    u32* sort_hist = nullptr;
+    size_t sort_cap = 0;
+    FetchHint fetch;
+    // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
+    // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
+    // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
+    fzb_matcher* order = nullptr;
+    std::vector<fzb_multi_matcher*> shard_clones;
+    std::vector<int> shard_devices;
 };
 
 
@@ -130,6 +175,15 @@ int fzb_order_finish(fzb_matcher* m, const OrderPlan& p, fzb_match_rec* dev_out,
 // k_merge_matches_by_* (src/k_merge.rs:56-132) over runs given by pointer
 int fzb_k_merge_runs(int32_t sort, const fzb_match* const* runs, const size_t* run_lens, size_t nruns, fzb_match* out);
 void fzb_shard_workers_free(void* workers);  // host_shard.hip
+// The multi-device query over a sharded corpus for either matcher type (host_shard.hip): `root` holds the ordering / staging / gather state
+// and one clone per shard whose stream and staging carry that shard's run; run(g, carrier, shard, index_offset, stream) writes shard g's
+// index-ordered records and their two count words into carrier->out_dev / carrier->count_dev (capacity carrier->out_cap) on `stream`.
+using ShardRunFn = std::function<int(size_t g, fzb_matcher* carrier, const fzb_corpus* shard, uint32_t index_offset, hipStream_t stream)>;
+int fzb_sharded_query(fzb_matcher* root, const fzb_sharded_corpus* sc, const ShardRunFn& run, fzb_match** out, size_t* out_len);
+// CompiledPatterns::Empty over n haystacks: every index from index_offset, score 0, reversed for the *Desc strategies, never sorted (host list)
+int fzb_empty_pattern_list(size_t n, uint32_t index_offset, int sort, fzb_match** out, size_t* out_len);
+// the multi matcher's ordering host (created on first use, host.hip)
+int fzb_multi_order_host(fzb_multi_matcher* mm, fzb_matcher** out);
 int fzb_build_filter_view(fzb_corpus* c);     // host_upload.hip
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

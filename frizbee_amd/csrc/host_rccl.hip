@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 
 #include "host_internal.h"
@@ -92,6 +93,10 @@ int need_rccl(RcclApi** out) {
         if (r_ != ncclSuccess) return fzb_fail(FZB_ERR_HIP, std::string(#expr) + ": " + (api)->GetErrorString(r_));      \
     } while (0)
 
+// Words per rank in the count all-gather: [0] records written, [1] matches found (what the pipeline writes: fzb_match_list_device's pair),
+// [2] status (0, or the error code of a rank-local step that failed), [3] the share's first global index.
+static constexpr int kWords = 4;
+
 struct fzb_shard_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1, device = -1;
@@ -100,7 +105,7 @@ struct fzb_shard_comm {
     size_t run_cap = 0;
     fzb_match_rec* gather = nullptr;  // the other ranks' runs, back to back in rank order (receivers only)
     size_t gather_cap = 0;
-    u32* words = nullptr;             // device: [0..1] this rank's count words, [2 .. 2 + 2 world) every rank's (the all-gather's output)
+    u32* words = nullptr;             // device: [0, kWords) this rank's words, [kWords, kWords + kWords world) every rank's (the all-gather's output)
     u32* words_host = nullptr;        // page-locked copy of the gathered words
     u64 bytes_sent = 0, bytes_received = 0;  // records of the last query, as bytes
 };
@@ -137,7 +142,7 @@ int fzb_shard_comm_create(const uint8_t id[FZB_RCCL_ID_BYTES], int rank, int wor
     ncclResult_t r = api->CommInitRank(&c->comm, world, uid, rank);  // collective: every rank of the world is inside this call
     if (r != ncclSuccess) { c->comm = nullptr; return fail_free(fzb_fail(FZB_ERR_HIP, std::string("ncclCommInitRank: ") + api->GetErrorString(r))); }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { c->stream = nullptr; return fail_free(fzb_fail(FZB_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e))); }
-    const size_t nwords = 2 + 2 * (size_t)world;
+    const size_t nwords = kWords + kWords * (size_t)world;
     if ((e = fzb_dev_alloc((void**)&c->words, nwords * sizeof(u32))) != hipSuccess) { c->words = nullptr; return fail_free(fzb_fail(FZB_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e))); }
     c->words_host = (u32*)fzb_pinned_get(nwords * sizeof(u32));
     if (!c->words_host) return fail_free(fzb_fail(FZB_ERR_HIP, "hipHostMalloc failed for the count words"));
@@ -181,86 +186,99 @@ static int grow(fzb_match_rec** p, size_t* cap, size_t want) {
     return FZB_OK;
 }
 
-// CompiledPatterns::Empty (src/matcher/mod.rs:194-196, 215-220, 381-384): every index of every share, score 0, reversed if the strategy says
-// so, never sorted.  Nothing is scored; the ranks only tell each other (share length, first global index) and a receiver writes the list.
-static int empty_pattern_list(RcclApi* api, fzb_matcher* m, size_t n, uint32_t index_offset, fzb_shard_comm* c, bool receiver, fzb_match** out, size_t* out_len) {
-    if ((u64)n + (u64)index_offset > 0xFFFFFFFFull)
-        return fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)n + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
-    c->words_host[0] = (u32)n;
-    c->words_host[1] = index_offset;
-    HIPCHK(hipMemcpyAsync(c->words, c->words_host, 2 * sizeof(u32), hipMemcpyHostToDevice, c->stream));
-    NCCLCHK(api, api->AllGather(c->words, c->words + 2, 2, ncclUint32, c->comm, c->stream));
-    HIPCHK(hipMemcpyAsync(c->words_host, c->words + 2, 2 * (size_t)c->world * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->bytes_sent = c->bytes_received = 0;
-    if (!receiver) return FZB_OK;
-    size_t total = 0;
-    for (int r = 0; r < c->world; r++) total += c->words_host[2 * r];
-    if (total > 0xFFFFFFFFull) return fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(total) + " > 4294967295 (index offset: 0)");
-    fzb_match* list = (fzb_match*)malloc(std::max<size_t>(total, 1) * sizeof(fzb_match));
-    if (!list) return fzb_fail(FZB_ERR_INVALID, "out of memory");
-    const int sort = m->config.sort;
-    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    size_t k = 0;
-    for (int r = 0; r < c->world; r++)
-        for (u32 i = 0; i < c->words_host[2 * r]; i++, k++) list[reversed ? total - 1 - k : k] = fzb_match{c->words_host[2 * r + 1] + i, 0, 0, 0};
-    *out = list;
-    *out_len = total;
-    return FZB_OK;
-}
-
-int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* c, int flags, fzb_match** out, size_t* out_len) {
-    if (!m || !shard || !c || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    *out_len = 0;
-    if (flags & ~FZB_GATHER_ALL) return fzb_fail(FZB_ERR_INVALID, "unknown flag");
-    RcclApi* api;
-    int rc = need_rccl(&api);
-    if (rc) return rc;
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != c->device) return fzb_fail(FZB_ERR_INVALID, "the communicator was created on device " + std::to_string(c->device) + " but device " + std::to_string(dev) + " is current");
+// The exchange of one query, for either matcher type.  `produce` writes this rank's index-ordered run into `run` (capacity records) and its
+// two count words into `words`, on `stream`; `order` is the matcher whose ordering / staging buffers a receiver merges with; `empty` =
+// CompiledPatterns::Empty (src/matcher/mod.rs:194-196, 215-220, 381-384: every index of every share, score 0, reversed if the strategy says
+// so, never sorted - nothing is scored, a receiver writes the list from the gathered (length, first index) pairs).
+// Every rank-local step runs BEFORE the count all-gather and a failure there travels in the status word: when any rank failed, every rank
+// returns that rank's error code, and none is left waiting inside the collective for a rank that has gone.
+using ProduceFn = std::function<int(fzb_match* run, size_t capacity, u32* words, hipStream_t stream)>;
+static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort, size_t n, uint32_t index_offset, fzb_shard_comm* c, int flags, const ProduceFn& produce,
+                         fzb_match** out, size_t* out_len) {
     const bool all = (flags & FZB_GATHER_ALL) != 0;
     const bool receiver = all || c->rank == 0;
-    const size_t n = shard->dev.n;
-    if (m->empty) return empty_pattern_list(api, m, n, index_offset, c, receiver, out, out_len);
-    // 1. this rank's run
-    if ((rc = grow(&c->run, &c->run_cap, n))) return rc;
-    if ((rc = fzb_match_list_device(m, shard, 0, n, index_offset, (fzb_match*)c->run, n ? n : 1, c->words, c->stream))) return rc;
-    // 2. every run's length
-    u32* all_words = c->words + 2;
-    NCCLCHK(api, api->AllGather(c->words, all_words, 2, ncclUint32, c->comm, c->stream));
-    HIPCHK(hipMemcpyAsync(c->words_host, all_words, 2 * (size_t)c->world * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    // 1. the rank-local steps: this rank's run (or, for Empty, nothing to score) and its words
+    int local = FZB_OK;
+    std::string local_msg;
+    {
+        int dev = -1;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) local = fzb_fail(FZB_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e));
+        else if (dev != c->device)
+            local = fzb_fail(FZB_ERR_INVALID, "the communicator was created on device " + std::to_string(c->device) + " but device " + std::to_string(dev) + " is current");
+        else if ((u64)n + (u64)index_offset > 0xFFFFFFFFull)
+            local = fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)n + index_offset) + " > 4294967295 (index offset: " +
+                                                std::to_string(index_offset) + ")");
+        else if (!empty && !(local = grow(&c->run, &c->run_cap, n)))
+            local = produce((fzb_match*)c->run, n ? n : 1, c->words, c->stream);
+        if (local) local_msg = fzb_last_error();
+    }
+    // status and first index from the host; a rank that failed (or has nothing scored: Empty) also writes its counts
+    c->words_host[0] = c->words_host[1] = empty && !local ? (u32)n : 0u;
+    c->words_host[2] = (u32)local;
+    c->words_host[3] = index_offset;
+    const bool counts_from_host = empty || local;
+    HIPCHK(hipMemcpyAsync(c->words + (counts_from_host ? 0 : 2), c->words_host + (counts_from_host ? 0 : 2), (counts_from_host ? 4 : 2) * sizeof(u32), hipMemcpyHostToDevice,
+                          c->stream));
+    // 2. every rank's words (kWords x 4 bytes per rank: the call's one host synchronisation before the result)
+    u32* all_words = c->words + kWords;
+    u32* words_host = c->words_host + kWords;
+    NCCLCHK(api, api->AllGather(c->words, all_words, kWords, ncclUint32, c->comm, c->stream));
+    HIPCHK(hipMemcpyAsync(words_host, all_words, kWords * (size_t)c->world * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(fzb_stream_wait(c->stream));
+    c->bytes_sent = c->bytes_received = 0;
+    for (int r = 0; r < c->world; r++) {
+        const u32 status = words_host[kWords * r + 2];
+        if (status)
+            return fzb_fail((int)status, "rank " + std::to_string(r) + " failed before the exchange" + (r == c->rank ? ": " + local_msg : " (error code " + std::to_string(status) + ")"));
+    }
     size_t others = 0, total = 0;
     for (int r = 0; r < c->world; r++) {
-        const u32 written = c->words_host[2 * r], found = c->words_host[2 * r + 1];
+        const u32 written = words_host[kWords * r], found = words_host[kWords * r + 1];
         if (found != written) return fzb_fail(FZB_ERR_CAPACITY, "rank " + std::to_string(r) + "'s run was truncated (" + std::to_string(found) + " matches, " + std::to_string(written) + " records)");
         total += written;
         if (r != c->rank) others += written;
     }
     if (total > 0xFFFFFFFFull) return fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(total) + " > 4294967295 (index offset: 0)");
+    if (empty) {
+        if (!receiver) return FZB_OK;
+        fzb_match* list = (fzb_match*)malloc(std::max<size_t>(total, 1) * sizeof(fzb_match));
+        if (!list) return fzb_fail(FZB_ERR_INVALID, "out of memory");
+        const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+        size_t k = 0;
+        for (int r = 0; r < c->world; r++)
+            for (u32 i = 0; i < words_host[kWords * r]; i++, k++) list[reversed ? total - 1 - k : k] = fzb_match{words_host[kWords * r + 3] + i, 0, 0, 0};
+        *out = list;
+        *out_len = total;
+        return FZB_OK;
+    }
     // 3. the records, each run exactly as long as it is
+    // (a receiver without room for the runs fails here, after the all-gather: its peers' sends then have no counterpart - the one step whose
+    // size is only known from the gathered counts)
+    int rc;
     if (receiver && (rc = grow(&c->gather, &c->gather_cap, others))) return rc;
-    const size_t mine = c->words_host[2 * c->rank];
-    c->bytes_sent = c->bytes_received = 0;
+    const size_t mine = words_host[kWords * c->rank];
     if (c->world > 1) {
         NCCLCHK(api, api->GroupStart());
+        ncclResult_t first = ncclSuccess;
+        const char* what = "";
         size_t off = 0;
-        for (int r = 0; r < c->world; r++) {
+        for (int r = 0; r < c->world && first == ncclSuccess; r++) {
             if (r == c->rank) continue;
-            const size_t cnt = c->words_host[2 * r];
+            const size_t cnt = words_host[kWords * r];
             if (receiver && cnt) {
-                NCCLCHK(api, api->Recv(c->gather + off, cnt * sizeof(fzb_match_rec), ncclUint8, r, c->comm, c->stream));
-                c->bytes_received += cnt * sizeof(fzb_match_rec);
+                if ((first = api->Recv(c->gather + off, cnt * sizeof(fzb_match_rec), ncclUint8, r, c->comm, c->stream)) != ncclSuccess) what = "ncclRecv";
+                else c->bytes_received += cnt * sizeof(fzb_match_rec);
             }
             off += cnt;
-            if ((all || r == 0) && mine) {
-                NCCLCHK(api, api->Send(c->run, mine * sizeof(fzb_match_rec), ncclUint8, r, c->comm, c->stream));
-                c->bytes_sent += mine * sizeof(fzb_match_rec);
+            if (first == ncclSuccess && (all || r == 0) && mine) {
+                if ((first = api->Send(c->run, mine * sizeof(fzb_match_rec), ncclUint8, r, c->comm, c->stream)) != ncclSuccess) what = "ncclSend";
+                else c->bytes_sent += mine * sizeof(fzb_match_rec);
             }
         }
-        NCCLCHK(api, api->GroupEnd());
+        const ncclResult_t end = api->GroupEnd();  // on every path: a group left open poisons the thread's next RCCL call
+        if (first != ncclSuccess) return fzb_fail(FZB_ERR_HIP, std::string(what) + ": " + api->GetErrorString(first));
+        if (end != ncclSuccess) return fzb_fail(FZB_ERR_HIP, std::string("ncclGroupEnd: ") + api->GetErrorString(end));
     }
     if (!receiver) {
         HIPCHK(hipStreamSynchronize(c->stream));  // the run may be overwritten by the next query only after it has left
@@ -272,13 +290,45 @@ int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32
     std::vector<size_t> caps((size_t)c->world);
     size_t off = 0;
     for (int r = 0; r < c->world; r++) {
-        const size_t cnt = c->words_host[2 * r];
+        const size_t cnt = words_host[kWords * r];
         runs[(size_t)r] = r == c->rank ? (const void*)c->run : (const void*)(c->gather + off);
         if (r != c->rank) off += cnt;
-        counts[(size_t)r] = all_words + 2 * r;
+        counts[(size_t)r] = all_words + kWords * r;
         caps[(size_t)r] = cnt;
     }
-    return fzb_merge_shard_runs(m, runs.data(), counts.data(), caps.data(), (size_t)c->world, c->stream, out, out_len);
+    return fzb_merge_shard_runs(order, runs.data(), counts.data(), caps.data(), (size_t)c->world, c->stream, out, out_len);
+}
+
+// the caller-side checks that do not depend on the rank (a bad handle cannot take part in the collective at all)
+static int rccl_begin(const void* m, const fzb_corpus* shard, fzb_shard_comm* c, int flags, fzb_match** out, size_t* out_len, RcclApi** api) {
+    if (!m || !shard || !c || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (flags & ~FZB_GATHER_ALL) return fzb_fail(FZB_ERR_INVALID, "unknown flag");
+    return need_rccl(api);
+}
+
+int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* c, int flags, fzb_match** out, size_t* out_len) {
+    RcclApi* api;
+    int rc = rccl_begin(m, shard, c, flags, out, out_len, &api);
+    if (rc) return rc;
+    const size_t n = shard->dev.n;
+    return rccl_exchange(api, m, m->empty, m->config.sort, n, index_offset, c, flags, [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+        return fzb_match_list_device(m, shard, 0, n, index_offset, run, cap, words, st);
+    }, out, out_len);
+}
+
+// the same exchange with this rank's AND / NOT composition (fzb_multi_match_list_device) as its run
+int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* c, int flags, fzb_match** out, size_t* out_len) {
+    RcclApi* api;
+    int rc = rccl_begin(mm, shard, c, flags, out, out_len, &api);
+    if (rc) return rc;
+    fzb_matcher* order = nullptr;
+    if ((rc = fzb_multi_order_host(mm, &order))) return rc;  // host memory only: cannot fail per rank
+    const size_t n = shard->dev.n;
+    return rccl_exchange(api, order, mm->patterns.empty(), mm->config.sort, n, index_offset, c, flags, [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+        return fzb_multi_match_list_device(mm, shard, 0, n, index_offset, run, cap, words, st);
+    }, out, out_len);
 }
 
 }  // extern "C"

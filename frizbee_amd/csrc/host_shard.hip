@@ -282,21 +282,24 @@ int fzb_sharded_corpus_shard(const fzb_sharded_corpus* sc, int g, uint64_t* lo, 
     return FZB_OK;
 }
 
-int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
-    if (!m || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+}  // extern "C"
+
+int fzb_empty_pattern_list(size_t n, uint32_t index_offset, int sort, fzb_match** out, size_t* out_len) {
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    fzb_match* r = (fzb_match*)malloc(std::max<size_t>(n, 1) * sizeof(fzb_match));
+    if (!r) return fzb_fail(FZB_ERR_INVALID, "out of memory");
+    for (size_t i = 0; i < n; i++) r[i] = fzb_match{(uint32_t)(index_offset + (reversed ? n - 1 - i : i)), 0, 0, 0};
+    *out = r;
+    *out_len = n;
+    return FZB_OK;
+}
+
+// The query of fzb_match_list_parallel_sharded / fzb_multi_match_list_parallel_sharded: `m` is the root's state (ordering, staging, the
+// shard clones that carry every shard's stream and run, workers, peer decisions, report); `run` produces shard g's run into its carrier.
+int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardRunFn& run, fzb_match** out, size_t* out_len) {
     *out = nullptr;
     *out_len = 0;
     const size_t ns = sc->shard.size();
-    const int sort = m->config.sort;
-    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    if (m->empty) {  // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
-        fzb_match* r = (fzb_match*)malloc(std::max<size_t>(sc->n, 1) * sizeof(fzb_match));
-        if (!r) return fzb_fail(FZB_ERR_INVALID, "out of memory");
-        for (size_t i = 0; i < sc->n; i++) r[i] = fzb_match{(uint32_t)(reversed ? sc->n - 1 - i : i), 0, 0, 0};
-        *out = r;
-        *out_len = sc->n;
-        return FZB_OK;
-    }
     // The ROOT: the device that is current on the calling thread.  It receives every shard's run and orders the whole list once.
     int rc = fzb_bind_device(m);
     if (rc) return rc;
@@ -387,7 +390,7 @@ int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc
         if (rc_) return rc_;
         // the shard's records in INDEX order, numbered from the shard's first index (what a worker of match_list_parallel pushes,
         // parallel.rs:55-63) - unsorted: the root orders the whole list
-        rc_ = fzb_match_list_device(cm, c, 0, count, (uint32_t)sc->bounds[g], (fzb_match*)cm->out_dev, cm->out_cap, cm->count_dev, one_stream ? m->shard_stream : cm->shard_stream);
+        rc_ = run(g, cm, c, (uint32_t)sc->bounds[g], one_stream ? m->shard_stream : cm->shard_stream);
         if (rc_) return rc_;
         if (one_stream) return FZB_OK;  // the concatenation follows on the same stream
         if (pull) {
@@ -501,7 +504,65 @@ int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc
     return FZB_OK;
 }
 
+extern "C" {
+
+int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
+    if (!m || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
+    if (m->empty) return fzb_empty_pattern_list(sc->n, 0, m->config.sort, out, out_len);
+    // the shard clones of the matcher score their shards themselves
+    return fzb_sharded_query(m, sc, [](size_t, fzb_matcher* cm, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
+        return fzb_match_list_device(cm, c, 0, c->dev.n, index_offset, (fzb_match*)cm->out_dev, cm->out_cap, cm->count_dev, st);
+    }, out, out_len);
+}
+
 const char* fzb_matcher_shard_report(const fzb_matcher* m) { return m ? m->shard_report.c_str() : ""; }
+
+// `Matcher::match_list_parallel` of a `from_patterns` matcher with one DEVICE per worker: the whole AND / NOT composition runs per shard
+// (the patterns are independent per haystack, so shard-local composition is exact) through a per-shard multi clone on the shard's
+// device, into the staging of the ordering host's shard clone; gather and ordering are fzb_match_list_parallel_sharded's.
+int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
+    if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (mm->patterns.empty()) return fzb_empty_pattern_list(sc->n, 0, mm->config.sort, out, out_len);
+    fzb_matcher* root = nullptr;
+    int rc = fzb_multi_order_host(mm, &root);
+    if (rc) return rc;
+    const size_t ns = sc->shard.size();
+    // one multi clone per shard; a clone whose shard moved to another device is released where it lives and made again
+    int cur = 0;
+    HIPCHK(hipGetDevice(&cur));
+    for (size_t g = 0; g < ns; g++) {
+        if (g < mm->shard_clones.size() && mm->shard_devices[g] >= 0 && mm->shard_devices[g] != sc->device[g]) {
+            (void)hipSetDevice(mm->shard_devices[g]);
+            fzb_multi_matcher_free(mm->shard_clones[g]);
+            (void)hipSetDevice(cur);
+            fzb_multi_matcher* cm = nullptr;
+            if ((rc = fzb_multi_matcher_clone(mm, &cm))) {
+                mm->shard_clones.erase(mm->shard_clones.begin() + (std::ptrdiff_t)g, mm->shard_clones.end());  // the rest is made on the next call
+                mm->shard_devices.resize(g);
+                return rc;
+            }
+            mm->shard_clones[g] = cm;
+            mm->shard_devices[g] = -1;
+        }
+        if (g >= mm->shard_clones.size()) {
+            fzb_multi_matcher* cm = nullptr;
+            if ((rc = fzb_multi_matcher_clone(mm, &cm))) return rc;
+            mm->shard_clones.push_back(cm);
+            mm->shard_devices.push_back(-1);
+        }
+    }
+    return fzb_sharded_query(root, sc, [&](size_t g, fzb_matcher* carrier, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
+        mm->shard_devices[g] = sc->device[g];  // (the worker runs on the shard's device)
+        return fzb_multi_match_list_device(mm->shard_clones[g], c, 0, c->dev.n, index_offset, (fzb_match*)carrier->out_dev, carrier->out_cap, carrier->count_dev, st);
+    }, out, out_len);
+}
+
+const char* fzb_multi_matcher_shard_report(const fzb_multi_matcher* mm) { return mm && mm->order ? mm->order->shard_report.c_str() : ""; }
 
 // The same combine for runs that are already on ONE device (frizbee_amd.distributed: the root rank after the RCCL gather of the
 // per-rank buffers): concatenation in run order -> reverse / stable radix sort -> one copy to the host.  dev_counts[g] points at run

@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 import ctypes as C
 
-from . import MATCH_DTYPE, SortStrategy, _check, _take, k_merge_matches, lib, radix_sort_matches
+from . import MATCH_DTYPE, MultiMatcher, SortStrategy, _check, _take, k_merge_matches, lib, radix_sort_matches
 
 
 def shard_range(n_total, rank, world):
@@ -309,9 +309,11 @@ class RcclShardComm:
         return bytes(buf)
 
     def match_list_parallel(self, matcher, shard, index_offset, all_ranks=False, copy=True):
-        """fzb_match_list_parallel_rccl (collective): `shard` = this rank's resident Corpus, `index_offset` = its first global index."""
+        """fzb_match_list_parallel_rccl (collective): `shard` = this rank's resident Corpus, `index_offset` = its first global index.
+        A `MultiMatcher` takes fzb_multi_match_list_parallel_rccl: this rank's AND / NOT composition is its run."""
+        fn = lib().fzb_multi_match_list_parallel_rccl if isinstance(matcher, MultiMatcher) else lib().fzb_match_list_parallel_rccl
         out, n = C.c_void_p(), C.c_size_t()
-        _check(lib().fzb_match_list_parallel_rccl(matcher.h, shard.h, int(index_offset), self.h, 1 if all_ranks else 0, C.byref(out), C.byref(n)))
+        _check(fn(matcher.h, shard.h, int(index_offset), self.h, 1 if all_ranks else 0, C.byref(out), C.byref(n)))
         return _take(out, n, copy)
 
     def last_exchange_bytes(self):

@@ -230,8 +230,10 @@ int fzb_merge_shard_runs(fzb_matcher* m, const void* const* dev_runs, const uint
  *                            `match_list_parallel` returns for the WHOLE list, to be freed with fzb_matches_free; on a rank that does
  *                            not receive, *out = NULL and *out_len = 0.  Every rank must pass a matcher of the same needle and config.
  *   fzb_shard_comm_last_exchange   out_bytes[0] / [1] = record bytes this rank sent / received in its last query.
- * As with any collective: a rank that fails BEFORE the exchange (a bad argument, no memory) leaves the others waiting inside RCCL - check arguments
- * that can differ per rank before the call, and treat an error of a collective call as the end of that communicator.  One communicator per thread;
+ * Every rank-local step (device check, u32 index guard, buffers, this rank's pipeline) runs before the count all-gather, and its outcome travels
+ * with the counts: when any rank failed there, EVERY rank returns that rank's error code and nothing is exchanged.  Only a NULL handle or an
+ * unknown flag returns before the collective (it cannot take part) - and a receiver that cannot grow its receive buffer after the all-gather
+ * leaves its senders without a counterpart; treat an error of a collective call as the end of that communicator.  One communicator per thread;
  * a communicator and the matchers used with it belong to the device that was current in fzb_shard_comm_create. */
 #define FZB_RCCL_ID_BYTES 128
 typedef struct fzb_shard_comm fzb_shard_comm;
@@ -324,6 +326,40 @@ int fzb_multi_match_list_indices_into(fzb_multi_matcher* mm, const fzb_corpus* c
 int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset,
                                 fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream);
 
+/* `Matcher::set_patterns` (src/matcher/mod.rs:170-176): skipped when the patterns are field-for-field the same; otherwise they are compiled
+ * as fzb_multi_matcher_create would, into the matcher's sub-matcher slots in order - a slot whose needle and resolved config are unchanged
+ * is left alone, any other is rebuilt in place (fzb_matcher_set_pattern's rule: its device workspace is kept), and a sub-matcher is
+ * created only when the compiled patterns outnumber the slots held (slots are released only by fzb_multi_matcher_free).  The
+ * composition, ordering and multi-device buffers are kept.  Empty / Single / Multi (mod.rs:178-190) as for a fresh create.  On error the
+ * matcher answers as before the call. */
+int fzb_multi_matcher_set_patterns(fzb_multi_matcher* mm, const fzb_pattern* patterns, size_t n_patterns);
+/* `Matcher::set_config` (src/matcher/mod.rs:154-162): no-op on an equal config (field by field); a change of `sort` alone rebuilds no
+ * sub-matcher (they run IndexAsc); any other change resolves every pattern again and updates its slot in place. */
+int fzb_multi_matcher_set_config(fzb_multi_matcher* mm, const fzb_config* config);
+/* fzb_matcher_reserve for the composition: the composition buffers, the ordering / staging buffers and every sub-matcher slot sized for
+ * `c` - a slot for ANY needle it may hold next, not only the one it holds now: the buffers of every filter / scorer form (fuzzy with or
+ * without typos, literal, unicode) and the multi-chunk scorer's parked rows for the largest needle of up to 64 bytes / 63 rows under the
+ * slot's scoring and lane pair (on a 256-CU device up to 512 MiB per slot).  Afterwards no query over `c` or a sub-range of it allocates
+ * device memory, also after any set_patterns / set_config that does not increase the number of compiled patterns - unless a needle goes
+ * beyond 64 bytes or a pattern's scoring or lane pair changes. */
+int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c);
+/* `impl Clone for Matcher` (src/matcher/parallel.rs:46): fzb_matcher_clone per compiled pattern (the resolved lane pairs are kept), the
+ * same config; its own buffers. */
+int fzb_multi_matcher_clone(const fzb_multi_matcher* mm, fzb_multi_matcher** out);
+/* `Matcher::match_list_parallel(&haystacks, threads)` (src/matcher/parallel.rs:18-89) of a `from_patterns` matcher: as
+ * fzb_match_list_parallel - 0 => FZB_ERR_PANIC "threads must be positive", otherwise fzb_multi_match_list's result. */
+int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, size_t threads, fzb_match** out, size_t* out_len);
+/* The multi-device form (see fzb_match_list_parallel_sharded): the whole AND / NOT composition runs per shard on the shard's device
+ * through per-shard clones the matcher keeps (they follow set_patterns / set_config), each run numbered from its shard's first index;
+ * the runs are gathered and ordered once on the root (the caller's current device).  Result = fzb_multi_match_list on the unsharded
+ * list for every sort strategy; with no compiled pattern every index, score 0, reversed for the *Desc strategies (mod.rs:215-220). */
+int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len);
+/* COLLECTIVE, one process per GPU (see fzb_match_list_parallel_rccl): this rank's composition is its run; the exchange is the same. */
+int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* comm,
+                                       int flags, fzb_match** out, size_t* out_len);
+/* fzb_matcher_shard_report for the last fzb_multi_match_list_parallel_sharded on `mm` ("" before the first) */
+const char* fzb_multi_matcher_shard_report(const fzb_multi_matcher* mm);
+
 /* Measurement hooks (bench.py): device time of the fzb_match_list_device calls made on this matcher since
  * fzb_set_profiling(m, 1), measured with HIP events recorded on the launch stream (event records only, no
  * synchronisation until read).  fzb_last_timings averages over those calls (at most the last 32):
@@ -353,6 +389,10 @@ int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len,
 /* test hook: the library's environment switches (frizbee_amd/csrc/knobs.h - comparison and debugging only, parsed once on first use) are
  * read again.  Matchers created before the call keep what was decided when they were created. */
 void fzb_debug_reload_knobs(void);
+
+/* test hook: device allocations (hipMalloc) this process's library has made so far - how a test sees that a re-query allocates nothing.
+ * Page-locked host result lists are not counted. */
+int fzb_debug_device_allocs(uint64_t* out);
 
 #ifdef __cplusplus
 }

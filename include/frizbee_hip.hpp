@@ -239,14 +239,25 @@ class Matcher {  // src/matcher/mod.rs:77-222
     const Config& config() const { return config_; }
     const std::vector<Pattern>& patterns() const { return patterns_; }
 
-    // `set_pattern` / `set_config` (src/matcher/mod.rs:143-176).  A single plain pattern keeps its device workspace.
+    // `set_pattern` / `set_patterns` / `set_config` (src/matcher/mod.rs:143-176).  A single plain pattern keeps its device workspace, and so
+    // does a multi-pattern matcher that stays one (fzb_multi_matcher_set_patterns / _set_config rebuild its sub-matchers in place); only a
+    // change between the two forms builds the other one.
     void set_pattern(const Pattern& p) {
         if (single_ && plain(p) && patterns_.size() == 1 && plain(patterns_[0])) {
             check(fzb_matcher_set_pattern(single_.get(), (const uint8_t*)p.needle.data(), p.needle.size()));
             patterns_ = {p};
             return;
         }
-        patterns_ = {p};
+        set_patterns({p});
+    }
+    void set_patterns(const std::vector<Pattern>& patterns) {
+        if (multi_ && !is_single(patterns)) {
+            const std::vector<fzb_pattern> raw = raw_patterns(patterns);
+            check(fzb_multi_matcher_set_patterns(multi_.get(), raw.data(), raw.size()));
+            patterns_ = patterns;
+            return;
+        }
+        patterns_ = patterns;
         build();
     }
     void set_config(const Config& c) {
@@ -255,7 +266,8 @@ class Matcher {  // src/matcher/mod.rs:77-222
             const fzb_config r = resolve(patterns_[0]);
             check(fzb_matcher_set_config(single_.get(), &r));
         } else {
-            build();
+            const fzb_config r = config_.raw();
+            check(fzb_multi_matcher_set_config(multi_.get(), &r));
         }
     }
 
@@ -337,27 +349,30 @@ class Matcher {  // src/matcher/mod.rs:77-222
         return match_list(Corpus(haystacks));
     }
 
-    // `match_list_parallel` with one DEVICE per worker (fzb_match_list_parallel_sharded): per shard pipeline + device sort on its GPU,
-    // k-way merge of the runs on this thread; the same list `match_list` returns.  Single-pattern matchers (the multi-pattern
-    // composition has no sharded entry point yet).
+    // `match_list_parallel` with one DEVICE per worker (fzb_match_list_parallel_sharded / fzb_multi_match_list_parallel_sharded): per
+    // shard the pipeline - or the whole multi-pattern composition - on its GPU, the runs gathered and ordered once on the current device;
+    // the same list `match_list` returns.
     std::vector<Match> match_list_parallel(const ShardedCorpus& corpus) {
-        if (!single_) throw Error(FZB_ERR_INVALID, "match_list_parallel over a sharded corpus needs a single-pattern matcher");
         fzb_match* out = nullptr;
         size_t n = 0;
-        check(fzb_match_list_parallel_sharded(single_.get(), corpus.raw(), &out, &n));
+        if (single_) check(fzb_match_list_parallel_sharded(single_.get(), corpus.raw(), &out, &n));
+        else check(fzb_multi_match_list_parallel_sharded(multi_.get(), corpus.raw(), &out, &n));
         return take(out, n);
     }
     // `match_list_parallel` with one PROCESS per worker (fzb_match_list_parallel_rccl, collective): this rank's share of the list (`shard`,
     // first global index `index_offset`); the whole list's result on rank 0 (`to_all`: on every rank), empty elsewhere.
     std::vector<Match> match_list_parallel(const Corpus& shard, uint32_t index_offset, ShardComm& comm, bool to_all = false) {
-        if (!single_) throw Error(FZB_ERR_INVALID, "match_list_parallel over a communicator needs a single-pattern matcher");
         fzb_match* out = nullptr;
         size_t n = 0;
-        check(fzb_match_list_parallel_rccl(single_.get(), shard.raw(), index_offset, comm.raw(), to_all ? FZB_GATHER_ALL : FZB_GATHER_ROOT, &out, &n));
+        const int flags = to_all ? FZB_GATHER_ALL : FZB_GATHER_ROOT;
+        if (single_) check(fzb_match_list_parallel_rccl(single_.get(), shard.raw(), index_offset, comm.raw(), flags, &out, &n));
+        else check(fzb_multi_match_list_parallel_rccl(multi_.get(), shard.raw(), index_offset, comm.raw(), flags, &out, &n));
         return take(out, n);
     }
-    // how the runs of that call reached the root device (fzb_matcher_shard_report: gather form, peer access per shard)
-    std::string shard_report() const { return single_ ? std::string(fzb_matcher_shard_report(single_.get())) : std::string(); }
+    // how the runs of the last sharded call reached the root device (gather form, peer access per shard)
+    std::string shard_report() const {
+        return std::string(single_ ? fzb_matcher_shard_report(single_.get()) : fzb_multi_matcher_shard_report(multi_.get()));
+    }
 
   private:
     static bool plain(const Pattern& p) {
@@ -372,23 +387,18 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (p.config.scoring) c.scoring_ = *p.config.scoring;
         return c.raw();
     }
-    void build() {  // build_patterns (src/matcher/mod.rs:178-190): one non-negated pattern -> the single-pattern matcher
-        single_.reset();
-        multi_.reset();
+    // build_patterns (src/matcher/mod.rs:178-190): one non-negated pattern -> the single-pattern matcher
+    static bool is_single(const std::vector<Pattern>& patterns, size_t* at = nullptr) {
         size_t live = 0, last = 0;
-        for (size_t i = 0; i < patterns_.size(); i++)
-            if (!patterns_[i].needle.empty()) { live++; last = i; }
-        if (live == 1 && !patterns_[last].negated) {
-            const fzb_config r = resolve(patterns_[last]);
-            fzb_matcher* m = nullptr;
-            check(fzb_matcher_create(&r, (const uint8_t*)patterns_[last].needle.data(), patterns_[last].needle.size(), &m));
-            single_.reset(m);
-            if (patterns_.size() != 1) patterns_ = {patterns_[last]};
-            return;
-        }
-        std::vector<fzb_pattern> raw(patterns_.size());
-        for (size_t i = 0; i < patterns_.size(); i++) {
-            const Pattern& p = patterns_[i];
+        for (size_t i = 0; i < patterns.size(); i++)
+            if (!patterns[i].needle.empty()) { live++; last = i; }
+        if (at) *at = last;
+        return live == 1 && !patterns[last].negated;
+    }
+    static std::vector<fzb_pattern> raw_patterns(const std::vector<Pattern>& patterns) {  // (the needles stay the caller's)
+        std::vector<fzb_pattern> raw(patterns.size());
+        for (size_t i = 0; i < patterns.size(); i++) {
+            const Pattern& p = patterns[i];
             fzb_pattern& r = raw[i];
             r = fzb_pattern{};
             r.needle_utf8 = (const uint8_t*)p.needle.data();
@@ -402,6 +412,21 @@ class Matcher {  // src/matcher/mod.rs:77-222
             r.has_scoring = p.config.scoring.has_value();
             if (p.config.scoring) r.scoring = p.config.scoring->raw();
         }
+        return raw;
+    }
+    void build() {
+        single_.reset();
+        multi_.reset();
+        size_t last = 0;
+        if (is_single(patterns_, &last)) {
+            const fzb_config r = resolve(patterns_[last]);
+            fzb_matcher* m = nullptr;
+            check(fzb_matcher_create(&r, (const uint8_t*)patterns_[last].needle.data(), patterns_[last].needle.size(), &m));
+            single_.reset(m);
+            if (patterns_.size() != 1) patterns_ = {patterns_[last]};
+            return;
+        }
+        const std::vector<fzb_pattern> raw = raw_patterns(patterns_);
         const fzb_config c = config_.raw();
         fzb_multi_matcher* mm = nullptr;
         check(fzb_multi_matcher_create(&c, raw.data(), raw.size(), &mm));

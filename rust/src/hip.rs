@@ -16,7 +16,7 @@
 //!      on the same list, 0.10 ms with the result left on the device): the interactive case (`Matcher::set_pattern` on
 //!      every keystroke against one file list) and the one the backend is for.
 //!   3. `ShardedCorpus` + `MatcherHip::match_list_parallel_sharded` — `match_list_parallel` with one GPU per worker.
-use crate::{CaseMatching, Config, Match, MatchIndices, SortStrategy, UnicodeMatching};
+use crate::{CaseMatching, Config, Match, MatchIndices, Pattern, SortStrategy, UnicodeMatching};
 use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)]
@@ -61,6 +61,21 @@ struct FzbMatchIndices {
     positions_len: u32,
 }
 
+/// `Pattern` + `PatternConfig` (src/pattern.rs:9-18, 230-262) as the header's `fzb_pattern`: -1 / has_* = 0 = inherit the matcher's config
+#[repr(C)]
+struct FzbPattern {
+    needle_utf8: *const u8,
+    needle_len: usize,
+    negated: i32,
+    has_max_typos: i32,
+    max_typos: i32,
+    casing: i32,
+    unicode: i32,
+    has_scoring: i32,
+    scoring: FzbScoring,
+    matching: i32,
+}
+
 const FZB_ERR_PANIC: c_int = 2;
 const FZB_SHARD_BY_BYTES: c_int = 1;
 
@@ -95,6 +110,32 @@ extern "C" {
     fn fzb_shard_comm_free(comm: *mut c_void);
     fn fzb_match_list_parallel_rccl(m: *mut c_void, shard: *const c_void, index_offset: u32, comm: *mut c_void, flags: c_int, out: *mut *mut FzbMatch,
                                     out_len: *mut usize) -> c_int;
+    // `Matcher::from_patterns` (src/matcher/mod.rs:95-111; composition src/matcher/multi.rs:84-152) and its lifecycle
+    fn fzb_multi_matcher_create(cfg: *const FzbConfig, patterns: *const FzbPattern, n_patterns: usize, out: *mut *mut c_void) -> c_int;
+    fn fzb_multi_matcher_free(mm: *mut c_void);
+    fn fzb_multi_matcher_len(mm: *const c_void) -> usize;
+    fn fzb_multi_match_list(mm: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_indices(mm: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
+                                    out_positions: *mut *mut u32) -> c_int;
+    fn fzb_multi_match_list_into(mm: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_indices_into(mm: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, index_offset: u32, out: *mut *mut FzbMatchIndices,
+                                         out_len: *mut usize, out_positions: *mut *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_device(mm: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, dev_out: *mut FzbMatch, capacity: usize,
+                                   dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_multi_matcher_set_patterns(mm: *mut c_void, patterns: *const FzbPattern, n_patterns: usize) -> c_int;
+    fn fzb_multi_matcher_set_config(mm: *mut c_void, cfg: *const FzbConfig) -> c_int;
+    fn fzb_multi_matcher_reserve(mm: *mut c_void, c: *const c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_matcher_clone(mm: *const c_void, out: *mut *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_parallel(mm: *mut c_void, c: *const c_void, threads: usize, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    fn fzb_multi_match_list_parallel_sharded(mm: *mut c_void, sc: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    fn fzb_multi_match_list_parallel_rccl(mm: *mut c_void, shard: *const c_void, index_offset: u32, comm: *mut c_void, flags: c_int, out: *mut *mut FzbMatch,
+                                          out_len: *mut usize) -> c_int;
+    fn fzb_multi_matcher_shard_report(mm: *const c_void) -> *const c_char;
 }
 
 /// The reference panics (`assert!`) where the ABI returns FZB_ERR_PANIC, with the same text; every other code is a backend
@@ -186,6 +227,50 @@ fn c_config(config: &Config, sort: i32) -> FzbConfig {
     }
 }
 
+/// `SortStrategy` as the header's FZB_SORT_* value (src/lib.rs:311-326)
+fn sort_code(sort: &SortStrategy) -> i32 {
+    match sort {
+        SortStrategy::ScoreThenIndexAsc => 0,
+        SortStrategy::ScoreThenIndexDesc => 1,
+        SortStrategy::IndexAsc => 2,
+        SortStrategy::IndexDesc => 3,
+    }
+}
+
+/// `&[Pattern]` -> the header's array; the needles are borrowed from `patterns` for the duration of the call
+fn c_patterns(patterns: &[Pattern]) -> Vec<FzbPattern> {
+    let zero = FzbScoring {
+        match_score: 0, mismatch_penalty: 0, gap_open_penalty: 0, gap_extend_penalty: 0, prefix_bonus: 0, capitalization_bonus: 0, matching_case_bonus: 0,
+        exact_match_bonus: 0, delimiter_bonus: 0,
+    };
+    patterns
+        .iter()
+        .map(|p| {
+            let pc = &p.config;
+            FzbPattern {
+                needle_utf8: p.needle.as_ptr(),
+                needle_len: p.needle.len(),
+                negated: p.negated as i32,
+                has_max_typos: pc.max_typos.is_some() as i32,
+                max_typos: pc.max_typos.map(|t| t as i32).unwrap_or(0),
+                casing: pc.casing.map(|c| match c { CaseMatching::Ignore => 0, CaseMatching::Smart => 1, CaseMatching::Respect => 2 }).unwrap_or(-1),
+                unicode: pc.unicode.map(|u| match u { UnicodeMatching::Ignore => 0, UnicodeMatching::Smart => 1, UnicodeMatching::Always => 2 }).unwrap_or(-1),
+                has_scoring: pc.scoring.is_some() as i32,
+                scoring: pc
+                    .scoring
+                    .as_ref()
+                    .map(|s| FzbScoring {
+                        match_score: s.match_score, mismatch_penalty: s.mismatch_penalty, gap_open_penalty: s.gap_open_penalty, gap_extend_penalty: s.gap_extend_penalty,
+                        prefix_bonus: s.prefix_bonus, capitalization_bonus: s.capitalization_bonus, matching_case_bonus: s.matching_case_bonus,
+                        exact_match_bonus: s.exact_match_bonus, delimiter_bonus: s.delimiter_bonus,
+                    })
+                    .unwrap_or(zero),
+                matching: pc.matching.map(|m| m as i32).unwrap_or(-1),
+            }
+        })
+        .collect()
+}
+
 fn copy_out(out: *mut FzbMatch, n: usize, matches: &mut Vec<Match>) {
     // Rust's `Match` layout is unspecified (not repr(C)): copy field-wise
     matches.extend(unsafe { std::slice::from_raw_parts(out, n) }.iter().map(|m| Match { index: m.index, score: m.score, exact: m.exact != 0 }));
@@ -196,13 +281,7 @@ impl MatcherHip {
     /// `MatcherImpl::new` (src/matcher/algo.rs:57-71).  `sort`: `Specialized::match_list` never sorts, so the backend variant is
     /// built with IndexAsc; the resident / sharded entry points below honour `config.sort` themselves.
     pub fn build(needle: &str, config: &Config) -> Self {
-        let sort = match config.sort {
-            SortStrategy::ScoreThenIndexAsc => 0,
-            SortStrategy::ScoreThenIndexDesc => 1,
-            SortStrategy::IndexAsc => 2,
-            SortStrategy::IndexDesc => 3,
-        };
-        let cfg = c_config(config, sort);
+        let cfg = c_config(config, sort_code(&config.sort));
         let mut handle = std::ptr::null_mut();
         check(unsafe { fzb_matcher_create(&cfg, needle.as_ptr(), needle.len(), &mut handle) });
         Self { handle }
@@ -285,6 +364,92 @@ impl Drop for MatcherHip {
 }
 // `Matcher: Send` in the reference; the handle owns device buffers and is used from one thread at a time (`&mut self`)
 unsafe impl Send for MatcherHip {}
+
+/// `Matcher::from_patterns(&patterns, &config)` (src/matcher/mod.rs:95-111): the AND / NOT composition of src/matcher/multi.rs on the
+/// GPU.  Interactive use keeps ONE of these and calls `set_patterns` with the re-parsed query on every keystroke: the sub-matchers are
+/// rebuilt in place and their device buffers kept (after `reserve`, a keystroke allocates nothing).
+pub struct HipMultiMatcher {
+    handle: *mut c_void,
+}
+
+impl HipMultiMatcher {
+    pub fn build(patterns: &[Pattern], config: &Config) -> Self {
+        let cfg = c_config(config, sort_code(&config.sort));
+        let pats = c_patterns(patterns);
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { fzb_multi_matcher_create(&cfg, pats.as_ptr(), pats.len(), &mut handle) });
+        Self { handle }
+    }
+
+    /// `Matcher::set_patterns` (src/matcher/mod.rs:170-176): skipped when the patterns are the same.
+    pub fn set_patterns(&mut self, patterns: &[Pattern]) {
+        let pats = c_patterns(patterns);
+        check(unsafe { fzb_multi_matcher_set_patterns(self.handle, pats.as_ptr(), pats.len()) });
+    }
+
+    /// `Matcher::set_config` (src/matcher/mod.rs:154-162): a change of `sort` alone rebuilds nothing.
+    pub fn set_config(&mut self, config: &Config) {
+        let cfg = c_config(config, sort_code(&config.sort));
+        check(unsafe { fzb_multi_matcher_set_config(self.handle, &cfg) });
+    }
+
+    /// Every device buffer queries over `corpus` can need, allocated now.
+    pub fn reserve(&mut self, corpus: &HipCorpus) {
+        check(unsafe { fzb_multi_matcher_reserve(self.handle, corpus.handle) });
+    }
+
+    /// compiled (non-empty) patterns
+    pub fn len(&self) -> usize {
+        unsafe { fzb_multi_matcher_len(self.handle) }
+    }
+
+    /// `Matcher::match_list_into` over the compiled patterns (src/matcher/mod.rs:373-392): input order, the list uploaded for this call.
+    pub fn match_list<H: AsRef<str>>(&mut self, haystacks: &[H], haystack_index_offset: u32, matches: &mut Vec<Match>) {
+        let corpus = HipCorpus::new(haystacks);
+        let (mut out, mut n) = (std::ptr::null_mut(), 0usize);
+        check(unsafe { fzb_multi_match_list_into(self.handle, corpus.handle, 0, corpus.len, haystack_index_offset, &mut out, &mut n) });
+        copy_out(out, n, matches);
+    }
+
+    /// `Matcher::match_list` over a resident list, ordered per `config.sort` on the device.
+    pub fn match_list_resident(&mut self, corpus: &HipCorpus) -> Vec<Match> {
+        let (mut out, mut n) = (std::ptr::null_mut(), 0usize);
+        check(unsafe { fzb_multi_match_list(self.handle, corpus.handle, &mut out, &mut n) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        v
+    }
+
+    /// `match_list_parallel` with the GPUs of the node as workers: the whole composition per shard on its GPU, gathered and ordered once
+    /// on the current device.  Same result as `match_list_resident` on the unsharded list.
+    pub fn match_list_parallel_sharded(&mut self, corpus: &ShardedCorpus) -> Vec<Match> {
+        let (mut out, mut n) = (std::ptr::null_mut(), 0usize);
+        check(unsafe { fzb_multi_match_list_parallel_sharded(self.handle, corpus.handle, &mut out, &mut n) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        v
+    }
+
+    /// One process per GPU (see `MatcherHip::match_list_parallel_rccl`): this rank's composition is its run.  Collective; a rank that fails
+    /// before the exchange makes every rank fail with its error.
+    pub fn match_list_parallel_rccl(&mut self, shard: &HipCorpus, index_offset: u32, comm: &mut ShardComm, to_all: bool) -> Vec<Match> {
+        let (mut out, mut n) = (std::ptr::null_mut(), 0usize);
+        check(unsafe { fzb_multi_match_list_parallel_rccl(self.handle, shard.handle, index_offset, comm.handle, to_all as c_int, &mut out, &mut n) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        v
+    }
+
+    pub fn shard_report(&self) -> String {
+        unsafe { std::ffi::CStr::from_ptr(fzb_multi_matcher_shard_report(self.handle)) }.to_string_lossy().into_owned()
+    }
+}
+impl Drop for HipMultiMatcher {
+    fn drop(&mut self) {
+        unsafe { fzb_multi_matcher_free(self.handle) }
+    }
+}
+unsafe impl Send for HipMultiMatcher {}
 
 
 /// The communicator of the one-process-per-GPU form (`fzb_shard_comm`: an RCCL communicator, a stream and the exchange buffers on the
