@@ -120,6 +120,7 @@ SYMBOLS = [
     "fzb_shard_comm_last_exchange",
     "fzb_multi_matcher_set_patterns", "fzb_multi_matcher_set_config", "fzb_multi_matcher_reserve", "fzb_multi_matcher_clone", "fzb_multi_match_list_parallel",
     "fzb_multi_match_list_parallel_sharded", "fzb_multi_match_list_parallel_rccl", "fzb_multi_matcher_shard_report", "fzb_debug_device_allocs",
+    "fzb_match_list_top", "fzb_match_list_top_device", "fzb_multi_match_list_top", "fzb_match_list_top_sharded", "fzb_multi_match_list_top_sharded",
 ]
 
 
@@ -205,6 +206,11 @@ def lib():
         l.fzb_multi_matcher_shard_report.argtypes = [C.c_void_p]
         l.fzb_multi_matcher_shard_report.restype = C.c_char_p
         l.fzb_debug_device_allocs.argtypes = [C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_multi_match_list_top.argtypes = l.fzb_match_list_top.argtypes
+        l.fzb_match_list_top_sharded.argtypes = l.fzb_match_list_top.argtypes
+        l.fzb_multi_match_list_top_sharded.argtypes = l.fzb_match_list_top.argtypes
         _lib = l
     return _lib
 
@@ -225,6 +231,13 @@ def pack(haystacks):
     ends = np.cumsum(np.fromiter((len(b) for b in bs), dtype=np.uint64, count=len(bs)), dtype=np.uint64) if bs else np.zeros(0, np.uint64)
     data = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy()
     return data, ends
+
+
+def _top(fn, handle, target, limit, copy):
+    """A top-`limit` entry point of the C ABI -> (records, found)."""
+    out, n, found = C.c_void_p(), C.c_size_t(), C.c_uint64()
+    _check(fn(handle, target, limit, C.byref(out), C.byref(n), C.byref(found)))
+    return _take(out, n, copy), found.value
 
 
 def _take(out, n, copy=True):
@@ -499,6 +512,15 @@ class MultiMatcher(_IterApi):
         _check(lib().fzb_multi_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
         return _take(out, n, copy)
 
+    def match_list_top(self, haystacks, limit, copy=True):
+        """(`match_list(haystacks)[:limit]`, len(`match_list(haystacks)`)), selected and ordered on the device (see `Matcher.match_list_top`)."""
+        cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
+        return _top(lib().fzb_multi_match_list_top, self.h, cp.h, limit, copy)
+
+    def match_list_top_sharded(self, sharded, limit, copy=True):
+        """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
+        return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
+
     def match_list_indices(self, haystacks, selection=None):
         """`Matcher::match_list_indices` over the compiled patterns (`match_one_indices_multi`, src/matcher/multi.rs:56-82); see
         `Matcher.match_list_indices` for `selection`."""
@@ -601,6 +623,21 @@ class Matcher(_IterApi):
         out, n = C.c_void_p(), C.c_size_t()
         _check(lib().fzb_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
         return _take(out, n, copy)
+
+    def match_list_top(self, haystacks, limit, copy=True):
+        """(`match_list(haystacks)[:limit]`, len(`match_list(haystacks)`)): the threshold score, the records of the head (ties at the cut
+        as the stable sort breaks them) and their order are found on the device; only `limit` records are copied.  The reference has no
+        such call - its caller truncates the Vec `match_list` returns (src/matcher/mod.rs:212-222)."""
+        return _top(lib().fzb_match_list_top, self.h, self._corpus(haystacks).h, limit, copy)
+
+    def match_list_top_device(self, corpus, limit, dev_out_ptr, capacity, dev_count_ptr, stream=0):
+        """`match_list_top` with the result left in HBM: `capacity` >= min(limit, len(corpus)) records at `dev_out_ptr`, two count words
+        (records written, matches found) at `dev_count_ptr`; asynchronous on `stream`."""
+        _check(lib().fzb_match_list_top_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_count_ptr, stream))
+
+    def match_list_top_sharded(self, sharded, limit, copy=True):
+        """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
+        return _top(lib().fzb_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
     def match_list_parallel(self, haystacks, threads):
         """`Matcher::match_list_parallel` (src/matcher/parallel.rs:18-89); identical result for every thread count."""

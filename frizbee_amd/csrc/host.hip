@@ -855,6 +855,7 @@ void fzb_matcher_free(fzb_matcher* m) {
     free_workspace(m->ws);
     if (m->out_dev) (void)hipFree(m->out_dev);
     if (m->count_dev) (void)hipFree(m->count_dev);
+    if (m->top_words) (void)hipFree(m->top_words);
     for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos})
         if (p) (void)hipFree(p);
     for (auto& tr : m->evring)
@@ -866,6 +867,7 @@ void fzb_matcher_free(fzb_matcher* m) {
     if (m->long_blob_dev) (void)hipFree(m->long_blob_dev);
     if (m->long_scratch) (void)hipFree(m->long_scratch);
     if (m->fetch.count_host) (void)hipHostFree(m->fetch.count_host);
+    if (m->fetch_top.count_host) (void)hipHostFree(m->fetch_top.count_host);
     if (m->shard_workers) fzb_shard_workers_free(m->shard_workers);  // joins the worker threads before their clones go
     m->shard_workers = nullptr;
     if (m->shard_stream) (void)hipStreamDestroy(m->shard_stream);
@@ -1759,6 +1761,7 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && m->nd.max_typos < 0 && (rc = ensure_aux_stream(m))) return rc;  // whole-haystack windows: the wide ones on the second stream
     if ((rc = fzb_ensure_out_staging(m, n))) return rc;
     if ((rc = ensure_sort_buffers(m, n))) return rc;
+    if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, 32, hipHostMallocDefault));  // (a top query's pinned count words)
     return FZB_OK;
 }
 
@@ -1821,12 +1824,17 @@ int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, s
 // `cap` records and says where the producer should write them (`plan.in`): with a single radix pass that is the sort's SECOND buffer and
 // the pass scatters into the caller's array - no copy back.  fzb_order_finish launches reverse / sort on `stream`; the record count is
 // read from device memory.  Producers: the pipeline (above), the concatenation of per-shard runs (host_shard.hip).
-int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p) {
+// What `match_list`'s post-step does for this matcher: the ONE place that decides it (fzb_order_begin and the top-`limit` selection both ask here - a
+// `one_pass` that is wrongly true would make the selection read the low byte only)
+void fzb_order_flags(const fzb_matcher* m, bool* reversed, bool* by_score, bool* one_pass) {
     const int sort = m->config.sort;
-    p->reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;          // src/matcher/mod.rs:215-217
-    p->by_score = sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;  // :218-220
+    *reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;          // src/matcher/mod.rs:215-217
+    *by_score = sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;  // :218-220
     // one radix pass is enough when no score can reach 256 (Scoring::guard's bound on the matrix + the exact-match bonus added after it)
-    p->one_pass = !m->sum_scores && !m->literal_mode && max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus < 256;
+    *one_pass = !m->sum_scores && !m->literal_mode && max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus < 256;
+}
+int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p) {
+    fzb_order_flags(m, &p->reversed, &p->by_score, &p->one_pass);
     p->via_tmp = p->by_score && p->one_pass && cap != 0;
     p->in = dev_out;
     if (p->by_score) {
@@ -2498,6 +2506,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = multi_ensure_out(mm, n)) || (rc = multi_ensure_sort(mm, n))) return rc;
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
+    if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
     return FZB_OK;
 }
 
@@ -2526,6 +2535,7 @@ void fzb_multi_matcher_free(fzb_multi_matcher* mm) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (mm->fetch.count_host) (void)hipHostFree(mm->fetch.count_host);
+    if (mm->fetch_top.count_host) (void)hipHostFree(mm->fetch_top.count_host);
     delete mm;
 }
 
@@ -2717,6 +2727,109 @@ int fzb_multi_match_list_into(fzb_multi_matcher* mm, const fzb_corpus* c, size_t
     int rc = fzb_multi_match_list_device(mm, c, first, count, index_offset, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
     if (rc) return rc;
     return fetch_records(mm->fetch, mm->out_dev, mm->count_dev, mm->out_cap, out, out_len);
+}
+
+// ---- top-`limit` queries ------------------------------------------------------------------------------------------------------
+// The reference has no such call: `match_list` returns a Vec the caller truncates.  top(limit) = the first min(limit, found) records of
+// what `match_list` returns (reverse for the *Desc strategies, then the stable radix sort: src/matcher/mod.rs:215-221, src/sort.rs:6-40),
+// ties at the cut included, and `found` = the length of the full list.  The pipeline writes its index-ordered records into the sort's
+// second buffer, the selection stage (kernels_topk.hip) keeps the records of the head in record order, the ordering step sorts those.
+}  // extern "C"
+int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap) { return ensure_sort_buffers(m, cap); }
+// The two count words and the records of a top result -> the host with ONE wait: at most `max_records` = min(limit, n) records exist, so
+// a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind the count, filled or not.  Beyond that the bound says little - a
+// `limit` at or above the list's length bounds the copy by n records, 80 MB on a 10 M list of which 4 MB exist: 1.5 ms at the 53 GB/s the
+// copy reaches against the 0.24 ms the call takes (profiles/topk.txt) - so such a head takes fzb_fetch_records' guess (the previous
+// result's size; a grown or first result costs a second copy and wait, as in fzb_match_list).  128 KB: copying 10 000 records whole was
+// measured at 5 us over copying 100 (C2, top(10 000) - top(100), their sort included), under the 10-20 us a second wait costs.
+#define FZB_TOP_COPY_WHOLE 16384
+int fzb_fetch_top(FetchHint& h, const void* dev_records, const u32* dev_words, size_t max_records, hipStream_t st, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (max_records <= FZB_TOP_COPY_WHOLE) h.last = max_records;
+    int rc = fzb_fetch_records(h, dev_records, dev_words, 0, max_records, st, out, out_len);
+    if (rc) return rc;
+    if (out_found) *out_found = h.count_host[1];
+    return FZB_OK;
+}
+// CompiledPatterns::Empty: every haystack matches with score 0, reversed for the *Desc strategies, never sorted (mod.rs:215-220, 381-384)
+int fzb_empty_pattern_top(size_t n, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    const size_t want = std::min(limit, n);
+    fzb_match* r = (fzb_match*)malloc(std::max<size_t>(want, 1) * sizeof(fzb_match));
+    if (!r) return fail(FZB_ERR_INVALID, "out of memory");
+    for (size_t i = 0; i < want; i++) r[i] = fzb_match{(uint32_t)(reversed ? n - 1 - i : i), 0, 0, 0};
+    *out = r;
+    *out_len = want;
+    if (out_found) *out_found = n;
+    return FZB_OK;
+}
+extern "C" {
+
+int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
+    if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
+        return FZB_OK;
+    }
+    int rc;
+    // (the range workspace first: growing it releases every workspace buffer, the sort's included)
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, n, st, true)) || (rc = ensure_sort_buffers(m, n))) return rc;
+    if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
+    bool reversed, by_score, one_pass;
+    fzb_order_flags(m, &reversed, &by_score, &one_pass);
+    Workspace& w = m->ws;
+    u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
+    if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort_tmp, n, raw_count, stream))) return rc;
+    const u32 ntiles_cap = (u32)(w.sort_cap / 2048 + 2);
+    const int grid = m->lc.num_cus * 2;
+    HIPCHK(fzb_launch_topk_select(w.sort_tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort_hist, ntiles_cap, grid, st));
+    fzb_launch_sort((fzb_match_rec*)dev_out, w.sort_tmp, dev_count, w.sort_hist, ntiles_cap, reversed, by_score, grid, st, one_pass ? 1 : 2);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
+int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (out_found) *out_found = 0;
+    const size_t n = c->dev.n;
+    if (m->empty) return fzb_empty_pattern_top(n, m->config.sort, limit, out, out_len, out_found);
+    if (n == 0) return FZB_OK;
+    const size_t want = std::min(limit, n);
+    if (int rc_ = fzb_ensure_out_staging(m, want)) return rc_;
+    int rc = fzb_match_list_top_device(m, c, limit, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr);
+    if (rc) return rc;
+    return fzb_fetch_top(m->fetch_top, m->out_dev, m->count_dev, want, nullptr, out, out_len, out_found);
+}
+
+int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (out_found) *out_found = 0;
+    const size_t n = c->dev.n;
+    if (n == 0) return FZB_OK;
+    const size_t want = std::min(limit, n);
+    int rc;
+    if ((rc = multi_ensure_out(mm, want)) || (rc = multi_ensure_sort(mm, n))) return rc;
+    u32* const raw_count = mm->count_dev + 4;
+    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort_tmp, n, raw_count, nullptr))) return rc;
+    const int sort = mm->config.sort;
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    const u32 ntiles_cap = (u32)(mm->sort_cap / 2048 + 2);
+    const int grid = mm->num_cus * 2;
+    // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
+    HIPCHK(fzb_launch_topk_select(mm->sort_tmp, raw_count, (u32)n, (u32)want, by_score, reversed, 0, mm->out_dev, (u32)want, mm->count_dev, mm->sort_hist, ntiles_cap, grid, nullptr));
+    fzb_launch_sort(mm->out_dev, mm->sort_tmp, mm->count_dev, mm->sort_hist, ntiles_cap, reversed, by_score, grid, nullptr);
+    HIPCHK(hipGetLastError());
+    return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
 }
 
 void fzb_matches_free(fzb_match* p) {

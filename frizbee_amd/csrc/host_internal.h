@@ -80,6 +80,7 @@ struct fzb_matcher {
     size_t out_cap = 0;
     u32* count_dev = nullptr;
     FetchHint fetch;
+    FetchHint fetch_top;  // the top-`limit` entry points' own (their result sizes say nothing about the next full list's)
     // fzb_match_list_indices: the selection (+ its length), the positions (`stride` per record) and their counts
     u32* trace_sel = nullptr;
     u32* trace_pos = nullptr;
@@ -111,6 +112,9 @@ struct fzb_matcher {
     std::string shard_report;
     // an ordering host of summed multi-pattern scores (fzb_multi_matcher::order): the radix sort always takes both passes
     bool sum_scores = false;
+    // sharded top-`limit` queries, on the root: the count pairs of the shards whose selected runs are copied (two words per shard)
+    u32* top_words = nullptr;
+    size_t top_words_cap = 0;
 };
 
 // ---- multi-pattern composition (src/matcher/multi.rs; host.hip) ----------------------------------------------------------
@@ -141,6 +145,7 @@ struct fzb_multi_matcher {
     u32* sort_hist = nullptr;
     size_t sort_cap = 0;
     FetchHint fetch;
+    FetchHint fetch_top;  // the top-`limit` entry points' own (their result sizes say nothing about the next full list's)
     // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
@@ -163,6 +168,12 @@ int fzb_bind_device(fzb_matcher* m);
 hipError_t fzb_stream_wait(hipStream_t st);
 int fzb_fetch_records(FetchHint& h, const void* dev_records, const u32* dev_words, int n_word, size_t capacity, hipStream_t st, fzb_match** out, size_t* out_len);
 int fzb_ensure_out_staging(fzb_matcher* m, size_t count);
+// top-`limit` queries (host.hip): the ordering flags of a matcher as fzb_order_begin decides them, the sort's buffers for `cap` records
+// (the selection stage's input and scratch), the one-wait copy of (count pair, <= max_records records), the no-pattern result
+void fzb_order_flags(const fzb_matcher* m, bool* reversed, bool* by_score, bool* one_pass);
+int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap);
+int fzb_fetch_top(FetchHint& h, const void* dev_records, const u32* dev_words, size_t max_records, hipStream_t st, fzb_match** out, size_t* out_len, uint64_t* out_found);
+int fzb_empty_pattern_top(size_t n, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 // the ordering post-step of `match_list` on the device (host.hip, next to fzb_sorted_range_device)
 struct OrderPlan {
     bool reversed, by_score, one_pass, via_tmp;
@@ -180,6 +191,7 @@ void fzb_shard_workers_free(void* workers);  // host_shard.hip
 // index-ordered records and their two count words into carrier->out_dev / carrier->count_dev (capacity carrier->out_cap) on `stream`.
 using ShardRunFn = std::function<int(size_t g, fzb_matcher* carrier, const fzb_corpus* shard, uint32_t index_offset, hipStream_t stream)>;
 int fzb_sharded_query(fzb_matcher* root, const fzb_sharded_corpus* sc, const ShardRunFn& run, fzb_match** out, size_t* out_len);
+int fzb_sharded_top_query(fzb_matcher* root, const fzb_sharded_corpus* sc, const ShardRunFn& run, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 // CompiledPatterns::Empty over n haystacks: every index from index_offset, score 0, reversed for the *Desc strategies, never sorted (host list)
 int fzb_empty_pattern_list(size_t n, uint32_t index_offset, int sort, fzb_match** out, size_t* out_len);
 // the multi matcher's ordering host (created on first use, host.hip)

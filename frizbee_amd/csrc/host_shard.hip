@@ -294,22 +294,61 @@ int fzb_empty_pattern_list(size_t n, uint32_t index_offset, int sort, fzb_match*
     return FZB_OK;
 }
 
-// The query of fzb_match_list_parallel_sharded / fzb_multi_match_list_parallel_sharded: `m` is the root's state (ordering, staging, the
-// shard clones that carry every shard's stream and run, workers, peer decisions, report); `run` produces shard g's run into its carrier.
-int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardRunFn& run, fzb_match** out, size_t* out_len) {
-    *out = nullptr;
-    *out_len = 0;
+// The pieces the two sharded drivers (the full list, the top-`limit` form) share ------------------------------------------------------
+// a clone's stream, event and pinned count words, created by the shard's worker on the shard's device at the clone's first query
+static int shard_clone_state(fzb_matcher* cm, int device) {
+    if (cm->shard_device >= 0) return FZB_OK;
+    HIPCHK(hipStreamCreateWithFlags(&cm->shard_stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&cm->shard_event, hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void**)&cm->shard_count_host, 16, hipHostMallocDefault));
+    cm->shard_device = device;
+    return FZB_OK;
+}
+// job(g) for every shard: by the calling thread one after the other, or by the matcher's persistent workers
+static int shard_dispatch(fzb_matcher* m, size_t ns, bool inline_enqueue, const std::function<int(size_t)>& job) {
+    if (inline_enqueue) {
+        int rc = FZB_OK;
+        for (size_t g = 0; g < ns && !rc; g++) {
+            rc = job(g);
+            if (rc) rc = fzb_fail(rc, "shard " + std::to_string(g) + ": " + fzb_last_error());
+        }
+        return rc;
+    }
+    ShardWorkers* pool = (ShardWorkers*)m->shard_workers;
+    if (!pool || pool->size() < ns) {
+        delete pool;
+        m->shard_workers = pool = new ShardWorkers(ns);
+    }
+    return pool->run(ns, job);
+}
+// a failure after the shards were started: what they have in flight writes into this matcher's buffers, so it is waited for before the
+// caller can retry or free anything (the message of the failure is kept)
+static int shard_drain(fzb_matcher* m, const std::vector<u8>& recorded, int code) {
+    const std::string msg = fzb_last_error();
+    for (size_t g = 0; g < recorded.size(); g++)
+        if (recorded[g]) (void)hipEventSynchronize(m->shard_clones[g]->shard_event);
+    (void)hipStreamSynchronize(m->shard_stream);
+    (void)hipGetLastError();
+    return fzb_fail(code, msg);
+}
+// the root's stream waits for every shard that recorded its event; fzb_last_counters on the parent = the sum over the shards
+static int shard_join(fzb_matcher* m, const std::vector<u8>& recorded) {
+    u32 agg[4] = {0, 0, 0, 0};
+    for (size_t g = 0; g < recorded.size(); g++) {
+        if (recorded[g]) {
+            hipError_t e_ = hipStreamWaitEvent(m->shard_stream, m->shard_clones[g]->shard_event, 0);
+            if (e_ != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e_));
+        }
+        for (int k = 0; k < 4; k++) agg[k] += m->shard_clones[g]->last_counters[k];
+    }
+    memcpy(m->last_counters, agg, sizeof(agg));
+    return FZB_OK;
+}
+
+// One clone of the matcher per shard and the peer-access decisions of a sharded query (the full-list form and the top form share them)
+static int shard_prepare(fzb_matcher* m, const fzb_sharded_corpus* sc, int root) {
     const size_t ns = sc->shard.size();
-    // The ROOT: the device that is current on the calling thread.  It receives every shard's run and orders the whole list once.
-    int rc = fzb_bind_device(m);
-    if (rc) return rc;
-    const int root = m->device;
-    if (!m->shard_stream) HIPCHK(hipStreamCreateWithFlags(&m->shard_stream, hipStreamNonBlocking));
-    if (sc->n == 0) return FZB_OK;
-    if ((rc = fzb_ensure_out_staging(m, sc->n))) return rc;
-    OrderPlan plan;
-    if ((rc = fzb_order_begin(m, sc->n, m->out_dev, &plan))) return rc;
-    fzb_match_rec* const gather = plan.in;  // the concatenation of the runs (the sort's second buffer when one radix pass orders it)
+    int rc;
     // one clone of the matcher per shard (host work only; its device state is created by the shard's worker on the shard's device and
     // kept across queries and across fzb_matcher_set_pattern / set_config).  A clone follows its shard to another device: its device
     // state is released where it lives and built again on first use.
@@ -353,6 +392,42 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
         (void)hipSetDevice(root);
         m->shard_peers.push_back({root, d, state});
     }
+    return FZB_OK;
+}
+
+// how every run travelled (fzb_matcher_shard_report)
+static void shard_write_report(fzb_matcher* m, const fzb_sharded_corpus* sc, int root, const char* gather) {
+    const size_t ns = sc->shard.size();
+    std::string rep = "root device " + std::to_string(root) + "; gather " + gather;
+    for (size_t g = 0; g < ns; g++) {
+        const int d = sc->device[g];
+        rep += "; shard " + std::to_string(g) + " on device " + std::to_string(d) + ": ";
+        if (d == root) { rep += "same device"; continue; }
+        int state = 0;
+        for (const auto& pr : m->shard_peers)
+            if (pr[0] == root && pr[1] == d) state = pr[2];
+        rep += state ? "peer access enabled (device to device over xGMI)" : "peer access REFUSED by the runtime (hipMemcpyPeerAsync stages the run through host memory)";
+    }
+    m->shard_report = rep;
+}
+
+// The query of fzb_match_list_parallel_sharded / fzb_multi_match_list_parallel_sharded: `m` is the root's state (ordering, staging, the
+// shard clones that carry every shard's stream and run, workers, peer decisions, report); `run` produces shard g's run into its carrier.
+int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardRunFn& run, fzb_match** out, size_t* out_len) {
+    *out = nullptr;
+    *out_len = 0;
+    const size_t ns = sc->shard.size();
+    // The ROOT: the device that is current on the calling thread.  It receives every shard's run and orders the whole list once.
+    int rc = fzb_bind_device(m);
+    if (rc) return rc;
+    const int root = m->device;
+    if (!m->shard_stream) HIPCHK(hipStreamCreateWithFlags(&m->shard_stream, hipStreamNonBlocking));
+    if (sc->n == 0) return FZB_OK;
+    if ((rc = fzb_ensure_out_staging(m, sc->n))) return rc;
+    OrderPlan plan;
+    if ((rc = fzb_order_begin(m, sc->n, m->out_dev, &plan))) return rc;
+    fzb_match_rec* const gather = plan.in;  // the concatenation of the runs (the sort's second buffer when one radix pass orders it)
+    if ((rc = shard_prepare(m, sc, root))) return rc;
     // How the runs reach the root.  PULL (every shard lives on the root device - one GPU holding several shards): the workers only enqueue
     // their pipelines; the root's stream waits for them and ONE kernel concatenates the runs, reading their lengths on the device - no
     // host round trip before the final list.  COPY (shards on other devices): each worker reads its count back (8 bytes) and copies its
@@ -380,12 +455,7 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
         const size_t count = (size_t)c->dev.n;
         HIPCHK(hipSetDevice(sc->device[g]));
         fzb_matcher* cm = m->shard_clones[g];
-        if (cm->shard_device < 0) {
-            HIPCHK(hipStreamCreateWithFlags(&cm->shard_stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&cm->shard_event, hipEventDisableTiming));
-            HIPCHK(hipHostMalloc((void**)&cm->shard_count_host, 16, hipHostMallocDefault));
-            cm->shard_device = sc->device[g];
-        }
+        if (int rc_i = shard_clone_state(cm, sc->device[g])) return rc_i;
         int rc_ = fzb_ensure_out_staging(cm, count);
         if (rc_) return rc_;
         // the shard's records in INDEX order, numbered from the shard's first index (what a worker of match_list_parallel pushes,
@@ -421,56 +491,16 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
     // Shards that share the root device are enqueued by the CALLING thread, one after the other: launches from several host threads onto
     // one device serialise inside the runtime anyway (measured with 8 shards on one GPU: 0.35 ms through the workers, see bench.py
     // `sharded`), and nothing waits between them in the pull form.  Shards on other devices go through their workers.
-    if (inline_enqueue) {
-        rc = FZB_OK;
-        for (size_t g = 0; g < ns && !rc; g++) {
-            rc = shard_job(g);
-            if (rc) rc = fzb_fail(rc, "shard " + std::to_string(g) + ": " + fzb_last_error());
-        }
-    } else {
-        ShardWorkers* pool = (ShardWorkers*)m->shard_workers;
-        if (!pool || pool->size() < ns) {
-            delete pool;
-            m->shard_workers = pool = new ShardWorkers(ns);
-        }
-        rc = pool->run(ns, shard_job);
-    }
+    rc = shard_dispatch(m, ns, inline_enqueue, shard_job);
     (void)hipSetDevice(root);
     // Every failure from here on leaves through `drained`: the copies (and pipelines) the shards have in flight write into this matcher's
     // buffers, so they are waited for before the caller can retry or free anything (the message of the failure is kept)
-    auto drained = [&](int code) -> int {
-        const std::string msg = fzb_last_error();
-        for (size_t g = 0; g < ns; g++)
-            if (copied[g]) (void)hipEventSynchronize(m->shard_clones[g]->shard_event);
-        (void)hipStreamSynchronize(m->shard_stream);
-        (void)hipGetLastError();
-        return fzb_fail(code, msg);
-    };
+    auto drained = [&](int code) -> int { return shard_drain(m, copied, code); };
     if (rc) return drained(rc);
-    {   // how every run travelled (fzb_matcher_shard_report)
-        std::string rep = "root device " + std::to_string(root) + "; gather " + (pull ? "pull (one concatenation kernel reads the runs)" : "copy (count to the host, run copied to its place)");
-        for (size_t g = 0; g < ns; g++) {
-            const int d = sc->device[g];
-            rep += "; shard " + std::to_string(g) + " on device " + std::to_string(d) + ": ";
-            if (d == root) { rep += "same device"; continue; }
-            int state = 0;
-            for (const auto& pr : m->shard_peers)
-                if (pr[0] == root && pr[1] == d) state = pr[2];
-            rep += state ? "peer access enabled (device to device over xGMI)" : "peer access REFUSED by the runtime (hipMemcpyPeerAsync stages the run through host memory)";
-        }
-        m->shard_report = rep;
-    }
+    shard_write_report(m, sc, root, pull ? "pull (one concatenation kernel reads the runs)" : "copy (count to the host, run copied to its place)");
     size_t total = 0;
-    u32 agg[4] = {0, 0, 0, 0};
-    for (size_t g = 0; g < ns; g++) {
-        total += (size_t)std::max<int64_t>(counts[g].load(std::memory_order_acquire), 0);
-        if (copied[g]) {
-            hipError_t e_ = hipStreamWaitEvent(m->shard_stream, m->shard_clones[g]->shard_event, 0);
-            if (e_ != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e_)));
-        }
-        for (int k = 0; k < 4; k++) agg[k] += m->shard_clones[g]->last_counters[k];
-    }
-    memcpy(m->last_counters, agg, sizeof(agg));  // fzb_last_counters on the parent = the sum over the shards
+    for (size_t g = 0; g < ns; g++) total += (size_t)std::max<int64_t>(counts[g].load(std::memory_order_acquire), 0);
+    if ((rc = shard_join(m, copied))) return drained(rc);
     if (pull) {
         std::vector<const void*> runs(ns);
         std::vector<const uint32_t*> cnts(ns);
@@ -504,6 +534,112 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
     return FZB_OK;
 }
 
+// The top-`limit` form of the query above.  Every shard runs its pipeline and the selection stage (kernels_topk.hip) locally: at most
+// min(limit, shard length) records, still in index order, picked by the global tie rule - so the head of the whole list is contained
+// in the union of the local heads.  Only those records reach the root: a shard on the root's device is read in place, any other copies
+// its slot and its count pair (no count is read back on the host: the slot has a fixed place).  The root concatenates the selected runs
+// in shard order, selects once more over at most shards x limit records, orders them and copies `limit` records to the host.
+int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardRunFn& run, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    *out = nullptr;
+    *out_len = 0;
+    if (out_found) *out_found = 0;
+    const size_t ns = sc->shard.size();
+    int rc = fzb_bind_device(m);
+    if (rc) return rc;
+    const int root = m->device;
+    if (!m->shard_stream) HIPCHK(hipStreamCreateWithFlags(&m->shard_stream, hipStreamNonBlocking));
+    if (sc->n == 0) return FZB_OK;
+    std::vector<size_t> slot(ns + 1, 0);  // shard g's selected records: at most slot[g + 1] - slot[g]
+    for (size_t g = 0; g < ns; g++) slot[g + 1] = slot[g] + std::min<size_t>(limit, (size_t)sc->shard[g]->dev.n);
+    const size_t cap = slot[ns];
+    if ((rc = fzb_ensure_out_staging(m, cap)) || (rc = fzb_ensure_sort_buffers(m, cap))) return rc;
+    if (m->top_words_cap < ns) {
+        if (m->top_words) (void)hipFree(m->top_words);
+        m->top_words = nullptr;
+        m->top_words_cap = 0;
+        HIPCHK(fzb_dev_alloc((void**)&m->top_words, ns * 8));
+        m->top_words_cap = ns;
+    }
+    if ((rc = shard_prepare(m, sc, root))) return rc;
+    bool reversed, by_score, one_pass;
+    fzb_order_flags(m, &reversed, &by_score, &one_pass);  // the root's: a carrier of a multi matcher's runs does not know that scores are sums
+    const bool copy_forced = fzb_knobs().shard_gather_copy;
+    bool all_local = !copy_forced;
+    for (size_t g = 0; g < ns; g++) all_local = all_local && sc->device[g] == root;
+    const bool inline_enqueue = all_local && fzb_knobs().shard_inline != 0;
+    const bool one_stream = inline_enqueue && ns == 1;
+    std::vector<u8> recorded(ns, 0);
+    auto shard_job = [&](size_t g) -> int {
+        const fzb_corpus* c = sc->shard[g];
+        const size_t count = (size_t)c->dev.n;
+        HIPCHK(hipSetDevice(sc->device[g]));
+        fzb_matcher* cm = m->shard_clones[g];
+        if (int rc_i = shard_clone_state(cm, sc->device[g])) return rc_i;
+        int rc_;
+        if ((rc_ = fzb_bind_device(cm)) || (rc_ = fzb_ensure_out_staging(cm, count))) return rc_;
+        hipStream_t st = one_stream ? m->shard_stream : cm->shard_stream;
+        if ((rc_ = run(g, cm, c, (uint32_t)sc->bounds[g], st))) return rc_;
+        // (behind the pipeline's own sizing: a workspace that grows releases the sort's buffers with it)
+        if ((rc_ = fzb_ensure_sort_buffers(cm, count))) return rc_;
+        const size_t keep = slot[g + 1] - slot[g];
+        fzb_match_rec* const sel = cm->ws.sort_tmp;
+        u32* const sel_count = cm->count_dev + 4;
+        HIPCHK(fzb_launch_topk_select(cm->out_dev, cm->count_dev, (u32)count, (u32)keep, by_score, reversed, one_pass, sel, (u32)keep, sel_count, cm->ws.sort_hist,
+                                      (u32)(cm->ws.sort_cap / 2048 + 2), cm->lc.num_cus * 2, st));
+        if (copy_forced || sc->device[g] != root) {  // the slot and its count pair travel to the root
+            if (sc->device[g] == root) {
+                if (keep) HIPCHK(hipMemcpyAsync(m->out_dev + slot[g], sel, keep * sizeof(fzb_match_rec), hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(m->top_words + 2 * g, sel_count, 8, hipMemcpyDeviceToDevice, st));
+            } else {
+                if (keep) HIPCHK(hipMemcpyPeerAsync(m->out_dev + slot[g], root, sel, sc->device[g], keep * sizeof(fzb_match_rec), st));
+                HIPCHK(hipMemcpyPeerAsync(m->top_words + 2 * g, root, sel_count, sc->device[g], 8, st));
+            }
+        }
+        if (one_stream) return FZB_OK;
+        HIPCHK(hipEventRecord(cm->shard_event, cm->shard_stream));
+        recorded[g] = 1;
+        return FZB_OK;
+    };
+    rc = shard_dispatch(m, ns, inline_enqueue, shard_job);
+    (void)hipSetDevice(root);
+    // every failure from here on waits for what the shards have in flight (it writes into this matcher's buffers)
+    auto drained = [&](int code) -> int { return shard_drain(m, recorded, code); };
+    if (rc) return drained(rc);
+    shard_write_report(m, sc, root, all_local ? "pull (one concatenation kernel reads the selected runs)"
+                                              : "copy (selected slots and their count pairs copied to the root, no count read back)");
+    if ((rc = shard_join(m, recorded))) return drained(rc);
+    hipStream_t st = m->shard_stream;
+    u32* words = m->count_dev;  // two alternating pairs (records, matches found) for the batches of FZB_MAX_RUNS runs; the result pair at [8]
+    const u32* base = nullptr;
+    u32* tot = words;
+    for (size_t g0 = 0; g0 < ns; g0 += FZB_MAX_RUNS) {
+        RunSet rs{};
+        rs.n = (int)std::min<size_t>(FZB_MAX_RUNS, ns - g0);
+        for (int k = 0; k < rs.n; k++) {
+            const size_t g = g0 + (size_t)k;
+            const bool local = !copy_forced && sc->device[g] == root;
+            rs.run[k] = local ? m->shard_clones[g]->ws.sort_tmp : m->out_dev + slot[g];
+            rs.count[k] = local ? m->shard_clones[g]->count_dev + 4 : m->top_words + 2 * g;
+            rs.cap[k] = (u32)(slot[g + 1] - slot[g]);
+        }
+        fzb_launch_topk_concat(rs, base, tot, m->ws.sort_tmp, (u32)cap, m->lc.num_cus * 2, st);
+        base = tot;
+        tot = tot == words ? words + 4 : words;
+    }
+    const size_t want = std::min(limit, cap);
+    const u32 ntiles_cap = (u32)(m->ws.sort_cap / 2048 + 2);
+    hipError_t e_sel = fzb_launch_topk_select(m->ws.sort_tmp, base, (u32)cap, (u32)want, by_score, reversed, one_pass, m->out_dev, (u32)want, words + 8, m->ws.sort_hist, ntiles_cap,
+                                              m->lc.num_cus * 2, st);
+    if (e_sel != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_sel)));
+    fzb_launch_sort(m->out_dev, m->ws.sort_tmp, words + 8, m->ws.sort_hist, ntiles_cap, reversed, by_score, m->lc.num_cus * 2, st, one_pass ? 1 : 2);
+    {
+        hipError_t e_ = hipGetLastError();
+        if (e_ != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_)));
+    }
+    rc = fzb_fetch_top(m->fetch_top, m->out_dev, words + 8, want, st, out, out_len, out_found);
+    return rc ? drained(rc) : FZB_OK;
+}
+
 extern "C" {
 
 int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
@@ -520,17 +656,10 @@ int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc
 
 const char* fzb_matcher_shard_report(const fzb_matcher* m) { return m ? m->shard_report.c_str() : ""; }
 
-// `Matcher::match_list_parallel` of a `from_patterns` matcher with one DEVICE per worker: the whole AND / NOT composition runs per shard
-// (the patterns are independent per haystack, so shard-local composition is exact) through a per-shard multi clone on the shard's
-// device, into the staging of the ordering host's shard clone; gather and ordering are fzb_match_list_parallel_sharded's.
-int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
-    if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    *out_len = 0;
-    if (mm->patterns.empty()) return fzb_empty_pattern_list(sc->n, 0, mm->config.sort, out, out_len);
-    fzb_matcher* root = nullptr;
-    int rc = fzb_multi_order_host(mm, &root);
-    if (rc) return rc;
+}  // extern "C"
+// one multi clone per shard of `sc` (the full-list form and the top form share them)
+static int multi_shard_clones(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc) {
+    int rc;
     const size_t ns = sc->shard.size();
     // one multi clone per shard; a clone whose shard moved to another device is released where it lives and made again
     int cur = 0;
@@ -556,10 +685,52 @@ int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_shard
             mm->shard_devices.push_back(-1);
         }
     }
+    return FZB_OK;
+}
+extern "C" {
+
+// `Matcher::match_list_parallel` of a `from_patterns` matcher with one DEVICE per worker: the whole AND / NOT composition runs per shard
+// (the patterns are independent per haystack, so shard-local composition is exact) through a per-shard multi clone on the shard's
+// device, into the staging of the ordering host's shard clone; gather and ordering are fzb_match_list_parallel_sharded's.
+int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len) {
+    if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (mm->patterns.empty()) return fzb_empty_pattern_list(sc->n, 0, mm->config.sort, out, out_len);
+    fzb_matcher* root = nullptr;
+    int rc = fzb_multi_order_host(mm, &root);
+    if (rc) return rc;
+    if ((rc = multi_shard_clones(mm, sc))) return rc;
     return fzb_sharded_query(root, sc, [&](size_t g, fzb_matcher* carrier, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
         mm->shard_devices[g] = sc->device[g];  // (the worker runs on the shard's device)
         return fzb_multi_match_list_device(mm->shard_clones[g], c, 0, c->dev.n, index_offset, (fzb_match*)carrier->out_dev, carrier->out_cap, carrier->count_dev, st);
     }, out, out_len);
+}
+
+// top-`limit` forms (the reference has no such call; the result is the prefix of what the calls above return)
+int fzb_match_list_top_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (!m || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (m->empty) return fzb_empty_pattern_top(sc->n, m->config.sort, limit, out, out_len, out_found);
+    return fzb_sharded_top_query(m, sc, [](size_t, fzb_matcher* cm, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
+        return fzb_match_list_device(cm, c, 0, c->dev.n, index_offset, (fzb_match*)cm->out_dev, cm->out_cap, cm->count_dev, st);
+    }, limit, out, out_len, out_found);
+}
+
+int fzb_multi_match_list_top_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (mm->patterns.empty()) return fzb_empty_pattern_top(sc->n, mm->config.sort, limit, out, out_len, out_found);
+    fzb_matcher* root = nullptr;
+    int rc = fzb_multi_order_host(mm, &root);
+    if (rc) return rc;
+    if ((rc = multi_shard_clones(mm, sc))) return rc;
+    return fzb_sharded_top_query(root, sc, [&](size_t g, fzb_matcher* carrier, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
+        mm->shard_devices[g] = sc->device[g];  // (the worker runs on the shard's device)
+        return fzb_multi_match_list_device(mm->shard_clones[g], c, 0, c->dev.n, index_offset, (fzb_match*)carrier->out_dev, carrier->out_cap, carrier->count_dev, st);
+    }, limit, out, out_len, out_found);
 }
 
 const char* fzb_multi_matcher_shard_report(const fzb_multi_matcher* mm) { return mm && mm->order ? mm->order->shard_report.c_str() : ""; }

@@ -158,6 +158,21 @@ int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, siz
  * both as device kernels).  fzb_match_list is this call + one device-to-host copy. */
 int fzb_match_list_sorted_device(fzb_matcher* m, const fzb_corpus* c, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream);
 
+/* TOP-`limit` QUERIES.  The reference has no such call: its `match_list` returns a Vec and the caller truncates it.  The contract here is
+ * exactly that truncation: top(limit) = the first min(limit, found) records of what fzb_match_list returns for the same matcher and
+ * corpus, in the same order, ties at the cut broken as the stable sort breaks them (the reverse for the *Desc strategies happens before
+ * the sort: src/matcher/mod.rs:215-221, src/sort.rs:6-40 - lowest indices win for ScoreThenIndexAsc, highest for ScoreThenIndexDesc;
+ * IndexAsc / IndexDesc: the first / last `limit` matches in index order), and found = the length of the full list.  limit = 0 is valid
+ * (no records, found still reported); limit >= found returns the whole list.  With an empty needle every haystack matches with score 0
+ * (host work, as in fzb_match_list).  The threshold score, the selection of the head's records and their ordering run on the device;
+ * only min(limit, corpus length) records are copied.
+ * Host result: *out (fzb_matches_free) holds min(limit, found) records; *out_found (optional) = matches found. */
+int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
+/* The same with the result left in HBM and no host synchronisation: dev_out has room for `capacity` >= min(limit, corpus length) records
+ * (less: FZB_ERR_CAPACITY, nothing launched), dev_count[0] = records written = min(limit, found), dev_count[1] = found; asynchronous on
+ * `stream`.  Not for an empty needle (FZB_ERR_INVALID). */
+int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream);
+
 /* `Matcher::match_list_parallel(&haystacks, threads)` (src/matcher/parallel.rs:18-89).  The GPU processes the
  * whole list in one pass, so `threads` only keeps the reference's contract: 0 => FZB_ERR_PANIC
  * "threads must be positive"; the result equals fzb_match_list for every thread count (parallel.rs:104-130). */
@@ -197,6 +212,9 @@ int fzb_sharded_corpus_shard(const fzb_sharded_corpus* sc, int g, uint64_t* lo, 
  * is the root (the matcher binds to it like on any first query).  fzb_last_counters on `m` afterwards = the sum over the shards.
  * Free the result with fzb_matches_free. */
 int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len);
+/* fzb_match_list_top over the sharded list: every shard selects its own head (at most `limit` records) on its device, only those
+ * travel to the root, which selects and orders once more; *out_found = the sum over the shards. */
+int fzb_match_list_top_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 /* How the runs of the last fzb_match_list_parallel_sharded on `m` reached the root, as text: the gather form and, per shard, "same
  * device", "peer access enabled (device to device over xGMI)" or "peer access REFUSED ..." (hipDeviceCanAccessPeer /
  * hipDeviceEnablePeerAccess are asked once per (root, device) pair; without peer access the runtime stages hipMemcpyPeerAsync through
@@ -311,6 +329,8 @@ void fzb_multi_matcher_free(fzb_multi_matcher* mm);
 size_t fzb_multi_matcher_len(const fzb_multi_matcher* mm); /* compiled (non-empty) patterns */
 /* `Matcher::match_list` over CompiledPatterns::{Empty, Single, Multi} (src/matcher/mod.rs:212-222, 373-392): ordered per config.sort */
 int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len);
+/* fzb_match_list_top for a `from_patterns` matcher: the first min(limit, found) records of fzb_multi_match_list's result */
+int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 /* `Matcher::match_list_indices` for a `from_patterns` matcher (see fzb_match_list_indices): CompiledPatterns::Multi runs
  * `match_one_indices_multi` (src/matcher/multi.rs:56-82) - a negated pattern that matches drops the haystack, every other pattern
  * must match, scores add with saturation, exact flags OR, and the patterns' positions are merged (descending, de-duplicated). */
@@ -354,6 +374,8 @@ int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, si
  * the runs are gathered and ordered once on the root (the caller's current device).  Result = fzb_multi_match_list on the unsharded
  * list for every sort strategy; with no compiled pattern every index, score 0, reversed for the *Desc strategies (mod.rs:215-220). */
 int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, fzb_match** out, size_t* out_len);
+/* fzb_match_list_top_sharded for a `from_patterns` matcher */
+int fzb_multi_match_list_top_sharded(fzb_multi_matcher* mm, const fzb_sharded_corpus* sc, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 /* COLLECTIVE, one process per GPU (see fzb_match_list_parallel_rccl): this rank's composition is its run; the exchange is the same. */
 int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* comm,
                                        int flags, fzb_match** out, size_t* out_len);

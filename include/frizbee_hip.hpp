@@ -282,6 +282,30 @@ class Matcher {  // src/matcher/mod.rs:77-222
     template <typename Strings>
     std::vector<Match> match_list(const Strings& haystacks) { return match_list(Corpus(haystacks)); }
 
+    // The first min(limit, found) entries of `match_list(&haystacks)`, selected and ordered on the device (fzb_match_list_top /
+    // fzb_multi_match_list_top; the reference's caller truncates the Vec instead); *found = the length of the whole list.
+    std::vector<Match> match_list_top(const Corpus& corpus, size_t limit, size_t* found = nullptr) {
+        fzb_match* out = nullptr;
+        size_t n = 0;
+        uint64_t f = 0;
+        if (single_) check(fzb_match_list_top(single_.get(), corpus.raw(), limit, &out, &n, &f));
+        else check(fzb_multi_match_list_top(multi_.get(), corpus.raw(), limit, &out, &n, &f));
+        if (found) *found = (size_t)f;
+        return take(out, n);
+    }
+    template <typename Strings>
+    std::vector<Match> match_list_top(const Strings& haystacks, size_t limit, size_t* found = nullptr) { return match_list_top(Corpus(haystacks), limit, found); }
+    // the same over a sharded list: every shard selects its own head, only those records travel to the root
+    std::vector<Match> match_list_top(const ShardedCorpus& corpus, size_t limit, size_t* found = nullptr) {
+        fzb_match* out = nullptr;
+        size_t n = 0;
+        uint64_t f = 0;
+        if (single_) check(fzb_match_list_top_sharded(single_.get(), corpus.raw(), limit, &out, &n, &f));
+        else check(fzb_multi_match_list_top_sharded(multi_.get(), corpus.raw(), limit, &out, &n, &f));
+        if (found) *found = (size_t)f;
+        return take(out, n);
+    }
+
     // `match_list_indices(&haystacks)` (src/matcher/mod.rs:234-275; multi-pattern: match_one_indices_multi, multi.rs:56-82).
     // `selection`: corpus indices standing in for the haystack list (the top of a match_list result); empty optional = the whole corpus.
     std::vector<MatchIndices> match_list_indices(const Corpus& corpus, const std::optional<std::vector<uint32_t>>& selection = std::nullopt) {

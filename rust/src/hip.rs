@@ -90,6 +90,11 @@ extern "C" {
     fn fzb_match_list(m: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_match_list_into(m: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_matches_free(p: *mut FzbMatch);
+    // top-`limit` queries: the first min(limit, found) records of `match_list`'s result, selected and ordered on the device
+    fn fzb_match_list_top(m: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_match_list_top_device(m: *mut c_void, c: *const c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_match_list_top_sharded(m: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_match_list_indices(m: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
                               out_positions: *mut *mut u32) -> c_int;
     fn fzb_match_indices_free(matches: *mut FzbMatchIndices, positions: *mut u32);
@@ -135,6 +140,8 @@ extern "C" {
     fn fzb_multi_match_list_parallel_sharded(mm: *mut c_void, sc: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_multi_match_list_parallel_rccl(mm: *mut c_void, shard: *const c_void, index_offset: u32, comm: *mut c_void, flags: c_int, out: *mut *mut FzbMatch,
                                           out_len: *mut usize) -> c_int;
+    fn fzb_multi_match_list_top(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_sharded(mm: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_multi_matcher_shard_report(mm: *const c_void) -> *const c_char;
 }
 
@@ -322,6 +329,26 @@ impl MatcherHip {
         v
     }
 
+    /// The first `min(limit, found)` entries of `match_list` and `found`, the length of the whole list: what a caller of the reference
+    /// gets from `match_list(..)` followed by `truncate(limit)`, with the selection and the ordering done on the device and only
+    /// `limit` records copied.
+    pub fn match_list_top(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<Match>, usize) {
+        let (mut out, mut n, mut found) = (std::ptr::null_mut(), 0usize, 0u64);
+        check(unsafe { fzb_match_list_top(self.handle, corpus.handle, limit, &mut out, &mut n, &mut found) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        (v, found as usize)
+    }
+
+    /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
+    pub fn match_list_top_sharded(&mut self, corpus: &ShardedCorpus, limit: usize) -> (Vec<Match>, usize) {
+        let (mut out, mut n, mut found) = (std::ptr::null_mut(), 0usize, 0u64);
+        check(unsafe { fzb_match_list_top_sharded(self.handle, corpus.handle, limit, &mut out, &mut n, &mut found) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        (v, found as usize)
+    }
+
     /// `match_list_parallel` with ONE PROCESS PER GPU: this rank scores `shard` (its contiguous share of the list, first global index
     /// `index_offset`), the library all-gathers the run lengths and moves the runs by RCCL over xGMI to rank 0 (`to_all`: to every
     /// rank), a receiver orders the whole list once on its device.  Collective: every rank of the communicator calls it with a matcher
@@ -428,6 +455,26 @@ impl HipMultiMatcher {
         let mut v = Vec::with_capacity(n);
         copy_out(out, n, &mut v);
         v
+    }
+
+    /// The first `min(limit, found)` entries of `match_list` and `found`, the length of the whole list: what a caller of the reference
+    /// gets from `match_list(..)` followed by `truncate(limit)`, with the selection and the ordering done on the device and only
+    /// `limit` records copied.
+    pub fn match_list_top(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<Match>, usize) {
+        let (mut out, mut n, mut found) = (std::ptr::null_mut(), 0usize, 0u64);
+        check(unsafe { fzb_multi_match_list_top(self.handle, corpus.handle, limit, &mut out, &mut n, &mut found) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        (v, found as usize)
+    }
+
+    /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
+    pub fn match_list_top_sharded(&mut self, corpus: &ShardedCorpus, limit: usize) -> (Vec<Match>, usize) {
+        let (mut out, mut n, mut found) = (std::ptr::null_mut(), 0usize, 0u64);
+        check(unsafe { fzb_multi_match_list_top_sharded(self.handle, corpus.handle, limit, &mut out, &mut n, &mut found) });
+        let mut v = Vec::with_capacity(n);
+        copy_out(out, n, &mut v);
+        (v, found as usize)
     }
 
     /// One process per GPU (see `MatcherHip::match_list_parallel_rccl`): this rank's composition is its run.  Collective; a rank that fails
