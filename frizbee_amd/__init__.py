@@ -121,6 +121,7 @@ SYMBOLS = [
     "fzb_multi_matcher_set_patterns", "fzb_multi_matcher_set_config", "fzb_multi_matcher_reserve", "fzb_multi_matcher_clone", "fzb_multi_match_list_parallel",
     "fzb_multi_match_list_parallel_sharded", "fzb_multi_match_list_parallel_rccl", "fzb_multi_matcher_shard_report", "fzb_debug_device_allocs",
     "fzb_match_list_top", "fzb_match_list_top_device", "fzb_multi_match_list_top", "fzb_match_list_top_sharded", "fzb_multi_match_list_top_sharded",
+    "fzb_corpus_reserve", "fzb_corpus_append", "fzb_corpus_truncate", "fzb_corpus_info", "fzb_debug_corpus_read",
 ]
 
 
@@ -211,6 +212,11 @@ def lib():
         l.fzb_multi_match_list_top.argtypes = l.fzb_match_list_top.argtypes
         l.fzb_match_list_top_sharded.argtypes = l.fzb_match_list_top.argtypes
         l.fzb_multi_match_list_top_sharded.argtypes = l.fzb_match_list_top.argtypes
+        l.fzb_corpus_reserve.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64]
+        l.fzb_corpus_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_truncate.argtypes = [C.c_void_p, C.c_size_t]
+        l.fzb_corpus_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_debug_corpus_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = l
     return _lib
 
@@ -287,6 +293,48 @@ class Corpus:
         built = C.c_int()
         _check(lib().fzb_corpus_build_view(self.h, C.byref(built)))
         return bool(built.value)
+
+    def append(self, haystacks=None, *, packed=None):
+        """fzb_corpus_append: the batch becomes haystacks len(self) .. of the resident list; only the batch crosses the link.  `packed` =
+        pack() of the batch alone.  For a corpus made by Corpus(...) - `Corpus([])` followed by appends is how a picker starts."""
+        data, ends = packed if packed is not None else pack(haystacks)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        _check(lib().fzb_corpus_append(self.h, data.ctypes.data, ends.ctypes.data if len(ends) else None, len(ends)))
+
+    def reserve(self, items, nbytes):
+        """fzb_corpus_reserve: room for `items` haystacks and `nbytes` padded bytes (<= raw bytes + 15 per haystack), so that appends
+        within it - and, after Matcher.reserve, the queries between them - allocate no device memory."""
+        _check(lib().fzb_corpus_reserve(self.h, items, nbytes))
+
+    def truncate(self, n):
+        """fzb_corpus_truncate: keep the first n haystacks (capacity is kept)."""
+        _check(lib().fzb_corpus_truncate(self.h, n))
+
+    INFO_FIELDS = ("items", "item_capacity", "bytes", "byte_capacity", "max_len", "uniform_len", "has_view", "view_nv", "outliers", "ends_u64", "regrows",
+                   "h2d_bytes")
+    DEBUG_ARRAYS = {"bytes": (0, np.uint8), "ends": (1, None), "vbytes": (2, np.uint8), "vgofs": (3, np.uint32), "vgnv": (4, np.uint8), "vlen": (5, np.uint16),
+                    "vperm": (6, np.uint16), "vlong": (7, np.uint32)}
+
+    def info(self):
+        """fzb_corpus_info as a dict (INFO_FIELDS)."""
+        out = (C.c_uint64 * 12)()
+        _check(lib().fzb_corpus_info(self.h, out))
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+    def debug_read(self, what):
+        """Test hook (fzb_debug_corpus_read): one of the corpus' device arrays (DEBUG_ARRAYS) as a numpy array."""
+        code, dtype = self.DEBUG_ARRAYS[what]
+        if dtype is None:
+            dtype = np.uint64 if self.info()["ends_u64"] else np.uint32
+        n = C.c_size_t()
+        rc = lib().fzb_debug_corpus_read(self.h, code, None, 0, C.byref(n))
+        if rc != 5:  # (FZB_ERR_CAPACITY carries the size)
+            _check(rc)
+        buf = np.zeros(n.value, np.uint8)
+        if n.value:
+            _check(lib().fzb_debug_corpus_read(self.h, code, buf.ctypes.data, buf.nbytes, C.byref(n)))
+        return buf.view(dtype)
 
     def __len__(self):
         return lib().fzb_corpus_len(self.h)

@@ -976,6 +976,8 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_ends) (void)hipFree(c->own_ends);
     for (void* q : c->own_view)
         if (q) (void)hipFree(q);
+    for (void* q : {c->stage_raw, c->stage_ends, c->stage_tiles, c->stage_stats})
+        if (q) (void)hipFree(q);
     delete c;
 }
 size_t fzb_corpus_len(const fzb_corpus* c) { return c ? (size_t)c->dev.n : 0; }
@@ -1749,13 +1751,14 @@ static int run_pipeline(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
 // (Matched-indices queries size their trace scratch from the selection, on first use.)
 int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
-    if (m->empty || c->dev.n == 0) return FZB_OK;
+    // (a corpus with room reserved: sized for that room, and for haystacks of any width - an append may bring them)
+    const size_t n = fzb_corpus_reserved_items(c);
+    if (m->empty || n == 0) return FZB_OK;
     int rc = fzb_bind_device(m);
     if (rc) return rc;
-    const size_t n = c->dev.n;
     rc = ensure_workspace(m, n);
     if (rc) return rc;
-    const bool no_wide = c->dev.max_len != 0 && c->dev.max_len <= (u32)m->lc.sw_lanes;
+    const bool no_wide = n == c->dev.n && c->dev.max_len != 0 && c->dev.max_len <= (u32)m->lc.sw_lanes;
     if (!m->long_needle && !m->literal_mode && !m->nd.unicode && !no_wide && ((rc = ensure_dp_scratch(m, m->lc.num_cus * 4)) || (rc = ensure_aux_stream(m)))) return rc;
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && fzb_knobs().unicode_multi != 0 && (rc = ensure_dp_scratch(m, m->lc.num_cus * 2))) return rc;
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && m->nd.max_typos < 0 && (rc = ensure_aux_stream(m))) return rc;  // whole-haystack windows: the wide ones on the second stream
@@ -1772,17 +1775,18 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
 // scoring and lanes; ASCII grid, the unicode scorer's is half of it).  Only a long needle (beyond 64 bytes / 63 rows) or another scoring /
 // lane pair can make the slot grow later.  A slot never runs the synchronous entry points: no staging or sort buffers.
 static int reserve_slot_any_needle(fzb_matcher* m, const fzb_corpus* c) {
-    if (m->empty || c->dev.n == 0) return FZB_OK;
+    const size_t n = fzb_corpus_reserved_items(c);
+    if (m->empty || n == 0) return FZB_OK;
     int rc = fzb_bind_device(m);
     if (rc) return rc;
-    if ((rc = ensure_workspace(m, c->dev.n, nullptr, false, true))) return rc;
+    if ((rc = ensure_workspace(m, n, nullptr, false, true))) return rc;
     size_t words = 0;
     for (int r = 1; r <= FZB_MAX_ROWS; r++) {
         const bool u8 = fits_in_u8((size_t)r, m->config.scoring);  // (a unicode needle of r scalars has >= r bytes: never a wider class)
         int pf = m->config.pf_lanes, sw = m->config.sw_lanes;
         if (pf == 0 && sw == 0) detect_host_lanes(u8, pf, sw);
         else if (sw == 0) sw = u8 ? pf : pf / 2;
-        const bool no_wide = c->dev.max_len != 0 && c->dev.max_len <= (u32)sw;  // (no window beyond one chunk: the scratch is never used)
+        const bool no_wide = n == c->dev.n && c->dev.max_len != 0 && c->dev.max_len <= (u32)sw;  // (no window beyond one chunk: the scratch is never used)
         if (!no_wide) words = std::max(words, dp_scratch_words(r, sw, m->lc.num_cus * 4));
     }
     if (words && (rc = ensure_dp_scratch_words(m, words))) return rc;
@@ -2498,7 +2502,7 @@ int fzb_multi_matcher_clone(const fzb_multi_matcher* src, fzb_multi_matcher** ou
 
 int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     if (!mm || !c) return fail(FZB_ERR_INVALID, "null argument");
-    const size_t n = c->dev.n;
+    const size_t n = fzb_corpus_reserved_items(c);
     int rc;
     for (auto& p : mm->patterns)
         if ((rc = reserve_slot_any_needle(p.m, c))) return rc;

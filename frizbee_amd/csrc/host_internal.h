@@ -34,7 +34,31 @@ struct fzb_corpus {
     void* own_bytes = nullptr;
     void* own_ends = nullptr;
     void* own_view[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // the filter's view: vbytes, vgofs, vgnv, vlen, vperm, vlong (CorpusDev)
+    // ---- a corpus that grows (fzb_corpus_append / _reserve / _truncate, host_upload.hip; only for a corpus the library uploaded) ----
+    // Everything behind the used part of `own_bytes` and of the view's bytes is ZERO (cleared when allocated, again by truncate), so the
+    // zero tail the kernels rely on is there wherever the list ends.
+    u64 cap_items = 0;       // haystacks `own_ends` (and the view's per-item arrays) hold
+    u64 cap_bytes = 0;       // bytes of `own_bytes`, the 96-byte tail included
+    u64 min_len = ~(u64)0;   // shortest / longest haystack, more than 256 bytes, longest of those within 256: what decides uniform_len
+    u64 max_len = 0;         // and whether the list calls for a view, kept on the host so that an append reads back its batch's stats only
+    u64 n_over256 = 0;
+    u64 max_short = 0;
+    u64 view_units = 0;      // used part of the view's bytes in 16-byte units
+    u64 view_items = 0;      // haystacks the view covers (the list's length while the corpus has a view)
+    u64 view_cap_items = 0;  // haystacks the view's arrays hold (own_view[1..5]); view_cap_units: 16-byte units of own_view[0], slack excluded
+    u64 view_cap_units = 0;
+    u64 regrows = 0;         // reallocations of the canonical arrays so far
+    u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
+    // staging of a batch, kept between appends: the batch as it arrived (bytes, u64 offsets), the layout pass' tile sums and stats
+    void* stage_raw = nullptr;
+    void* stage_ends = nullptr;
+    void* stage_tiles = nullptr;
+    void* stage_stats = nullptr;
+    u64 stage_raw_cap = 0, stage_items_cap = 0, stage_tiles_cap = 0;
+    int device = -1;         // where an uploaded corpus lives
 };
+// the haystacks a matcher's buffers are sized for: the list's length, or what fzb_corpus_reserve made room for
+inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c->cap_items > c->dev.n ? c->cap_items : c->dev.n); }
 
 // what the synchronous entry points remember between two results (fetch_records, host.hip)
 struct FetchHint {

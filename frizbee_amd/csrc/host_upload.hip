@@ -27,17 +27,21 @@ namespace {
 constexpr int UP_TILE = 1024;
 constexpr int UP_THREADS = 256;
 
-// stats block (device, 64 bytes): [0] total padded bytes (u64) [1] min len [2] max len (u64 each) [3] bad flag
+// stats block (device): [0] total padded bytes (u64) [1] min len [2] max len (u64 each) [3] bad flag [4] haystacks beyond 256 bytes
+// [5] the longest haystack within 256 bytes ([4], [5]: what decides whether the list calls for a filter view)
 struct UpStats {
-    u64 total_padded, min_len, max_len, bad;
+    u64 total_padded, min_len, max_len, bad, n_long, max_short;
 };
 
 __global__ __launch_bounds__(UP_THREADS) void k_up_tiles(const u64* __restrict__ ends, u64 n, u64 ends_base, u64* __restrict__ tile_sums, UpStats* __restrict__ stats) {
     __shared__ u64 s_sum[UP_THREADS / 64];
     __shared__ u64 s_min[UP_THREADS / 64];
     __shared__ u64 s_max[UP_THREADS / 64];
+    __shared__ u64 s_short[UP_THREADS / 64];
+    __shared__ u32 s_nlong[UP_THREADS / 64];
     const u64 tile = blockIdx.x;
-    u64 sum = 0, mn = ~(u64)0, mx = 0;
+    u64 sum = 0, mn = ~(u64)0, mx = 0, ms = 0;
+    u32 nl = 0;
     bool bad = false;
 #pragma unroll
     for (int k = 0; k < UP_TILE / UP_THREADS; k++) {
@@ -49,30 +53,69 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_tiles(const u64* __restrict__
             sum += (len + 15) & ~(u64)15;
             mn = min(mn, len);
             mx = max(mx, len);
+            if (len > 256) nl++;
+            else ms = max(ms, len);
         }
     }
     for (int off = 32; off > 0; off >>= 1) {
         sum += __shfl_xor(sum, off);
         mn = min(mn, (u64)__shfl_xor(mn, off));
         mx = max(mx, (u64)__shfl_xor(mx, off));
+        ms = max(ms, (u64)__shfl_xor(ms, off));
+        nl += __shfl_xor(nl, off);
     }
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr((unsigned long long*)&stats->bad, 1ull);
     if ((threadIdx.x & 63) == 0) {
         s_sum[threadIdx.x >> 6] = sum;
         s_min[threadIdx.x >> 6] = mn;
         s_max[threadIdx.x >> 6] = mx;
+        s_short[threadIdx.x >> 6] = ms;
+        s_nlong[threadIdx.x >> 6] = nl;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        u64 t = 0, a = ~(u64)0, b = 0;
+        u64 t = 0, a = ~(u64)0, b = 0, sh = 0, l = 0;
         for (int w = 0; w < UP_THREADS / 64; w++) {
             t += s_sum[w];
             a = min(a, s_min[w]);
             b = max(b, s_max[w]);
+            sh = max(sh, s_short[w]);
+            l += s_nlong[w];
         }
         tile_sums[tile] = t;
         atomicMin((unsigned long long*)&stats->min_len, (unsigned long long)a);
         atomicMax((unsigned long long*)&stats->max_len, (unsigned long long)b);
+        atomicMax((unsigned long long*)&stats->max_short, (unsigned long long)sh);
+        if (l) atomicAdd((unsigned long long*)&stats->n_long, (unsigned long long)l);
+    }
+}
+
+// The same four figures (min / max length, haystacks beyond 256 bytes, longest within 256) of the first n haystacks of a RESIDENT list,
+// read from its padded-layout offsets: what fzb_corpus_truncate re-measures for the kept prefix, and what a borrowed corpus' view goes by.
+template <typename ET>
+__global__ __launch_bounds__(UP_THREADS) void k_up_measure(const ET* __restrict__ ends, u64 n, UpStats* __restrict__ stats) {
+    u64 mn = ~(u64)0, mx = 0, ms = 0;
+    u32 nl = 0;
+    const u64 stride = (u64)gridDim.x * UP_THREADS;
+    for (u64 i = (u64)blockIdx.x * UP_THREADS + threadIdx.x; i < n; i += stride) {
+        const u64 st = i ? ((u64)ends[i - 1] + 15) & ~(u64)15 : 0;
+        const u64 e = (u64)ends[i], len = e >= st ? e - st : 0;
+        mn = min(mn, len);
+        mx = max(mx, len);
+        if (len > 256) nl++;
+        else ms = max(ms, len);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = min(mn, (u64)__shfl_xor(mn, off));
+        mx = max(mx, (u64)__shfl_xor(mx, off));
+        ms = max(ms, (u64)__shfl_xor(ms, off));
+        nl += __shfl_xor(nl, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin((unsigned long long*)&stats->min_len, (unsigned long long)mn);
+        atomicMax((unsigned long long*)&stats->max_len, (unsigned long long)mx);
+        atomicMax((unsigned long long*)&stats->max_short, (unsigned long long)ms);
+        if (nl) atomicAdd((unsigned long long*)&stats->n_long, (unsigned long long)nl);
     }
 }
 
@@ -104,14 +147,16 @@ __global__ __launch_bounds__(1024) void k_up_scan(u64* __restrict__ tile_sums, u
 }
 
 // ET = u32 / u64 end offsets of the padded layout.  COPY = false: the raw buffer already is the padded layout (only offsets are written).
+// The batch is laid out BEHIND what is resident: its first haystack starts at byte `out_base` (a multiple of 16) of `padded` and is
+// haystack `index_base` of `ends_out` (0, 0 for a whole list).
 template <typename ET, bool COPY>
 __global__ __launch_bounds__(UP_THREADS) void k_up_build(const u8* __restrict__ raw, const u64* __restrict__ ends, u64 n, u64 ends_base, const u64* __restrict__ tile_base,
-                                                         u8* __restrict__ padded, ET* __restrict__ ends_out) {
+                                                         u8* __restrict__ padded, ET* __restrict__ ends_out, u64 out_base, u64 index_base) {
     __shared__ u64 s_pstart[UP_TILE + 1];  // padded start of each haystack of the tile, relative to the tile's base
     __shared__ u64 s_wave[UP_THREADS / 64];
     const u64 tile = blockIdx.x;
     const u64 i0 = tile * UP_TILE;
-    const u64 base = tile_base[tile];
+    const u64 base = tile_base[tile] + out_base;
     // every thread owns 4 CONSECUTIVE haystacks: serial prefix of their padded lengths, then a scan over the threads
     const u64 first = i0 + (u64)threadIdx.x * 4;
     const u64 e_prev = first == 0 ? ends_base : (first <= n ? ends[first - 1] : 0);
@@ -137,7 +182,7 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_build(const u8* __restrict__ 
     for (int k = 0; k < 4; k++) {
         const u64 i = first + k;
         s_pstart[threadIdx.x * 4 + k] = run;
-        if (i < n) ends_out[i] = (ET)(base + run + (e[k] - (k ? e[k - 1] : e_prev)));
+        if (i < n) ends_out[index_base + i] = (ET)(base + run + (e[k] - (k ? e[k - 1] : e_prev)));
         run += plen[k];
     }
     if (threadIdx.x == UP_THREADS - 1) s_pstart[UP_TILE] = run;
@@ -186,18 +231,21 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_build(const u8* __restrict__ 
 //   (k_up_scan: exclusive scan of the tile sizes - the same kernel the canonical layout uses)
 //   k_up_view_fill   writes the groups' block offsets and copies every vector to its interleaved position (the buffer was cleared: the
 //                    zero vectors behind a group's shorter members are already there)
+// Both take the FIRST TILE they work on (workgroup b = tile first_tile + b): an append re-sorts and re-fills only the tiles from the last,
+// partial one on (view_sync below); the fill then places tile first_tile at `unit_base`, the offset that tile already had.
+//   k_up_vlong_prune drops the outliers of the tiles about to be re-sorted from the list (they re-enter it from the sort), in place
 #define FV_CLASSES 258  // sort key = the haystack's LENGTH, 0..256 bytes (round 5; rounds 3-4: its vector count, 18 classes), and a guard class
 // Round 5: a group's LAST vector row is stored as narrow as its longest member's tail allows - 4, 8, 12 or 16 bytes per member instead of 16
 // (vgnv[group] = vectors per member | (tail bytes / 4 - 1) << 5) - and the tile is sorted by exact length, so that the 64 members of a group end
 // within a few bytes of each other: the view of the C4 shard shrinks from 1.19 to 1.12 x the haystack bytes (padded-16 alone costs 1.106).
 template <typename ET>
 __global__ __launch_bounds__(UP_THREADS) void k_up_view_sort(const ET* __restrict__ ends, u64 n, u16* __restrict__ vperm, u16* __restrict__ vlen, u8* __restrict__ vgnv,
-                                                             u64* __restrict__ tile_units, UpStats* __restrict__ stats, u32* __restrict__ vlong, u32 long_cap) {
+                                                             u64* __restrict__ tile_units, UpStats* __restrict__ stats, u32* __restrict__ vlong, u32 long_cap, u32 first_tile) {
     __shared__ u32 s_len[UP_TILE];
     __shared__ u16 s_inv[UP_TILE];
     __shared__ u32 s_hist[FV_CLASSES], s_base[FV_CLASSES];
     __shared__ u32 s_gunits[UP_TILE / 64];
-    const u64 i0 = (u64)blockIdx.x * UP_TILE;
+    const u64 i0 = ((u64)blockIdx.x + first_tile) * UP_TILE;
     const u32 nt = (u32)min((u64)UP_TILE, n - i0);
     const int tid = threadIdx.x;
     for (int c = tid; c < FV_CLASSES; c += UP_THREADS) s_hist[c] = 0;
@@ -266,13 +314,14 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_view_sort(const ET* __restric
 
 template <typename ET>
 __global__ __launch_bounds__(UP_THREADS) void k_up_view_fill(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 n, const u16* __restrict__ vperm,
-                                                             const u8* __restrict__ vgnv, const u64* __restrict__ tile_base_units, u8* __restrict__ vbytes, u32* __restrict__ vgofs) {
+                                                             const u8* __restrict__ vgnv, const u64* __restrict__ tile_base_units, u8* __restrict__ vbytes, u32* __restrict__ vgofs,
+                                                             u32 first_tile, u64 unit_base) {
     __shared__ u32 s_gofs[UP_TILE / 64], s_gnv[UP_TILE / 64], s_gtw[UP_TILE / 64];
-    const u64 i0 = (u64)blockIdx.x * UP_TILE;
+    const u64 i0 = ((u64)blockIdx.x + first_tile) * UP_TILE;
     const u32 nt = (u32)min((u64)UP_TILE, n - i0);
     const int tid = threadIdx.x;
     if (tid == 0) {
-        u64 run = tile_base_units[blockIdx.x];
+        u64 run = tile_base_units[blockIdx.x] + unit_base;
         for (int g = 0; g < UP_TILE / 64; g++) {
             const u32 code = vgnv[i0 / 64 + g], nv = code & 31u, tw = nv ? ((code >> 5) + 1u) * 4u : 0u;
             s_gofs[g] = (u32)run;
@@ -307,6 +356,35 @@ __global__ __launch_bounds__(UP_THREADS) void k_up_view_fill(const u8* __restric
     }
 }
 
+// keeps the outliers below haystack `limit`, in their order, and leaves their number in stats->bad (where k_up_view_sort goes on counting):
+// one workgroup, chunks of 1024 entries with a running carry - an entry is written at or before the place it was read from
+__global__ __launch_bounds__(1024) void k_up_vlong_prune(u32* __restrict__ vlong, u32 n_long, u32 limit, UpStats* __restrict__ stats) {
+    __shared__ u32 s_wave[16];
+    __shared__ u32 s_carry;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (u32 base = 0; base < n_long; base += 1024) {
+        const u32 i = base + threadIdx.x;
+        const u32 v = i < n_long ? vlong[i] : 0u;
+        const bool keep = i < n_long && v < limit;
+        const u64 m = __ballot(keep);
+        const u32 rank = (u32)__popcll(m & (((u64)1 << (threadIdx.x & 63)) - 1));
+        if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = (u32)__popcll(m);
+        __syncthreads();  // (every entry of the chunk has been read)
+        u32 wave_base = 0, total = 0;
+        for (u32 w = 0; w < 16; w++) {
+            if (w < (threadIdx.x >> 6)) wave_base += s_wave[w];
+            total += s_wave[w];
+        }
+        const u32 carry = s_carry;
+        if (keep) vlong[carry + wave_base + rank] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) s_carry = carry + total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) stats->bad = s_carry;
+}
+
 // ---- host -> device at link speed ---------------------------------------------------------------------------------------------
 // One hipMemcpy per array straight from the caller's pageable memory: 52-53 GB/s measured (profiles/r03_upload_modes.txt; hipHostRegister
 // first and a pool of threads with pinned staging buffers were both slower there and left with round 6's prune).
@@ -327,6 +405,244 @@ hipError_t h2d_all(const std::vector<H2DJob>& jobs, int device) {
     return hipSuccess;
 }
 
+const UpStats UP_STATS_INIT{0, ~(u64)0, 0, 0, 0, 0};
+inline u64 up_tiles(u64 n) { return (n + UP_TILE - 1) / UP_TILE; }
+// outliers (haystacks beyond 256 bytes) the view of n haystacks tolerates: one in 256, at least 64 - more, and the list is not a short-haystack list
+inline u64 long_cap_of(u64 n) { return std::min<u64>(n / 256 + 64, 0x7FFFFFFFu); }
+
+// ---- "lay out a batch behind position p": the two halves of the layout pass, for a whole list (upload) and for an appended batch ----
+// The batch is resident as it arrived: d_ends64[i] = exclusive end of its haystack i counted from `ends_base`.
+// First half: per-tile sums of the padded lengths, their exclusive scan (d_tiles), and the batch's stats - padded size, min / max length,
+// "offsets decrease" flag, outlier figures - read back: the one synchronisation, before anything of the corpus is written.
+hipError_t batch_measure(const u64* d_ends64, u64 n, u64 ends_base, u64* d_tiles, UpStats* d_stats, UpStats* st) {
+    hipError_t e = hipMemcpy(d_stats, &UP_STATS_INIT, sizeof(UpStats), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_up_tiles, dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_ends64, n, ends_base, d_tiles, d_stats);
+    hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_tiles, up_tiles(n), d_stats);
+    return hipMemcpy(st, d_stats, sizeof(UpStats), hipMemcpyDeviceToHost);
+}
+// Second half: the batch's bytes from byte `out_base` of `out_bytes` on (copy = false: they are there already, `raw` is the padded layout)
+// and its end offsets from entry `index_base` of `out_ends` on, in the padded layout's terms.
+void batch_lay_out(const u8* d_raw, const u64* d_ends64, u64 n, u64 ends_base, const u64* d_tiles, u8* out_bytes, u64 out_base, void* out_ends, u64 index_base, bool ends_u64,
+                   bool copy) {
+#define FZB_UP_BUILD(ET, COPY) \
+    hipLaunchKernelGGL((k_up_build<ET, COPY>), dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_raw, d_ends64, n, ends_base, d_tiles, out_bytes, (ET*)out_ends, out_base, index_base)
+    if (ends_u64) { if (copy) FZB_UP_BUILD(u64, true); else FZB_UP_BUILD(u64, false); }
+    else { if (copy) FZB_UP_BUILD(u32, true); else FZB_UP_BUILD(u32, false); }
+#undef FZB_UP_BUILD
+}
+
+// the host's figures of a list -> what the kernels go by (as a fresh upload sets them)
+void set_measured(fzb_corpus* c) {
+    const u64 n = c->dev.n;
+    if (!n) { c->min_len = ~(u64)0; c->max_len = 0; c->n_over256 = 0; c->max_short = 0; }
+    c->dev.max_len = (u32)std::min<u64>(c->max_len, 0xFFFFFFFFu);
+    c->dev.uniform_len = (n && c->min_len == c->max_len && c->max_len && c->max_len < 0xFFFFFFFFu) ? (u32)c->max_len : 0u;  // kernels then skip the end offsets
+}
+
+// the tile sums / tile units scratch and the stats block of the layout and view passes, kept with the corpus
+hipError_t ensure_tiles_scratch(fzb_corpus* c, u64 tiles) {
+    if (!c->stage_stats) {
+        hipError_t e = fzb_dev_alloc(&c->stage_stats, sizeof(UpStats));
+        if (e != hipSuccess) return e;
+    }
+    if (c->stage_tiles && c->stage_tiles_cap >= tiles) return hipSuccess;
+    void* p = nullptr;
+    hipError_t e = fzb_dev_alloc(&p, std::max<u64>(tiles, 1) * 8);
+    if (e != hipSuccess) return e;
+    if (c->stage_tiles) (void)hipFree(c->stage_tiles);
+    c->stage_tiles = p;
+    c->stage_tiles_cap = std::max<u64>(tiles, 1);
+    return hipSuccess;
+}
+
+// ---- the filter's view, kept in step with the list -------------------------------------------------------------------------------
+// A view of n haystacks never takes more than their padded bytes + 16 KiB per tile: a group's block is 64 x its longest member (rounded
+// to 4 bytes), which every member of the group before it - the tile is sorted - is at least as long as; the tile's first group has
+// nobody before it: 64 x 256 bytes.
+inline u64 view_units_bound(u64 items, u64 padded_bytes) { return padded_bytes / 16 + up_tiles(items) * 1024; }
+
+void view_free(fzb_corpus* c) {
+    for (int q = 0; q < 6; q++) {
+        if (c->own_view[q]) (void)hipFree(c->own_view[q]);
+        c->own_view[q] = nullptr;
+    }
+    c->view_cap_items = c->view_cap_units = 0;
+    (void)hipGetLastError();
+}
+// the corpus goes on without a view; its buffers stay for the list that calls for one again (their used part cleared)
+hipError_t view_deactivate(fzb_corpus* c) {
+    hipError_t e = hipSuccess;
+    if (c->dev.vbytes && c->own_view[0] && c->view_units) e = hipMemsetAsync(c->own_view[0], 0, c->view_units * 16, nullptr);
+    c->dev.vbytes = nullptr; c->dev.vgofs = nullptr; c->dev.vgnv = nullptr; c->dev.vlen = nullptr; c->dev.vperm = nullptr; c->dev.vlong = nullptr;
+    c->dev.view_nv = 0;
+    c->dev.n_long = 0;
+    c->view_units = c->view_items = 0;
+    return e;
+}
+// Room for the per-haystack arrays of `items` haystacks (own_view[1..5]) and for `units` 16-byte units of view bytes (own_view[0], its
+// 1 KiB of slack behind them; 0 = leave them as they are); what is in use of a live view (`keep_items` haystacks, `keep_units` units) moves device to device.
+// hipErrorOutOfMemory: nothing has changed.
+hipError_t view_ensure_room(fzb_corpus* c, u64 items, u64 units, u64 keep_items, u64 keep_units) {
+    const bool live = c->dev.vbytes != nullptr;
+    if (c->view_cap_items < items || !c->own_view[1]) {
+        const u64 groups = up_tiles(items) * (UP_TILE / 64), keep_groups = up_tiles(keep_items) * (UP_TILE / 64);
+        const size_t sizes[6] = {0, (size_t)groups * 4, (size_t)groups, (size_t)items * 2, (size_t)items * 2, (size_t)long_cap_of(items) * 4};
+        const size_t keep[6] = {0, (size_t)keep_groups * 4, (size_t)keep_groups, (size_t)keep_items * 2, (size_t)keep_items * 2, (size_t)c->dev.n_long * 4};
+        void* fresh[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipError_t e = hipSuccess;
+        for (int q = 1; q < 6 && e == hipSuccess; q++) {
+            e = fzb_dev_alloc(&fresh[q], sizes[q]);
+            if (e == hipSuccess && live && keep[q]) e = hipMemcpy(fresh[q], c->own_view[q], keep[q], hipMemcpyDeviceToDevice);
+        }
+        if (e != hipSuccess) {
+            for (void* p : fresh)
+                if (p) (void)hipFree(p);
+            return e;
+        }
+        for (int q = 1; q < 6; q++) {
+            if (c->own_view[q]) (void)hipFree(c->own_view[q]);
+            c->own_view[q] = fresh[q];
+        }
+        c->view_cap_items = items;
+        if (live) {
+            c->dev.vgofs = (const u32*)c->own_view[1]; c->dev.vgnv = (const u8*)c->own_view[2]; c->dev.vlen = (const u16*)c->own_view[3];
+            c->dev.vperm = (const u16*)c->own_view[4]; c->dev.vlong = (const u32*)c->own_view[5];
+        }
+    }
+    if (units && (c->view_cap_units < units || !c->own_view[0])) {
+        void* p = nullptr;
+        hipError_t e = fzb_dev_alloc(&p, (size_t)units * 16 + 1024);
+        if (e == hipSuccess) e = hipMemset(p, 0, (size_t)units * 16 + 1024);
+        if (e == hipSuccess && live && keep_units) e = hipMemcpy(p, c->own_view[0], (size_t)keep_units * 16, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (p) (void)hipFree(p);
+            return e;
+        }
+        if (c->own_view[0]) (void)hipFree(c->own_view[0]);
+        c->own_view[0] = p;
+        c->view_cap_units = units;
+        if (live) c->dev.vbytes = (const u8*)p;
+    }
+    return hipSuccess;
+}
+
+// Brings the view in step with the list, whose figures (n, uniform_len, n_over256, max_short) are current.  The view's data for the first
+// `n_valid` haystacks is good (0 for a first build; the old length after an append; the new one after a truncate): only the tiles from
+// the one that holds haystack n_valid on are sorted and filled - the last, partial tile of before and what came behind it.
+// No view, and FZB_OK, when the list does not call for one or the device has no room (see fzb_build_filter_view).
+int view_sync(fzb_corpus* c, u64 n_valid) {
+    const u64 n = c->dev.n;
+    const bool want = !fzb_knobs().no_filter_view && n && !c->dev.uniform_len && c->max_short > 32 && c->n_over256 <= long_cap_of(n);
+    auto bail = [&](hipError_t e) {
+        (void)view_deactivate(c);
+        view_free(c);
+        return fzb_fail(FZB_ERR_HIP, std::string("filter view: ") + hipGetErrorString(e));
+    };
+    auto no_room = [&]() {  // the view is an accelerator, not part of the corpus: the filter then streams the canonical layout
+        (void)view_deactivate(c);
+        view_free(c);
+        return FZB_OK;
+    };
+    hipError_t e;
+    if (!want) {
+        e = view_deactivate(c);
+        return e == hipSuccess ? FZB_OK : bail(e);
+    }
+    const bool live = c->dev.vbytes != nullptr;
+    if (!live) n_valid = 0;
+    n_valid = std::min(n_valid, n);
+    const u64 t0 = n_valid / UP_TILE, ntiles = up_tiles(n), tiles_r = ntiles - t0;
+    const u64 old_units = live ? c->view_units : 0, old_tiles = live ? up_tiles(c->view_items) : 0;
+    e = ensure_tiles_scratch(c, tiles_r);
+    if (e == hipSuccess) e = view_ensure_room(c, std::max<u64>(n, c->cap_items), 0, std::min(c->view_items, t0 * UP_TILE + UP_TILE), old_units);
+    if (e == hipErrorOutOfMemory) return no_room();
+    if (e != hipSuccess) return bail(e);
+    // where tile t0 starts in the view: where it started before, or - a tile of its own - behind everything
+    u64 base_units = old_units;
+    if (live && t0 < old_tiles) {
+        u32 g = 0;
+        e = hipMemcpy(&g, (const u32*)c->own_view[1] + t0 * (UP_TILE / 64), 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return bail(e);
+        base_units = g;
+    }
+    UpStats* d_stats = (UpStats*)c->stage_stats;
+    u64* d_vt = (u64*)c->stage_tiles;
+    UpStats init = UP_STATS_INIT;
+    init.bad = live ? c->dev.n_long : 0;  // the outlier list is appended to
+    e = hipMemcpy(d_stats, &init, sizeof(init), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return bail(e);
+    if (live && c->dev.n_long && c->view_items > t0 * UP_TILE)
+        hipLaunchKernelGGL(k_up_vlong_prune, dim3(1), dim3(1024), 0, nullptr, (u32*)c->own_view[5], c->dev.n_long, (u32)(t0 * UP_TILE), d_stats);
+    const u32 long_room = (u32)long_cap_of(c->view_cap_items);
+    if (tiles_r) {
+        if (c->dev.ends_u64)
+            hipLaunchKernelGGL((k_up_view_sort<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
+        else
+            hipLaunchKernelGGL((k_up_view_sort<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
+        hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_vt, tiles_r, d_stats);  // total_padded = the rebuilt tiles' size in 16-byte units
+    }
+    UpStats vst = UP_STATS_INIT;
+    e = hipMemcpy(&vst, d_stats, sizeof(vst), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return bail(e);
+    const u64 units = base_units + vst.total_padded;
+    // no view: group offsets beyond 32 bits of 16-byte units (64 GB); (more outliers than the list holds: decided above, from the host's count)
+    if (units > 0xFFFFFFF0ull || vst.bad > long_cap_of(n)) {
+        e = view_deactivate(c);
+        return e == hipSuccess ? FZB_OK : bail(e);
+    }
+    if (units > c->view_cap_units || !c->own_view[0]) {  // grows like the canonical arrays: twice the old room, or what a full list of the reserved size can take
+        const u64 geo = std::max<u64>({units, 2 * c->view_cap_units, c->cap_items > n ? view_units_bound(c->cap_items, c->cap_bytes) : 0});
+        e = view_ensure_room(c, c->view_cap_items, geo, 0, base_units);
+        if (e == hipErrorOutOfMemory && geo > units) { (void)hipGetLastError(); e = view_ensure_room(c, c->view_cap_items, units, 0, base_units); }
+        if (e == hipErrorOutOfMemory) return no_room();
+        if (e != hipSuccess) return bail(e);
+    }
+    // the rebuilt tiles' old blocks: cleared (zero vectors behind a group's shorter members); everything behind the used part is zero already
+    if (old_units > base_units) {
+        e = hipMemsetAsync((u8*)c->own_view[0] + base_units * 16, 0, (old_units - base_units) * 16, nullptr);
+        if (e != hipSuccess) return bail(e);
+    }
+    if (tiles_r) {
+        if (c->dev.ends_u64)
+            hipLaunchKernelGGL((k_up_view_fill<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
+        else
+            hipLaunchKernelGGL((k_up_view_fill<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
+    }
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return bail(e);
+    c->dev.vbytes = (const u8*)c->own_view[0];
+    c->dev.vgofs = (const u32*)c->own_view[1];
+    c->dev.vgnv = (const u8*)c->own_view[2];
+    c->dev.vlen = (const u16*)c->own_view[3];
+    c->dev.vperm = (const u16*)c->own_view[4];
+    c->dev.vlong = (const u32*)c->own_view[5];
+    c->dev.view_nv = (u32)((c->max_short + 15) >> 4);  // the view's widest member in vectors (outliers are not in it)
+    c->dev.n_long = (u32)vst.bad;
+    c->view_units = units;
+    c->view_items = n;
+    return FZB_OK;
+}
+
+// min / max length and the outlier figures of the first n haystacks of the resident list, into the corpus' host figures
+hipError_t measure_resident(fzb_corpus* c, u64 n) {
+    hipError_t e = ensure_tiles_scratch(c, 1);
+    if (e != hipSuccess) return e;
+    UpStats st = UP_STATS_INIT;
+    if (n) {
+        e = hipMemcpy(c->stage_stats, &UP_STATS_INIT, sizeof(UpStats), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        const unsigned grid = (unsigned)std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 2048);
+        if (c->dev.ends_u64) hipLaunchKernelGGL((k_up_measure<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (UpStats*)c->stage_stats);
+        else hipLaunchKernelGGL((k_up_measure<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (UpStats*)c->stage_stats);
+        e = hipMemcpy(&st, c->stage_stats, sizeof(st), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+    }
+    c->min_len = st.min_len; c->max_len = st.max_len; c->n_over256 = st.n_long; c->max_short = st.max_short;
+    return hipSuccess;
+}
+
 }  // namespace
 
 // The streaming filter's view of a corpus whose canonical layout is resident (uploaded or borrowed), on the CURRENT device.  Sets
@@ -335,76 +651,15 @@ hipError_t h2d_all(const std::vector<H2DJob>& jobs, int device) {
 // the canonical layout), nothing beyond 32, a uniform-length list - or when the device has no room: the view is an accelerator,
 // not part of the corpus (the filter then streams the canonical layout).  Any other error is reported.
 int fzb_build_filter_view(fzb_corpus* c) {
-    const bool want_view = !fzb_knobs().no_filter_view;
-    const u64 n = c->dev.n;
-    if (!want_view || !n || c->dev.uniform_len || c->dev.vbytes) return FZB_OK;
-    const u64 ntiles = (n + UP_TILE - 1) / UP_TILE;
-    const size_t ngroups = (size_t)ntiles * (UP_TILE / 64);
-    u64* d_vt = nullptr;
-    UpStats* d_stats = nullptr;
-    // outliers (haystacks beyond 256 bytes) the view tolerates: one in 256, at least 64 - more, and the list is not a short-haystack list
-    const u32 long_cap = (u32)std::min<u64>(n / 256 + 64, 0x7FFFFFFFu);
-    auto drop_view = [&]() {
-        if (d_vt) (void)hipFree(d_vt);
-        if (d_stats) (void)hipFree(d_stats);
-        d_vt = nullptr;
-        d_stats = nullptr;
-        for (int q = 0; q < 6; q++) { if (c->own_view[q]) (void)hipFree(c->own_view[q]); c->own_view[q] = nullptr; }
-        (void)hipGetLastError();
-    };
-    auto bail = [&](hipError_t e) {
-        drop_view();
-        return fzb_fail(FZB_ERR_HIP, std::string("filter view: ") + hipGetErrorString(e));
-    };
-    hipError_t e = fzb_dev_alloc(&c->own_view[3], n * 2);
-    if (e == hipSuccess) e = fzb_dev_alloc(&c->own_view[4], n * 2);
-    if (e == hipSuccess) e = fzb_dev_alloc(&c->own_view[2], ngroups);
-    if (e == hipSuccess) e = fzb_dev_alloc(&c->own_view[1], ngroups * 4);
-    if (e == hipSuccess) e = fzb_dev_alloc(&c->own_view[5], (size_t)long_cap * 4);
-    if (e == hipSuccess) e = fzb_dev_alloc((void**)&d_vt, (size_t)ntiles * 8);
-    if (e == hipSuccess) e = fzb_dev_alloc((void**)&d_stats, sizeof(UpStats));
-    if (e == hipErrorOutOfMemory) { drop_view(); return FZB_OK; }
-    if (e != hipSuccess) return bail(e);
-    const UpStats init{0, ~(u64)0, 0, 0};
-    e = hipMemcpy(d_stats, &init, sizeof(init), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(e);
-    if (c->dev.ends_u64)
-        hipLaunchKernelGGL((k_up_view_sort<u64>), dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_cap);
-    else
-        hipLaunchKernelGGL((k_up_view_sort<u32>), dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_cap);
-    hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_vt, ntiles, d_stats);  // total_padded = the view's size in 16-byte units
-    UpStats vst{0, 0, 0, 0};
-    e = hipMemcpy(&vst, d_stats, sizeof(vst), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bail(e);
-    // (min_len / max_len are in VECTORS here, outliers excluded; bad = the number of outliers) no view: more outliers beyond 256 bytes than
-    // the list holds, nothing beyond 32 bytes (the short kernels serve that list), or group offsets beyond 32 bits of 16-byte units (64 GB)
-    if (vst.bad > long_cap || vst.max_len > 16 || vst.max_len <= 2 || vst.total_padded > 0xFFFFFFF0ull) { drop_view(); return FZB_OK; }
-    const u64 view_bytes = vst.total_padded * 16;
-    e = fzb_dev_alloc(&c->own_view[0], view_bytes + 1024);
-    if (e == hipErrorOutOfMemory) { drop_view(); return FZB_OK; }
-    if (e == hipSuccess) e = hipMemsetAsync(c->own_view[0], 0, view_bytes + 1024, nullptr);
-    if (e != hipSuccess) return bail(e);
-    if (c->dev.ends_u64)
-        hipLaunchKernelGGL((k_up_view_fill<u64>), dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1]);
-    else
-        hipLaunchKernelGGL((k_up_view_fill<u32>), dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1]);
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return bail(e);
-    (void)hipFree(d_vt);
-    (void)hipFree(d_stats);
-    c->dev.vbytes = (const u8*)c->own_view[0];
-    c->dev.vgofs = (const u32*)c->own_view[1];
-    c->dev.vgnv = (const u8*)c->own_view[2];
-    c->dev.vlen = (const u16*)c->own_view[3];
-    c->dev.vperm = (const u16*)c->own_view[4];
-    c->dev.view_nv = (u32)vst.max_len;
-    c->dev.vlong = (const u32*)c->own_view[5];
-    c->dev.n_long = (u32)vst.bad;
-    return FZB_OK;
+    if (!c->dev.n || c->dev.uniform_len || c->dev.vbytes) return FZB_OK;
+    if (!c->own_bytes) {  // borrowed: the lengths are read from the end offsets (an uploaded corpus knows its figures)
+        const hipError_t e = measure_resident(c, c->dev.n);
+        if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("filter view: ") + hipGetErrorString(e));
+    }
+    return view_sync(c, 0);
 }
 
-// For a BORROWED corpus (fzb_corpus_from_device; fzb_corpus_upload builds the view itself): the lengths are read from the end offsets,
+// For a BORROWED corpus (fzb_corpus_upload builds the view itself): the lengths are read from the end offsets,
 // so no hint is needed and a wrong fzb_corpus_set_max_len cannot mislead it.  *out_built (optional) = 1 when the corpus has a view now.
 extern "C" int fzb_corpus_build_view(fzb_corpus* c, int* out_built) {
     if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
@@ -423,14 +678,13 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
     int device = 0;
     HIPCHK(hipGetDevice(&device));
     const u64 raw_bytes = n ? end_offsets[n - 1] - ends_base : 0;
-    const u64 ntiles = (n + UP_TILE - 1) / UP_TILE;
+    const u64 ntiles = up_tiles(n);
     auto c = new fzb_corpus();
+    c->device = device;
     u8* d_raw = nullptr;
     u64* d_ends64 = nullptr;
-    u64* d_tiles = nullptr;
-    UpStats* d_stats = nullptr;
     auto cleanup = [&]() {
-        for (void* p : {(void*)d_raw, (void*)d_ends64, (void*)d_tiles, (void*)d_stats})
+        for (void* p : {(void*)d_raw, (void*)d_ends64})
             if (p) (void)hipFree(p);
     };
     auto bail = [&](hipError_t e, const char* what) {
@@ -440,19 +694,15 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
     };
     hipError_t e = fzb_dev_alloc((void**)&d_raw, raw_bytes + 96);
     if (e == hipSuccess) e = fzb_dev_alloc((void**)&d_ends64, std::max<size_t>(n, 1) * 8);
-    if (e == hipSuccess) e = fzb_dev_alloc((void**)&d_tiles, std::max<u64>(ntiles, 1) * 8);
-    if (e == hipSuccess) e = fzb_dev_alloc((void**)&d_stats, sizeof(UpStats));
+    if (e == hipSuccess) e = ensure_tiles_scratch(c, ntiles);  // (tile sums + stats stay with the corpus: the view's passes and later appends use them)
     if (e != hipSuccess) return bail(e, "device buffers");
-    const UpStats init{0, ~(u64)0, 0, 0};
-    e = hipMemcpy(d_stats, &init, sizeof(init), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_raw + raw_bytes, 0, 96);
+    e = hipMemset(d_raw + raw_bytes, 0, 96);
     if (e == hipSuccess) e = h2d_all({H2DJob{d_ends64, end_offsets, n * 8}, H2DJob{d_raw, bytes, (size_t)raw_bytes}}, device);
     if (e != hipSuccess) return bail(e, "host to device");
-    UpStats st{0, 0, 0, 0};
+    c->h2d_bytes = raw_bytes + (u64)n * 8;
+    UpStats st = UP_STATS_INIT;
     if (n) {
-        hipLaunchKernelGGL(k_up_tiles, dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, d_ends64, (u64)n, ends_base, d_tiles, d_stats);
-        hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_tiles, ntiles, d_stats);
-        e = hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost);  // the one synchronisation of the upload: sizes the padded buffer
+        e = batch_measure(d_ends64, n, ends_base, (u64*)c->stage_tiles, (UpStats*)c->stage_stats, &st);  // the one synchronisation of the upload: sizes the padded buffer
         if (e != hipSuccess) return bail(e, "layout pass");
         if (st.bad) {
             cleanup();
@@ -466,8 +716,8 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
     c->dev.n = n;
     c->dev.total_bytes = total;
     c->dev.ends_u64 = ends_u64;
-    c->dev.max_len = (u32)std::min<u64>(st.max_len, 0xFFFFFFFFu);
-    c->dev.uniform_len = (n && st.min_len == st.max_len && st.max_len && st.max_len < 0xFFFFFFFFu) ? (u32)st.max_len : 0u;  // kernels then skip the end offsets
+    c->min_len = st.min_len; c->max_len = st.max_len; c->n_over256 = st.n_long; c->max_short = st.max_short;
+    set_measured(c);
     e = fzb_dev_alloc(&c->own_ends, std::max<size_t>(n, 1) * (ends_u64 ? 8 : 4));
     if (e == hipSuccess && !adopt) e = fzb_dev_alloc(&c->own_bytes, total);
     if (e != hipSuccess) return bail(e, "padded layout");
@@ -478,25 +728,19 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
         e = hipMemsetAsync((u8*)c->own_bytes + st.total_padded, 0, 96, nullptr);
         if (e != hipSuccess) return bail(e, "padded layout");
     }
-    if (n) {
-#define FZB_UP_BUILD(ET, COPY) \
-    hipLaunchKernelGGL((k_up_build<ET, COPY>), dim3((unsigned)ntiles), dim3(UP_THREADS), 0, nullptr, (const u8*)(adopt ? (u8*)c->own_bytes : d_raw), d_ends64, (u64)n, ends_base, d_tiles, (u8*)c->own_bytes, (ET*)c->own_ends)
-        if (ends_u64) { if (adopt) FZB_UP_BUILD(u64, false); else FZB_UP_BUILD(u64, true); }
-        else { if (adopt) FZB_UP_BUILD(u32, false); else FZB_UP_BUILD(u32, true); }
-#undef FZB_UP_BUILD
-    }
+    c->cap_items = std::max<size_t>(n, 1);
+    c->cap_bytes = total;
+    if (n) batch_lay_out(adopt ? (const u8*)c->own_bytes : d_raw, d_ends64, n, ends_base, (const u64*)c->stage_tiles, (u8*)c->own_bytes, 0, c->own_ends, 0, ends_u64, !adopt);
     c->dev.bytes = (const u8*)c->own_bytes;
     c->dev.ends = c->own_ends;
     // the streaming filter's view (CorpusDev::vbytes): ragged lists whose haystacks are 33..256 bytes.  A second copy of the bytes (+ ~5 %
     // for the zero vectors behind shorter group members, + 4.2 bytes per haystack); FZB_FILTER_VIEW=0 turns it off.
-    if (n && !c->dev.uniform_len && c->dev.max_len > 32) {  // (a list with more than a few haystacks beyond 256 bytes gets none: the builder decides)
-        int rc = fzb_build_filter_view(c);
-        if (rc) {
-            const std::string msg = fzb_last_error();
-            cleanup();
-            fzb_corpus_free(c);
-            return fzb_fail(rc, msg);
-        }
+    int rc = view_sync(c, 0);  // (a list with more than a few haystacks beyond 256 bytes gets none)
+    if (rc) {
+        const std::string msg = fzb_last_error();
+        cleanup();
+        fzb_corpus_free(c);
+        return fzb_fail(rc, msg);
     }
     e = hipDeviceSynchronize();  // the temporaries are released below; the corpus is complete when the call returns
     if (e == hipSuccess) e = hipGetLastError();
@@ -509,3 +753,241 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
 extern "C" int fzb_corpus_upload(const uint8_t* bytes, const uint64_t* end_offsets, size_t n, fzb_corpus** out) {
     return fzb_corpus_upload_impl(bytes, end_offsets, n, 0, out);
 }
+
+// ---- a corpus that grows ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// set-up calls on a corpus the library owns, on its device, with nothing of the device's earlier work outstanding
+int grow_begin(fzb_corpus* c, const char* what) {
+    if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    if (!c->own_bytes)
+        return fzb_fail(FZB_ERR_INVALID, std::string(what) + ": the corpus borrows its device memory (fzb_corpus_from_device); only a corpus made by fzb_corpus_upload can change");
+    int device = 0;
+    HIPCHK(hipGetDevice(&device));
+    if (device != c->device) return fzb_fail(FZB_ERR_INVALID, std::string(what) + ": the corpus lives on device " + std::to_string(c->device) + ", the current device is " + std::to_string(device));
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
+}
+
+// a fresh device buffer of `bytes` (first try) or `exact` bytes; *got = the size obtained
+hipError_t alloc_geometric(void** p, u64 bytes, u64 exact, u64* got) {
+    hipError_t e = fzb_dev_alloc(p, bytes);
+    *got = bytes;
+    if (e == hipErrorOutOfMemory && exact < bytes) {
+        (void)hipGetLastError();
+        e = fzb_dev_alloc(p, exact);
+        *got = exact;
+    }
+    return e;
+}
+
+// Room for `items` haystacks and `bytes` bytes of padded layout + tail in the canonical arrays; what is resident moves device to device.
+// geometric: an array that lacks room gets at least twice what it had (the exact size when the device refuses that).  On an error
+// nothing has changed.
+hipError_t canon_ensure_room(fzb_corpus* c, u64 items, u64 bytes, bool geometric) {
+    const u64 esz = c->dev.ends_u64 ? 8 : 4;
+    void *nb = nullptr, *ne = nullptr;
+    u64 got_b = 0, got_e = 0;
+    hipError_t e = hipSuccess;
+    u64 want_bytes = bytes > c->cap_bytes ? (geometric ? std::max(bytes, 2 * c->cap_bytes) : bytes) : c->cap_bytes;
+    if (items > c->cap_items) {
+        const u64 want_items = geometric ? std::max(items, 2 * c->cap_items) : items;
+        // the bytes follow the items: room for the new item capacity at the list's average length so far (+ 1/16), so that the two arrays
+        // regrow in the same call and the regrows of a list ingested in equal batches stay logarithmic in their number
+        if (geometric && bytes > 96) want_bytes = std::max(want_bytes, std::min<u64>((u64)((double)(bytes - 96) / (double)items * (double)want_items * 1.0625) + 96,
+                                                                                       c->dev.ends_u64 ? ~(u64)0 : 0xFFFFFFF0ull));
+        e = alloc_geometric(&ne, want_items * esz, items * esz, &got_e);
+        if (e == hipSuccess && c->dev.n) e = hipMemcpy(ne, c->own_ends, c->dev.n * esz, hipMemcpyDeviceToDevice);
+    }
+    if (e == hipSuccess && want_bytes > c->cap_bytes) {
+        if (bytes > c->cap_bytes) e = alloc_geometric(&nb, want_bytes, bytes, &got_b);
+        else if (fzb_dev_alloc(&nb, want_bytes) == hipSuccess) got_b = want_bytes;  // (following the items only: refused by the device, the bytes stay as they are)
+        else { nb = nullptr; (void)hipGetLastError(); }
+        const u64 used = c->dev.total_bytes - 96;
+        if (e == hipSuccess && nb && used) e = hipMemcpy(nb, c->own_bytes, used, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && nb) e = hipMemset((u8*)nb + used, 0, got_b - used);  // zero behind the list, wherever it will end
+    }
+    if (e != hipSuccess) {
+        if (nb) (void)hipFree(nb);
+        if (ne) (void)hipFree(ne);
+        return e;
+    }
+    if (ne) {
+        (void)hipFree(c->own_ends);
+        c->own_ends = ne;
+        c->dev.ends = ne;
+        c->cap_items = got_e / esz;
+    }
+    if (nb) {
+        (void)hipFree(c->own_bytes);
+        c->own_bytes = nb;
+        c->dev.bytes = (const u8*)nb;
+        c->cap_bytes = got_b;
+    }
+    if (nb || ne) c->regrows++;
+    return hipSuccess;
+}
+
+// the landing place of a batch as it arrives: `items` u64 offsets, `raw` bytes (+ the slack k_up_build's dword reads may touch)
+hipError_t stage_ensure_room(fzb_corpus* c, u64 items, u64 raw) {
+    hipError_t e = ensure_tiles_scratch(c, up_tiles(items) + 1);
+    if (e == hipSuccess && (!c->stage_ends || c->stage_items_cap < items)) {
+        void* p = nullptr;
+        e = fzb_dev_alloc(&p, std::max<u64>(items, 1) * 8);
+        if (e == hipSuccess) {
+            if (c->stage_ends) (void)hipFree(c->stage_ends);
+            c->stage_ends = p;
+            c->stage_items_cap = std::max<u64>(items, 1);
+        }
+    }
+    if (e == hipSuccess && (!c->stage_raw || c->stage_raw_cap < raw)) {
+        void* p = nullptr;
+        e = fzb_dev_alloc(&p, raw + 96);
+        if (e == hipSuccess) {
+            if (c->stage_raw) (void)hipFree(c->stage_raw);
+            c->stage_raw = p;
+            c->stage_raw_cap = raw;
+        }
+    }
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
+    int rc = grow_begin(c, "fzb_corpus_reserve");
+    if (rc) return rc;
+    if (items > 0xFFFFFFFFull)
+        return fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(items) + " > 4294967295 (index offset: 0)");
+    if (!c->dev.ends_u64 && bytes + 96 > 0xFFFFFFF0ull)
+        return fzb_fail(FZB_ERR_CAPACITY, "fzb_corpus_reserve: a corpus whose end offsets are 32-bit holds less than 4 GiB of padded bytes");
+    const u64 regrows = c->regrows;
+    hipError_t e = canon_ensure_room(c, items, bytes + 96, false);
+    c->regrows = regrows;  // (room asked for is not a regrow)
+    // a batch may be as large as the room: its landing place, and - unless FZB_FILTER_VIEW=0 - the view's arrays, are sized for that
+    if (e == hipSuccess) e = stage_ensure_room(c, c->cap_items - c->dev.n, c->cap_bytes - c->dev.total_bytes);
+    if (e == hipSuccess) e = ensure_tiles_scratch(c, up_tiles(c->cap_items) + 1);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_reserve: ") + hipGetErrorString(e));
+    if (!fzb_knobs().no_filter_view) {
+        const u64 live_units = c->dev.vbytes ? c->view_units : 0;
+        e = view_ensure_room(c, c->cap_items, std::max(c->view_cap_units, view_units_bound(c->cap_items, c->cap_bytes)), c->view_items, live_units);
+        if (e == hipErrorOutOfMemory) (void)hipGetLastError();  // the view is an accelerator: the corpus has its room, the view grows - or goes - when it must
+        else if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_reserve (filter view): ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
+}
+
+int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_offsets, size_t n_new) {
+    if (!c || (n_new && !end_offsets)) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    const u64 raw = n_new ? end_offsets[n_new - 1] : 0;
+    if (raw && !bytes) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    int rc = grow_begin(c, "fzb_corpus_append");
+    if (rc) return rc;
+    if (!n_new) return FZB_OK;
+    const u64 n_old = c->dev.n;
+    if (n_old + (u64)n_new > 0xFFFFFFFFull)
+        return fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n_old + (u64)n_new) + " > 4294967295 (index offset: 0)");
+    // the batch travels as it is, one copy per array, and is validated where it lands: nothing of the corpus is written before
+    hipError_t e = stage_ensure_room(c, n_new, raw);
+    if (e == hipSuccess) e = h2d_all({H2DJob{c->stage_ends, end_offsets, n_new * 8}, H2DJob{c->stage_raw, bytes, (size_t)raw}}, c->device);
+    UpStats st = UP_STATS_INIT;
+    if (e == hipSuccess) e = batch_measure((const u64*)c->stage_ends, n_new, 0, (u64*)c->stage_tiles, (UpStats*)c->stage_stats, &st);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_append (host to device): ") + hipGetErrorString(e));
+    if (st.bad) return fzb_fail(FZB_ERR_INVALID, "end_offsets must be non-decreasing");
+    const u64 used = c->dev.total_bytes - 96;  // a multiple of 16: where the batch's first haystack starts
+    const u64 total = used + st.total_padded + 96;
+    if (!c->dev.ends_u64 && total > 0xFFFFFFF0ull)
+        return fzb_fail(FZB_ERR_CAPACITY, "fzb_corpus_append: the batch takes the padded list to 4 GiB, beyond this corpus' 32-bit end offsets; upload such a list in one piece");
+    e = canon_ensure_room(c, n_old + n_new, total, true);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_append (room for the batch): ") + hipGetErrorString(e));
+    batch_lay_out((const u8*)c->stage_raw, (const u64*)c->stage_ends, n_new, 0, (const u64*)c->stage_tiles, (u8*)c->own_bytes, used, c->own_ends, n_old, c->dev.ends_u64 != 0, true);
+    c->h2d_bytes += raw + (u64)n_new * 8;
+    c->dev.n = n_old + n_new;
+    c->dev.total_bytes = total;
+    c->min_len = std::min(c->min_len, st.min_len);
+    c->max_len = std::max(c->max_len, st.max_len);
+    c->max_short = std::max(c->max_short, st.max_short);
+    c->n_over256 += st.n_long;
+    set_measured(c);
+    rc = view_sync(c, n_old);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc) return rc;
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_append (layout kernels): ") + hipGetErrorString(e));
+    return FZB_OK;
+}
+
+int fzb_corpus_truncate(fzb_corpus* c, size_t n) {
+    int rc = grow_begin(c, "fzb_corpus_truncate");
+    if (rc) return rc;
+    if (n > c->dev.n) return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_truncate: " + std::to_string(n) + " is beyond the corpus' " + std::to_string(c->dev.n) + " haystacks");
+    if (n == c->dev.n) return FZB_OK;
+    u64 used = 0;
+    if (n) {  // the kept list ends where its last haystack does, rounded up to the layout's 16 bytes
+        u64 last = 0;
+        const size_t esz = c->dev.ends_u64 ? 8 : 4;
+        HIPCHK(hipMemcpy(&last, (const u8*)c->own_ends + (n - 1) * esz, esz, hipMemcpyDeviceToHost));
+        used = (last + 15) & ~(u64)15;
+    }
+    const u64 old_used = c->dev.total_bytes - 96;
+    if (old_used > used) HIPCHK(hipMemsetAsync((u8*)c->own_bytes + used, 0, old_used - used, nullptr));  // gaps and tail are zero
+    hipError_t e = measure_resident(c, n);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_truncate: ") + hipGetErrorString(e));
+    c->dev.n = n;
+    c->dev.total_bytes = used + 96;
+    set_measured(c);
+    rc = view_sync(c, n);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc) return rc;
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_truncate: ") + hipGetErrorString(e));
+    return FZB_OK;
+}
+
+int fzb_corpus_info(const fzb_corpus* c, uint64_t out[12]) {
+    if (!c || !out) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    const bool own = c->own_bytes != nullptr;
+    out[0] = c->dev.n;
+    out[1] = own ? std::max<u64>(c->cap_items, c->dev.n) : c->dev.n;
+    out[2] = c->dev.total_bytes >= 96 && own ? c->dev.total_bytes - 96 : c->dev.total_bytes;
+    out[3] = own ? c->cap_bytes - 96 : c->dev.total_bytes;
+    out[4] = c->dev.max_len;
+    out[5] = c->dev.uniform_len;
+    out[6] = c->dev.vbytes != nullptr;
+    out[7] = c->dev.vbytes ? c->dev.view_nv : 0;
+    out[8] = c->dev.vbytes ? c->dev.n_long : 0;
+    out[9] = c->dev.ends_u64 != 0;
+    out[10] = c->regrows;
+    out[11] = c->h2d_bytes;
+    return FZB_OK;
+}
+
+int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes) {
+    if (!c || !out_bytes) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    const u64 n = c->dev.n, groups = up_tiles(n) * (UP_TILE / 64);
+    const bool view = c->dev.vbytes != nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+        case 0: src = c->dev.bytes; bytes = c->own_bytes ? (size_t)c->dev.total_bytes : 0; break;  // (a borrowed buffer's tail is its owner's)
+        case 1: src = c->dev.ends; bytes = (size_t)n * (c->dev.ends_u64 ? 8 : 4); break;
+        case 2: src = c->dev.vbytes; bytes = view ? (size_t)c->view_units * 16 : 0; break;
+        case 3: src = c->dev.vgofs; bytes = view ? (size_t)groups * 4 : 0; break;
+        case 4: src = c->dev.vgnv; bytes = view ? (size_t)groups : 0; break;
+        case 5: src = c->dev.vlen; bytes = view ? (size_t)n * 2 : 0; break;
+        case 6: src = c->dev.vperm; bytes = view ? (size_t)n * 2 : 0; break;
+        case 7: src = c->dev.vlong; bytes = view ? (size_t)c->dev.n_long * 4 : 0; break;
+        default: return fzb_fail(FZB_ERR_INVALID, "fzb_debug_corpus_read: unknown array " + std::to_string(what));
+    }
+    *out_bytes = bytes;
+    if (!bytes) return FZB_OK;
+    if (!host_out || cap_bytes < bytes) return fzb_fail(FZB_ERR_CAPACITY, "fzb_debug_corpus_read: the array has " + std::to_string(bytes) + " bytes");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    return FZB_OK;
+}
+
+}  // extern "C"

@@ -124,6 +124,37 @@ int fzb_corpus_set_uniform_len(fzb_corpus* c, uint32_t len);
 void fzb_corpus_free(fzb_corpus* c);
 size_t fzb_corpus_len(const fzb_corpus* c);
 
+/* A corpus that GROWS (a picker's list arrives in batches while the user types).  For a corpus the library owns - made by
+ * fzb_corpus_upload, also with n = 0, which is how a picker starts; a borrowed one (fzb_corpus_from_device) gets FZB_ERR_INVALID.
+ * After any sequence of these calls the corpus answers every query - every entry point that takes an fzb_corpus - exactly as a
+ * fzb_corpus_upload of the same list would: same padded-16 layout, same measured max_len / uniform_len (fzb_corpus_set_max_len /
+ * _set_uniform_len accept the values as they are after the call), same decision about the filter's view.  fzb_sharded_corpus and the
+ * RCCL form are out of scope: a sharded corpus stays as uploaded.
+ * All three are SET-UP calls like the upload: they wait for the device's outstanding work on entry and are complete on return, on the
+ * device the corpus was uploaded on (which must be current).  The caller must not run them concurrently with queries over the same
+ * corpus from other threads.  An error leaves the corpus as it was, answering as before the call. */
+/* room for `items` haystacks and `bytes` padded bytes without another device allocation; never shrinks */
+int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes);
+/* (padded bytes: every haystack rounded up to 16, at most the raw bytes + 15 per haystack.  The room covers the canonical layout, the
+ * landing place of a batch as large as the room, and - unless FZB_FILTER_VIEW=0 - the filter's view of a full list.  With
+ * fzb_matcher_reserve / fzb_multi_matcher_reserve made afterwards - they size for max(len, reserved items) - neither an append within
+ * the room nor a query allocates device memory.) */
+/* haystacks n .. n+n_new-1: `bytes` = the batch's haystacks back to back, end_offsets[i] = exclusive end of batch item i
+ * counted from the batch's first byte (what pack() yields for the batch alone) */
+int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_offsets, size_t n_new);
+/* (Each haystack crosses the link once: the two arrays are copied as they are and laid out on the device behind the last haystack;
+ * nothing resident is copied unless room is lacking - then the array that lacks it grows to at least twice its size, or to the exact
+ * size when the device refuses that, FZB_ERR_HIP when it refuses both.  The filter's view is rebuilt from the last, partial tile of
+ * 1024 haystacks on.  n_new == 0 is a no-op.  Offsets that decrease: FZB_ERR_INVALID "end_offsets must be non-decreasing"; more than
+ * 4 294 967 295 haystacks: FZB_ERR_PANIC with the reference's text.  End offsets stay 32-bit on a corpus that was uploaded with less
+ * than 4 GiB of padded bytes: a batch that would take it past 0xFFFFFFF0 is REFUSED with FZB_ERR_CAPACITY - they are not widened.) */
+/* keep the first n haystacks (n <= len; n == 0 empties the corpus); capacity is kept */
+int fzb_corpus_truncate(fzb_corpus* c, size_t n);
+/* introspection: out[0]=items [1]=item capacity [2]=padded bytes used [3]=byte capacity [4]=max_len [5]=uniform_len [6]=has a filter view
+ * (0/1) [7]=view_nv [8]=outliers (haystacks beyond 256 bytes the view lists) [9]=end offsets are u64 (0/1) [10]=regrows so far
+ * [11]=bytes copied host to device so far (haystack bytes + 8 per offset) */
+int fzb_corpus_info(const fzb_corpus* c, uint64_t out[12]);
+
 /* `Matcher::match_list(&haystacks)` (src/matcher/mod.rs:212-222) = `match_list_into(.., offset 0)` ->
 * `Specialized::match_list::<TYPOS,UNICODE,_>` (src/matcher/algo.rs:78-103) and the reverse / `radix_sort_matches`
  * post-step (src/sort.rs:6-40), all on the GPU.  `*out` is malloc'd by the library
@@ -415,6 +446,11 @@ void fzb_debug_reload_knobs(void);
 /* test hook: device allocations (hipMalloc) this process's library has made so far - how a test sees that a re-query allocates nothing.
  * Page-locked host result lists are not counted. */
 int fzb_debug_device_allocs(uint64_t* out);
+
+/* test hook: copies one of the corpus' device arrays to the host - what: 0 = canonical bytes up to the padded size + the 96-byte tail,
+ * 1 = end offsets (u32 or u64, fzb_corpus_info out[9]), 2 = vbytes, 3 = vgofs, 4 = vgnv, 5 = vlen, 6 = vperm, 7 = vlong (2..7: the
+ * filter's view, nothing without one).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
+int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes);
 
 #ifdef __cplusplus
 }

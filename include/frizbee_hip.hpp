@@ -167,6 +167,30 @@ class Corpus {
     }
     size_t len() const { return fzb_corpus_len(h_.get()); }
     const fzb_corpus* raw() const { return h_.get(); }
+    // A corpus that grows (fzb_corpus_append and friends): the batch becomes haystacks len() .. of the resident list, only the batch
+    // crosses the link.  `Corpus(std::vector<std::string>{})` followed by appends is how a picker starts.
+    template <typename Strings>
+    void append(const Strings& batch) {
+        std::string bytes;
+        std::vector<uint64_t> ends;
+        for (const auto& h : batch) {
+            const std::string_view v(h);
+            bytes.append(v.data(), v.size());
+            ends.push_back(bytes.size());
+        }
+        check(fzb_corpus_append(h_.get(), (const uint8_t*)bytes.data(), ends.data(), ends.size()));
+    }
+    // room for `items` haystacks and `bytes` padded bytes (<= raw bytes + 15 per haystack): appends within it allocate nothing
+    void reserve(size_t items, uint64_t bytes) { check(fzb_corpus_reserve(h_.get(), items, bytes)); }
+    void truncate(size_t n) { check(fzb_corpus_truncate(h_.get(), n)); }  // keep the first n haystacks; capacity is kept
+    struct Info {
+        uint64_t items, item_capacity, bytes, byte_capacity, max_len, uniform_len, has_view, view_nv, outliers, ends_u64, regrows, h2d_bytes;
+    };
+    Info info() const {
+        uint64_t o[12] = {};
+        check(fzb_corpus_info(h_.get(), o));
+        return Info{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11]};
+    }
 
   private:
     struct Del { void operator()(fzb_corpus* c) const { fzb_corpus_free(c); } };

@@ -87,6 +87,12 @@ extern "C" {
     fn fzb_matcher_free(m: *mut c_void);
     fn fzb_corpus_upload(bytes: *const u8, ends: *const u64, n: usize, out: *mut *mut c_void) -> c_int;
     fn fzb_corpus_free(c: *mut c_void);
+    // a corpus that grows: batches behind the resident list, room ahead of them, the first n kept (set-up calls, like the upload)
+    fn fzb_corpus_append(c: *mut c_void, bytes: *const u8, ends: *const u64, n_new: usize) -> c_int;
+    fn fzb_corpus_reserve(c: *mut c_void, items: usize, bytes: u64) -> c_int;
+    fn fzb_corpus_truncate(c: *mut c_void, n: usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_corpus_info(c: *const c_void, out: *mut u64) -> c_int;
     fn fzb_match_list(m: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_match_list_into(m: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_matches_free(p: *mut FzbMatch);
@@ -182,6 +188,22 @@ impl HipCorpus {
     }
     pub fn len(&self) -> usize {
         self.len
+    }
+    /// The batch becomes haystacks `len()..` of the resident list: only the batch crosses the link (a picker's list arrives in pieces;
+    /// `HipCorpus::new::<&str>(&[])` is how it starts).  Queries answer as over one upload of the whole list.
+    pub fn append<H: AsRef<str>>(&mut self, batch: &[H]) {
+        let (bytes, ends) = pack(batch);
+        check(unsafe { fzb_corpus_append(self.handle, bytes.as_ptr(), ends.as_ptr(), ends.len()) });
+        self.len += ends.len();
+    }
+    /// Room for `items` haystacks and `bytes` padded bytes (at most the raw bytes + 15 per haystack): appends within it allocate nothing.
+    pub fn reserve(&mut self, items: usize, bytes: u64) {
+        check(unsafe { fzb_corpus_reserve(self.handle, items, bytes) });
+    }
+    /// Keeps the first `n` haystacks; capacity is kept.
+    pub fn truncate(&mut self, n: usize) {
+        check(unsafe { fzb_corpus_truncate(self.handle, n) });
+        self.len = n;
     }
 }
 impl Drop for HipCorpus {

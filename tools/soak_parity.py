@@ -1,6 +1,7 @@
 """Parity soak on a GPU box: random needles, scorings, typo budgets, lane widths and list shapes - fresh seeds every run - HIP path against the
 oracle until the time budget is spent (tests/test_gpu_fuzz_isa.py's generators and checker, which raise with the first differing record and its
-haystack).  Usage: python tools/soak_parity.py [seconds=600] [seed=time | reuse]   Prints one line per 50 lists and a summary; exit code 1 on a difference."""
+haystack).  Usage: python tools/soak_parity.py [seconds=600] [seed=time | reuse | append]   Prints one line per 50 lists and a summary; exit code 1 on a
+difference.  `append`: every list reaches the device in random batches (fzb_corpus_append), now and then cut back (fzb_corpus_truncate) and appended again."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,7 +9,7 @@ import numpy as np
 import test_gpu_fuzz_isa as T
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 600.0
-seed = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != "reuse" else int(time.time())
+seed = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] not in ("reuse", "append") else int(time.time())
 REUSE = "reuse" in sys.argv[2:]  # one long-lived matcher per lane width, re-targeted by set_config / set_pattern: the workspace and table-upload paths of a session
 if REUSE:
     import frizbee_amd as F, oracle_lib as O
@@ -31,6 +32,38 @@ if REUSE:
             raise AssertionError((tag, "records", len(got), len(want), "first difference at", bad, got[bad:bad + 1].tolist(), want[bad:bad + 1].tolist()))
         return len(ends)
     T.check = _check_reuse
+if "append" in sys.argv[2:]:  # the list arrives in batches: a corpus that grows (and shrinks) must answer as the oracle does over the whole list
+    import frizbee_amd as F, oracle_lib as O
+    _split = np.random.default_rng(seed + 1)
+    def _batch(cp, data, ends, lo, hi):
+        b0 = int(ends[lo - 1]) if lo else 0
+        cp.append(packed=(np.ascontiguousarray(data[b0:int(ends[hi - 1]) + 1]), (ends[lo:hi] - np.uint64(b0)).astype(np.uint64)))
+    def _check_append(needle, data, ends, lanes, tag, **cfg):
+        pf, sw8, sw16 = T.LANE_TRIPLES[lanes]
+        om = O.Matcher(needle, lanes=(pf, sw8, sw16), sort="IndexAsc", **cfg)
+        fc = F.Config(max_typos=cfg.get("max_typos", 0), scoring=F.Scoring(*cfg.get("scoring", T.DEFAULT)), pf_lanes=pf,
+                      unicode=F.UnicodeMatching[cfg.get("unicode", "Smart")], casing=F.CaseMatching[cfg.get("casing", "Smart")])
+        fm = F.Matcher(needle, fc)
+        want = om.match_packed(data, ends)
+        data = np.concatenate([np.asarray(data, np.uint8), np.zeros(1, np.uint8)])
+        ends = np.asarray(ends, np.uint64)
+        n = len(ends)
+        cuts = sorted(set(int(x) for x in _split.integers(1, max(n, 2), int(_split.integers(1, 9))) if 0 < x < n))
+        edges = [0] + cuts + [n]
+        cp = F.Corpus([])
+        for k, (lo, hi) in enumerate(zip(edges[:-1], edges[1:])):
+            _batch(cp, data, ends, lo, hi)
+            if k and _split.random() < 0.3:  # cut back into an earlier batch, then bring the rest again
+                back = int(_split.integers(0, hi))
+                cp.truncate(back)
+                if back < hi:
+                    _batch(cp, data, ends, back, hi)
+        got = fm.match_list_into(cp)
+        if got.tolist() != want.tolist():
+            bad = next((i for i in range(min(len(got), len(want))) if got[i].tolist() != want[i].tolist()), min(len(got), len(want)))
+            raise AssertionError((tag, "appended at", edges, "records", len(got), len(want), "first difference at", bad, got[bad:bad + 1].tolist(), want[bad:bad + 1].tolist()))
+        return len(ends)
+    T.check = _check_append
 rng = np.random.default_rng(seed)
 print(f"soak seed {seed}, {budget:.0f} s", flush=True)
 ALPHA = b"abcdefABCDEF_-/ .019xyzXYZ"
