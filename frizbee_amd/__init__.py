@@ -122,6 +122,7 @@ SYMBOLS = [
     "fzb_multi_match_list_parallel_sharded", "fzb_multi_match_list_parallel_rccl", "fzb_multi_matcher_shard_report", "fzb_debug_device_allocs",
     "fzb_match_list_top", "fzb_match_list_top_device", "fzb_multi_match_list_top", "fzb_match_list_top_sharded", "fzb_multi_match_list_top_sharded",
     "fzb_corpus_reserve", "fzb_corpus_append", "fzb_corpus_truncate", "fzb_corpus_info", "fzb_debug_corpus_read",
+    "fzb_corpus_remove", "fzb_corpus_remove_device", "fzb_corpus_replace", "fzb_corpus_edit_info",
 ]
 
 
@@ -217,6 +218,10 @@ def lib():
         l.fzb_corpus_truncate.argtypes = [C.c_void_p, C.c_size_t]
         l.fzb_corpus_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_debug_corpus_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.fzb_corpus_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_remove_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_replace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_corpus_edit_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         _lib = l
     return _lib
 
@@ -310,6 +315,36 @@ class Corpus:
     def truncate(self, n):
         """fzb_corpus_truncate: keep the first n haystacks (capacity is kept)."""
         _check(lib().fzb_corpus_truncate(self.h, n))
+
+    def remove(self, indices):
+        """fzb_corpus_remove: drops the haystacks named by `indices` (any order, repeats allowed); the others keep their order and are
+        renumbered, as a list comprehension over the kept ones would.  Only the indices cross the link."""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        _check(lib().fzb_corpus_remove(self.h, ix.ctypes.data if len(ix) else None, len(ix)))
+
+    def remove_device(self, ptr, stride, count_ptr, max_count):
+        """fzb_corpus_remove_device: the index list lies in HBM - entry k is the uint32 at byte k * stride of `ptr`, min(*count_ptr,
+        max_count) entries.  stride 8 reads the records Matcher.match_list_device wrote over the whole corpus: drop everything that matches."""
+        _check(lib().fzb_corpus_remove_device(self.h, ptr, stride, count_ptr, max_count))
+
+    def replace(self, indices, haystacks=None, *, packed=None):
+        """fzb_corpus_replace: batch item k becomes the content of haystack indices[k] (unique indices, any order).  `packed` = pack() of
+        the batch alone."""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        data, ends = packed if packed is not None else pack(haystacks)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        if len(ix) != len(ends):
+            raise FrizbeeError(1, f"Corpus.replace: {len(ix)} indices for {len(ends)} haystacks")
+        _check(lib().fzb_corpus_replace(self.h, ix.ctypes.data if len(ix) else None, len(ix), data.ctypes.data, ends.ctypes.data if len(ends) else None))
+
+    EDIT_INFO_FIELDS = ("first", "bytes_written", "view_tiles", "temp_bytes")
+
+    def edit_info(self):
+        """fzb_corpus_edit_info as a dict (EDIT_INFO_FIELDS): the last remove / replace that changed the corpus."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_corpus_edit_info(self.h, out))
+        return dict(zip(self.EDIT_INFO_FIELDS, (int(v) for v in out)))
 
     INFO_FIELDS = ("items", "item_capacity", "bytes", "byte_capacity", "max_len", "uniform_len", "has_view", "view_nv", "outliers", "ends_u64", "regrows",
                    "h2d_bytes")

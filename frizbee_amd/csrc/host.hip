@@ -187,6 +187,7 @@ FzbKnobs parse_knobs() {
     k.shard_gather_copy = getenv("FZB_SHARD_GATHER") != nullptr && !strcmp(getenv("FZB_SHARD_GATHER"), "copy");
     k.shard_inline = num("FZB_SHARD_INLINE", -1);
     k.spin_wait_us = num("FZB_SPIN_WAIT_US", 1000);
+    k.edit_chunk_items = std::max(1024, num("FZB_EDIT_CHUNK_ITEMS", 1 << 20) / 1024 * 1024);
     return k;
 }
 FzbKnobs& knobs_storage() {

@@ -49,6 +49,7 @@ struct fzb_corpus {
     u64 view_cap_units = 0;
     u64 regrows = 0;         // reallocations of the canonical arrays so far
     u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
+    u64 edit_info[4] = {0, 0, 0, 0};  // the last successful fzb_corpus_remove / _replace (fzb_corpus_edit_info)
     // staging of a batch, kept between appends: the batch as it arrived (bytes, u64 offsets), the layout pass' tile sums and stats
     void* stage_raw = nullptr;
     void* stage_ends = nullptr;

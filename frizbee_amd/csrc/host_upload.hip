@@ -991,3 +991,509 @@ int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t 
 }
 
 }  // extern "C"
+
+// ---- a corpus that is EDITED: haystacks removed or replaced anywhere in the list ----------------------------------------------------
+// One pass serves both ("Layout under edit").  i0 = the first touched haystack; nothing in front of it is read or
+// written.  The suffix from i0 on is cut into tiles of 1024 SOURCE haystacks:
+//   k_ed_mark     checks the index list where it lies (HBM) and sets one bit per touched haystack (vector atomics on u32 words); the
+//                 lowest touched index and the first bad position come back in the pass' first readback
+//   k_ed_tiles    per tile: sum of the NEW padded lengths (0 for a dropped haystack, the batch item's for a replaced one) and the
+//                 number of haystacks kept
+//   k_ed_scan     exclusive scan of both (one workgroup); the totals - the suffix' new size - come back in the second readback, which
+//                 decides capacity, room and scratch: every check and allocation lies before the first write to a resident array
+//   k_ed_gather   per tile: new starts and end offsets (scan in LDS), and the bytes - one thread per 16-byte OUTPUT vector, as in
+//                 k_up_build; a kept haystack is read as whole aligned vectors from the resident layout (its zero padding comes along),
+//                 a replacement through the funnel shift from the staged batch
+//   k_ed_place    copies what the gather produced to its place in the canonical arrays
+// The gather writes to SCRATCH, never to the resident arrays: a removal moves data towards lower addresses, so a tile's destination
+// overlaps sources of tiles that another workgroup may not have read yet.  Nothing rests on the order in which the workgroups of one
+// launch run: gather and place are separate, stream-ordered launches.  The suffix goes through the scratch in CHUNKS of
+// FZB_EDIT_CHUNK_ITEMS source haystacks (knobs.h; 1 Mi by default), gather then place per chunk, front to back: placing chunk c is safe when
+// its destination ends at or before the place where chunk c + 1's first source haystack starts - always so for a removal, and for a
+// replace unless growing items push data towards higher addresses; k_ed_scan checks every chunk boundary, and a pass that fails the
+// check takes the whole suffix through the scratch as one chunk.  A memset clears what the list no longer covers.
+namespace {
+
+struct EdStats {
+    u64 bad_pos, first, count, new_bytes, new_items, start0;
+    u64 max_chunk_bytes, forward_ok;  // the largest chunk's new bytes; 1 = chunks can be placed front to back
+};
+const EdStats ED_STATS_INIT{~(u64)0, ~(u64)0, 0, 0, 0, 0, 0, 0};
+
+// what a touched haystack becomes: dropped (replace = 0), or item rk[k] of the staged batch, k = the position of its index in the sorted ridx
+struct EdSrc {
+    const u32* bitmap;
+    const u32* ridx;
+    const u32* rk;
+    const u64* bends;  // the batch's exclusive end offsets, from its first byte
+    u32 n_repl;
+    u32 replace;
+};
+
+__device__ __forceinline__ bool ed_touched(const EdSrc& s, u64 i) { return (s.bitmap[i >> 5] >> (i & 31)) & 1u; }
+// the batch item that replaces haystack i (i is in ridx): its first byte in the batch and its length
+__device__ __forceinline__ void ed_batch_item(const EdSrc& s, u64 i, u64* from, u64* len) {
+    u32 lo = 0, hi = s.n_repl;
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (s.ridx[mid] <= (u32)i) lo = mid;
+        else hi = mid;
+    }
+    const u32 k = s.rk[lo];
+    const u64 b = k ? s.bends[k - 1] : 0;
+    *from = b;
+    *len = s.bends[k] - b;
+}
+
+// entry k of the list = the u32 at word k * stride_words; count = min(*dev_count, max_count) (dev_count == nullptr: max_count)
+__global__ __launch_bounds__(UP_THREADS) void k_ed_mark(const u32* __restrict__ idx, u64 stride_words, const u32* __restrict__ dev_count, u64 max_count, u64 n,
+                                                        u32* __restrict__ bitmap, EdStats* __restrict__ st) {
+    const u64 cnt = dev_count ? min((u64)*dev_count, max_count) : max_count;
+    u64 first = ~(u64)0, bad = ~(u64)0;
+    const u64 stride = (u64)gridDim.x * UP_THREADS;
+    for (u64 k = (u64)blockIdx.x * UP_THREADS + threadIdx.x; k < cnt; k += stride) {
+        const u32 v = idx[k * stride_words];
+        if (v >= n) bad = min(bad, k);
+        else {
+            atomicOr(&bitmap[v >> 5], 1u << (v & 31));
+            first = min(first, (u64)v);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        first = min(first, (u64)__shfl_xor(first, off));
+        bad = min(bad, (u64)__shfl_xor(bad, off));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (first != ~(u64)0) atomicMin((unsigned long long*)&st->first, (unsigned long long)first);
+        if (bad != ~(u64)0) atomicMin((unsigned long long*)&st->bad_pos, (unsigned long long)bad);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->count = cnt;
+}
+
+template <typename ET>
+__global__ __launch_bounds__(UP_THREADS) void k_ed_tiles(const ET* __restrict__ ends, u64 n, u64 i0, EdSrc src, u64* __restrict__ tile_bytes, u64* __restrict__ tile_cnt,
+                                                         u64* __restrict__ tile_start, EdStats* __restrict__ st) {
+    __shared__ u64 s_sum[UP_THREADS / 64];
+    __shared__ u32 s_cnt[UP_THREADS / 64];
+    u64 sum = 0;
+    u32 kept = 0;
+#pragma unroll
+    for (int k = 0; k < UP_TILE / UP_THREADS; k++) {
+        const u64 i = i0 + (u64)blockIdx.x * UP_TILE + (u64)k * UP_THREADS + threadIdx.x;
+        if (i < n) {
+            const u64 start = i ? ((u64)ends[i - 1] + 15) & ~(u64)15 : 0;
+            u64 len = (u64)ends[i] - start, from;
+            bool keep = true;
+            if (ed_touched(src, i)) {
+                if (src.replace) ed_batch_item(src, i, &from, &len);
+                else keep = false;
+            }
+            if (keep) {
+                sum += (len + 15) & ~(u64)15;
+                kept++;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        sum += __shfl_xor(sum, off);
+        kept += __shfl_xor(kept, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_sum[threadIdx.x >> 6] = sum;
+        s_cnt[threadIdx.x >> 6] = kept;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 t = 0, k = 0;
+        for (int w = 0; w < UP_THREADS / 64; w++) {
+            t += s_sum[w];
+            k += s_cnt[w];
+        }
+        tile_bytes[blockIdx.x] = t;
+        tile_cnt[blockIdx.x] = k;
+        // where the tile's first haystack starts NOW: a later chunk's gather cannot read it from the end offsets, which an earlier chunk's
+        // place may have rewritten up to the entry before it
+        const u64 t0 = i0 + (u64)blockIdx.x * UP_TILE;
+        tile_start[blockIdx.x] = t0 ? ((u64)ends[t0 - 1] + 15) & ~(u64)15 : 0;
+        if (blockIdx.x == 0) st->start0 = tile_start[0];  // where haystack i0 starts: where the new suffix will
+    }
+}
+
+// exclusive scan of the tiles' new bytes and kept counts in place (k_up_scan's form, two values at a time); entry [ntiles] = the totals.
+// Then, over the chunks of `chunk_tiles` tiles: the largest chunk's new bytes, and whether every chunk's destination ends at or before
+// the start of the first source haystack behind it.
+__global__ __launch_bounds__(1024) void k_ed_scan(u64* __restrict__ tile_bytes, u64* __restrict__ tile_cnt, const u64* __restrict__ tile_start, u64 ntiles, EdStats* __restrict__ st,
+                                                  u64 chunk_tiles) {
+    __shared__ u64 s_wb[16], s_wc[16];
+    __shared__ u64 s_cb, s_cc;
+    if (threadIdx.x == 0) s_cb = s_cc = 0;
+    __syncthreads();
+    for (u64 base = 0; base < ntiles; base += 1024) {
+        const u64 i = base + threadIdx.x;
+        const u64 vb = i < ntiles ? tile_bytes[i] : 0, vc = i < ntiles ? tile_cnt[i] : 0;
+        u64 ib = vb, ic = vc;
+        for (int off = 1; off < 64; off <<= 1) {
+            const u64 tb = __shfl_up(ib, off), tc = __shfl_up(ic, off);
+            if ((int)(threadIdx.x & 63) >= off) {
+                ib += tb;
+                ic += tc;
+            }
+        }
+        if ((threadIdx.x & 63) == 63) {
+            s_wb[threadIdx.x >> 6] = ib;
+            s_wc[threadIdx.x >> 6] = ic;
+        }
+        __syncthreads();
+        u64 wb = 0, wc = 0;
+        for (u32 w = 0; w < (threadIdx.x >> 6); w++) {
+            wb += s_wb[w];
+            wc += s_wc[w];
+        }
+        const u64 cb = s_cb, cc = s_cc;
+        if (i < ntiles) {
+            tile_bytes[i] = cb + wb + ib - vb;
+            tile_cnt[i] = cc + wc + ic - vc;
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) {
+            s_cb = cb + wb + ib;
+            s_cc = cc + wc + ic;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        st->new_bytes = s_cb;
+        st->new_items = s_cc;
+        tile_bytes[ntiles] = s_cb;
+        tile_cnt[ntiles] = s_cc;
+    }
+    __syncthreads();
+    const u64 start0 = tile_start[0];
+    u64 mx = 0;
+    bool ok = true;
+    for (u64 t = (u64)threadIdx.x * chunk_tiles; t < ntiles; t += 1024 * chunk_tiles) {
+        const u64 te = min(ntiles, t + chunk_tiles);
+        mx = max(mx, tile_bytes[te] - tile_bytes[t]);
+        if (te < ntiles && start0 + tile_bytes[te] > tile_start[te]) ok = false;  // (tile te's first haystack: the first source behind the chunk)
+    }
+    if (mx) atomicMax((unsigned long long*)&st->max_chunk_bytes, (unsigned long long)mx);
+    if (threadIdx.x == 0) st->forward_ok = 1;
+    __syncthreads();
+    if (!ok) st->forward_ok = 0;
+}
+
+// One chunk of the new suffix (the tiles from `tile_first` on, one per workgroup), out of place: its bytes from byte 0 of `out` on, its
+// end offsets - in the canonical layout's terms, where the suffix starts at byte start0 - from entry 0 of `out_ends` on.
+template <typename ET>
+__global__ __launch_bounds__(UP_THREADS) void k_ed_gather(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 n, u64 i0, EdSrc src, const u8* __restrict__ braw,
+                                                          const u64* __restrict__ tile_bytes, const u64* __restrict__ tile_cnt, const u64* __restrict__ tile_start, u8* __restrict__ out,
+                                                          ET* __restrict__ out_ends, u64 start0, u64 tile_first) {
+    __shared__ u64 s_pstart[UP_TILE + 1];  // new padded start of each source haystack of the tile, relative to the tile's base (a dropped one takes no room)
+    __shared__ u64 s_from[UP_TILE];        // where its bytes are read: byte position in the resident layout, or in the batch | FROM_BATCH
+    __shared__ u64 s_len[UP_TILE];
+    __shared__ u64 s_wave[UP_THREADS / 64];
+    __shared__ u32 s_wcnt[UP_THREADS / 64];
+    constexpr u64 FROM_BATCH = (u64)1 << 63;
+    const u64 tile = tile_first + blockIdx.x;
+    const u64 t0 = i0 + tile * UP_TILE;
+    const u64 base = tile_bytes[tile], chunk_base = tile_bytes[tile_first];
+    const u64 first = t0 + (u64)threadIdx.x * 4;
+    u64 prev_end = threadIdx.x == 0 ? tile_start[tile] : (first < n ? (u64)ends[first - 1] : 0);  // (a start is its own round-up)
+    u64 plen[4], len[4], mine = 0;
+    u32 keep[4], mykept = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const u64 i = first + k;
+        u64 from = 0;
+        len[k] = 0;
+        keep[k] = 0;
+        if (i < n) {
+            const u64 start = (prev_end + 15) & ~(u64)15;
+            prev_end = (u64)ends[i];
+            len[k] = prev_end - start;
+            from = start;
+            keep[k] = 1;
+            if (ed_touched(src, i)) {
+                if (src.replace) {
+                    ed_batch_item(src, i, &from, &len[k]);
+                    from |= FROM_BATCH;
+                } else {
+                    keep[k] = 0;
+                    len[k] = 0;
+                }
+            }
+        }
+        s_from[threadIdx.x * 4 + k] = from;
+        s_len[threadIdx.x * 4 + k] = len[k];
+        plen[k] = (len[k] + 15) & ~(u64)15;
+        mine += plen[k];
+        mykept += keep[k];
+    }
+    u64 incl = mine;
+    u32 cincl = mykept;
+    for (int off = 1; off < 64; off <<= 1) {
+        const u64 t = __shfl_up(incl, off);
+        const u32 c = __shfl_up(cincl, off);
+        if ((int)(threadIdx.x & 63) >= off) {
+            incl += t;
+            cincl += c;
+        }
+    }
+    if ((threadIdx.x & 63) == 63) {
+        s_wave[threadIdx.x >> 6] = incl;
+        s_wcnt[threadIdx.x >> 6] = cincl;
+    }
+    __syncthreads();
+    u64 run = incl - mine;
+    u64 rank = tile_cnt[tile] - tile_cnt[tile_first] + cincl - mykept;
+    for (u32 w = 0; w < (threadIdx.x >> 6); w++) {
+        run += s_wave[w];
+        rank += s_wcnt[w];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        s_pstart[threadIdx.x * 4 + k] = run;
+        if (keep[k]) out_ends[rank++] = (ET)(start0 + base + run + len[k]);
+        run += plen[k];
+    }
+    if (threadIdx.x == UP_THREADS - 1) s_pstart[UP_TILE] = run;
+    __syncthreads();
+    const u64 tile_total = s_pstart[UP_TILE];
+    const u32 cnt = (u32)min((u64)UP_TILE, n - t0);
+    for (u64 v = (u64)threadIdx.x * 16u; v < tile_total; v += UP_THREADS * 16u) {
+        // the haystack this output vector belongs to: last j with pstart[j] <= v (dropped and empty haystacks share a start with their
+        // successor: the search lands on the last of them, the one that owns the bytes)
+        u32 lo = 0, hi = cnt;
+        while (hi - lo > 1) {
+            const u32 mid = (lo + hi) >> 1;
+            if (s_pstart[mid] <= v) lo = mid;
+            else hi = mid;
+        }
+        const u64 off = v - s_pstart[lo], from = s_from[lo];
+        const u64 hlen = s_len[lo];
+        uint4 q = make_uint4(0, 0, 0, 0);
+        if (off < hlen) {
+            if (!(from & FROM_BATCH)) {
+                q = *(const uint4*)(bytes + from + off);  // resident: aligned, and zero behind the haystack's last byte
+            } else {
+                const u64 p = (from & ~FROM_BATCH) + off;  // byte position in the batch
+                const u32 rem = (u32)min((u64)16, hlen - off);
+                const u32* a = (const u32*)(braw + (p & ~(u64)3));
+                const u32 sh = (u32)(p & 3);
+                // 16 bytes from an arbitrary byte position: five aligned dwords, funnel-shifted (the landing buffer has 96 readable bytes of slack)
+                const u32 w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3], w4 = sh ? a[4] : 0u;
+                u32 x[4] = {__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh), __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh)};
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const u32 lo_b = 4u * k;
+                    if (rem <= lo_b) x[k] = 0;
+                    else if (rem - lo_b < 4) x[k] &= (1u << (8 * (rem - lo_b))) - 1;
+                }
+                q = make_uint4(x[0], x[1], x[2], x[3]);
+            }
+        }
+        *(uint4*)(out + (base - chunk_base) + v) = q;
+    }
+}
+
+// the chunk of tiles [tile_first, tile_end), gathered into `src_b` / `src_e`, to its place: bytes to start0 + its base, offsets to i0 + its rank
+template <typename ET>
+__global__ __launch_bounds__(UP_THREADS) void k_ed_place(const u8* __restrict__ src_b, const ET* __restrict__ src_e, const u64* __restrict__ tile_bytes,
+                                                         const u64* __restrict__ tile_cnt, u64 tile_first, u64 tile_end, u8* __restrict__ bytes, ET* __restrict__ ends, u64 start0, u64 i0) {
+    const u64 vecs = (tile_bytes[tile_end] - tile_bytes[tile_first]) / 16, items = tile_cnt[tile_end] - tile_cnt[tile_first];
+    const uint4* s = (const uint4*)src_b;
+    uint4* d = (uint4*)(bytes + start0 + tile_bytes[tile_first]);
+    ET* de = ends + i0 + tile_cnt[tile_first];
+    const u64 stride = (u64)gridDim.x * UP_THREADS;
+    for (u64 v = (u64)blockIdx.x * UP_THREADS + threadIdx.x; v < vecs; v += stride) d[v] = s[v];
+    for (u64 k = (u64)blockIdx.x * UP_THREADS + threadIdx.x; k < items; k += stride) de[k] = src_e[k];
+}
+
+inline u64 round_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
+
+struct EditRequest {
+    const char* what;
+    // the touched indices: in host memory (copied into the pass' scratch), or where the caller keeps them in HBM
+    const u32* host_idx = nullptr;
+    const void* dev_idx = nullptr;
+    u64 stride_words = 1;
+    const u32* dev_count = nullptr;
+    u64 max_count = 0;
+    // replace: host_idx is sorted, host_rk[k] = the item of the staged batch (c->stage_raw / c->stage_ends) that haystack host_idx[k] becomes
+    const u32* host_rk = nullptr;
+    u64 batch_h2d = 0;
+};
+
+// grow_begin has passed.  Everything up to canon_ensure_room only reads the corpus: an error before it leaves nothing to undo.
+int edit_run(fzb_corpus* c, const EditRequest& rq) {
+    const std::string what = rq.what;
+    const bool replace = rq.host_rk != nullptr;
+    const u64 n = c->dev.n, esz = c->dev.ends_u64 ? 8 : 4;
+    const u64 tiles_cap = up_tiles(n) + 1;
+    // scratch of the pass itself, one allocation: stats | bitmap | three tile arrays | the index list (host form) | the batch's item numbers
+    const u64 off_bitmap = 64, off_tb = off_bitmap + round_up((n + 31) / 32 * 4, 8), off_tc = off_tb + tiles_cap * 8, off_ts = off_tc + tiles_cap * 8, off_idx = off_ts + tiles_cap * 8;
+    const u64 off_rk = off_idx + (rq.host_idx ? round_up(rq.max_count * 4, 8) : 0), aux_bytes = off_rk + (replace ? rq.max_count * 4 : 0);
+    u8* aux = nullptr;
+    u8* work = nullptr;
+    auto done = [&](int rc) {
+        if (aux) (void)hipFree(aux);
+        if (work) (void)hipFree(work);
+        return rc;
+    };
+    auto hip_fail = [&](hipError_t e, const char* where) { return done(fzb_fail(FZB_ERR_HIP, what + " (" + where + "): " + hipGetErrorString(e))); };
+    hipError_t e = fzb_dev_alloc((void**)&aux, aux_bytes);
+    if (e != hipSuccess) { aux = nullptr; return hip_fail(e, "scratch"); }
+    EdStats* d_st = (EdStats*)aux;
+    u32* d_bitmap = (u32*)(aux + off_bitmap);
+    u64 *d_tb = (u64*)(aux + off_tb), *d_tc = (u64*)(aux + off_tc), *d_ts = (u64*)(aux + off_ts);
+    e = hipMemsetAsync(aux, 0, off_tb, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(d_st, &ED_STATS_INIT, sizeof(EdStats), hipMemcpyHostToDevice);
+    if (e == hipSuccess && rq.host_idx) e = hipMemcpy(aux + off_idx, rq.host_idx, rq.max_count * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && replace) e = hipMemcpy(aux + off_rk, rq.host_rk, rq.max_count * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "scratch");
+    const u32* d_idx = rq.host_idx ? (const u32*)(aux + off_idx) : (const u32*)rq.dev_idx;
+    const unsigned mark_grid = (unsigned)std::max<u64>(1, std::min<u64>((rq.max_count + UP_THREADS - 1) / UP_THREADS, 2048));
+    hipLaunchKernelGGL(k_ed_mark, dim3(mark_grid), dim3(UP_THREADS), 0, nullptr, d_idx, rq.stride_words, rq.dev_count, rq.max_count, n, d_bitmap, d_st);
+    EdStats st = ED_STATS_INIT;
+    e = hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost);  // first readback: is the list valid, and where does the edit begin
+    if (e != hipSuccess) return hip_fail(e, "index list");
+    if (st.bad_pos != ~(u64)0)
+        return done(fzb_fail(FZB_ERR_INVALID, what + ": the index at position " + std::to_string(st.bad_pos) + " of the list is beyond the corpus' " + std::to_string(n) + " haystacks"));
+    if (!st.count) return done(FZB_OK);
+    const u64 i0 = st.first, tiles = up_tiles(n - i0);
+    EdSrc src{d_bitmap, replace ? d_idx : nullptr, replace ? (const u32*)(aux + off_rk) : nullptr, (const u64*)c->stage_ends, (u32)(replace ? rq.max_count : 0), replace ? 1u : 0u};
+    if (c->dev.ends_u64) hipLaunchKernelGGL((k_ed_tiles<u64>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
+    else hipLaunchKernelGGL((k_ed_tiles<u32>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
+    const u64 chunk_knob = (u64)fzb_knobs().edit_chunk_items / UP_TILE;
+    hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(1024), 0, nullptr, d_tb, d_tc, (const u64*)d_ts, tiles, d_st, chunk_knob);
+    e = hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost);  // second readback: the new suffix' size
+    if (e != hipSuccess) return hip_fail(e, "sizing pass");
+    const u64 old_used = c->dev.total_bytes - 96, new_used = st.start0 + st.new_bytes, total = new_used + 96, n_new = i0 + st.new_items;
+    if (!c->dev.ends_u64 && total > 0xFFFFFFF0ull)
+        return done(fzb_fail(FZB_ERR_CAPACITY, what + ": the new content takes the padded list to 4 GiB, beyond this corpus' 32-bit end offsets; upload such a list in one piece"));
+    // where the new suffix is gathered: the corpus' landing buffers when they are free (a replace's batch lies in them) and large enough
+    const u64 chunk_tiles = st.forward_ok ? chunk_knob : tiles;  // (front to back, or everything through the scratch at once)
+    const u64 need_b = st.forward_ok ? st.max_chunk_bytes : st.new_bytes, need_e = std::min(st.new_items, chunk_tiles * UP_TILE) * esz;
+    u8* out_b = (!replace && c->stage_raw && c->stage_raw_cap + 96 >= need_b) ? (u8*)c->stage_raw : nullptr;
+    u8* out_e = (!replace && c->stage_ends && c->stage_items_cap * 8 >= need_e) ? (u8*)c->stage_ends : nullptr;
+    const u64 work_b = out_b ? 0 : round_up(need_b, 16), work_bytes = work_b + (out_e ? 0 : need_e);
+    if (work_bytes) {
+        e = fzb_dev_alloc((void**)&work, work_bytes);
+        if (e != hipSuccess) { work = nullptr; return hip_fail(e, "scratch for the new suffix"); }
+        if (!out_b) out_b = work;
+        if (!out_e) out_e = work + work_b;
+    }
+    if (total > c->cap_bytes) {
+        e = canon_ensure_room(c, n_new, total, true);
+        if (e != hipSuccess) return hip_fail(e, "room for the new content");
+    }
+    // ---- from here on the corpus changes ----
+    for (u64 ta = 0; ta < tiles; ta += chunk_tiles) {
+        const u64 te = std::min(tiles, ta + chunk_tiles);
+        const unsigned place_grid = (unsigned)std::min<u64>((te - ta) * 4, 4096);
+        if (c->dev.ends_u64) {
+            hipLaunchKernelGGL((k_ed_gather<u64>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u64*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u64*)out_e, st.start0, ta);
+            hipLaunchKernelGGL((k_ed_place<u64>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u64*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u64*)c->own_ends, st.start0, i0);
+        } else {
+            hipLaunchKernelGGL((k_ed_gather<u32>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u32*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u32*)out_e, st.start0, ta);
+            hipLaunchKernelGGL((k_ed_place<u32>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u32*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u32*)c->own_ends, st.start0, i0);
+        }
+    }
+    e = hipSuccess;
+    if (e == hipSuccess && old_used > new_used) e = hipMemsetAsync((u8*)c->own_bytes + new_used, 0, old_used - new_used, nullptr);  // gaps and tail are zero
+    const bool had_view = c->dev.vbytes != nullptr;
+    if (e == hipSuccess) e = measure_resident(c, n_new);
+    if (e != hipSuccess) return hip_fail(e, "layout");
+    c->dev.n = n_new;
+    c->dev.total_bytes = total;
+    c->h2d_bytes += rq.batch_h2d;
+    set_measured(c);
+    const int rc = view_sync(c, i0);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc) return done(rc);
+    if (e != hipSuccess) return hip_fail(e, "layout kernels");
+    c->edit_info[0] = i0;
+    c->edit_info[1] = st.new_bytes + (old_used > new_used ? old_used - new_used : 0) + st.new_items * esz;
+    c->edit_info[2] = c->dev.vbytes ? up_tiles(n_new) - (had_view ? std::min(i0, n_new) / UP_TILE : 0) : 0;
+    c->edit_info[3] = aux_bytes + work_bytes;
+    return done(FZB_OK);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fzb_corpus_remove_device(fzb_corpus* c, const void* dev_indices, size_t stride_bytes, const uint32_t* dev_count, size_t max_count) {
+    if (!c || !dev_indices || !dev_count) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    if (stride_bytes < 4 || (stride_bytes & 3)) return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_remove_device: stride_bytes must be a multiple of 4, at least 4");
+    if (((uintptr_t)dev_indices & 3) || ((uintptr_t)dev_count & 3)) return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_remove_device: dev_indices and dev_count must be 4-byte aligned");
+    int rc = grow_begin(c, "fzb_corpus_remove_device");
+    if (rc) return rc;
+    if (!max_count) return FZB_OK;
+    EditRequest rq;
+    rq.what = "fzb_corpus_remove_device";
+    rq.dev_idx = dev_indices;
+    rq.stride_words = stride_bytes / 4;
+    rq.dev_count = dev_count;
+    rq.max_count = max_count;
+    return edit_run(c, rq);
+}
+
+int fzb_corpus_remove(fzb_corpus* c, const uint32_t* indices, size_t n_indices) {
+    if (!c || (n_indices && !indices)) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    int rc = grow_begin(c, "fzb_corpus_remove");
+    if (rc) return rc;
+    if (!n_indices) return FZB_OK;
+    for (size_t k = 0; k < n_indices; k++)
+        if (indices[k] >= c->dev.n)
+            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_remove: index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " + std::to_string(c->dev.n) + " haystacks");
+    EditRequest rq;  // the device form over a copy of the list
+    rq.what = "fzb_corpus_remove";
+    rq.host_idx = indices;
+    rq.max_count = n_indices;
+    return edit_run(c, rq);
+}
+
+int fzb_corpus_replace(fzb_corpus* c, const uint32_t* indices, size_t n, const uint8_t* bytes, const uint64_t* end_offsets) {
+    if (!c || (n && (!indices || !end_offsets))) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    const u64 raw = n ? end_offsets[n - 1] : 0;
+    if (raw && !bytes) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    int rc = grow_begin(c, "fzb_corpus_replace");
+    if (rc) return rc;
+    if (!n) return FZB_OK;
+    for (size_t k = 0; k < n; k++) {
+        if (indices[k] >= c->dev.n)
+            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_replace: index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " + std::to_string(c->dev.n) + " haystacks");
+        if (end_offsets[k] < (k ? end_offsets[k - 1] : 0)) return fzb_fail(FZB_ERR_INVALID, "end_offsets must be non-decreasing");
+    }
+    // sorted by haystack: the pass finds a touched haystack's batch item by binary search
+    std::vector<u32> order(n), sorted_idx(n);
+    for (size_t k = 0; k < n; k++) order[k] = (u32)k;
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return indices[a] < indices[b]; });
+    for (size_t k = 0; k < n; k++) {
+        sorted_idx[k] = indices[order[k]];
+        if (k && sorted_idx[k] == sorted_idx[k - 1])
+            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_replace: haystack " + std::to_string(sorted_idx[k]) + " is named twice (positions " + std::to_string(std::min(order[k - 1], order[k])) + " and " +
+                                                 std::to_string(std::max(order[k - 1], order[k])) + ")");
+    }
+    // the batch travels as an appended one does: as it is, into the corpus' landing buffers
+    hipError_t e = stage_ensure_room(c, n, raw);
+    if (e == hipSuccess) e = h2d_all({H2DJob{c->stage_ends, end_offsets, n * 8}, H2DJob{c->stage_raw, bytes, (size_t)raw}}, c->device);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_replace (host to device): ") + hipGetErrorString(e));
+    EditRequest rq;
+    rq.what = "fzb_corpus_replace";
+    rq.host_idx = sorted_idx.data();
+    rq.max_count = n;
+    rq.host_rk = order.data();
+    rq.batch_h2d = raw + (u64)n * 8;
+    return edit_run(c, rq);
+}
+
+int fzb_corpus_edit_info(const fzb_corpus* c, uint64_t out[4]) {
+    if (!c || !out) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = c->edit_info[k];
+    return FZB_OK;
+}
+
+}  // extern "C"

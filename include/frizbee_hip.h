@@ -155,6 +155,45 @@ int fzb_corpus_truncate(fzb_corpus* c, size_t n);
  * [11]=bytes copied host to device so far (haystack bytes + 8 per offset) */
 int fzb_corpus_info(const fzb_corpus* c, uint64_t out[12]);
 
+/* A corpus that is EDITED: haystacks removed or replaced anywhere in the list (a file watcher reports a deleted or renamed path, the
+ * user hides a directory).  Same family, same rules as the calls above: only for a corpus made by fzb_corpus_upload (a borrowed one gets
+ * FZB_ERR_INVALID); fzb_sharded_corpus and the RCCL form are out of scope; SET-UP calls that wait for the device's outstanding work
+ * on entry and are complete on return, on the corpus' device (which must be current); not to be run concurrently with queries over
+ * the same corpus.  Afterwards the corpus answers every entry point that takes an fzb_corpus exactly as a fzb_corpus_upload of the
+ * edited list would: same padded-16 bytes and zero tail, same end offsets, same re-measured max_len / uniform_len (a removal can lower
+ * max_len or make the list uniform), same decision about the filter's view; capacity and the width of the end offsets are kept.
+ * An error leaves the corpus exactly as it was: every check and every allocation comes before the first write to a resident array.
+ * Work: with i0 = the first touched haystack, nothing in front of i0 is read or written; the suffix from i0 on is laid out again on the
+ * device (one read and one write of it through scratch, plus the copy into place) and the filter's view is rebuilt from tile
+ * i0 / 1024 on.  Only the indices - and a replace's new bytes - cross the link.
+ * Temporary device memory, released before the call returns: len / 8 bytes (one bit per haystack) + 24 bytes per 1024 haystacks +
+ * the index list (host forms) + the scratch the suffix passes through: one chunk of FZB_EDIT_CHUNK_ITEMS source haystacks (default
+ * 1 048 576) at a time - that chunk's new padded bytes + 8 (4) bytes per haystack of it - taken from the corpus' landing buffers where
+ * they are large enough.  A replace whose growing items push later haystacks towards HIGHER addresses cannot go chunk by chunk: it
+ * takes the whole new suffix through the scratch at once.  A refused allocation: FZB_ERR_HIP, corpus unchanged. */
+/* Removes the haystacks named by `indices` (host memory, any order; a repeated index removes its haystack once).  The others keep
+ * their order and are renumbered, as Vec::retain would.  n_indices == 0 is a no-op.  An index >= len: FZB_ERR_INVALID, the message
+ * names the first offending position. */
+int fzb_corpus_remove(fzb_corpus* c, const uint32_t* indices, size_t n_indices);
+/* The same with the index list in HBM: entry k is the uint32 at byte k * stride_bytes of dev_indices (stride_bytes >= 4 and a multiple
+ * of 4; both pointers 4-byte aligned), the number of entries is min(*dev_count, max_count).  With stride_bytes = 8 this reads the
+ * record buffer that fzb_match_list_device or fzb_multi_match_list_device wrote over the WHOLE corpus with index_offset 0 (an fzb_match is 8 bytes and
+ * begins with its uint32 index; dev_count = their dev_count, whose first word is the number of records written): "drop everything that matches this query" without a host
+ * round trip.  The list cannot be checked on the host: a kernel validates it and its result is read back before anything is written;
+ * an entry >= len gives FZB_ERR_INVALID (naming the first offending position) and leaves the corpus unchanged. */
+int fzb_corpus_remove_device(fzb_corpus* c, const void* dev_indices, size_t stride_bytes, const uint32_t* dev_count, size_t max_count);
+/* Batch item k (`bytes` / `end_offsets`: the batch format of fzb_corpus_append) becomes the content of haystack indices[k].  Lengths may
+ * change in either direction, to empty and to beyond 256 bytes.  Indices must be in range and unique (a duplicate: FZB_ERR_INVALID);
+ * their order is free.  Offsets that decrease: FZB_ERR_INVALID "end_offsets must be non-decreasing".  Room is found as in append
+ * (geometric regrow, counted in fzb_corpus_info's regrows), and the 4 GiB rule is append's: FZB_ERR_CAPACITY when the new content would
+ * take a corpus with 32-bit end offsets past 0xFFFFFFF0 padded bytes - they are not widened.  n == 0 is a no-op. */
+int fzb_corpus_replace(fzb_corpus* c, const uint32_t* indices, size_t n, const uint8_t* bytes, const uint64_t* end_offsets);
+/* The last successful fzb_corpus_remove / _remove_device / _replace that changed the corpus (all zero before the first): out[0] = first
+ * haystack index whose position or content changed, [1] = bytes of the canonical layout written (new suffix + cleared bytes + end
+ * offsets: at most the old used bytes behind start(out[0]) - more only where a replace grew the list - + 8 per offset behind out[0]),
+ * [2] = 1024-haystack tiles of the filter's view rebuilt, [3] = peak temporary device bytes. */
+int fzb_corpus_edit_info(const fzb_corpus* c, uint64_t out[4]);
+
 /* `Matcher::match_list(&haystacks)` (src/matcher/mod.rs:212-222) = `match_list_into(.., offset 0)` ->
 * `Specialized::match_list::<TYPOS,UNICODE,_>` (src/matcher/algo.rs:78-103) and the reverse / `radix_sort_matches`
  * post-step (src/sort.rs:6-40), all on the GPU.  `*out` is malloc'd by the library

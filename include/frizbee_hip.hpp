@@ -191,6 +191,35 @@ class Corpus {
         check(fzb_corpus_info(h_.get(), o));
         return Info{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11]};
     }
+    // A corpus that is edited (fzb_corpus_remove and friends): the other haystacks keep their order and are renumbered, as Vec::retain
+    // would; only the indices - and a replace's new bytes - cross the link, nothing in front of the first touched haystack moves.
+    void remove(const std::vector<uint32_t>& indices) { check(fzb_corpus_remove(h_.get(), indices.data(), indices.size())); }
+    // the index list in HBM: entry k = the uint32 at byte k * stride_bytes, min(*dev_count, max_count) entries (stride 8: the records of
+    // Matcher::match_list_device over the whole corpus - "drop everything that matches")
+    void remove_device(const void* dev_indices, size_t stride_bytes, const uint32_t* dev_count, size_t max_count) {
+        check(fzb_corpus_remove_device(h_.get(), dev_indices, stride_bytes, dev_count, max_count));
+    }
+    // batch item k becomes the content of haystack indices[k] (unique indices, any order)
+    template <typename Strings>
+    void replace(const std::vector<uint32_t>& indices, const Strings& batch) {
+        std::string bytes;
+        std::vector<uint64_t> ends;
+        for (const auto& h : batch) {
+            const std::string_view v(h);
+            bytes.append(v.data(), v.size());
+            ends.push_back(bytes.size());
+        }
+        if (ends.size() != indices.size()) throw Error(FZB_ERR_INVALID, "Corpus::replace: one haystack per index");
+        check(fzb_corpus_replace(h_.get(), indices.data(), indices.size(), (const uint8_t*)bytes.data(), ends.data()));
+    }
+    struct EditInfo {
+        uint64_t first, bytes_written, view_tiles, temp_bytes;
+    };
+    EditInfo edit_info() const {
+        uint64_t o[4] = {};
+        check(fzb_corpus_edit_info(h_.get(), o));
+        return EditInfo{o[0], o[1], o[2], o[3]};
+    }
 
   private:
     struct Del { void operator()(fzb_corpus* c) const { fzb_corpus_free(c); } };

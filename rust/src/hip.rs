@@ -93,6 +93,13 @@ extern "C" {
     fn fzb_corpus_truncate(c: *mut c_void, n: usize) -> c_int;
     #[allow(dead_code)]
     fn fzb_corpus_info(c: *const c_void, out: *mut u64) -> c_int;
+    // a corpus that is edited: haystacks removed or replaced anywhere; only the indices (and a replace's new bytes) cross the link
+    fn fzb_corpus_remove(c: *mut c_void, indices: *const u32, n_indices: usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_corpus_remove_device(c: *mut c_void, dev_indices: *const c_void, stride_bytes: usize, dev_count: *const u32, max_count: usize) -> c_int;
+    fn fzb_corpus_replace(c: *mut c_void, indices: *const u32, n: usize, bytes: *const u8, ends: *const u64) -> c_int;
+    fn fzb_corpus_edit_info(c: *const c_void, out: *mut u64) -> c_int;
+    fn fzb_corpus_len(c: *const c_void) -> usize;
     fn fzb_match_list(m: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_match_list_into(m: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_matches_free(p: *mut FzbMatch);
@@ -204,6 +211,24 @@ impl HipCorpus {
     pub fn truncate(&mut self, n: usize) {
         check(unsafe { fzb_corpus_truncate(self.handle, n) });
         self.len = n;
+    }
+    /// Removes the haystacks named by `indices` (any order, repeats allowed); the others keep their order and are renumbered, as
+    /// `Vec::retain` would.  Nothing in front of the first touched haystack moves.
+    pub fn remove(&mut self, indices: &[u32]) {
+        check(unsafe { fzb_corpus_remove(self.handle, indices.as_ptr(), indices.len()) });
+        self.len = unsafe { fzb_corpus_len(self.handle) };
+    }
+    /// `batch[k]` becomes the content of haystack `indices[k]` (unique indices, any order; lengths may change).
+    pub fn replace<H: AsRef<str>>(&mut self, indices: &[u32], batch: &[H]) {
+        assert_eq!(indices.len(), batch.len(), "one haystack per index");
+        let (bytes, ends) = pack(batch);
+        check(unsafe { fzb_corpus_replace(self.handle, indices.as_ptr(), indices.len(), bytes.as_ptr(), ends.as_ptr()) });
+    }
+    /// The last edit: [first changed haystack, canonical bytes written, view tiles rebuilt, peak temporary device bytes].
+    pub fn edit_info(&self) -> [u64; 4] {
+        let mut out = [0u64; 4];
+        check(unsafe { fzb_corpus_edit_info(self.handle, out.as_mut_ptr()) });
+        out
     }
 }
 impl Drop for HipCorpus {
