@@ -10,6 +10,7 @@
 // Arithmetic is done per lane in 32-bit registers and wrapped to the emulated lane type (u8 / u16) after
 // every add, so it follows the reference's wrapping add / saturating sub literally.
 #include "kernels_common.h"
+#include "trace_walk.h"
 
 #define GEN_WAVES 4
 
@@ -92,9 +93,10 @@ __device__ u32 greedy_score(const ND& nd, const u8* __restrict__ h, u32 hlen, bo
 // TRACE = the matched-indices form (src/smith_waterman/algo/mod.rs:49-152, alignment_iter.rs:35-181): direct mode only; every
 // (row, column) cell is also written to the wave's slot of `trace.cells` (score | match bit << 16, the reference's score_matrix
 // and match_masks), and lane 0 then walks the alignment back from the first column of the last row that holds the score,
-// writing the matched byte positions (reverse order, as the reference returns them) to trace.pos[opos * stride ..].
+// writing the matched byte positions (reverse order, as the reference returns them) to trace.pos[opos * stride ..].  The walk itself
+// is trace_walk.h's, which the host tests compile too.
 struct TraceArgs {
-    u32* cells;   // per wave: (rows + 1) x TRACE_W dwords
+    u32* cells;   // per wave: (rows + 1) x TRACE_W dwords (trace_walk.h)
     u32* pos;     // per output record: `stride` positions
     u32* npos;    // per output record: how many
     u32 stride;
@@ -107,7 +109,6 @@ struct GateArgs {
     const u32* alt_list;   // outside [lo, hi): walk this list instead (entry q at alt_list - 4 (q + 1)), *alt_count entries; nullptr: return
     const u32* alt_count;
 };
-#define TRACE_W (FZB_MAX_HAYSTACK_LEN + 2 * 64)  // columns: the zero chunk + up to 1024 bytes rounded up to a chunk
 
 template <int SWL, bool UNICODE, bool TRACE, typename ND = NeedleDev, bool SLAB = ND::kLong>
 __global__ __launch_bounds__(GEN_WAVES * 64) void k2c_generic(const u8* __restrict__ bytes, const EndsAny ends, u64 first, u32 index_offset,
@@ -380,39 +381,7 @@ __global__ __launch_bounds__(GEN_WAVES * 64) void k2c_generic(const u8* __restri
                         if (r == 0 || c < (u32)SWL) return 0u;  // row 0 and the zero chunk
                         return __hip_atomic_load(&cells[(size_t)r * TRACE_W + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     };
-                    const int mt = nd.max_typos;
-                    u32 r = rows, typos = 0, sc = score, prev = 0xFFFFFFFFu;
-                    for (;;) {
-                        if (r == 0) break;
-                        if (mt >= 0 && typos > (u32)mt) break;
-                        if (col < (u32)SWL || sc == 0) break;  // at the left edge (only moves up remain) or lost the alignment
-                        const u32 hidx = col - SWL;
-                        if (UNICODE && hidx < m && (th[hidx] & 0xC0) == 0x80) {  // continuation byte: walk left
-                            col--;
-                            sc = cell(r, col) & 0xFFFFu;
-                            continue;
-                        }
-                        if (cell(r, col) >> 16) {
-                            const u32 p = hidx + sp;
-                            if (UNICODE) {
-                                if (prev != p) {
-                                    for (int off = (int)nd.ulen[r - 1] - 1; off >= 0; off--)
-                                        if (npos < trace.stride) posv[npos++] = p + (u32)off;
-                                    prev = p;
-                                }
-                            } else if (npos < trace.stride) {
-                                posv[npos++] = p;
-                            }
-                            r--;
-                            col--;
-                            sc = cell(r, col) & 0xFFFFu;
-                            continue;
-                        }
-                        const u32 dg = cell(r - 1, col - 1) & 0xFFFFu, lf = cell(r, col - 1) & 0xFFFFu, upv = cell(r - 1, col) & 0xFFFFu;
-                        if (dg >= lf && dg >= upv) { r--; col--; typos++; sc = dg; }
-                        else if (lf >= upv) { col--; sc = lf; }
-                        else { typos++; r--; sc = upv; }
-                    }
+                    npos = trace_walk<UNICODE, SWL>(cell, rows, col, score, nd.max_typos, th, m, sp, nd.ulen, posv, trace.stride);  // trace_walk.h
                 }
             }
         }
