@@ -123,6 +123,7 @@ SYMBOLS = [
     "fzb_match_list_top", "fzb_match_list_top_device", "fzb_multi_match_list_top", "fzb_match_list_top_sharded", "fzb_multi_match_list_top_sharded",
     "fzb_corpus_reserve", "fzb_corpus_append", "fzb_corpus_truncate", "fzb_corpus_info", "fzb_debug_corpus_read",
     "fzb_corpus_remove", "fzb_corpus_remove_device", "fzb_corpus_replace", "fzb_corpus_edit_info",
+    "fzb_match_list_top_indices", "fzb_match_list_top_indices_device", "fzb_matcher_reserve_top_indices", "fzb_multi_match_list_top_indices",
 ]
 
 
@@ -222,6 +223,10 @@ def lib():
         l.fzb_corpus_remove_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         l.fzb_corpus_replace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.fzb_corpus_edit_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_indices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_matcher_reserve_top_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        l.fzb_multi_match_list_top_indices.argtypes = l.fzb_match_list_top_indices.argtypes
         _lib = l
     return _lib
 
@@ -604,6 +609,12 @@ class MultiMatcher(_IterApi):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
+    def match_list_top_indices(self, haystacks, limit):
+        """(`match_list_indices(haystacks)[:limit]` with `index` = the corpus index, len of the full list) for the compiled patterns: a
+        host composition - `match_list_top`, then the matched-indices pass in list order over that head (see `Matcher.match_list_top_indices`)."""
+        cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
+        return _top_indices(lib().fzb_multi_match_list_top_indices, self.h, cp, limit)
+
     def match_list_indices(self, haystacks, selection=None):
         """`Matcher::match_list_indices` over the compiled patterns (`match_one_indices_multi`, src/matcher/multi.rs:56-82); see
         `Matcher.match_list_indices` for `selection`."""
@@ -642,6 +653,18 @@ def _match_list_indices(fn, handle, cp, selection, index_offset=None):
     out, n, pos = C.c_void_p(), C.c_size_t(), C.c_void_p()
     args = (handle, cp.h, sel.ctypes.data if sel is not None else None, 0 if sel is None else len(sel)) + (() if index_offset is None else (index_offset,))
     _check(fn(*args, C.byref(out), C.byref(n), C.byref(pos)))
+    return _take_indices(out, n, pos)
+
+
+def _top_indices(fn, handle, cp, limit):
+    """A top-`limit` matched-positions entry point of the C ABI -> (list[MatchIndices], found)."""
+    out, n, pos, found = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_uint64()
+    _check(fn(handle, cp.h, limit, C.byref(out), C.byref(n), C.byref(pos), C.byref(found)))
+    return _take_indices(out, n, pos), found.value
+
+
+def _take_indices(out, n, pos):
+    """Records + flat positions of a *_indices result -> list[MatchIndices]; releases the library's arrays."""
     try:
         recs = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), shape=(max(n.value, 1) * 16,))[: n.value * 16].view(MATCH_INDICES_DTYPE).copy()
         total = int((recs["positions_begin"].astype(np.int64) + recs["positions_len"]).max()) if len(recs) else 0
@@ -721,6 +744,25 @@ class Matcher(_IterApi):
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_match_list_top_sharded, self.h, sharded.h, limit, copy)
+
+    def match_list_top_indices(self, haystacks, limit):
+        """(the first min(limit, found) entries of `Matcher::match_list_indices` over the whole list, found): what a picker shows after a
+        keystroke.  `index` is the corpus index, `indices` the matched byte positions in reverse order.  The reference's caller truncates
+        the Vec (src/matcher/mod.rs:234-275); here the top stage, a traced pass over its head and the packing of the positions are ONE
+        device call with one host wait."""
+        return _top_indices(lib().fzb_match_list_top_indices, self.h, self._corpus(haystacks), limit)
+
+    def match_list_top_indices_device(self, corpus, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream=0):
+        """`match_list_top_indices` with the result left in HBM, asynchronous on `stream`: `capacity` >= min(limit, len(corpus)) records of
+        MATCH_INDICES_DTYPE at `dev_out_ptr`, `positions_capacity` >= min(limit, len(corpus)) * len(needle) uint32 at `dev_positions_ptr`
+        (dense: `positions_begin` / `positions_len` index it), four count words at `dev_count_ptr`: records written, matches found,
+        positions written, 0 (non-zero: the traced pass disagreed with the top stage)."""
+        _check(lib().fzb_match_list_top_indices_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream))
+
+    def reserve_top_indices(self, corpus, limit, max_needle_bytes):
+        """After `reserve(corpus)`: no `match_list_top_indices` call with this `limit` or a smaller one, on a needle of up to
+        `max_needle_bytes` bytes, allocates device memory - also across `set_pattern` / `set_config`."""
+        _check(lib().fzb_matcher_reserve_top_indices(self.h, corpus.h, limit, max_needle_bytes))
 
     def match_list_parallel(self, haystacks, threads):
         """`Matcher::match_list_parallel` (src/matcher/parallel.rs:18-89); identical result for every thread count."""

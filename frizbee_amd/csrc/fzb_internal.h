@@ -101,6 +101,15 @@ struct fzb_match_rec {  // == fzb_match; `_pad` carries the valid flag between k
     u8 valid;
 };
 
+struct fzb_indices_rec {  // == fzb_match_indices (include/frizbee_hip.h): what the pack kernels write (kernels_indices.hip)
+    u32 index;
+    u16 score;
+    u8 exact;
+    u8 _pad;
+    u32 positions_begin;
+    u32 positions_len;
+};
+
 // Per-call device workspace (owned by the matcher, grown on demand)
 struct Workspace {
     u64* bitmap;        // count/64 words: filter decisions
@@ -233,6 +242,11 @@ void fzb_launch_concat_runs(const RunSet& rs, const u32* base_in, u32* total_out
 hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, u32 in_cap, u32 limit, int by_score, int desc, int one_pass, fzb_match_rec* out, u32 out_cap,
                             u32* out_count, u32* scratch, u32 ntiles_cap, int grid, hipStream_t st);
 void fzb_launch_topk_concat(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, hipStream_t st);
+// kernels_indices.hip: the glue of the fused top + matched-positions query (item list from the sorted head; packing of the traced positions)
+void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st);
+size_t fzb_indices_pack_tile_words(size_t max_records);
+void fzb_launch_indices_pack(const fzb_match_rec* head, const u32* head_count, const fzb_match_rec* traced, const u32* traced_count, const u32* npos, const u32* pos, u32 stride,
+                             fzb_indices_rec* out, u32 out_cap, u32* dense, u32 dense_cap, u32* dev_count, u32* tiles, u32 max_records, int grid, hipStream_t st);
 // kernels_multi.hip
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st);
 void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u32* count_out, int grid, hipStream_t st);

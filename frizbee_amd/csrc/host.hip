@@ -778,6 +778,22 @@ static int rebuild_matcher(fzb_matcher* m, const fzb_config* config, const uint8
     std::swap(fresh->fetch, m->fetch);
     std::swap(fresh->long_scratch, m->long_scratch);
     std::swap(fresh->long_scratch_bytes, m->long_scratch_bytes);
+    std::swap(fresh->trace_sel, m->trace_sel);  // the matched-indices scratch and the fused top + positions query's buffers
+    std::swap(fresh->trace_pos, m->trace_pos);
+    std::swap(fresh->trace_npos, m->trace_npos);
+    std::swap(fresh->trace_cap, m->trace_cap);
+    std::swap(fresh->trace_pos_words, m->trace_pos_words);
+    std::swap(fresh->top_head, m->top_head);
+    std::swap(fresh->top_traced, m->top_traced);
+    std::swap(fresh->top_idx_words, m->top_idx_words);
+    std::swap(fresh->top_tiles, m->top_tiles);
+    std::swap(fresh->top_cap, m->top_cap);
+    std::swap(fresh->top_packed, m->top_packed);
+    std::swap(fresh->top_dense, m->top_dense);
+    std::swap(fresh->top_packed_cap, m->top_packed_cap);
+    std::swap(fresh->top_dense_words, m->top_dense_words);
+    std::swap(fresh->top_last_records, m->top_last_records);
+    std::swap(fresh->top_last_positions, m->top_last_positions);
     std::swap(fresh->aux_stream, m->aux_stream);
     std::swap(fresh->ev_fork, m->ev_fork);
     std::swap(fresh->ev_join, m->ev_join);
@@ -857,7 +873,8 @@ void fzb_matcher_free(fzb_matcher* m) {
     if (m->out_dev) (void)hipFree(m->out_dev);
     if (m->count_dev) (void)hipFree(m->count_dev);
     if (m->top_words) (void)hipFree(m->top_words);
-    for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos})
+    for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos, (void*)m->top_head, (void*)m->top_traced, (void*)m->top_idx_words, (void*)m->top_tiles,
+                    (void*)m->top_packed, (void*)m->top_dense})
         if (p) (void)hipFree(p);
     for (auto& tr : m->evring)
         for (auto& e : tr)
@@ -1525,19 +1542,24 @@ static bool ascii_split_classes(const fzb_matcher* m, const CorpusDev& cd) {
 }
 static u32 pipe_qcap(const Pipe& p) { return (u32)std::min<u64>((u64)p.cnt + FZB_UNICODE_FWD_CAP, 0xFFFFFFFFull); }
 
-// matched indices: one traced generic scorer for every window width, ASCII and unicode (kernels_generic.hip)
+// matched indices: one traced generic scorer for every window width, ASCII and unicode (kernels_generic.hip); its grid for `cnt` items and
+// its per-wave matrices (grown here on first use, or ahead of it by fzb_matcher_reserve_top_indices)
+static int traced_grid(int cus, size_t cnt) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)cus / 2, (cnt + 3) / 4)); }
+static int ensure_trace_cells(fzb_matcher* m, size_t words) {
+    Workspace& w = m->ws;
+    if (w.trace_cells_words >= words) return FZB_OK;
+    if (w.trace_cells) HIPCHK(hipFree(w.trace_cells));
+    w.trace_cells = nullptr;
+    w.trace_cells_words = 0;
+    HIPCHK(dev_alloc((void**)&w.trace_cells, words * 4));
+    w.trace_cells_words = words;
+    return FZB_OK;
+}
 static int pipe_score_traced(Pipe& p) {
     fzb_matcher* m = p.m;
     Workspace& w = m->ws;
-    const int tgrid = (int)std::max<size_t>(1, std::min<size_t>((size_t)p.cus / 2, ((size_t)p.cnt + 3) / 4));
-    const size_t words = fzb_trace_scratch_words(m->nd, tgrid);
-    if (w.trace_cells_words < words) {
-        if (w.trace_cells) HIPCHK(hipFree(w.trace_cells));
-        w.trace_cells = nullptr;
-        w.trace_cells_words = 0;
-        HIPCHK(dev_alloc((void**)&w.trace_cells, words * 4));
-        w.trace_cells_words = words;
-    }
+    const int tgrid = traced_grid(p.cus, p.cnt);
+    if (int rc = ensure_trace_cells(m, fzb_trace_scratch_words(m->nd, tgrid))) return rc;
     fzb_launch_generic_trace(p.cd, p.first, p.index_offset, p.items, p.win, p.wmode, p.n_items_ptr, m->nd, m->lc.sw_lanes, m->nd.unicode, p.out, p.cap32, p.dev_count, w.counters, w.trace_cells,
                              p.trace->pos, p.trace->npos, p.trace->stride, tgrid, p.st);
     FZB_STAGE("generic(trace)");
@@ -1749,7 +1771,8 @@ static int run_pipeline(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
 // Sizes every device buffer a query over `c` can need (range workspace incl. the typo-path arrays, multi-chunk scorer scratch when
 // the corpus has haystacks wider than a chunk, staging + sort buffers of the synchronous / sorted entry points), so that the queries
 // that follow - also after fzb_matcher_set_pattern / fzb_matcher_set_config, which keep the workspace - never allocate.
-// (Matched-indices queries size their trace scratch from the selection, on first use.)
+// (Matched-indices queries size their trace scratch from the selection, on first use; fzb_matcher_reserve_top_indices sizes it - and the
+// fused top + positions query's own buffers - ahead of that.)
 int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
     // (a corpus with room reserved: sized for that room, and for haystacks of any width - an append may bring them)
@@ -2045,6 +2068,24 @@ int check_selection(const fzb_corpus* c, const uint32_t* selection, size_t n_sel
     return FZB_OK;
 }
 
+// The matched-indices scratch of a matcher: the item list (+ room for its length word behind `count` entries and at the buffer's end), the
+// position counts, the positions (`stride` per record)
+int ensure_trace_buffers(fzb_matcher* m, size_t count, size_t pos_words) {
+    if (m->trace_cap >= count && m->trace_pos_words >= pos_words && m->trace_sel) return FZB_OK;
+    count = std::max(count, m->trace_cap);  // (neither dimension shrinks: what a reserve sized for the longest needle stays)
+    pos_words = std::max(pos_words, m->trace_pos_words);
+    for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos})
+        if (p) HIPCHK(hipFree(p));
+    m->trace_sel = m->trace_pos = m->trace_npos = nullptr;
+    m->trace_cap = m->trace_pos_words = 0;
+    HIPCHK(dev_alloc((void**)&m->trace_sel, (count + 4) * 4));  // [count] = the list length
+    HIPCHK(dev_alloc((void**)&m->trace_npos, count * 4));
+    HIPCHK(dev_alloc((void**)&m->trace_pos, pos_words * 4));
+    m->trace_cap = count;
+    m->trace_pos_words = pos_words;
+    return FZB_OK;
+}
+
 // One pattern over the list, LIST order (match_list_indices_impl, algo.rs:196-227): recs[k].index = position in the list,
 // its positions appended to `positions`.  An empty needle matches everything with no positions.
 int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t count, std::vector<fzb_match_indices>& recs, std::vector<u32>& positions) {
@@ -2056,17 +2097,7 @@ int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* s
     }
     if (!count) return FZB_OK;
     const u32 stride = (u32)std::max(1, m->nd.nbytes);
-    if (m->trace_cap < count || m->trace_pos_words < count * (size_t)stride) {
-        for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos})
-            if (p) HIPCHK(hipFree(p));
-        m->trace_sel = m->trace_pos = m->trace_npos = nullptr;
-        m->trace_cap = m->trace_pos_words = 0;
-        HIPCHK(dev_alloc((void**)&m->trace_sel, (count + 4) * 4));  // [count] = the list length
-        HIPCHK(dev_alloc((void**)&m->trace_npos, count * 4));
-        HIPCHK(dev_alloc((void**)&m->trace_pos, count * (size_t)stride * 4));
-        m->trace_cap = count;
-        m->trace_pos_words = count * (size_t)stride;
-    }
+    if (int rc_ = ensure_trace_buffers(m, count, count * (size_t)stride)) return rc_;
     if (int rc_ = fzb_ensure_out_staging(m, count)) return rc_;
     const u32* items_dev = nullptr;
     const u32* n_items_dev = nullptr;
@@ -2835,6 +2866,237 @@ int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t 
     fzb_launch_sort(mm->out_dev, mm->sort_tmp, mm->count_dev, mm->sort_hist, ntiles_cap, reversed, by_score, grid, nullptr);
     HIPCHK(hipGetLastError());
     return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
+}
+
+// ---- top-`limit` with matched positions: one fused device call ------------------------------------------------------------------
+// The reference has no such call: the caller truncates what `Matcher::match_list_indices` returns (src/matcher/mod.rs:234-275).  Here the top
+// stage leaves its sorted head in HBM (m->top_head), k_top_items makes it the item list of a traced second pass (run_pipeline's item form
+// with a TraceOut: records in head order into m->top_traced - neither the head nor the caller's output -, strided positions into the
+// matched-indices scratch), and the pack kernels (kernels_indices.hip) write the caller's records and dense positions while checking that
+// the two passes agree (the accept decision and the scores of match_list and match_list_indices are the same code in the reference:
+// src/matcher/algo.rs:78-103 against :196-227).  Nothing is read back between the stages.
+}  // extern "C"
+static_assert(sizeof(fzb_indices_rec) == sizeof(fzb_match_indices) && offsetof(fzb_indices_rec, positions_begin) == offsetof(fzb_match_indices, positions_begin) &&
+                  offsetof(fzb_indices_rec, positions_len) == offsetof(fzb_match_indices, positions_len),
+              "the pack kernels write fzb_match_indices");
+namespace {
+template <typename T>
+int grow_dev(T** p, size_t* have, size_t want, size_t slack) {  // a buffer that only grows; *have = elements it holds, the slack excluded
+    if (*p && *have >= want) return FZB_OK;
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *have = 0;
+    HIPCHK(dev_alloc((void**)p, (want + slack) * sizeof(T)));
+    *have = want;
+    return FZB_OK;
+}
+// the buffers of a fused query with a head of up to `want` records and `stride` position dwords per record (everything but the traced
+// scorer's matrices, which are workspace); staging: the host form's packed result too
+int ensure_top_indices_buffers(fzb_matcher* m, size_t want, size_t stride, bool staging) {
+    int rc = ensure_trace_buffers(m, want, want * stride);
+    if (rc) return rc;
+    if (!m->top_idx_words) HIPCHK(dev_alloc((void**)&m->top_idx_words, 64));
+    if (!m->top_head || !m->top_traced || !m->top_tiles || m->top_cap < want) {
+        for (void* p : {(void*)m->top_head, (void*)m->top_traced, (void*)m->top_tiles})
+            if (p) HIPCHK(hipFree(p));
+        m->top_head = m->top_traced = nullptr;
+        m->top_tiles = nullptr;
+        m->top_cap = 0;
+        HIPCHK(dev_alloc((void**)&m->top_head, (want + 16) * sizeof(fzb_match_rec)));
+        HIPCHK(dev_alloc((void**)&m->top_traced, (want + 16) * sizeof(fzb_match_rec)));
+        HIPCHK(dev_alloc((void**)&m->top_tiles, fzb_indices_pack_tile_words(want) * 4));
+        m->top_cap = want;
+    }
+    if (!staging) return FZB_OK;
+    if ((rc = grow_dev(&m->top_packed, &m->top_packed_cap, want, 1))) return rc;
+    return grow_dev(&m->top_dense, &m->top_dense_words, want * stride, 1);
+}
+u32 trace_stride(const fzb_matcher* m) { return (u32)std::max(1, m->nd.nbytes); }  // position dwords per record: as indices_in_list_order
+
+// malloc'ed result of the *_indices entry points (fzb_match_indices_free): nrec records, npos positions, copied from `recs` / `pos`
+int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos, size_t npos, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
+    fzb_match_indices* r = (fzb_match_indices*)malloc(std::max<size_t>(nrec, 1) * sizeof(fzb_match_indices));
+    u32* p = (u32*)malloc(std::max<size_t>(npos, 1) * 4);
+    if (!r || !p) {
+        free(r);
+        free(p);
+        return fail(FZB_ERR_INVALID, "out of memory");
+    }
+    if (nrec) memcpy(r, recs, nrec * sizeof(fzb_match_indices));
+    if (npos) memcpy(p, pos, npos * 4);
+    *out = r;
+    *out_len = nrec;
+    *out_positions = p;
+    return FZB_OK;
+}
+}  // namespace
+extern "C" {
+
+int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                      uint32_t* dev_count, void* stream) {
+    if (!m || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top_indices");
+    const u32 stride = trace_stride(m);
+    if (positions_capacity < want * (size_t)stride)
+        return fail(FZB_ERR_CAPACITY, "positions buffer smaller than min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(want * (size_t)stride));
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if ((u64)want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
+        return FZB_OK;
+    }
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false))) return rc;
+    u32* const head_count = m->top_idx_words;        // (records, matches found) of the head
+    u32* const traced_count = m->top_idx_words + 2;  // the traced pass' pair
+    u32* const n_items = m->trace_sel + m->trace_cap;
+    if ((rc = fzb_match_list_top_device(m, c, limit, (fzb_match*)m->top_head, want, head_count, stream))) return rc;
+    const int grid = m->lc.num_cus * 2;
+    fzb_launch_top_items(m->top_head, head_count, (u32)want, m->trace_sel, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
+    const TraceOut tr{m->trace_pos, m->trace_npos, stride};
+    // (grids from min(limit, n) on the host, trimmed by the item count on the device; want == 0 - limit 0 - clears the pair and launches nothing)
+    if ((rc = run_pipeline(m, c, 0, want, 0, m->trace_sel, n_items, (fzb_match*)m->top_traced, want, traced_count, stream, &tr))) return rc;
+    fzb_launch_indices_pack(m->top_head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top_tiles, (u32)want, grid, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
+int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (!m || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (m->empty) {  // fzb_empty_pattern_top's rule: the first / last min(limit, n) indices, score 0; no positions
+        const bool reversed = m->config.sort == FZB_SORT_INDEX_DESC || m->config.sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+        std::vector<fzb_match_indices> recs(want);
+        for (size_t i = 0; i < want; i++) recs[i] = fzb_match_indices{(uint32_t)(reversed ? n - 1 - i : i), 0, 0, 0, 0, 0};
+        if (out_found) *out_found = n;
+        return hand_over_indices(recs.data(), want, nullptr, 0, out, out_len, out_positions);
+    }
+    if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
+    const size_t stride = trace_stride(m);
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
+    u32* const words = m->top_idx_words + 4;
+    if ((rc = fzb_match_list_top_indices_device(m, c, limit, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense, m->top_dense_words, words, nullptr))) return rc;
+    // ONE wait for the four words, the records and the packed positions: a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind
+    // the words, filled or not (fzb_fetch_top's rule), and so are its positions while they are no more than the records would be at that
+    // bound (256 KB); beyond, the copy takes the previous result's size and a little more, and a result that outgrew it costs a second wait
+    const size_t max_pos = want * stride;
+    auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
+    const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(m->top_last_records, want);
+    const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(m->top_last_positions, max_pos);
+    u8* stage = (u8*)fzb_pinned_get(32 + grec * sizeof(fzb_match_indices) + gpos * 4);
+    if (!stage) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
+    const u32* const hw = (const u32*)stage;
+    const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + 32);
+    const u32* const hpos = (const u32*)(stage + 32 + grec * sizeof(fzb_match_indices));
+    hipError_t e = hipMemcpyAsync(stage, words, 16, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, m->top_packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, m->top_dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess) e = fzb_stream_wait(nullptr);
+    if (e != hipSuccess) {
+        fzb_pinned_put(stage);
+        return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
+    }
+    const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
+    if (hw[3]) {
+        const u32 why = hw[3];
+        fzb_pinned_put(stage);
+        return fail(FZB_ERR_HIP, std::string("internal: the traced pass disagrees with the top stage (") + ((why & 1u) ? "record count" : "a record's index, score or exact flag") + ")");
+    }
+    rc = hand_over_indices(hrec, std::min(nrec, grec), hpos, std::min(npos, gpos), out, out_len, out_positions);
+    fzb_pinned_put(stage);
+    if (rc) return rc;
+    if (nrec > grec || npos > gpos) {  // the result outgrew the guess: the rest in a second copy, straight into the caller's arrays
+        fzb_match_indices* r = (fzb_match_indices*)realloc(*out, std::max<size_t>(nrec, 1) * sizeof(fzb_match_indices));
+        if (r) *out = r;
+        u32* p = r ? (u32*)realloc(*out_positions, std::max<size_t>(npos, 1) * 4) : nullptr;
+        if (p) *out_positions = p;
+        e = (r && p) ? hipSuccess : hipErrorOutOfMemory;
+        if (e == hipSuccess && nrec > grec) e = hipMemcpy(r + grec, m->top_packed + grec, (nrec - grec) * sizeof(fzb_match_indices), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && npos > gpos) e = hipMemcpy(p + gpos, m->top_dense + gpos, (npos - gpos) * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            fzb_match_indices_free(*out, *out_positions);
+            *out = nullptr;
+            *out_positions = nullptr;
+            *out_len = 0;
+            return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
+        }
+        *out_len = nrec;
+    }
+    m->top_last_records = nrec;
+    m->top_last_positions = npos;
+    if (out_found) *out_found = found;
+    return FZB_OK;
+}
+
+// Sizes what fzb_matcher_reserve leaves to the first matched-indices query - item list, position counts, strided positions, the traced
+// scorer's matrices - and the fused query's own buffers (head, traced records, tile sums, packed records and positions), for heads of up to
+// min(limit, haystacks the corpus has room for) records and needles of up to max_needle_bytes bytes.
+int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, size_t max_needle_bytes) {
+    if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = fzb_corpus_reserved_items(c);
+    const size_t want = std::min(limit, n);
+    if (want == 0) return FZB_OK;
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    const size_t stride = std::max<size_t>(std::max<size_t>(max_needle_bytes, 1), m->empty ? 1 : trace_stride(m));
+    if ((u64)want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    int rc = fzb_bind_device(m);
+    if (rc) return rc;
+    // (the range workspace first: growing it releases every workspace buffer, the traced scorer's matrices included)
+    if (!m->empty && (rc = ensure_workspace(m, n))) return rc;
+    if ((rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
+    // the traced scorer's matrices: one (rows + 1) x TRACE_W slab per wave of its grid; a needle of b bytes has at most b rows, and one the
+    // by-value NeedleDev holds at most FZB_MAX_ROWS (a longer needle's scratch is its own: ensure_long_needle grows it on first use)
+    NeedleDev probe = m->nd;
+    probe.rows = (int32_t)std::min<size_t>(stride, FZB_MAX_ROWS);
+    return ensure_trace_cells(m, fzb_trace_scratch_words(probe, traced_grid(m->lc.num_cus, want)));
+}
+
+// The `from_patterns` form, a host composition of the existing pieces: the multi top goes to the host, then the multi matched-indices
+// implementation runs in LIST order over that selection (the head is already in order, so nothing is re-ordered) and `index` is mapped back
+// from the position in the selection to the corpus index.
+int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    fzb_match* head = nullptr;
+    size_t nhead = 0;
+    uint64_t found = 0;
+    int rc = fzb_multi_match_list_top(mm, c, limit, &head, &nhead, &found);
+    if (rc) return rc;
+    std::vector<u32> sel(nhead);
+    for (size_t k = 0; k < nhead; k++) sel[k] = head[k].index;
+    std::vector<fzb_match> kept(head, head + nhead);
+    fzb_matches_free(head);
+    if (out_found) *out_found = found;
+    if (nhead == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
+    if ((rc = multi_match_list_indices_impl(mm, c, sel.data(), nhead, FZB_SORT_INDEX_ASC, 0, out, out_len, out_positions))) return rc;
+    bool same = *out_len == nhead;
+    for (size_t k = 0; same && k < nhead; k++) {
+        fzb_match_indices& r = (*out)[k];
+        same = r.index == k && r.score == kept[k].score && (r.exact != 0) == (kept[k].exact != 0);
+        r.index = sel[k];
+    }
+    if (!same) {
+        fzb_match_indices_free(*out, *out_positions);
+        *out = nullptr;
+        *out_positions = nullptr;
+        *out_len = 0;
+        return fail(FZB_ERR_HIP, "internal: the matched-indices pass disagrees with the top stage");
+    }
+    return FZB_OK;
 }
 
 void fzb_matches_free(fzb_match* p) {

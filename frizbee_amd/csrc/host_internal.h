@@ -111,6 +111,18 @@ struct fzb_matcher {
     u32* trace_pos = nullptr;
     u32* trace_npos = nullptr;
     size_t trace_cap = 0, trace_pos_words = 0;
+    // fzb_match_list_top_indices*: the top stage's sorted head, the traced second pass' records, the count words of both passes
+    // ([0..1] head pair, [2..3] traced pair, [4..7] the host form's four result words), the pack's tile sums - for `top_cap` records; the
+    // host form's packed staging (records, dense positions) and what its previous result held (the guess of the next copy)
+    fzb_match_rec* top_head = nullptr;
+    fzb_match_rec* top_traced = nullptr;
+    u32* top_idx_words = nullptr;
+    u32* top_tiles = nullptr;
+    size_t top_cap = 0;
+    fzb_indices_rec* top_packed = nullptr;
+    u32* top_dense = nullptr;
+    size_t top_packed_cap = 0, top_dense_words = 0;
+    size_t top_last_records = 0, top_last_positions = 0;
     // a needle beyond NeedleDev's arrays (> 64 bytes or > 63 rows): scalars in `ndl`, the arrays in one device blob (uploaded on first
     // use), and the global scratch of its kernels (N-typo path state, per-row previous-chunk vectors, traced cells)
     bool long_needle = false;

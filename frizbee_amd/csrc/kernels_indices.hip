@@ -1,0 +1,185 @@
+// gfx950 kernels, the glue of the fused "top + matched positions" query (fzb_match_list_top_indices*): between the top stage's ordering
+// step and the traced pipeline, and behind the traced pipeline.
+//
+// The reference has no such call: its caller truncates what `Matcher::match_list_indices` returns (src/matcher/mod.rs:234-275).  Here the
+// sorted head of the top stage stays in HBM; k_top_items turns it into the item list (+ its length word) of the traced second pass, and
+// the pack kernels turn that pass' strided positions into the caller's dense array (indices_pack.h says how) while holding every traced
+// record to the head's record at its place.  Nothing is read back in between; the record count lives in device memory and the grids are
+// sized by the caller from min(limit, haystacks).
+//   * a head of up to IPACK_TILE records - the picker's case - is packed by ONE launch of one workgroup: every thread scans its share of
+//     IPACK_SHARE consecutive records, the shares are scanned across the wave with shuffles and across the four waves through LDS, the
+//     records are written, and then the threads walk the tile's DENSE positions (thread t takes position t, t + 256, ..: the stores are
+//     coalesced, the loads are runs of one record's positions), finding each position's record by bisection of the begins kept in LDS;
+//   * a longer head takes three launches, as the selection stage does (kernels_topk.hip): per-tile sums, their exclusive scan (one wave),
+//     and the same scatter kernel with every tile starting at its scanned base.  No workgroup waits for another one, nothing is ordered by
+//     an atomic.
+#include "kernels_common.h"
+#include "indices_pack.h"
+
+#define IPACK_THREADS (IPACK_TILE / IPACK_SHARE)
+static_assert(IPACK_THREADS == 256, "four waves scan a tile");
+
+struct PackArgs {
+    const fzb_match_rec* head;     // the sorted head and its pair (records, matches found)
+    const u32* head_count;
+    const fzb_match_rec* traced;   // the traced pass' records in item order and its pair
+    const u32* traced_count;
+    const u32* npos;               // per traced record: positions found; its positions at pos[k * stride ..]
+    const u32* pos;
+    u32 stride;
+    fzb_indices_rec* out;          // the packed records, the dense positions, the four result words
+    u32 out_cap;
+    u32* dense;
+    u32 dense_cap;
+    u32* dev_count;
+    u32* tiles;                    // [0, ntiles_cap) tile sums, [ntiles_cap, 2 ntiles_cap) their exclusive scan (heads beyond one tile)
+    u32 ntiles_cap;
+};
+
+__device__ __forceinline__ u32 ipack_count(const PackArgs& a) { return min(a.head_count[0], a.out_cap); }
+
+// exclusive scan of one value per thread over the workgroup (four waves); *total = the workgroup's sum.  Two barriers.
+__device__ __forceinline__ u32 ipack_block_scan(u32 v, u32* s_wave, u32* total) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    u32 incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const u32 x = __shfl_up(incl, o);
+        if (lane >= o) incl += x;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    u32 before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < IPACK_THREADS / 64; w++) {
+        if (w < wave) before += s_wave[w];
+        all += s_wave[w];
+    }
+    __syncthreads();  // (s_wave is written again by the next tile)
+    *total = all;
+    return before + incl - v;
+}
+
+// the head's corpus indices in head order + their number: the item list of the traced pass.  Clears the two result words the pack
+// kernels only ever raise (positions written, inconsistency).
+__global__ __launch_bounds__(256) void k_top_items(const fzb_match_rec* __restrict__ head, const u32* __restrict__ head_count, u32 cap, u32* __restrict__ items,
+                                                   u32* __restrict__ n_items, u32* __restrict__ dev_count) {
+    const u32 n = min(head_count[0], cap);
+    for (u32 j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) items[j] = head[j].index;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        n_items[0] = n;
+        dev_count[2] = 0;
+        dev_count[3] = 0;
+    }
+}
+
+// heads beyond one tile, first launch: positions per tile
+__global__ __launch_bounds__(IPACK_THREADS) void k_ipack_tile_sums(const PackArgs a) {
+    __shared__ u32 s_wave[IPACK_THREADS / 64];
+    const u32 n = ipack_count(a);
+    const u32 ntiles = min(ipack_ntiles(n), a.ntiles_cap);
+    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        u32 lo, hi;
+        ipack_tile_range(tile, n, &lo, &hi);
+        const u32 first = min(lo + threadIdx.x * IPACK_SHARE, hi);
+        u32 begins[IPACK_SHARE];
+        const u32 mine = ipack_scan_share(a.npos, first, min(hi - first, (u32)IPACK_SHARE), a.stride, begins);
+        u32 total;
+        (void)ipack_block_scan(mine, s_wave, &total);
+        if (threadIdx.x == 0) a.tiles[tile] = total;
+    }
+}
+
+// second launch: exclusive scan of the tile sums (one wave); the grand total is the number of position dwords
+__global__ __launch_bounds__(64) void k_ipack_scan_tiles(const PackArgs a) {
+    const u32 n = ipack_count(a);
+    const u32 ntiles = min(ipack_ntiles(n), a.ntiles_cap);
+    const int lane = lane_id();
+    u32 carry = 0;
+    for (u32 t0 = 0; t0 < ntiles; t0 += 64) {  // uniform trip count: every lane takes part in the shuffles
+        const u32 t = t0 + lane;
+        const u32 v = t < ntiles ? a.tiles[t] : 0u;
+        u32 incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const u32 x = __shfl_up(incl, o);
+            if (lane >= o) incl += x;
+        }
+        if (t < ntiles) a.tiles[a.ntiles_cap + t] = carry + incl - v;
+        carry += __shfl(incl, 63);
+    }
+    if (lane == 0) a.dev_count[2] = min(carry, a.dense_cap);
+}
+
+// the scan inside a tile, the records, the gather of the positions and the check against the head.  MULTI: the tile's base comes from
+// the scanned tile sums; otherwise there is one tile, its base is 0 and its total is the result's.
+template <bool MULTI>
+__global__ __launch_bounds__(IPACK_THREADS) void k_ipack_scatter(const PackArgs a) {
+    __shared__ u32 s_begin[IPACK_TILE];
+    __shared__ u32 s_wave[IPACK_THREADS / 64];
+    const u32 n = ipack_count(a);
+    const u32 ntiles = min(ipack_ntiles(n), MULTI ? a.ntiles_cap : 1u);
+    u32 bad = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.dev_count[0] = n;
+        a.dev_count[1] = a.head_count[1];  // matches found
+        bad |= ipack_check_count(a.head_count[0], a.traced_count[0]);
+    }
+    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        u32 lo, hi;
+        ipack_tile_range(tile, n, &lo, &hi);
+        const u32 first = min(lo + threadIdx.x * IPACK_SHARE, hi);
+        const u32 cnt = min(hi - first, (u32)IPACK_SHARE);
+        u32 begins[IPACK_SHARE];
+        const u32 mine = ipack_scan_share(a.npos, first, cnt, a.stride, begins);
+        u32 total;
+        const u32 before = ipack_block_scan(mine, s_wave, &total);
+        const u32 base = MULTI ? a.tiles[a.ntiles_cap + tile] : 0u;
+#pragma unroll
+        for (u32 r = 0; r < IPACK_SHARE; r++) {
+            if (r >= cnt) break;
+            const u32 k = first + r;
+            const fzb_match_rec h = a.head[k], t = a.traced[k];
+            bad |= ipack_check_record(h.index, h.score, h.exact, t.index, t.score, t.exact);
+            s_begin[k - lo] = before + begins[r];
+            fzb_indices_rec o;
+            o.index = h.index;
+            o.score = h.score;
+            o.exact = h.exact;
+            o._pad = 0;
+            o.positions_begin = base + before + begins[r];
+            o.positions_len = ipack_len(a.npos[k], a.stride);
+            a.out[k] = o;
+        }
+        __syncthreads();
+        for (u32 d = threadIdx.x; d < total; d += IPACK_THREADS) {
+            const u32 r = ipack_find_record(s_begin, hi - lo, d);
+            if (base + d < a.dense_cap) a.dense[base + d] = a.pos[(size_t)(lo + r) * a.stride + (d - s_begin[r])];
+        }
+        if (!MULTI && threadIdx.x == 0) a.dev_count[2] = min(total, a.dense_cap);
+        __syncthreads();  // (s_begin is written again by the next tile)
+    }
+    if (bad) a.dev_count[3] = bad;  // (k_top_items cleared it; every writer stores a non-zero word)
+}
+
+void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_top_items, dim3(grid), dim3(256), 0, st, head, head_count, cap, items, n_items, dev_count);
+}
+
+// u32 words of `tiles` the pack needs for heads of up to max_records records
+size_t fzb_indices_pack_tile_words(size_t max_records) { return 2 * ((max_records + IPACK_TILE - 1) / IPACK_TILE + 1); }
+
+// head / traced: max_records-record buffers with their count pairs; npos / pos: the traced pass' counts and strided positions.  out (room
+// for out_cap >= max_records records), dense (dense_cap dwords) and dev_count (four words, [2] and [3] cleared by k_top_items) receive the
+// result.  tiles: fzb_indices_pack_tile_words(max_records) words (not read for max_records <= IPACK_TILE).
+void fzb_launch_indices_pack(const fzb_match_rec* head, const u32* head_count, const fzb_match_rec* traced, const u32* traced_count, const u32* npos, const u32* pos, u32 stride,
+                             fzb_indices_rec* out, u32 out_cap, u32* dense, u32 dense_cap, u32* dev_count, u32* tiles, u32 max_records, int grid, hipStream_t st) {
+    const u32 ntiles_cap = (max_records + IPACK_TILE - 1) / IPACK_TILE + 1;
+    const PackArgs a{head, head_count, traced, traced_count, npos, pos, stride, out, std::min<u32>(out_cap, max_records), dense, dense_cap, dev_count, tiles, ntiles_cap};
+    if (max_records <= IPACK_TILE) {
+        hipLaunchKernelGGL((k_ipack_scatter<false>), dim3(1), dim3(IPACK_THREADS), 0, st, a);
+        return;
+    }
+    const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, ntiles_cap));
+    hipLaunchKernelGGL(k_ipack_tile_sums, dim3(g), dim3(IPACK_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_ipack_scan_tiles, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_ipack_scatter<true>), dim3(g), dim3(IPACK_THREADS), 0, st, a);
+}

@@ -362,6 +362,35 @@ int fzb_match_list_indices_into(fzb_matcher* m, const fzb_corpus* c, const uint3
                                 fzb_match_indices** out, size_t* out_len, uint32_t** out_positions);
 void fzb_match_indices_free(fzb_match_indices* matches, uint32_t* positions);
 
+/* TOP-`limit` WITH MATCHED POSITIONS, one fused call: what a picker shows after a keystroke.  The reference has no such call: its caller
+ * truncates the Vec that `Matcher::match_list_indices(&haystacks)` returns over the whole list (src/matcher/mod.rs:234-275), exactly as for
+ * fzb_match_list_top.  The contract is that truncation: the first min(limit, found) elements of that Vec, in its order - list order,
+ * reversed for the *Desc strategies, then stably sorted by descending score for the Score* strategies.  `index` is the CORPUS index (the
+ * list is the whole corpus), the positions are the matched byte positions in reverse order as in fzb_match_list_indices, and found = the
+ * length of the full list.  On the device: the top stage's sorted head stays in HBM and becomes the item list of a traced second pass, whose
+ * positions are packed densely; every traced record is checked against the head's record at its place (same index, score and exact flag,
+ * same count: the accept decision and the scores of match_list and match_list_indices are the same code in the reference,
+ * src/matcher/algo.rs:78-103 against :196-227).  ONE host wait brings back counts, records and positions.  limit = 0 is valid (no records,
+ * found still reported); an empty needle matches every haystack with score 0 and no positions (the first / last min(limit, n) indices, host
+ * work).  Free with fzb_match_indices_free; *out_found is optional.  A disagreement between the two passes: FZB_ERR_HIP, "internal: ...". */
+int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions,
+                               uint64_t* out_found);
+/* The same with the result left in HBM and no host synchronisation; asynchronous on `stream`.  dev_out has room for `capacity` >=
+ * min(limit, corpus length) records, dev_positions for `positions_capacity` >= min(limit, corpus length) x needle bytes dwords (less of
+ * either: FZB_ERR_CAPACITY, nothing launched).  dev_out[k].positions_begin / positions_len index the DENSE dev_positions.  dev_count (four
+ * words): [0] = records written = min(limit, found), [1] = found, [2] = position dwords written, [3] = 0, or non-zero when the traced pass
+ * disagreed with the top stage (bit 0: record count, bit 1: a record).  An empty corpus zeroes the four words.  Not for an empty needle
+ * (FZB_ERR_INVALID). */
+int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                      size_t positions_capacity, uint32_t* dev_count, void* stream);
+/* After fzb_matcher_reserve(m, c) and this call, no fzb_match_list_top_indices[_device] call with this `limit` or a smaller one, on any
+ * needle of at most max_needle_bytes bytes, allocates device memory - also across fzb_matcher_set_pattern / fzb_matcher_set_config.  Sizes
+ * the item list, the position counts, the strided positions, the traced scorer's matrices, the head, the traced records, and the packed
+ * records and positions of the host form.  (Without it these grow on first use, sized by min(limit, corpus length).  A needle beyond 64
+ * bytes / 63 rows keeps its own scratch, which grows when such a needle is first used, and a new config whose filter form needs workspace
+ * arrays the reserved form did not - typos after none - regrows the range workspace once: both as for fzb_matcher_reserve.) */
+int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, size_t max_needle_bytes);
+
 /* `radix_sort_matches(&mut [Match])` (src/sort.rs:6-40): stable, descending score, host side */
 void fzb_radix_sort_matches(fzb_match* matches, size_t n);
 /* `k_merge_matches_by_*` (src/k_merge.rs:56-132): merges per-shard runs (each sorted per `sort`) - the
@@ -406,6 +435,13 @@ int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t 
  * must match, scores add with saturation, exact flags OR, and the patterns' positions are merged (descending, de-duplicated). */
 int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection,
                                  fzb_match_indices** out, size_t* out_len, uint32_t** out_positions);
+/* fzb_match_list_top_indices for a `from_patterns` matcher: the first min(limit, found) elements of what `Matcher::match_list_indices`
+ * returns over the whole list for `Matcher::from_patterns` (src/matcher/mod.rs:234-275).  A HOST composition of the existing pieces:
+ * fzb_multi_match_list_top brings the head to the host, fzb_multi_match_list_indices' implementation then runs in list order over that
+ * selection and `index` is mapped back to the corpus index; the head is already in order, so nothing is re-ordered.  (The per-haystack
+ * union of the patterns' positions stays host work; a device-fused multi form, the sharded and the RCCL forms are not built.) */
+int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions,
+                                     uint64_t* out_found);
 /* list-order forms (see fzb_match_list_into / fzb_match_list_indices_into): `Matcher::match_list_into` over CompiledPatterns
  * (src/matcher/mod.rs:373-392) with the result on the host, and what `match_iter` / `match_one` / `match_iter_indices` yield
  * (`match_one_multi`, `match_one_indices_multi`, src/matcher/multi.rs:29-82) */

@@ -107,6 +107,12 @@ extern "C" {
     fn fzb_match_list_top(m: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     #[allow(dead_code)]
     fn fzb_match_list_top_device(m: *mut c_void, c: *const c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_match_list_top_indices(m: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize, out_positions: *mut *mut u32,
+                                  out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_match_list_top_indices_device(m: *mut c_void, c: *const c_void, limit: usize, dev_out: *mut FzbMatchIndices, capacity: usize, dev_positions: *mut u32,
+                                         positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_matcher_reserve_top_indices(m: *mut c_void, c: *const c_void, limit: usize, max_needle_bytes: usize) -> c_int;
     fn fzb_match_list_top_sharded(m: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_match_list_indices(m: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
                               out_positions: *mut *mut u32) -> c_int;
@@ -154,6 +160,8 @@ extern "C" {
     fn fzb_multi_match_list_parallel_rccl(mm: *mut c_void, shard: *const c_void, index_offset: u32, comm: *mut c_void, flags: c_int, out: *mut *mut FzbMatch,
                                           out_len: *mut usize) -> c_int;
     fn fzb_multi_match_list_top(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_indices(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize, out_positions: *mut *mut u32,
+                                        out_found: *mut u64) -> c_int;
     fn fzb_multi_match_list_top_sharded(mm: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_multi_matcher_shard_report(mm: *const c_void) -> *const c_char;
 }
@@ -387,6 +395,22 @@ impl MatcherHip {
         (v, found as usize)
     }
 
+    /// The first `min(limit, found)` entries of `match_list_indices` over the whole list (`index` = the corpus index) and `found`: what a
+    /// picker shows after a keystroke - the best matches with their matched positions.  The reference's caller truncates the Vec
+    /// `match_list_indices` returns (src/matcher/mod.rs:234-275); here the top stage, a traced pass over its head and the packing of the
+    /// positions are one device call with one host wait.
+    pub fn match_list_top_indices(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<MatchIndices>, usize) {
+        let (mut out, mut n, mut pos, mut found) = (std::ptr::null_mut(), 0usize, std::ptr::null_mut(), 0u64);
+        check(unsafe { fzb_match_list_top_indices(self.handle, corpus.handle, limit, &mut out, &mut n, &mut pos, &mut found) });
+        (take_indices(out, n, pos), found as usize)
+    }
+
+    /// After `reserve`: no `match_list_top_indices` call with this `limit` or a smaller one, on a needle of up to `max_needle_bytes` bytes,
+    /// allocates device memory - also across `set_pattern` / `set_config`.
+    pub fn reserve_top_indices(&mut self, corpus: &HipCorpus, limit: usize, max_needle_bytes: usize) {
+        check(unsafe { fzb_matcher_reserve_top_indices(self.handle, corpus.handle, limit, max_needle_bytes) });
+    }
+
     /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
     pub fn match_list_top_sharded(&mut self, corpus: &ShardedCorpus, limit: usize) -> (Vec<Match>, usize) {
         let (mut out, mut n, mut found) = (std::ptr::null_mut(), 0usize, 0u64);
@@ -430,6 +454,20 @@ impl MatcherHip {
         unsafe { fzb_match_indices_free(out, pos) };
         v
     }
+}
+// records + flat positions of a *_indices result -> Vec<MatchIndices>; releases the library's arrays
+fn take_indices(out: *mut FzbMatchIndices, n: usize, pos: *mut u32) -> Vec<MatchIndices> {
+    let v = unsafe { std::slice::from_raw_parts(out, n) }
+        .iter()
+        .map(|m| MatchIndices {
+            index: m.index,
+            score: m.score,
+            exact: m.exact != 0,
+            indices: unsafe { std::slice::from_raw_parts(pos.add(m.positions_begin as usize), m.positions_len as usize) }.to_vec(),
+        })
+        .collect();
+    unsafe { fzb_match_indices_free(out, pos) };
+    v
 }
 impl Drop for MatcherHip {
     fn drop(&mut self) {
@@ -513,6 +551,14 @@ impl HipMultiMatcher {
         let mut v = Vec::with_capacity(n);
         copy_out(out, n, &mut v);
         (v, found as usize)
+    }
+
+    /// `MatcherHip::match_list_top_indices` for `from_patterns`: a host composition - the multi top, then the multi matched-indices pass in
+    /// list order over that head (already in order: nothing is re-ordered), `index` mapped back to the corpus index.
+    pub fn match_list_top_indices(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<MatchIndices>, usize) {
+        let (mut out, mut n, mut pos, mut found) = (std::ptr::null_mut(), 0usize, std::ptr::null_mut(), 0u64);
+        check(unsafe { fzb_multi_match_list_top_indices(self.handle, corpus.handle, limit, &mut out, &mut n, &mut pos, &mut found) });
+        (take_indices(out, n, pos), found as usize)
     }
 
     /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
