@@ -124,6 +124,7 @@ SYMBOLS = [
     "fzb_corpus_reserve", "fzb_corpus_append", "fzb_corpus_truncate", "fzb_corpus_info", "fzb_debug_corpus_read",
     "fzb_corpus_remove", "fzb_corpus_remove_device", "fzb_corpus_replace", "fzb_corpus_edit_info",
     "fzb_match_list_top_indices", "fzb_match_list_top_indices_device", "fzb_matcher_reserve_top_indices", "fzb_multi_match_list_top_indices",
+    "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold",
 ]
 
 
@@ -227,6 +228,10 @@ def lib():
         l.fzb_match_list_top_indices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.fzb_matcher_reserve_top_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         l.fzb_multi_match_list_top_indices.argtypes = l.fzb_match_list_top_indices.argtypes
+        l.fzb_corpus_signature_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+        l.fzb_debug_needle_signature.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        l.fzb_debug_signature_threshold.argtypes = []
+        l.fzb_debug_signature_threshold.restype = C.c_uint32
         _lib = l
     return _lib
 
@@ -354,7 +359,13 @@ class Corpus:
     INFO_FIELDS = ("items", "item_capacity", "bytes", "byte_capacity", "max_len", "uniform_len", "has_view", "view_nv", "outliers", "ends_u64", "regrows",
                    "h2d_bytes")
     DEBUG_ARRAYS = {"bytes": (0, np.uint8), "ends": (1, None), "vbytes": (2, np.uint8), "vgofs": (3, np.uint32), "vgnv": (4, np.uint8), "vlen": (5, np.uint16),
-                    "vperm": (6, np.uint16), "vlong": (7, np.uint32)}
+                    "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32)}
+
+    def signature_info(self):
+        """fzb_corpus_signature_info: (built, bytes) - whether the corpus has letter signatures and their size in device memory."""
+        built, nbytes = C.c_int(), C.c_uint64()
+        _check(lib().fzb_corpus_signature_info(self.h, C.byref(built), C.byref(nbytes)))
+        return bool(built.value), int(nbytes.value)
 
     def info(self):
         """fzb_corpus_info as a dict (INFO_FIELDS)."""

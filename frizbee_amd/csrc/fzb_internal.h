@@ -92,6 +92,9 @@ struct CorpusDev {
     // would cost a million-item list its view.
     const u32* vlong;
     u32 n_long;
+    // LETTER SIGNATURES (sig_filter.h) of a list whose haystacks all fit 32 bytes (the lists k1_dfa serves): sig[i] = which letters / byte
+    // classes occur in haystack i; nullptr = none.  A 0-typo ASCII query reads these 4 bytes per haystack and the bytes of the rows that can match only.
+    const u32* sig;
 };
 
 struct fzb_match_rec {  // == fzb_match; `_pad` carries the valid flag between kernels (0 in final output)
@@ -197,7 +200,7 @@ struct RejectOut {
 void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* table, const u8* dfa, u32 dead, int rows, int mode, int need, u32 min_len,
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m = nullptr, u32* tile_counts_m = nullptr,
                        u64* reject_bits = nullptr, u32* tile_rejects = nullptr, int nul_safe = 0, int acc_lo = -1, const u8* cdfa = nullptr, u32 cdfa_bytes = 0,
-                       int cdfa_K = 0, int cdfa_G = 0);
+                       int cdfa_K = 0, int cdfa_G = 0, u32 needle_sig = 0, int sig_ok = 0);  // sig_ok: the needle is eligible for the signature form (sig_filter.h)
 void fzb_launch_scan_rejects(const u32* tile_rejects, u32 ntiles, const u32* reject_count, u32* rej_prefix, hipStream_t st);
 void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st);  // the 16-word counter block: [0] = n0, the rest 0
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,

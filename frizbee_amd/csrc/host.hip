@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "host_internal.h"
+#include "sig_filter.h"
 
 namespace {
 #include "unicode_case_table.inc"
@@ -174,6 +175,7 @@ FzbKnobs parse_knobs() {
     k.debug_sync = set("FZB_DEBUG_SYNC");
     k.typo_exact_window = on("FZB_TYPO_EXACT_WINDOW");
     k.no_filter_view = getenv("FZB_FILTER_VIEW") != nullptr && atoi(getenv("FZB_FILTER_VIEW")) == 0;
+    k.no_signature = on("FZB_NO_SIGNATURE");
     k.verify_promises = num("FZB_VERIFY_PROMISES", 1) != 0;
     k.no_lcs_dfa = set("FZB_NO_LCS_DFA");
     k.no_cdfa = set("FZB_NO_CDFA");
@@ -758,6 +760,9 @@ int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, siz
     build_lcs_dfa(m);
     build_cdfa(m);
     set_scorer_forms(m, needle_utf8, needle_len);
+    // the stream stage of these queries is the ordered-subsequence automaton over the needle's bytes and their case flips
+    m->sig_eligible = !m->unicode && lc.filter_mode == 1 && lc.filter_exact && needle_sig_eligible(needle_utf8, needle_len, k, m->literal_mode);
+    m->needle_sig = m->sig_eligible ? needle_sig(needle_utf8, needle_len) : 0u;
     *out = mp.release();
     return FZB_OK;
 }
@@ -992,6 +997,7 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (!c) return;
     if (c->own_bytes) (void)hipFree(c->own_bytes);
     if (c->own_ends) (void)hipFree(c->own_ends);
+    if (c->own_sig) (void)hipFree(c->own_sig);
     for (void* q : c->own_view)
         if (q) (void)hipFree(q);
     for (void* q : {c->stage_raw, c->stage_ends, c->stage_tiles, c->stage_stats})
@@ -1016,7 +1022,7 @@ int fzb_corpus_set_uniform_len(fzb_corpus* c, uint32_t len) {
     if (!len && c->dev.uniform_len && c->dev.max_len == c->dev.uniform_len) c->dev.max_len = 0;  // clearing the promise also clears the bound it implied
     c->dev.uniform_len = len;
     if (len) c->dev.max_len = len;  // (overwrites an earlier fzb_corpus_set_max_len)
-    return FZB_OK;
+    return fzb_sig_sync_borrowed(c);  // the letter signatures of a list of short haystacks; a cleared promise drops them
 }
 
 int fzb_corpus_set_max_len(fzb_corpus* c, uint32_t max_len) {
@@ -1037,7 +1043,7 @@ int fzb_corpus_set_max_len(fzb_corpus* c, uint32_t max_len) {
         if (vrc) return vrc;
     }
     c->dev.max_len = max_len;
-    return FZB_OK;
+    return fzb_sig_sync_borrowed(c);  // the letter signatures when the bound is within 32 bytes; a looser or cleared bound drops them
 }
 
 }  // extern "C"
@@ -1486,7 +1492,8 @@ static int pipe_filter_stage(Pipe& p) {
                               nullptr, nullptr, nullptr, lc.pad_ok, m->lcs_acc_lo, m->cdfa_src == 3 ? w.cdfa : nullptr, (u32)m->cdfa.size(), m->cdfa_K, m->cdfa_G);
         else
             fzb_launch_filter(p.cd, p.first, p.cnt, w.table, w.dfa, lc.dead_byte, nd.rows, lc.filter_mode, need, (u32)nd.min_haystack_len, w.bitmap, w.tile_counts, w.counters, p.cus * 8, p.st, nullptr, nullptr,
-                              nullptr, nullptr, lc.pad_ok, -1, (lc.filter_mode == 1 && m->cdfa_src == 1) ? w.cdfa : nullptr, (u32)m->cdfa.size(), m->cdfa_K, m->cdfa_G);
+                              nullptr, nullptr, lc.pad_ok, -1, (lc.filter_mode == 1 && m->cdfa_src == 1) ? w.cdfa : nullptr, (u32)m->cdfa.size(), m->cdfa_K, m->cdfa_G, m->needle_sig,
+                              m->sig_eligible && lc.filter_mode == 1);  // (eligible needle + a list with signatures: k1_dfa_sig)
         FZB_PEV(3);
         FZB_STAGE("filter");
         // ragged ASCII list, exact filter (0 typos) or whole-haystack windows: compaction and classification in ONE launch (k_compact1's grid: its
@@ -3249,6 +3256,14 @@ int fzb_debug_lcs_dfa_accepts(const fzb_matcher* m, const uint8_t* bytes, size_t
 // Test hook (host only): the class-composite form of the matcher's streaming automaton run over one haystack, G bytes per step (the
 // tail padded with a byte of the "matches nothing" class, as the kernel sees zero fill): 1 / 0 = accepts / rejects, -1 if the matcher has none.
 // out_kg (optional): [0] = K, [1] = G.
+int fzb_debug_needle_signature(const fzb_matcher* m, uint32_t* out_mask, int* out_eligible) {
+    if (!m) return fail(FZB_ERR_INVALID, "null argument");
+    if (out_mask) *out_mask = m->needle_sig;
+    if (out_eligible) *out_eligible = m->sig_eligible ? 1 : 0;
+    return FZB_OK;
+}
+uint32_t fzb_debug_signature_threshold(void) { return std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE); }
+
 int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len, int32_t* out_kg) {
     if (out_kg) { out_kg[0] = m ? m->cdfa_K : 0; out_kg[1] = m ? m->cdfa_G : 0; }
     if (!m || m->cdfa.empty() || (!bytes && len)) return -1;

@@ -47,6 +47,9 @@ struct fzb_corpus {
     u64 view_items = 0;      // haystacks the view covers (the list's length while the corpus has a view)
     u64 view_cap_items = 0;  // haystacks the view's arrays hold (own_view[1..5]); view_cap_units: 16-byte units of own_view[0], slack excluded
     u64 view_cap_units = 0;
+    void* own_sig = nullptr; // the letter signatures (CorpusDev::sig; also of a borrowed corpus: the library's own array), room for sig_cap_items haystacks
+    u64 sig_cap_items = 0;
+    int sig_device = -1;     // a borrowed corpus: the device the signatures were built on (where its bytes live)
     u64 regrows = 0;         // reallocations of the canonical arrays so far
     u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
     u64 edit_info[4] = {0, 0, 0, 0};  // the last successful fzb_corpus_remove / _replace (fzb_corpus_edit_info)
@@ -89,6 +92,9 @@ struct fzb_matcher {
     // k1_cdfa_ragged).  Empty when states x K^G does not fit 16 KB even for G = 2.
     std::vector<u8> cdfa;
     int cdfa_src = 0, cdfa_K = 0, cdfa_G = 0;
+    // the needle's letter signature and whether the signature form of the filter may decide for it (sig_filter.h: fuzzy, 0 typos, ASCII, no NUL)
+    u32 needle_sig = 0;
+    bool sig_eligible = false;
     Workspace ws{};
     int device = -1;
     bool profiling = false;
@@ -234,5 +240,10 @@ int fzb_empty_pattern_list(size_t n, uint32_t index_offset, int sort, fzb_match*
 // the multi matcher's ordering host (created on first use, host.hip)
 int fzb_multi_order_host(fzb_multi_matcher* mm, fzb_matcher** out);
 int fzb_build_filter_view(fzb_corpus* c);     // host_upload.hip
+// The letter signatures in step with the list (host_upload.hip): built from haystack n_valid on when the list is one k1_dfa serves (max_len known
+// and <= 32), dropped otherwise.  Enqueued on the null stream of the current device; fzb_sig_sync_borrowed finds the device of a borrowed
+// corpus itself and synchronises.
+int fzb_sig_sync(fzb_corpus* c, u64 n_valid);
+int fzb_sig_sync_borrowed(fzb_corpus* c);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

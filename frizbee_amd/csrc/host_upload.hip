@@ -21,6 +21,8 @@
 #include <thread>
 
 #include "host_internal.h"
+#include "kernels_common.h"
+#include "sig_filter.h"
 
 namespace {
 
@@ -643,7 +645,99 @@ hipError_t measure_resident(fzb_corpus* c, u64 n) {
     return hipSuccess;
 }
 
+// ---- the letter signatures (sig_filter.h), kept in step with the list -----------------------------------------------------------------
+// One thread per haystack of [first, first + count): both 16-byte vectors, cut to the haystack's length, OR-ed into CorpusDev::sig.
+template <typename ET>
+__global__ __launch_bounds__(UP_THREADS) void k_sig_build(const u8* __restrict__ bytes, const ET* __restrict__ ends, u32 ulen, u64 first, u64 count, u32* __restrict__ sig) {
+    const u64 stride = (u64)gridDim.x * UP_THREADS;
+    for (u64 k = (u64)blockIdx.x * UP_THREADS + threadIdx.x; k < count; k += stride) {
+        u64 hs;
+        u32 L;
+        haystack_span_u(ends, ulen, first + k, hs, L);
+        L = min(L, 32u);  // (the list's bound: fzb_sig_sync builds signatures for lists within it only)
+        const uint4* vp = (const uint4*)(bytes + hs);
+        uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
+        if (L > 0) a = vp[0];
+        if (L > 16) b = vp[1];
+        u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        u32 s = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const u32 nvb = L > 4u * j ? L - 4u * j : 0u;
+            if (nvb < 4) w[j] &= (1u << (8 * nvb)) - 1;
+            s |= sig_of_word(w[j]);
+        }
+        sig[first + k] = s;
+    }
+}
+
 }  // namespace
+
+int fzb_sig_sync(fzb_corpus* c, u64 n_valid) {
+    const u64 n = c->dev.n;
+    const bool want = !fzb_knobs().no_signature && n && c->dev.max_len != 0 && c->dev.max_len <= 32;
+    if (!want) {  // (the array stays for the list that calls for signatures again)
+        c->dev.sig = nullptr;
+        return FZB_OK;
+    }
+    if (!c->dev.sig) n_valid = 0;
+    n_valid = std::min(n_valid, n);
+    if (!c->own_sig || c->sig_cap_items < n) {
+        const u64 items = std::max<u64>(n, c->cap_items);
+        void* p = nullptr;
+        hipError_t e = fzb_dev_alloc(&p, (size_t)items * 4);
+        if (e == hipSuccess && n_valid) e = hipMemcpy(p, c->own_sig, (size_t)n_valid * 4, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {  // an accelerator, like the view: without room the corpus goes on without it
+            if (p) (void)hipFree(p);
+            (void)hipGetLastError();
+            c->dev.sig = nullptr;
+            if (e == hipErrorOutOfMemory) return FZB_OK;
+            return fzb_fail(FZB_ERR_HIP, std::string("letter signatures: ") + hipGetErrorString(e));
+        }
+        if (c->own_sig) (void)hipFree(c->own_sig);
+        c->own_sig = p;
+        c->sig_cap_items = items;
+    }
+    if (n > n_valid) {
+        const u64 cnt = n - n_valid;
+        const unsigned grid = (unsigned)std::min<u64>((cnt + UP_THREADS - 1) / UP_THREADS, 8192);
+        if (c->dev.ends_u64) hipLaunchKernelGGL((k_sig_build<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
+        else hipLaunchKernelGGL((k_sig_build<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
+    }
+    c->dev.sig = (const u32*)c->own_sig;
+    return FZB_OK;
+}
+
+// A borrowed corpus (fzb_corpus_set_uniform_len / _set_max_len, behind their verifying pass): on the device its bytes live on
+int fzb_sig_sync_borrowed(fzb_corpus* c) {
+    int prev_dev = 0, own_dev = 0;
+    HIPCHK(hipGetDevice(&prev_dev));
+    own_dev = prev_dev;
+    hipPointerAttribute_t attr;
+    if (c->dev.bytes && hipPointerGetAttributes(&attr, c->dev.bytes) == hipSuccess && attr.type == hipMemoryTypeDevice) own_dev = attr.device;
+    else (void)hipGetLastError();
+    struct DeviceGuard {
+        int prev, cur;
+        ~DeviceGuard() { if (cur != prev) (void)hipSetDevice(prev); }
+    } guard{prev_dev, own_dev};
+    if (own_dev != prev_dev) HIPCHK(hipSetDevice(own_dev));
+    if (c->own_sig && c->sig_device != own_dev) {  // (the array follows the bytes)
+        (void)hipFree(c->own_sig);
+        c->own_sig = nullptr; c->sig_cap_items = 0;
+    }
+    c->dev.sig = nullptr;  // the promise changed: nothing of an earlier build is taken over
+    // FZB_VERIFY_PROMISES=0: nobody has checked the end offsets, and this set-up pass must not read wherever they point
+    if (!fzb_knobs().verify_promises) return FZB_OK;
+    HIPCHK(hipDeviceSynchronize());  // the caller may have filled the buffers on any stream of that device
+    const int rc = fzb_sig_sync(c, 0);
+    if (rc) return rc;
+    if (c->dev.sig) {
+        c->sig_device = own_dev;
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipGetLastError());
+    }
+    return FZB_OK;
+}
 
 // The streaming filter's view of a corpus whose canonical layout is resident (uploaded or borrowed), on the CURRENT device.  Sets
 // c->dev.v* and view_nv on success; leaves the corpus without a view (and returns FZB_OK) when the list does not call for one - more
@@ -736,6 +830,7 @@ int fzb_corpus_upload_impl(const uint8_t* bytes, const uint64_t* end_offsets, si
     // the streaming filter's view (CorpusDev::vbytes): ragged lists whose haystacks are 33..256 bytes.  A second copy of the bytes (+ ~5 %
     // for the zero vectors behind shorter group members, + 4.2 bytes per haystack); FZB_FILTER_VIEW=0 turns it off.
     int rc = view_sync(c, 0);  // (a list with more than a few haystacks beyond 256 bytes gets none)
+    if (!rc) rc = fzb_sig_sync(c, 0);  // the letter signatures of a list of short haystacks (4 bytes per haystack)
     if (rc) {
         const std::string msg = fzb_last_error();
         cleanup();
@@ -876,6 +971,21 @@ int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
         if (e == hipErrorOutOfMemory) (void)hipGetLastError();  // the view is an accelerator: the corpus has its room, the view grows - or goes - when it must
         else if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_reserve (filter view): ") + hipGetErrorString(e));
     }
+    // the letter signatures of a list that has (or, still empty, may get) them: room for the item capacity, so that appends allocate nothing
+    if (!fzb_knobs().no_signature && (!c->dev.n || (c->dev.max_len != 0 && c->dev.max_len <= 32)) && c->sig_cap_items < c->cap_items) {
+        void* p = nullptr;
+        e = fzb_dev_alloc(&p, (size_t)c->cap_items * 4);
+        if (e == hipSuccess && c->dev.sig && c->dev.n) e = hipMemcpy(p, c->own_sig, (size_t)c->dev.n * 4, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) {
+            if (c->own_sig) (void)hipFree(c->own_sig);
+            c->own_sig = p;
+            c->sig_cap_items = c->cap_items;
+            if (c->dev.sig) c->dev.sig = (const u32*)p;
+        } else {
+            if (p) (void)hipFree(p);
+            (void)hipGetLastError();  // (an accelerator: it grows - or goes - when it must)
+        }
+    }
     HIPCHK(hipDeviceSynchronize());
     return FZB_OK;
 }
@@ -913,6 +1023,7 @@ int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_o
     c->n_over256 += st.n_long;
     set_measured(c);
     rc = view_sync(c, n_old);
+    if (!rc) rc = fzb_sig_sync(c, n_old);
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     if (rc) return rc;
@@ -940,6 +1051,7 @@ int fzb_corpus_truncate(fzb_corpus* c, size_t n) {
     c->dev.total_bytes = used + 96;
     set_measured(c);
     rc = view_sync(c, n);
+    if (!rc) rc = fzb_sig_sync(c, n);
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     if (rc) return rc;
@@ -965,6 +1077,13 @@ int fzb_corpus_info(const fzb_corpus* c, uint64_t out[12]) {
     return FZB_OK;
 }
 
+int fzb_corpus_signature_info(const fzb_corpus* c, int* out_built, uint64_t* out_bytes) {
+    if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    if (out_built) *out_built = c->dev.sig != nullptr;
+    if (out_bytes) *out_bytes = c->dev.sig ? (uint64_t)c->dev.n * 4 : 0;
+    return FZB_OK;
+}
+
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes) {
     if (!c || !out_bytes) return fzb_fail(FZB_ERR_INVALID, "null argument");
     const u64 n = c->dev.n, groups = up_tiles(n) * (UP_TILE / 64);
@@ -980,6 +1099,7 @@ int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t 
         case 5: src = c->dev.vlen; bytes = view ? (size_t)n * 2 : 0; break;
         case 6: src = c->dev.vperm; bytes = view ? (size_t)n * 2 : 0; break;
         case 7: src = c->dev.vlong; bytes = view ? (size_t)c->dev.n_long * 4 : 0; break;
+        case 8: src = c->dev.sig; bytes = c->dev.sig ? (size_t)n * 4 : 0; break;
         default: return fzb_fail(FZB_ERR_INVALID, "fzb_debug_corpus_read: unknown array " + std::to_string(what));
     }
     *out_bytes = bytes;
@@ -1408,7 +1528,8 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     c->dev.total_bytes = total;
     c->h2d_bytes += rq.batch_h2d;
     set_measured(c);
-    const int rc = view_sync(c, i0);
+    int rc = view_sync(c, i0);
+    if (!rc) rc = fzb_sig_sync(c, i0);
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     if (rc) return done(rc);

@@ -11,6 +11,7 @@
 #include "kernels_common.h"
 #include "compact1.h"
 #include "dfa_lds.h"
+#include "sig_filter.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -138,6 +139,67 @@ __global__ __launch_bounds__(256) void k1_filter(const u8* __restrict__ bytes, c
 // ---------------------------------------------------------------------------------------------------
 // (Round 5 measured an instantiation without per-lane lengths for uniform 32-byte lists and the table at a 256-byte row pitch - 7.5 M instead of
 // 10.7 M VALU instructions per launch, the same 57 us, more LDS bank conflicts; round 6 closed the topic: profiles/r06_corun.txt, profiles/HISTORY.md.)
+// One tile of k1_dfa: the four haystacks thread `tid` owns (positions p * 256 + tid), decided and written to the bitmap; returns the
+// lane's share of the tile's count (non-zero in lane 0 of every wave only).  Shared by k1_dfa and by k1_dfa_sig's dense tiles.
+template <typename ET>
+__device__ __forceinline__ u32 dfa_stream_tile(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 first, u32 count, u32 tile, int tid, u32 ulen, u32 min_len,
+                                               u32 acc_lo, const u8* dfa, u64* __restrict__ bitmap) {
+    u64 hs[4];
+    u32 hl[4];
+    uint4 v0[4], v1[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const u32 li = tile * FZB_TILE + p * 256 + tid;
+        hs[p] = 0;
+        hl[p] = 0;
+        if (li < count) haystack_span_u(ends, ulen, first + li, hs[p], hl[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        v0[p] = make_uint4(0, 0, 0, 0);
+        v1[p] = make_uint4(0, 0, 0, 0);
+        const uint4* vp = (const uint4*)(bytes + hs[p]);
+        // (plain loads: with the non-temporal hint the second vector's request finds the line gone from the vector cache - a wave's two
+        // load instructions share every line of a 32-byte-record list - and the kernel takes 62 us instead of 57)
+        if (hl[p] > 0) v0[p] = vp[0];
+        if (hl[p] > 16) v1[p] = vp[1];
+    }
+    u32 st[4] = {0, 0, 0, 0};
+    // short haystacks (<= 32 bytes): both vectors are already in flight
+    if (hl[0] >= 16 && hl[1] >= 16 && hl[2] >= 16 && hl[3] >= 16) {
+        { const u32 w[4] = {v0[0].x, v0[1].x, v0[2].x, v0[3].x}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v0[0].y, v0[1].y, v0[2].y, v0[3].y}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v0[0].z, v0[1].z, v0[2].z, v0[3].z}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v0[0].w, v0[1].w, v0[2].w, v0[3].w}; dfa_word4<true>(st, w, dfa); }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; p++) st[p] = dfa_partial<true>(st[p], v0[p], hl[p] >= 16 ? 16u : hl[p], dfa);
+    }
+    if (hl[0] >= 32 && hl[1] >= 32 && hl[2] >= 32 && hl[3] >= 32) {
+        { const u32 w[4] = {v1[0].x, v1[1].x, v1[2].x, v1[3].x}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v1[0].y, v1[1].y, v1[2].y, v1[3].y}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v1[0].z, v1[1].z, v1[2].z, v1[3].z}; dfa_word4<true>(st, w, dfa); }
+        { const u32 w[4] = {v1[0].w, v1[1].w, v1[2].w, v1[3].w}; dfa_word4<true>(st, w, dfa); }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            if (hl[p] > 16) st[p] = dfa_partial<true>(st[p], v1[p], hl[p] >= 32 ? 16u : hl[p] - 16, dfa);
+    }
+    u32 cnt = 0;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const u32 L = hl[p];
+        const u32 li = tile * FZB_TILE + p * 256 + tid;
+        const bool matched = li < count && L >= min_len && st[p] >= acc_lo;
+        const u64 b = __ballot(matched);
+        if (lane_id() == 0) {
+            bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
+            cnt += __popcll(b);
+        }
+    }
+    return cnt;
+}
+
 template <typename ET>
 __global__ __launch_bounds__(256) void k1_dfa(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 first, u32 count,
                                               const u8* __restrict__ dfa_g, int rows, u32 min_len, u32 dead, u32 acc_lo, u64* __restrict__ bitmap,
@@ -156,63 +218,131 @@ __global__ __launch_bounds__(256) void k1_dfa(const u8* __restrict__ bytes, cons
     for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         if (tid == 0) s_cnt = 0;
         __syncthreads();
-        u64 hs[4];
-        u32 hl[4];
-        uint4 v0[4], v1[4];
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            const u32 li = tile * FZB_TILE + p * 256 + tid;
-            hs[p] = 0;
-            hl[p] = 0;
-            if (li < count) haystack_span_u(ends, ulen, first + li, hs[p], hl[p]);
-        }
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            v0[p] = make_uint4(0, 0, 0, 0);
-            v1[p] = make_uint4(0, 0, 0, 0);
-            const uint4* vp = (const uint4*)(bytes + hs[p]);
-            // (plain loads: with the non-temporal hint the second vector's request finds the line gone from the vector cache - a wave's two
-            // load instructions share every line of a 32-byte-record list - and the kernel takes 62 us instead of 57)
-            if (hl[p] > 0) v0[p] = vp[0];
-            if (hl[p] > 16) v1[p] = vp[1];
-        }
-        u32 st[4] = {0, 0, 0, 0};
-        // short haystacks (<= 32 bytes): both vectors are already in flight
-        if (hl[0] >= 16 && hl[1] >= 16 && hl[2] >= 16 && hl[3] >= 16) {
-            { const u32 w[4] = {v0[0].x, v0[1].x, v0[2].x, v0[3].x}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v0[0].y, v0[1].y, v0[2].y, v0[3].y}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v0[0].z, v0[1].z, v0[2].z, v0[3].z}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v0[0].w, v0[1].w, v0[2].w, v0[3].w}; dfa_word4<true>(st, w, dfa); }
-        } else {
-#pragma unroll
-            for (int p = 0; p < 4; p++) st[p] = dfa_partial<true>(st[p], v0[p], hl[p] >= 16 ? 16u : hl[p], dfa);
-        }
-        if (hl[0] >= 32 && hl[1] >= 32 && hl[2] >= 32 && hl[3] >= 32) {
-            { const u32 w[4] = {v1[0].x, v1[1].x, v1[2].x, v1[3].x}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v1[0].y, v1[1].y, v1[2].y, v1[3].y}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v1[0].z, v1[1].z, v1[2].z, v1[3].z}; dfa_word4<true>(st, w, dfa); }
-            { const u32 w[4] = {v1[0].w, v1[1].w, v1[2].w, v1[3].w}; dfa_word4<true>(st, w, dfa); }
-        } else {
-#pragma unroll
-            for (int p = 0; p < 4; p++)
-                if (hl[p] > 16) st[p] = dfa_partial<true>(st[p], v1[p], hl[p] >= 32 ? 16u : hl[p] - 16, dfa);
-        }
-        u32 cnt = 0;
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            const u32 L = hl[p];
-            const u32 li = tile * FZB_TILE + p * 256 + tid;
-            const bool matched = li < count && L >= min_len && st[p] >= acc_lo;
-            const u64 b = __ballot(matched);
-            if (lane_id() == 0) {
-                bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
-                cnt += __popcll(b);
-            }
-        }
+        const u32 cnt = dfa_stream_tile<ET>(bytes, ends, first, count, tile, tid, ulen, min_len, acc_lo, dfa, bitmap);
         if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
         __syncthreads();
         if (tid == 0) tile_counts[tile] = s_cnt;
         __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K1-DFA behind the corpus' letter signatures (sig_filter.h): the same automaton, the same table at LDS address 0, the same persistent
+// grid and the same outputs (bitmap word per 64 haystacks, count per tile, counter reset) - but a tile first reads its 1024 signatures
+// (4 KB instead of 32 KB) and only the rows whose signature holds every needle letter are looked at.  Their positions go into an LDS
+// queue (one LDS atomic per wave); a tile with few of them (<= gather_max) GATHERS them - thread t runs queued row t, t + 256, .. as one
+// chain and sets its bit in an LDS bitmap - and a tile with many runs k1_dfa's streaming body, so the worst case is the 4 extra bytes per
+// haystack.  (Requesting the next tile's signatures before the gather - four registers, one of the two load latencies hidden - measured
+// slower: 70.8 against 67.8 us per step, profiles/sig_filter.txt; not kept.)
+// Only for needles sig_filter.h calls eligible: a zero byte then matches no row, and rows are masked to their length before the chain.
+// No spin-waits, no ordering between workgroups.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 sig_mask_vec(uint4 q, u32 nbytes) {  // bytes [nbytes, 16) -> 0
+    u32 w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const u32 nvb = nbytes > 4u * j ? nbytes - 4u * j : 0u;
+        w[j] = nvb >= 4 ? w[j] : (w[j] & ((1u << (8 * nvb)) - 1));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ u32 dfa_chain16(u32 st, const uint4& q, const u8* dfa) {
+    const u32 w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        st = dfa_step<0>(st, w[j], dfa);
+        st = dfa_step<1>(st, w[j], dfa);
+        st = dfa_step<2>(st, w[j], dfa);
+        st = dfa_step<3>(st, w[j], dfa);
+    }
+    return st;
+}
+// (8 waves per SIMD like k1_dfa, whose grid - 8 workgroups per CU - it shares: without the bound the kernel takes 68 VGPRs and a CU holds 7)
+template <typename ET>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k1_dfa_sig(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u32* __restrict__ sig, u32 nsig, u64 first, u32 count,
+                                                  const u8* __restrict__ dfa_g, int rows, u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts,
+                                                  u32* __restrict__ reset_counters, u32 ulen, u32 gather_max) {
+    if (blockIdx.x == 0 && threadIdx.x < 16) reset_counters[threadIdx.x] = 0;
+    // LDS behind the table (which stays the first object, at address 0): tile count, queue length, the tile's 1024 decision bits, the queue
+    extern __shared__ __attribute__((aligned(16))) u8 dfa[];
+    u32& s_cnt = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows));
+    u32& s_q = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows) + 4);
+    u32* const s_bits = (u32*)(dfa + FZB_DFA_LDS_BYTES(rows) + 16);
+    u16* const queue = (u16*)(dfa + FZB_DFA_LDS_BYTES(rows) + 16 + 128);
+    const int tid = threadIdx.x, lane = tid & 63;
+    dfa_require_lds_base0(dfa);
+    dfa_load_lds(dfa, dfa_g, rows);
+    const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
+    const bool vec = (first & 3) == 0;  // the thread's four signatures are one aligned 16-byte vector
+    // signatures of the rows 4 tid .. 4 tid + 3 of a tile; 0 (fails every test: the needle is not empty) at or beyond `count`
+    auto load_sigs = [&](u32 tile) -> uint4 {
+        const u32 li = tile * FZB_TILE + 4u * (u32)tid;
+        uint4 s = make_uint4(0, 0, 0, 0);
+        if (vec && li + 4 <= count) {
+            s = *(const uint4*)(sig + first + li);
+        } else {
+            if (li < count) s.x = sig[first + li];
+            if (li + 1 < count) s.y = sig[first + li + 1];
+            if (li + 2 < count) s.z = sig[first + li + 2];
+            if (li + 3 < count) s.w = sig[first + li + 3];
+        }
+        return s;
+    };
+    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if (tid == 0) s_cnt = 0, s_q = 0;
+        if (tid < 32) s_bits[tid] = 0;
+        const uint4 s = load_sigs(tile);
+        __syncthreads();
+        const u32 sv[4] = {s.x, s.y, s.z, s.w};
+        u64 pb[4];
+        u32 tot = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            pb[j] = __ballot((sv[j] & nsig) == nsig);
+            tot += (u32)__popcll(pb[j]);
+        }
+        if (tot) {  // wave-uniform
+            u32 base = 0;
+            if (lane == 0) base = atomicAdd(&s_q, tot);
+            base = __shfl(base, 0);
+            const u64 below = ((u64)1 << lane) - 1;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if ((pb[j] >> lane) & 1) queue[base + (u32)__popcll(pb[j] & below)] = (u16)(4 * tid + j);
+                base += (u32)__popcll(pb[j]);
+            }
+        }
+        __syncthreads();
+        const u32 Q = s_q;  // the same for the whole workgroup: so is the branch
+        if (Q > gather_max) {
+            const u32 cnt = dfa_stream_tile<ET>(bytes, ends, first, count, tile, tid, ulen, min_len, acc_lo, dfa, bitmap);
+            if (lane == 0 && cnt) atomicAdd(&s_cnt, cnt);
+        } else {
+            for (u32 e = tid; e < Q; e += 256) {
+                const u32 pos = queue[e];
+                u64 hs;
+                u32 L;
+                haystack_span_u(ends, ulen, first + (u64)tile * FZB_TILE + pos, hs, L);
+                const uint4* vp = (const uint4*)(bytes + hs);
+                uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
+                if (L > 0) a = vp[0];
+                if (L > 16) b = vp[1];
+                if (L < 16) a = sig_mask_vec(a, L);
+                if (L < 32) b = sig_mask_vec(b, L > 16 ? L - 16 : 0u);
+                u32 st = dfa_chain16(0u, a, dfa);
+                st = dfa_chain16(st, b, dfa);
+                if (L >= min_len && st >= acc_lo) atomicOr(&s_bits[pos >> 5], 1u << (pos & 31));
+            }
+            __syncthreads();
+            if (tid < FZB_TILE / 64) {
+                const u64 word = (u64)s_bits[2 * tid] | ((u64)s_bits[2 * tid + 1] << 32);
+                bitmap[(size_t)tile * (FZB_TILE / 64) + tid] = word;
+                const u32 c = (u32)__popcll(word);
+                if (c) atomicAdd(&s_cnt, c);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) tile_counts[tile] = s_cnt;
     }
 }
 
@@ -762,7 +892,7 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
 // ---------------------------------------------------------------------------------------------------
 void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* table, const u8* dfa, u32 dead, int rows, int mode, int need, u32 min_len,
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m, u32* tile_counts_m, u64* reject_bits, u32* tile_rejects, int nul_safe,
-                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G) {
+                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G, u32 needle_sig, int sig_ok) {
     // mode 1: `dfa` has rows + 1 states, start state 0, and accepts in the states >= acc (the subsequence / unicode / KMP automata: the last
     // state; the LCS automaton of a typo configuration: every state whose LCS reaches the need)
     const u32 acc = acc_lo < 0 ? (u32)rows : (u32)acc_lo;
@@ -773,6 +903,13 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
     if (mode == 1) {
         const size_t lds = (size_t)(rows + 1) * FZB_DFA_STRIDE + 16;  // table + the tile counter
         const bool shortc = c.max_len != 0 && c.max_len <= 32;  // every haystack fits the two pre-requested vectors
+        if (shortc && sig_ok && needle_sig && c.sig && !fzb_knobs().no_signature) {  // an eligible needle over a list with signatures (host.hip decides eligibility)
+            const size_t lds_s = lds + 128 + 2 * FZB_TILE;  // + the tile's decision bits and the queue of passing rows
+#define FZB_K1S(ET) hipLaunchKernelGGL((k1_dfa_sig<ET>), dim3(grid), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE))
+            if (c.ends_u64) FZB_K1S(u64); else FZB_K1S(u32);
+#undef FZB_K1S
+            return;
+        }
         if (shortc) {
 #define FZB_K1D(ET) hipLaunchKernelGGL((k1_dfa<ET>), dim3(grid), dim3(256), lds, st, c.bytes, (const ET*)c.ends, first, count, dfa, rows, min_len, dead, acc, bitmap, tile_counts, reset_counters, c.uniform_len)
             if (c.ends_u64) FZB_K1D(u64); else FZB_K1D(u32);

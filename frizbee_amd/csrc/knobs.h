@@ -10,6 +10,7 @@ struct FzbKnobs {
     bool debug_sync = false;         // FZB_DEBUG_SYNC=1        synchronise and report after every stage of the pipeline
     bool typo_exact_window = false;  // FZB_TYPO_EXACT_WINDOW=1 no typo fast path: every survivor of a typo query re-decided at the exact lane width (nothing rests on DESIGN.md "Typo configurations")
     bool no_filter_view = false;     // FZB_FILTER_VIEW=0       no interleaved filter view (not built at upload - saves a second copy of the bytes in HBM -, not used by the filter)
+    bool no_signature = false;       // FZB_NO_SIGNATURE=1      no letter signatures (not built with the corpus - saves 4 bytes per haystack in HBM -, not used by the filter: k1_dfa reads every row instead of k1_dfa_sig)
     bool verify_promises = true;     // FZB_VERIFY_PROMISES=0   fzb_corpus_set_uniform_len / _set_max_len on BORROWED memory accepted without the device pass over the end offsets
     // --- force the form that serves inputs outside the fast form's preconditions ---
     bool no_lcs_dfa = false;         // FZB_NO_LCS_DFA=1        typo filter: the bit-vector kernel k1_filter (needles whose LCS automaton has more than 226 states) instead of the automaton in k1_dfa

@@ -1,0 +1,45 @@
+// The LETTER SIGNATURE of a haystack: one u32 that says which letters (either case) and which classes of other bytes occur in it.
+// It depends on the haystack alone, so a resident list computes it once (k_sig_build, host_upload.hip) and every 0-typo ASCII query
+// reads 4 bytes per haystack to learn which rows CAN match before it touches their 32 (k1_dfa_sig, kernels_filter.hip).
+//
+// The one property everything rests on: the ordered-subsequence automaton of an eligible needle advances on byte b only if b is a needle
+// byte or its ASCII case flip, and both have the same sig_bit.  So   accepted  =>  (sig & needle_sig) == needle_sig.
+// The converse does not hold (order, repeats, bytes that share a bit): every row the signature passes still goes through the automaton.
+//
+// Pure functions, host and device: tests/test_signature_host.py compiles this header for the CPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#ifndef FZB_SIG_FN
+#define FZB_SIG_FN __host__ __device__ inline
+#endif
+
+// 0..25: the letter's index, either case; 26..31: every other non-zero byte, by b % 6.  (Call with b != 0: a zero byte sets no bit.)
+FZB_SIG_FN uint32_t sig_bit(uint32_t b) {
+    const uint32_t l = (b | 0x20u) - 'a';
+    return l < 26u ? l : 26u + b % 6u;
+}
+FZB_SIG_FN uint32_t sig_of_byte(uint32_t b) { return b ? 1u << sig_bit(b) : 0u; }
+FZB_SIG_FN uint32_t sig_of_word(uint32_t w) { return sig_of_byte(w & 0xFF) | sig_of_byte((w >> 8) & 0xFF) | sig_of_byte((w >> 16) & 0xFF) | sig_of_byte(w >> 24); }
+FZB_SIG_FN uint32_t sig_of_bytes(const uint8_t* p, size_t n) {
+    uint32_t s = 0;
+    for (size_t i = 0; i < n; i++) s |= sig_of_byte(p[i]);
+    return s;
+}
+FZB_SIG_FN uint32_t needle_sig(const uint8_t* needle, size_t n) { return sig_of_bytes(needle, n); }
+
+// The queries the signature may decide for: fuzzy matching with max_typos = 0 (the stream stage is the ordered-subsequence automaton) of
+// an ASCII needle without a NUL byte.  literal_mode: 0 = fuzzy (fzb_config::matching).
+FZB_SIG_FN bool needle_sig_eligible(const uint8_t* needle, size_t n, int max_typos, int literal_mode) {
+    if (literal_mode != 0 || max_typos != 0 || n == 0) return false;
+    for (size_t i = 0; i < n; i++)
+        if (needle[i] == 0 || needle[i] >= 0x80) return false;
+    return true;
+}
+
+// Tiles of k1_dfa_sig with more passing rows than this stream the whole tile (coalesced loads, four chains per thread) instead of
+// gathering the passing rows one chain per thread.
+#ifndef FZB_SIG_GATHER_MAX
+#define FZB_SIG_GATHER_MAX 384u
+#endif

@@ -106,7 +106,10 @@ int fzb_corpus_from_device(const void* dev_bytes, const void* dev_ends, int ends
  * it: on a corpus it uploaded a looser value (or 0) is ignored and a value below the measured one is refused (FZB_ERR_INVALID).  On
  * borrowed memory the bound is CHECKED when it is given: one device pass over the end offsets (a set-up call: it synchronises the
  * device); a haystack longer than max_len, or offsets that decrease / leave the buffer, make the call fail with FZB_ERR_INVALID and name
- * the first offending index.  FZB_VERIFY_PROMISES=0 in the environment skips the pass. */
+ * the first offending index.  FZB_VERIFY_PROMISES=0 in the environment skips the pass.
+ * A bound within 32 bytes also builds the corpus' LETTER SIGNATURES in the same set-up call (fzb_corpus_signature_info): one 32-bit word
+ * per haystack that 0-typo ASCII queries read instead of the bytes of the rows that cannot match.  The corpus' bytes and end offsets must
+ * not change after the promise is made; a looser bound, or 0, drops the signatures. */
 int fzb_corpus_set_max_len(fzb_corpus* c, uint32_t max_len);
 /* Optional accelerator for borrowed RAGGED corpora (fzb_corpus_upload builds it itself): the streaming filter's view of the list - a
  * second copy of the bytes, every 1024-haystack tile sorted by length and stored interleaved in groups of 64, so that a wavefront's
@@ -119,8 +122,15 @@ int fzb_corpus_build_view(fzb_corpus* c, int* out_built);
  * dependent load less per survivor).  fzb_corpus_upload detects it by itself, and on a corpus it uploaded only the detected value is
  * accepted (FZB_ERR_INVALID otherwise).  A non-zero `len` also becomes the corpus' max_len (overwriting fzb_corpus_set_max_len);
  * 0 clears the promise and the bound it implied.  On borrowed memory the promise is CHECKED against the end offsets when it is made (one
- * device pass, as for fzb_corpus_set_max_len): a wrong promise would mis-span every haystack, so it is refused with FZB_ERR_INVALID. */
+ * device pass, as for fzb_corpus_set_max_len): a wrong promise would mis-span every haystack, so it is refused with FZB_ERR_INVALID.
+ * A uniform length within 32 bytes builds the letter signatures as fzb_corpus_set_max_len does, and the same rule holds: the corpus'
+ * bytes and end offsets must not change after the promise is made.  0 drops the signatures with the promise. */
 int fzb_corpus_set_uniform_len(fzb_corpus* c, uint32_t len);
+/* The corpus' letter signatures (frizbee_amd/csrc/sig_filter.h): built by fzb_corpus_upload, by the two promises above on borrowed memory and kept in step by
+ * fzb_corpus_append / _truncate / _remove / _replace, for every list whose longest haystack is known and within 32 bytes; an accelerator,
+ * like the view: a device without room (or FZB_NO_SIGNATURE=1) leaves the corpus without them and every query as it was.
+ * *out_built (optional) = 1 when the corpus has them, *out_bytes (optional) = their size in device memory (4 per haystack). */
+int fzb_corpus_signature_info(const fzb_corpus* c, int* out_built, uint64_t* out_bytes);
 void fzb_corpus_free(fzb_corpus* c);
 size_t fzb_corpus_len(const fzb_corpus* c);
 
@@ -514,6 +524,12 @@ int fzb_debug_lcs_dfa_accepts(const fzb_matcher* m, const uint8_t* bytes, size_t
  * classes; the ragged filter's table) run over one haystack: 1 / 0 = accepts / rejects, -1 if the matcher has none; out_kg[0] = K, [1] = G */
 int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len, int32_t* out_kg);
 
+/* test hook, host only: the needle's letter signature (*out_mask, optional; 0 when not eligible) and whether the signature form of the
+ * streaming filter may decide for this matcher (*out_eligible, optional: fuzzy matching, max_typos = 0, an ASCII needle without a NUL byte) */
+int fzb_debug_needle_signature(const fzb_matcher* m, uint32_t* out_mask, int* out_eligible);
+/* test hook: a 1024-haystack tile with more rows than this passing the signature test is streamed whole instead of gathered */
+uint32_t fzb_debug_signature_threshold(void);
+
 /* test hook: the library's environment switches (frizbee_amd/csrc/knobs.h - comparison and debugging only, parsed once on first use) are
  * read again.  Matchers created before the call keep what was decided when they were created. */
 void fzb_debug_reload_knobs(void);
@@ -524,7 +540,7 @@ int fzb_debug_device_allocs(uint64_t* out);
 
 /* test hook: copies one of the corpus' device arrays to the host - what: 0 = canonical bytes up to the padded size + the 96-byte tail,
  * 1 = end offsets (u32 or u64, fzb_corpus_info out[9]), 2 = vbytes, 3 = vgofs, 4 = vgnv, 5 = vlen, 6 = vperm, 7 = vlong (2..7: the
- * filter's view, nothing without one).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
+ * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes);
 
 #ifdef __cplusplus
