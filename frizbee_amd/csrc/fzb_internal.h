@@ -113,6 +113,14 @@ struct fzb_indices_rec {  // == fzb_match_indices (include/frizbee_hip.h): what 
     u32 positions_len;
 };
 
+// The device radix sort's buffers for `cap` records (fzb_sort_ensure / fzb_sort_release, host.hip): the ping-pong buffer and the digit-major
+// tile histograms with their totals.  The top-`limit` selection borrows both (its input and its scratch).
+struct SortBuffers {
+    fzb_match_rec* tmp;
+    u32* hist;
+    size_t cap;
+};
+
 // Per-call device workspace (owned by the matcher, grown on demand)
 struct Workspace {
     u64* bitmap;        // count/64 words: filter decisions
@@ -122,9 +130,7 @@ struct Workspace {
     u32* overflow;      // queue of (output position, window start, window end, haystack): multi-chunk windows from the front, > 1024-byte windows from the back
     u32* dp_scratch;    // multi-chunk DP: parked row/gap vectors, [row][dword][thread]
     size_t dp_scratch_words;
-    fzb_match_rec* sort_tmp;  // device radix sort: ping-pong buffer + digit-major tile histogram
-    u32* sort_hist;
-    size_t sort_cap;
+    SortBuffers sort;   // device radix sort of the ordered entry points
     u64* bitmap2;       // second-level keep bits (after the lane-exact prefilter)
     u32* tile_counts2;
     u32* items2;        // local haystack index of kept survivor

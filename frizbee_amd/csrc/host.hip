@@ -216,15 +216,50 @@ void fzb_config_default(fzb_config* out) {
 
 static void free_workspace(Workspace& w) {
     // (table / dfa / uni_dfa / lcs_dfa / cdfa point into tables_blob)
-    void* ptrs[] = {w.bitmap, w.tile_counts, w.surv_idx, w.win, w.overflow, w.dp_scratch, w.sort_tmp, w.sort_hist, w.bitmap2, w.tile_counts2, w.items2, w.win2, w.counters, w.tables_blob,
+    void* ptrs[] = {w.bitmap, w.tile_counts, w.surv_idx, w.win, w.overflow, w.dp_scratch, w.bitmap2, w.tile_counts2, w.items2, w.win2, w.counters, w.tables_blob,
                     w.trace_cells, w.bitmap_m, w.tile_counts_m, w.marg_list, w.reject_bits, w.tile_rejects, w.rej_prefix, w.cls_win, w.cls_lists};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    fzb_sort_release(w.sort);
     if (w.tables_ev_pending) (void)hipEventSynchronize(w.tables_ev);
     if (w.tables_host) (void)hipHostFree(w.tables_host);
     if (w.tables_ev) (void)hipEventDestroy(w.tables_ev);
     w = Workspace{};
 }
+
+}  // extern "C"
+void fzb_sort_release(SortBuffers& s) {
+    if (s.tmp) (void)hipFree(s.tmp);
+    if (s.hist) (void)hipFree(s.hist);
+    s = SortBuffers{};
+}
+void fzb_out_release(OutStaging& o) {
+    if (o.out_dev) (void)hipFree(o.out_dev);
+    if (o.count_dev) (void)hipFree(o.count_dev);
+    if (o.fetch.count_host) (void)hipHostFree(o.fetch.count_host);
+    if (o.fetch_top.count_host) (void)hipHostFree(o.fetch_top.count_host);
+    o = OutStaging{};
+}
+// Everything a MatcherState owns but its shard clones (fzb_matcher_free walks them, each on its own device)
+static void release_state(MatcherState& s) {
+    free_workspace(s.ws);
+    fzb_out_release(s);
+    for (void* p : {(void*)s.top_words, (void*)s.trace_sel, (void*)s.trace_pos, (void*)s.trace_npos, (void*)s.top_head, (void*)s.top_traced, (void*)s.top_idx_words, (void*)s.top_tiles,
+                    (void*)s.top_packed, (void*)s.top_dense, s.long_blob_dev, (void*)s.long_scratch})
+        if (p) (void)hipFree(p);
+    for (auto& tr : s.evring)
+        for (auto& e : tr)
+            if (e) (void)hipEventDestroy(e);
+    if (s.ev_fork) (void)hipEventDestroy(s.ev_fork);
+    if (s.ev_join) (void)hipEventDestroy(s.ev_join);
+    if (s.aux_stream) (void)hipStreamDestroy(s.aux_stream);
+    if (s.shard_workers) fzb_shard_workers_free(s.shard_workers);  // joins the worker threads before their clones go
+    s.shard_workers = nullptr;
+    if (s.shard_stream) (void)hipStreamDestroy(s.shard_stream);
+    if (s.shard_event) (void)hipEventDestroy(s.shard_event);
+    if (s.shard_count_host) (void)hipHostFree(s.shard_count_host);
+}
+extern "C" {
 
 // The matcher's byte tables on the device: [filter table 2 KB | subsequence DFA | unicode DFA | LCS automaton | class-composite automaton], each
 // with room for any needle's (fzb_matcher_set_pattern re-uploads in place).  One copy out of the pinned staging buffer, asynchronous on `st`
@@ -263,7 +298,7 @@ static int upload_tables(fzb_matcher* m, hipStream_t st, bool have_stream) {
 
 // ---- fzb_matcher_create, piece by piece ------------------------------------------------------------------------------------------
 // NeedleDev's scalars: what `Prefilter::new` / `SmithWaterman::new` precompute (src/prefilter/algo/mod.rs:30-42, src/smith_waterman/algo/mod.rs:21-42)
-static void fill_needle_scalars(fzb_matcher* m, size_t needle_len, size_t n_scalars) {
+static void fill_needle_scalars(CompiledNeedle* m, size_t needle_len, size_t n_scalars) {
     const fzb_config& config = m->config;
     const fzb_scoring& sc = config.scoring;
     NeedleDev& nd = m->nd;
@@ -286,11 +321,11 @@ static void fill_needle_scalars(fzb_matcher* m, size_t needle_len, size_t n_scal
     nd.match_score = sc.match_score;
     nd.gap_open = sc.gap_open_penalty;
 }
-static u8 flip_ascii_byte(const fzb_matcher* m, u8 c) { return m->case_sensitive ? c : (c >= 'a' && c <= 'z') ? (u8)(c - 32) : (c >= 'A' && c <= 'Z') ? (u8)(c + 32) : c; }
+static u8 flip_ascii_byte(const CompiledNeedle* m, u8 c) { return m->case_sensitive ? c : (c >= 'a' && c <= 'z') ? (u8)(c - 32) : (c >= 'A' && c <= 'Z') ? (u8)(c + 32) : c; }
 
 // A needle beyond NeedleDev's by-value arrays: the arrays go to one host blob (uploaded on first use), the scalars to NeedleLongDev, and the
 // stage configuration is "lane-exact prefilter kernel (or the streaming subsequence automaton) first, wave- or thread-per-window scorer"
-static void build_long_needle(fzb_matcher* m, const uint8_t* needle_utf8, size_t needle_len, const std::vector<u32>& cps) {
+static void build_long_needle(CompiledNeedle* m, const uint8_t* needle_utf8, size_t needle_len, const std::vector<u32>& cps) {
     const fzb_config* config = &m->config;
     const fzb_scoring& sc = config->scoring;
     NeedleDev& nd = m->nd;
@@ -360,7 +395,7 @@ static void build_long_needle(fzb_matcher* m, const uint8_t* needle_utf8, size_t
 
 // The streaming filter's byte tables: `table[b]` = needle rows byte b can match (the LCS filter's M), the dead byte, the ordered-subsequence
 // DFA (state s = rows matched so far) - or, for the literal substring mode on the ASCII path, the needle's Knuth-Morris-Pratt automaton
-static void build_filter_tables(fzb_matcher* m) {
+static void build_filter_tables(CompiledNeedle* m) {
     const NeedleDev& nd = m->nd;
     LaunchCfg& lc = m->lc;
     m->table.assign(256, 0);
@@ -397,7 +432,7 @@ static void build_filter_tables(fzb_matcher* m) {
     }
 }
 
-static void build_unicode_dfa(fzb_matcher* m) {
+static void build_unicode_dfa(CompiledNeedle* m) {
     const fzb_config* config = &m->config;
     const NeedleDev& nd = m->nd;
     const LaunchCfg& lc = m->lc;
@@ -469,7 +504,7 @@ static void build_unicode_dfa(fzb_matcher* m) {
 // occurs inside a scalar).  States are numbered by ascending LCS of V (an unfinished scalar counts for nothing), start state first.
 // (Rounds 2-5 ran the byte-level LCS over the scalars' LAST bytes here - a looser superset that needed the lane-exact window kernel for every
 // survivor; with the exact criterion single-chunk lists are decided in the stream: pipe_unicode_typo_fast_path.)
-static bool build_scalar_lcs_dfa(fzb_matcher* m) {
+static bool build_scalar_lcs_dfa(CompiledNeedle* m) {
     const NeedleDev& nd = m->nd;
     const int rows = m->rows, k = m->config.max_typos;
     const u64 mask = rows >= 64 ? ~(u64)0 : (((u64)1 << rows) - 1);
@@ -549,7 +584,7 @@ static bool build_scalar_lcs_dfa(fzb_matcher* m) {
     return true;
 }
 
-static void build_lcs_dfa(fzb_matcher* m) {
+static void build_lcs_dfa(CompiledNeedle* m) {
     const LaunchCfg& lc = m->lc;
     const int k = m->config.max_typos;
     m->lcs_states = 0;
@@ -613,7 +648,7 @@ static void build_lcs_dfa(fzb_matcher* m) {
     }
 }
 
-static void build_cdfa(fzb_matcher* m) {
+static void build_cdfa(CompiledNeedle* m) {
     const LaunchCfg& lc = m->lc;
     // The class-composite form of the automaton the streaming filter runs (ragged lists: kernels_filter.hip, k1_cdfa_ragged): bytes with
     // identical columns are one class (K of them), G transitions are composed into one table indexed by
@@ -673,7 +708,7 @@ static void build_cdfa(fzb_matcher* m) {
 }
 
 // which forms of the scorers this needle and scoring allow
-static void set_scorer_forms(fzb_matcher* m, const uint8_t* needle_utf8, size_t needle_len) {
+static void set_scorer_forms(CompiledNeedle* m, const uint8_t* needle_utf8, size_t needle_len) {
     const fzb_scoring& sc = m->config.scoring;
     LaunchCfg& lc = m->lc;
     lc.pad_ok = 1;
@@ -690,15 +725,16 @@ static void set_scorer_forms(fzb_matcher* m, const uint8_t* needle_utf8, size_t 
     lc.cfu_ok = lc.bias_ok && 2 * (u32)sc.gap_extend_penalty <= (u32)sc.mismatch_penalty && !fzb_knobs().no_dp_cfu;  // (knob: the unicode scorer's first form)
 }
 
-int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, size_t needle_len, fzb_matcher** out) {
-    if (!config || !out || (!needle_utf8 && needle_len)) return fail(FZB_ERR_INVALID, "null argument");
+// (config, needle) -> everything a matcher holds on the host; no HIP call.  `cn` comes in default-constructed and is only to be used when
+// this returns FZB_OK.
+static int compile_needle(CompiledNeedle& cn, const fzb_config* config, const uint8_t* needle_utf8, size_t needle_len) {
+    if (!config || (!needle_utf8 && needle_len)) return fail(FZB_ERR_INVALID, "null argument");
     if (config->casing < 0 || config->casing > 2 || config->unicode < 0 || config->unicode > 2 || config->sort < 0 || config->sort > 3 || config->max_typos < -1 ||
         config->max_typos > 0xFFFF)
         return fail(FZB_ERR_INVALID, "config enum/range out of bounds");
     std::vector<u32> cps;
     if (!decode_utf8(needle_utf8, needle_len, cps)) return fail(FZB_ERR_INVALID, "needle is not valid UTF-8");
-    std::unique_ptr<fzb_matcher> mp(new fzb_matcher());
-    fzb_matcher* m = mp.get();
+    CompiledNeedle* m = &cn;
     m->config = *config;
     m->needle.assign((const char*)needle_utf8, needle_len);
     m->empty = needle_len == 0;
@@ -711,10 +747,7 @@ int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, siz
         return fail(FZB_ERR_INVALID, "pf_lanes must be 16/32/64 and sw_lanes 8/16/32/64 (or both 0 = auto)");
     m->lc.pf_lanes = pf;
     m->lc.sw_lanes = sw;
-    if (m->empty) {  // CompiledPatterns::Empty (src/matcher/mod.rs:194-196)
-        *out = mp.release();
-        return FZB_OK;
-    }
+    if (m->empty) return FZB_OK;  // CompiledPatterns::Empty (src/matcher/mod.rs:194-196)
     // CaseMatching::respects_case_for (src/lib.rs:370-376), UnicodeMatching::respects_unicode_for (:394-400)
     bool any_upper = false, ascii = true;
     for (u32 cp : cps) { any_upper |= is_uppercase(cp); ascii &= cp < 0x80; }
@@ -733,7 +766,6 @@ int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, siz
     fill_needle_scalars(m, needle_len, cps.size());
     if (m->long_needle) {
         build_long_needle(m, needle_utf8, needle_len, cps);
-        *out = mp.release();
         return FZB_OK;
     }
     NeedleDev& nd = m->nd;
@@ -763,64 +795,35 @@ int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, siz
     // the stream stage of these queries is the ordered-subsequence automaton over the needle's bytes and their case flips
     m->sig_eligible = !m->unicode && lc.filter_mode == 1 && lc.filter_exact && needle_sig_eligible(needle_utf8, needle_len, k, m->literal_mode);
     m->needle_sig = m->sig_eligible ? needle_sig(needle_utf8, needle_len) : 0u;
+    return FZB_OK;
+}
+
+int fzb_matcher_create(const fzb_config* config, const uint8_t* needle_utf8, size_t needle_len, fzb_matcher** out) {
+    if (!out) return fail(FZB_ERR_INVALID, "null argument");
+    std::unique_ptr<fzb_matcher> mp(new fzb_matcher());
+    if (int rc = compile_needle(*mp, config, needle_utf8, needle_len)) return rc;
     *out = mp.release();
     return FZB_OK;
 }
 
-// `Matcher::set_pattern` / `Matcher::set_config` (src/matcher/mod.rs:154-176): the matcher is rebuilt for the new needle or config
-// exactly as fzb_matcher_create would build it, but keeps its device workspace (sized by the corpus, not by the needle), so a
-// re-query after every keystroke costs two small table uploads instead of a round of device allocations.
+// `Matcher::set_pattern` / `Matcher::set_config` (src/matcher/mod.rs:154-176): the matcher's CompiledNeedle half is compiled anew, exactly
+// as fzb_matcher_create would, and takes the old one's place; its MatcherState half - the workspace, staging, scratch, streams, events,
+// pinned words, shard clones and workers, all sized by the corpus and the session, not by the needle - stays as it is.  So a re-query
+// after every keystroke costs one small table upload instead of a round of device allocations, and a buffer added to MatcherState is
+// kept without being named here.  What does depend on the needle is reset below, line by line.
 static int rebuild_matcher(fzb_matcher* m, const fzb_config* config, const uint8_t* needle_utf8, size_t needle_len) {
-    fzb_matcher* fresh = nullptr;
-    int rc = fzb_matcher_create(config, needle_utf8, needle_len, &fresh);
+    CompiledNeedle fresh;
+    int rc = compile_needle(fresh, config, needle_utf8, needle_len);
     if (rc) return rc;  // m is left as it was
-    // device-side state moves over to the rebuilt matcher ...
-    std::swap(fresh->ws, m->ws);
-    fresh->ws.tables_stale = true;
-    std::swap(fresh->out_dev, m->out_dev);
-    std::swap(fresh->out_cap, m->out_cap);
-    std::swap(fresh->count_dev, m->count_dev);
-    std::swap(fresh->fetch, m->fetch);
-    std::swap(fresh->long_scratch, m->long_scratch);
-    std::swap(fresh->long_scratch_bytes, m->long_scratch_bytes);
-    std::swap(fresh->trace_sel, m->trace_sel);  // the matched-indices scratch and the fused top + positions query's buffers
-    std::swap(fresh->trace_pos, m->trace_pos);
-    std::swap(fresh->trace_npos, m->trace_npos);
-    std::swap(fresh->trace_cap, m->trace_cap);
-    std::swap(fresh->trace_pos_words, m->trace_pos_words);
-    std::swap(fresh->top_head, m->top_head);
-    std::swap(fresh->top_traced, m->top_traced);
-    std::swap(fresh->top_idx_words, m->top_idx_words);
-    std::swap(fresh->top_tiles, m->top_tiles);
-    std::swap(fresh->top_cap, m->top_cap);
-    std::swap(fresh->top_packed, m->top_packed);
-    std::swap(fresh->top_dense, m->top_dense);
-    std::swap(fresh->top_packed_cap, m->top_packed_cap);
-    std::swap(fresh->top_dense_words, m->top_dense_words);
-    std::swap(fresh->top_last_records, m->top_last_records);
-    std::swap(fresh->top_last_positions, m->top_last_positions);
-    std::swap(fresh->aux_stream, m->aux_stream);
-    std::swap(fresh->ev_fork, m->ev_fork);
-    std::swap(fresh->ev_join, m->ev_join);
-    fresh->device = m->device;
-    fresh->lc.num_cus = m->lc.num_cus;
-    fresh->profiling = m->profiling;
-    fresh->prof_calls = m->prof_calls;
-    for (int i = 0; i < fzb_matcher::PROF_SLOTS; i++) {
-        for (int k = 0; k < 5; k++) std::swap(fresh->evring[i][k], m->evring[i][k]);
-        fresh->ev_filter[i] = m->ev_filter[i];
-    }
-    std::swap(fresh->shard_stream, m->shard_stream);  // the multi-device form's state: a clone's stream / event / count, the parent's workers
-    std::swap(fresh->shard_event, m->shard_event);
-    std::swap(fresh->shard_count_host, m->shard_count_host);
-    std::swap(fresh->shard_device, m->shard_device);
-    std::swap(fresh->shard_workers, m->shard_workers);
-    std::swap(fresh->shard_clones, m->shard_clones);
-    // ... and then the handle the caller holds takes the rebuilt matcher's place
-    std::swap(*fresh, *m);
-    fzb_matcher_free(fresh);
+    const int num_cus = m->lc.num_cus;
+    static_cast<CompiledNeedle&>(*m) = std::move(fresh);
+    m->lc.num_cus = num_cus;      // the bound device's, not the needle's (fzb_bind_device)
+    m->ws.tables_stale = true;    // the next query uploads the new needle's tables
+    if (m->long_blob_dev) (void)hipFree(m->long_blob_dev);  // the old long needle's arrays: `ndl` points nowhere until ensure_long_needle uploads the new blob
+    m->long_blob_dev = nullptr;
+    memset(m->last_counters, 0, sizeof(m->last_counters));
     // the per-shard clones of the multi-device form follow (same needle, same config with the resolved lane pair); their device
-    // workspaces stay where they are
+    // state stays where it is
     if (!m->shard_clones.empty()) {
         fzb_config ccfg = m->config;
         ccfg.pf_lanes = (uint16_t)m->lc.pf_lanes;
@@ -874,28 +877,7 @@ int fzb_matcher_clone(const fzb_matcher* src, fzb_matcher** out) {
 
 void fzb_matcher_free(fzb_matcher* m) {
     if (!m) return;
-    free_workspace(m->ws);
-    if (m->out_dev) (void)hipFree(m->out_dev);
-    if (m->count_dev) (void)hipFree(m->count_dev);
-    if (m->top_words) (void)hipFree(m->top_words);
-    for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos, (void*)m->top_head, (void*)m->top_traced, (void*)m->top_idx_words, (void*)m->top_tiles,
-                    (void*)m->top_packed, (void*)m->top_dense})
-        if (p) (void)hipFree(p);
-    for (auto& tr : m->evring)
-        for (auto& e : tr)
-            if (e) (void)hipEventDestroy(e);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    if (m->aux_stream) (void)hipStreamDestroy(m->aux_stream);
-    if (m->long_blob_dev) (void)hipFree(m->long_blob_dev);
-    if (m->long_scratch) (void)hipFree(m->long_scratch);
-    if (m->fetch.count_host) (void)hipHostFree(m->fetch.count_host);
-    if (m->fetch_top.count_host) (void)hipHostFree(m->fetch_top.count_host);
-    if (m->shard_workers) fzb_shard_workers_free(m->shard_workers);  // joins the worker threads before their clones go
-    m->shard_workers = nullptr;
-    if (m->shard_stream) (void)hipStreamDestroy(m->shard_stream);
-    if (m->shard_event) (void)hipEventDestroy(m->shard_event);
-    if (m->shard_count_host) (void)hipHostFree(m->shard_count_host);
+    release_state(*m);
     if (!m->shard_clones.empty()) {
         // a clone's device state lives on its shard's device
         int cur = 0;
@@ -1157,41 +1139,29 @@ static int ensure_aux_stream(fzb_matcher* m) {
     return FZB_OK;
 }
 static size_t dp_scratch_words(int rows, int sw_lanes, int mgrid) { return (size_t)(rows + 1) * (size_t)(sw_lanes / 2) * (size_t)mgrid * 128; }
-static int ensure_dp_scratch_words(fzb_matcher* m, size_t words) {
-    Workspace& w = m->ws;
-    if (w.dp_scratch_words >= words) return FZB_OK;
-    if (w.dp_scratch) HIPCHK(hipFree(w.dp_scratch));
-    w.dp_scratch = nullptr;
-    w.dp_scratch_words = 0;
-    HIPCHK(dev_alloc((void**)&w.dp_scratch, words * 4));
-    w.dp_scratch_words = words;
-    return FZB_OK;
-}
+static int ensure_dp_scratch_words(fzb_matcher* m, size_t words) { return fzb_grow_dev(&m->ws.dp_scratch, &m->ws.dp_scratch_words, words); }
 static int ensure_dp_scratch(fzb_matcher* m, int mgrid) {  // parked rows of the multi-chunk scorer
     return ensure_dp_scratch_words(m, dp_scratch_words(m->nd.rows, m->lc.sw_lanes, mgrid));
 }
-static int ensure_sort_buffers(fzb_matcher* m, size_t cap) {  // ping-pong buffer + tile histograms of the device radix sort
-    Workspace& w = m->ws;
-    if (w.sort_cap >= cap && w.sort_tmp) return FZB_OK;
-    if (w.sort_tmp) HIPCHK(hipFree(w.sort_tmp));
-    if (w.sort_hist) HIPCHK(hipFree(w.sort_hist));
-    w.sort_tmp = nullptr; w.sort_hist = nullptr; w.sort_cap = 0;
-    HIPCHK(dev_alloc((void**)&w.sort_tmp, (cap + 16) * sizeof(fzb_match_rec)));
-    const size_t hist_words = (size_t)2 * 256 * (cap / 2048 + 2);  // tile histograms + their scan; behind them two sets of digit totals + the phase word
-    HIPCHK(dev_alloc((void**)&w.sort_hist, (hist_words + 1024) * 4));
-    HIPCHK(hipMemset(w.sort_hist + hist_words, 0, 1024 * 4));
-    w.sort_cap = cap;
+}  // extern "C"
+// ping-pong buffer + tile histograms of the device radix sort, for `cap` records
+int fzb_sort_ensure(SortBuffers& s, size_t cap) {
+    if (s.cap >= cap && s.tmp) return FZB_OK;
+    s.cap = 0;
+    int rc;
+    const size_t hist_words = (size_t)2 * 256 * (cap / 2048 + 2);  // tile histograms + their scan; behind them two sets of digit totals + the phase word (kernels_sort.hip)
+    if ((rc = fzb_dev_renew(&s.tmp, cap + 16)) || (rc = fzb_dev_renew(&s.hist, hist_words + 1024))) return rc;
+    HIPCHK(hipMemset(s.hist + hist_words, 0, 1024 * 4));
+    s.cap = cap;
     return FZB_OK;
 }
-}  // extern "C"
-int fzb_ensure_out_staging(fzb_matcher* m, size_t count) {  // device-side result of the synchronous entry points
-    if (m->out_cap >= count && m->count_dev && m->out_dev) return FZB_OK;
-    if (m->out_dev) (void)hipFree(m->out_dev);
-    m->out_dev = nullptr;
-    m->out_cap = 0;
-    HIPCHK(dev_alloc((void**)&m->out_dev, (count + 16) * sizeof(fzb_match_rec)));
-    m->out_cap = count;
-    if (!m->count_dev) HIPCHK(dev_alloc((void**)&m->count_dev, 64));
+static int ensure_sort_buffers(fzb_matcher* m, size_t cap) { return fzb_sort_ensure(m->ws.sort, cap); }
+int fzb_out_ensure(OutStaging& o, size_t count) {  // device-side result of the synchronous entry points
+    if (o.out_cap >= count && o.count_dev && o.out_dev) return FZB_OK;
+    o.out_cap = 0;
+    if (int rc = fzb_dev_renew(&o.out_dev, count + 16)) return rc;
+    o.out_cap = count;
+    if (!o.count_dev) HIPCHK(fzb_dev_alloc((void**)&o.count_dev, 64));
     return FZB_OK;
 }
 extern "C" {
@@ -1214,14 +1184,7 @@ static int ensure_long_needle(fzb_matcher* m, size_t scratch_bytes) {  // the ne
         m->ndl.uf = (const u8(*)[4])(b + m->long_off_uf);
         m->ndl.ulen = b + m->long_off_ulen;
     }
-    if (m->long_scratch_bytes < scratch_bytes) {
-        if (m->long_scratch) HIPCHK(hipFree(m->long_scratch));
-        m->long_scratch = nullptr;
-        m->long_scratch_bytes = 0;
-        HIPCHK(dev_alloc(&m->long_scratch, scratch_bytes));
-        m->long_scratch_bytes = scratch_bytes;
-    }
-    return FZB_OK;
+    return scratch_bytes ? fzb_grow_dev(&m->long_scratch, &m->long_scratch_bytes, scratch_bytes) : FZB_OK;
 }
 
 // The pipeline of a LONG needle (> 64 bytes or > 63 rows; the reference takes them up to Scoring::max_needle_len(), src/lib.rs:480-503).
@@ -1552,16 +1515,7 @@ static u32 pipe_qcap(const Pipe& p) { return (u32)std::min<u64>((u64)p.cnt + FZB
 // matched indices: one traced generic scorer for every window width, ASCII and unicode (kernels_generic.hip); its grid for `cnt` items and
 // its per-wave matrices (grown here on first use, or ahead of it by fzb_matcher_reserve_top_indices)
 static int traced_grid(int cus, size_t cnt) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)cus / 2, (cnt + 3) / 4)); }
-static int ensure_trace_cells(fzb_matcher* m, size_t words) {
-    Workspace& w = m->ws;
-    if (w.trace_cells_words >= words) return FZB_OK;
-    if (w.trace_cells) HIPCHK(hipFree(w.trace_cells));
-    w.trace_cells = nullptr;
-    w.trace_cells_words = 0;
-    HIPCHK(dev_alloc((void**)&w.trace_cells, words * 4));
-    w.trace_cells_words = words;
-    return FZB_OK;
-}
+static int ensure_trace_cells(fzb_matcher* m, size_t words) { return fzb_grow_dev(&m->ws.trace_cells, &m->ws.trace_cells_words, words); }
 static int pipe_score_traced(Pipe& p) {
     fzb_matcher* m = p.m;
     Workspace& w = m->ws;
@@ -1875,15 +1829,15 @@ int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPla
     if (p->by_score) {
         int rc = ensure_sort_buffers(m, cap);
         if (rc) return rc;
-        if (p->via_tmp) p->in = m->ws.sort_tmp;
+        if (p->via_tmp) p->in = m->ws.sort.tmp;
     }
     return FZB_OK;
 }
 int fzb_order_finish(fzb_matcher* m, const OrderPlan& p, fzb_match_rec* dev_out, const u32* dev_count, hipStream_t stream) {
     if (!p.reversed && !p.by_score) return FZB_OK;
     Workspace& w = m->ws;
-    if (p.by_score && !w.sort_tmp) return fail(FZB_ERR_INVALID, "fzb_order_finish without fzb_order_begin");
-    fzb_launch_sort(dev_out, w.sort_tmp, dev_count, w.sort_hist, (u32)(w.sort_cap / 2048 + 2), p.reversed, p.by_score, m->lc.num_cus * 2, stream, p.via_tmp ? -1 : p.one_pass ? 1 : 2);
+    if (p.by_score && !w.sort.tmp) return fail(FZB_ERR_INVALID, "fzb_order_finish without fzb_order_begin");
+    fzb_launch_sort(dev_out, w.sort.tmp, dev_count, w.sort.hist, (u32)(w.sort.cap / 2048 + 2), p.reversed, p.by_score, m->lc.num_cus * 2, stream, p.via_tmp ? -1 : p.one_pass ? 1 : 2);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
@@ -2081,13 +2035,11 @@ int ensure_trace_buffers(fzb_matcher* m, size_t count, size_t pos_words) {
     if (m->trace_cap >= count && m->trace_pos_words >= pos_words && m->trace_sel) return FZB_OK;
     count = std::max(count, m->trace_cap);  // (neither dimension shrinks: what a reserve sized for the longest needle stays)
     pos_words = std::max(pos_words, m->trace_pos_words);
-    for (void* p : {(void*)m->trace_sel, (void*)m->trace_pos, (void*)m->trace_npos})
-        if (p) HIPCHK(hipFree(p));
-    m->trace_sel = m->trace_pos = m->trace_npos = nullptr;
     m->trace_cap = m->trace_pos_words = 0;
-    HIPCHK(dev_alloc((void**)&m->trace_sel, (count + 4) * 4));  // [count] = the list length
-    HIPCHK(dev_alloc((void**)&m->trace_npos, count * 4));
-    HIPCHK(dev_alloc((void**)&m->trace_pos, pos_words * 4));
+    int rc;
+    if ((rc = fzb_dev_renew(&m->trace_sel, count + 4)) ||  // [count] = the list length
+        (rc = fzb_dev_renew(&m->trace_npos, count)) || (rc = fzb_dev_renew(&m->trace_pos, pos_words)))
+        return rc;
     m->trace_cap = count;
     m->trace_pos_words = pos_words;
     return FZB_OK;
@@ -2304,6 +2256,11 @@ static void multi_free_buffers(fzb_multi_matcher* mm) {
     mm->tile_counts = nullptr;
     mm->cap = 0;
 }
+static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and pinned word the composition itself owns
+    multi_free_buffers(mm);
+    fzb_sort_release(mm->sort);
+    fzb_out_release(*mm);
+}
 
 // the composition's buffers for ranges of up to `count` haystacks
 static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
@@ -2317,32 +2274,6 @@ static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
     HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
     HIPCHK(dev_alloc((void**)&mm->tile_counts, ((cap + FZB_TILE - 1) / FZB_TILE + 2) * 4));
     mm->cap = cap;
-    return FZB_OK;
-}
-
-// the device-side result of the synchronous entry points
-static int multi_ensure_out(fzb_multi_matcher* mm, size_t count) {
-    if (mm->out_cap >= count && mm->count_dev && mm->out_dev) return FZB_OK;
-    if (mm->out_dev) (void)hipFree(mm->out_dev);
-    mm->out_dev = nullptr;
-    mm->out_cap = 0;
-    HIPCHK(dev_alloc((void**)&mm->out_dev, (count + 16) * sizeof(fzb_match_rec)));
-    mm->out_cap = count;
-    if (!mm->count_dev) HIPCHK(dev_alloc((void**)&mm->count_dev, 64));
-    return FZB_OK;
-}
-
-// ping-pong buffer + tile histograms of the device radix sort (match_list's Score* strategies)
-static int multi_ensure_sort(fzb_multi_matcher* mm, size_t count) {
-    if (mm->sort_cap >= count && mm->sort_tmp) return FZB_OK;
-    if (mm->sort_tmp) (void)hipFree(mm->sort_tmp);
-    if (mm->sort_hist) (void)hipFree(mm->sort_hist);
-    mm->sort_tmp = nullptr; mm->sort_hist = nullptr; mm->sort_cap = 0;
-    HIPCHK(dev_alloc((void**)&mm->sort_tmp, (count + 16) * sizeof(fzb_match_rec)));
-    const size_t hist_words = (size_t)2 * 256 * (count / 2048 + 2);  // (+ the digit totals and the phase word: kernels_sort.hip)
-    HIPCHK(dev_alloc((void**)&mm->sort_hist, (hist_words + 1024) * 4));
-    HIPCHK(hipMemset(mm->sort_hist + hist_words, 0, 1024 * 4));
-    mm->sort_cap = count;
     return FZB_OK;
 }
 
@@ -2547,7 +2478,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
         if ((rc = reserve_slot_any_needle(p.m, c))) return rc;
     for (fzb_matcher* m : mm->spare)
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
-    if ((rc = multi_ensure_buffers(mm, n)) || (rc = multi_ensure_out(mm, n)) || (rc = multi_ensure_sort(mm, n))) return rc;
+    if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
     if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
     return FZB_OK;
@@ -2573,12 +2504,7 @@ void fzb_multi_matcher_free(fzb_multi_matcher* mm) {
     }
     for (auto& p : mm->patterns) fzb_matcher_free(p.m);
     for (fzb_matcher* m : mm->spare) fzb_matcher_free(m);
-    multi_free_buffers(mm);
-    void* ptrs[] = {mm->out_dev, mm->count_dev, mm->sort_tmp, mm->sort_hist};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (mm->fetch.count_host) (void)hipHostFree(mm->fetch.count_host);
-    if (mm->fetch_top.count_host) (void)hipHostFree(mm->fetch_top.count_host);
+    multi_release(mm);
     delete mm;
 }
 
@@ -2662,7 +2588,7 @@ int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match**
     const size_t count = c->dev.n;
     *out = nullptr;
     *out_len = 0;
-    if (int rc_ = multi_ensure_out(mm, count)) return rc_;
+    if (int rc_ = fzb_out_ensure(*mm, count)) return rc_;
     int rc = fzb_multi_match_list_device(mm, c, 0, count, 0, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
     if (rc) return rc;
     // Matcher::match_list (src/matcher/mod.rs:212-222): reverse, then the stable radix sort unless there is no pattern at all
@@ -2671,8 +2597,8 @@ int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match**
     const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
     if ((reversed || by_score) && count) {
         if (by_score)
-            if (int rc_ = multi_ensure_sort(mm, count)) return rc_;
-        fzb_launch_sort(mm->out_dev, mm->sort_tmp, mm->count_dev, mm->sort_hist, (u32)(mm->sort_cap / 2048 + 2), reversed, by_score, mm->num_cus * 2, nullptr);
+            if (int rc_ = fzb_sort_ensure(mm->sort, count)) return rc_;
+        fzb_launch_sort(mm->out_dev, mm->sort.tmp, mm->count_dev, mm->sort.hist, (u32)(mm->sort.cap / 2048 + 2), reversed, by_score, mm->num_cus * 2, nullptr);
         HIPCHK(hipGetLastError());
     }
     return fetch_records(mm->fetch, mm->out_dev, mm->count_dev, mm->out_cap, out, out_len);
@@ -2766,7 +2692,7 @@ int fzb_multi_match_list_into(fzb_multi_matcher* mm, const fzb_corpus* c, size_t
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
     *out = nullptr;
     *out_len = 0;
-    if (int rc_ = multi_ensure_out(mm, count)) return rc_;
+    if (int rc_ = fzb_out_ensure(*mm, count)) return rc_;
     int rc = fzb_multi_match_list_device(mm, c, first, count, index_offset, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
     if (rc) return rc;
     return fetch_records(mm->fetch, mm->out_dev, mm->count_dev, mm->out_cap, out, out_len);
@@ -2778,7 +2704,6 @@ int fzb_multi_match_list_into(fzb_multi_matcher* mm, const fzb_corpus* c, size_t
 // ties at the cut included, and `found` = the length of the full list.  The pipeline writes its index-ordered records into the sort's
 // second buffer, the selection stage (kernels_topk.hip) keeps the records of the head in record order, the ordering step sorts those.
 }  // extern "C"
-int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap) { return ensure_sort_buffers(m, cap); }
 // The two count words and the records of a top result -> the host with ONE wait: at most `max_records` = min(limit, n) records exist, so
 // a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind the count, filled or not.  Beyond that the bound says little - a
 // `limit` at or above the list's length bounds the copy by n records, 80 MB on a 10 M list of which 4 MB exist: 1.5 ms at the 53 GB/s the
@@ -2827,11 +2752,11 @@ int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit,
     fzb_order_flags(m, &reversed, &by_score, &one_pass);
     Workspace& w = m->ws;
     u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
-    if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort_tmp, n, raw_count, stream))) return rc;
-    const u32 ntiles_cap = (u32)(w.sort_cap / 2048 + 2);
+    if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort.tmp, n, raw_count, stream))) return rc;
+    const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
     const int grid = m->lc.num_cus * 2;
-    HIPCHK(fzb_launch_topk_select(w.sort_tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort_hist, ntiles_cap, grid, st));
-    fzb_launch_sort((fzb_match_rec*)dev_out, w.sort_tmp, dev_count, w.sort_hist, ntiles_cap, reversed, by_score, grid, st, one_pass ? 1 : 2);
+    HIPCHK(fzb_launch_topk_select(w.sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort.hist, ntiles_cap, grid, st));
+    fzb_launch_sort((fzb_match_rec*)dev_out, w.sort.tmp, dev_count, w.sort.hist, ntiles_cap, reversed, by_score, grid, st, one_pass ? 1 : 2);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
@@ -2860,17 +2785,17 @@ int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t 
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
     int rc;
-    if ((rc = multi_ensure_out(mm, want)) || (rc = multi_ensure_sort(mm, n))) return rc;
+    if ((rc = fzb_out_ensure(*mm, want)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
     u32* const raw_count = mm->count_dev + 4;
-    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort_tmp, n, raw_count, nullptr))) return rc;
+    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, nullptr))) return rc;
     const int sort = mm->config.sort;
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
     const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
-    const u32 ntiles_cap = (u32)(mm->sort_cap / 2048 + 2);
+    const u32 ntiles_cap = (u32)(mm->sort.cap / 2048 + 2);
     const int grid = mm->num_cus * 2;
     // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
-    HIPCHK(fzb_launch_topk_select(mm->sort_tmp, raw_count, (u32)n, (u32)want, by_score, reversed, 0, mm->out_dev, (u32)want, mm->count_dev, mm->sort_hist, ntiles_cap, grid, nullptr));
-    fzb_launch_sort(mm->out_dev, mm->sort_tmp, mm->count_dev, mm->sort_hist, ntiles_cap, reversed, by_score, grid, nullptr);
+    HIPCHK(fzb_launch_topk_select(mm->sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, 0, mm->out_dev, (u32)want, mm->count_dev, mm->sort.hist, ntiles_cap, grid, nullptr));
+    fzb_launch_sort(mm->out_dev, mm->sort.tmp, mm->count_dev, mm->sort.hist, ntiles_cap, reversed, by_score, grid, nullptr);
     HIPCHK(hipGetLastError());
     return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
 }
@@ -2887,16 +2812,6 @@ static_assert(sizeof(fzb_indices_rec) == sizeof(fzb_match_indices) && offsetof(f
                   offsetof(fzb_indices_rec, positions_len) == offsetof(fzb_match_indices, positions_len),
               "the pack kernels write fzb_match_indices");
 namespace {
-template <typename T>
-int grow_dev(T** p, size_t* have, size_t want, size_t slack) {  // a buffer that only grows; *have = elements it holds, the slack excluded
-    if (*p && *have >= want) return FZB_OK;
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    HIPCHK(dev_alloc((void**)p, (want + slack) * sizeof(T)));
-    *have = want;
-    return FZB_OK;
-}
 // the buffers of a fused query with a head of up to `want` records and `stride` position dwords per record (everything but the traced
 // scorer's matrices, which are workspace); staging: the host form's packed result too
 int ensure_top_indices_buffers(fzb_matcher* m, size_t want, size_t stride, bool staging) {
@@ -2904,19 +2819,14 @@ int ensure_top_indices_buffers(fzb_matcher* m, size_t want, size_t stride, bool 
     if (rc) return rc;
     if (!m->top_idx_words) HIPCHK(dev_alloc((void**)&m->top_idx_words, 64));
     if (!m->top_head || !m->top_traced || !m->top_tiles || m->top_cap < want) {
-        for (void* p : {(void*)m->top_head, (void*)m->top_traced, (void*)m->top_tiles})
-            if (p) HIPCHK(hipFree(p));
-        m->top_head = m->top_traced = nullptr;
-        m->top_tiles = nullptr;
         m->top_cap = 0;
-        HIPCHK(dev_alloc((void**)&m->top_head, (want + 16) * sizeof(fzb_match_rec)));
-        HIPCHK(dev_alloc((void**)&m->top_traced, (want + 16) * sizeof(fzb_match_rec)));
-        HIPCHK(dev_alloc((void**)&m->top_tiles, fzb_indices_pack_tile_words(want) * 4));
+        if ((rc = fzb_dev_renew(&m->top_head, want + 16)) || (rc = fzb_dev_renew(&m->top_traced, want + 16)) || (rc = fzb_dev_renew(&m->top_tiles, fzb_indices_pack_tile_words(want))))
+            return rc;
         m->top_cap = want;
     }
     if (!staging) return FZB_OK;
-    if ((rc = grow_dev(&m->top_packed, &m->top_packed_cap, want, 1))) return rc;
-    return grow_dev(&m->top_dense, &m->top_dense_words, want * stride, 1);
+    if ((rc = fzb_grow_dev(&m->top_packed, &m->top_packed_cap, want, 1))) return rc;
+    return fzb_grow_dev(&m->top_dense, &m->top_dense_words, want * stride, 1);
 }
 u32 trace_stride(const fzb_matcher* m) { return (u32)std::max(1, m->nd.nbytes); }  // position dwords per record: as indices_in_list_order
 

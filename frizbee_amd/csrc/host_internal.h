@@ -64,20 +64,52 @@ struct fzb_corpus {
 // the haystacks a matcher's buffers are sized for: the list's length, or what fzb_corpus_reserve made room for
 inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c->cap_items > c->dev.n ? c->cap_items : c->dev.n); }
 
+// A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
+// null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).
+template <typename T>
+int fzb_dev_renew(T** p, size_t elems) {
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    HIPCHK(fzb_dev_alloc((void**)p, elems * sizeof(T)));
+    return FZB_OK;
+}
+template <typename T>
+int fzb_grow_dev(T** p, size_t* have, size_t want, size_t slack = 0) {
+    if (*p && *have >= want) return FZB_OK;
+    *have = 0;
+    if (int rc = fzb_dev_renew(p, want + slack)) return rc;
+    *have = want;
+    return FZB_OK;
+}
+int fzb_sort_ensure(SortBuffers& s, size_t cap);  // host.hip
+void fzb_sort_release(SortBuffers& s);
+
 // what the synchronous entry points remember between two results (fetch_records, host.hip)
 struct FetchHint {
     size_t last = 0;            // records of the previous result: the next one's records are copied speculatively, behind the count
     u32* count_host = nullptr;  // page-locked landing place of the two counters
 };
+// staging of the synchronous entry points, of either matcher type: the device-side result and what the copies to the host remember
+struct OutStaging {
+    fzb_match_rec* out_dev = nullptr;
+    size_t out_cap = 0;
+    u32* count_dev = nullptr;
+    FetchHint fetch;
+    FetchHint fetch_top;  // the top-`limit` entry points' own (their result sizes say nothing about the next full list's)
+};
+int fzb_out_ensure(OutStaging& o, size_t count);  // host.hip
+void fzb_out_release(OutStaging& o);
 
-struct fzb_matcher {
+// A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle
+// (host.hip) computes all of it and makes no HIP call.  fzb_matcher_set_pattern / _set_config replace it as a whole.
+struct CompiledNeedle {
     fzb_config config{};
     std::string needle;
     bool empty = false, case_sensitive = false, unicode = false, use_u8 = false;
     int literal_mode = 0;  // 0 = fuzzy; else FZB_MATCH_EXACT / PREFIX / SUFFIX / SUBSTRING (src/literal)
     int rows = 0;
     NeedleDev nd{};
-    LaunchCfg lc{};
+    LaunchCfg lc{};          // (num_cus is the bound device's, not the needle's: fzb_bind_device sets it, a needle change carries it over)
     std::vector<u64> table;  // host copy of the filter table
     std::vector<u8> dfa;     // host copy of the subsequence DFA
     std::vector<u8> uni_dfa; // unicode path, 0 typos: byte-level DFA of the exact prefilter (empty if it needs more than 255 states)
@@ -95,6 +127,20 @@ struct fzb_matcher {
     // the needle's letter signature and whether the signature form of the filter may decide for it (sig_filter.h: fuzzy, 0 typos, ASCII, no NUL)
     u32 needle_sig = 0;
     bool sig_eligible = false;
+    // a needle beyond NeedleDev's arrays (> 64 bytes or > 63 rows): scalars in `ndl`, the arrays in one host blob with its section offsets
+    // (MatcherState::long_blob_dev is its device copy, uploaded on first use: until then ndl's pointers are null)
+    bool long_needle = false;
+    bool long_dfa = false;  // a long ASCII needle of up to 200 rows, 0 typos: `dfa` holds its ordered-subsequence automaton and the streaming filter is the first stage
+    bool long_upper = false;  // a long ASCII needle with an uppercase letter among its rows (k2d_dp_long's form)
+    NeedleLongDev ndl{};
+    std::vector<u8> long_blob_host;
+    size_t long_off_c = 0, long_off_f = 0, long_off_uc = 0, long_off_uf = 0, long_off_ulen = 0;
+};
+
+// MatcherState: what a session has accumulated on the device - buffers, streams, events, pinned words, the multi-device form's clones and
+// workers.  It survives a needle or config change untouched (but for the few resets rebuild_matcher names); release_state (host.hip) is the
+// one place that frees what it owns.  A matcher that gains a buffer adds it here and there.
+struct MatcherState : OutStaging {
     Workspace ws{};
     int device = -1;
     bool profiling = false;
@@ -106,12 +152,6 @@ struct fzb_matcher {
     u64 prof_calls = 0;
 
     u32 last_counters[4] = {0, 0, 0, 0};
-    // staging for the synchronous API
-    fzb_match_rec* out_dev = nullptr;
-    size_t out_cap = 0;
-    u32* count_dev = nullptr;
-    FetchHint fetch;
-    FetchHint fetch_top;  // the top-`limit` entry points' own (their result sizes say nothing about the next full list's)
     // fzb_match_list_indices: the selection (+ its length), the positions (`stride` per record) and their counts
     u32* trace_sel = nullptr;
     u32* trace_pos = nullptr;
@@ -129,16 +169,10 @@ struct fzb_matcher {
     u32* top_dense = nullptr;
     size_t top_packed_cap = 0, top_dense_words = 0;
     size_t top_last_records = 0, top_last_positions = 0;
-    // a needle beyond NeedleDev's arrays (> 64 bytes or > 63 rows): scalars in `ndl`, the arrays in one device blob (uploaded on first
-    // use), and the global scratch of its kernels (N-typo path state, per-row previous-chunk vectors, traced cells)
-    bool long_needle = false;
-    bool long_dfa = false;  // a long ASCII needle of up to 200 rows, 0 typos: `dfa` holds its ordered-subsequence automaton and the streaming filter is the first stage
-    bool long_upper = false;  // a long ASCII needle with an uppercase letter among its rows (k2d_dp_long's form)
-    NeedleLongDev ndl{};
-    std::vector<u8> long_blob_host;
-    size_t long_off_c = 0, long_off_f = 0, long_off_uc = 0, long_off_uf = 0, long_off_ulen = 0;
+    // a long needle's arrays on the device (the copy of CompiledNeedle::long_blob_host: dropped with the needle it belongs to) and the global
+    // scratch of its kernels (N-typo path state, per-row previous-chunk vectors, traced cells)
     void* long_blob_dev = nullptr;
-    void* long_scratch = nullptr;
+    u8* long_scratch = nullptr;
     size_t long_scratch_bytes = 0;
     // multi-device form (host_shard.hip): the per-shard clones of this matcher (their device state lives on the shard's device);
     // on a clone: its stream and the device it is bound to
@@ -157,11 +191,13 @@ struct fzb_matcher {
     bool sum_scores = false;
     // sharded top-`limit` queries, on the root: the count pairs of the shards whose selected runs are copied (two words per shard)
     u32* top_words = nullptr;
-    size_t top_words_cap = 0;
+    size_t top_words_cap = 0;  // in words
 };
 
+struct fzb_matcher : CompiledNeedle, MatcherState {};
+
 // ---- multi-pattern composition (src/matcher/multi.rs; host.hip) ----------------------------------------------------------
-struct fzb_multi_matcher {
+struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entry points)
     fzb_config config{};
     struct Compiled { bool negated; fzb_matcher* m; };
     std::vector<Compiled> patterns;  // empty needles dropped (src/matcher/mod.rs:193-195)
@@ -180,15 +216,7 @@ struct fzb_multi_matcher {
     u32* items = nullptr;
     u64* bitmap = nullptr;
     u32* tile_counts = nullptr;
-    // ordering + staging for the synchronous API
-    fzb_match_rec* out_dev = nullptr;
-    size_t out_cap = 0;
-    u32* count_dev = nullptr;
-    fzb_match_rec* sort_tmp = nullptr;
-    u32* sort_hist = nullptr;
-    size_t sort_cap = 0;
-    FetchHint fetch;
-    FetchHint fetch_top;  // the top-`limit` entry points' own (their result sizes say nothing about the next full list's)
+    SortBuffers sort{};  // ordering of the synchronous entry points
     // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
@@ -210,11 +238,11 @@ int fzb_bind_device(fzb_matcher* m);
 // the wait of a synchronous entry point: polls the stream for up to FZB_SPIN_WAIT_US (default 1 ms), then blocks (host.hip)
 hipError_t fzb_stream_wait(hipStream_t st);
 int fzb_fetch_records(FetchHint& h, const void* dev_records, const u32* dev_words, int n_word, size_t capacity, hipStream_t st, fzb_match** out, size_t* out_len);
-int fzb_ensure_out_staging(fzb_matcher* m, size_t count);
+inline int fzb_ensure_out_staging(fzb_matcher* m, size_t count) { return fzb_out_ensure(*m, count); }
 // top-`limit` queries (host.hip): the ordering flags of a matcher as fzb_order_begin decides them, the sort's buffers for `cap` records
 // (the selection stage's input and scratch), the one-wait copy of (count pair, <= max_records records), the no-pattern result
 void fzb_order_flags(const fzb_matcher* m, bool* reversed, bool* by_score, bool* one_pass);
-int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap);
+inline int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap) { return fzb_sort_ensure(m->ws.sort, cap); }
 int fzb_fetch_top(FetchHint& h, const void* dev_records, const u32* dev_words, size_t max_records, hipStream_t st, fzb_match** out, size_t* out_len, uint64_t* out_found);
 int fzb_empty_pattern_top(size_t n, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
 // the ordering post-step of `match_list` on the device (host.hip, next to fzb_sorted_range_device)

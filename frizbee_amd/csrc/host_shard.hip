@@ -553,13 +553,7 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
     for (size_t g = 0; g < ns; g++) slot[g + 1] = slot[g] + std::min<size_t>(limit, (size_t)sc->shard[g]->dev.n);
     const size_t cap = slot[ns];
     if ((rc = fzb_ensure_out_staging(m, cap)) || (rc = fzb_ensure_sort_buffers(m, cap))) return rc;
-    if (m->top_words_cap < ns) {
-        if (m->top_words) (void)hipFree(m->top_words);
-        m->top_words = nullptr;
-        m->top_words_cap = 0;
-        HIPCHK(fzb_dev_alloc((void**)&m->top_words, ns * 8));
-        m->top_words_cap = ns;
-    }
+    if ((rc = fzb_grow_dev(&m->top_words, &m->top_words_cap, 2 * ns))) return rc;
     if ((rc = shard_prepare(m, sc, root))) return rc;
     bool reversed, by_score, one_pass;
     fzb_order_flags(m, &reversed, &by_score, &one_pass);  // the root's: a carrier of a multi matcher's runs does not know that scores are sums
@@ -582,10 +576,10 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
         // (behind the pipeline's own sizing: a workspace that grows releases the sort's buffers with it)
         if ((rc_ = fzb_ensure_sort_buffers(cm, count))) return rc_;
         const size_t keep = slot[g + 1] - slot[g];
-        fzb_match_rec* const sel = cm->ws.sort_tmp;
+        fzb_match_rec* const sel = cm->ws.sort.tmp;
         u32* const sel_count = cm->count_dev + 4;
-        HIPCHK(fzb_launch_topk_select(cm->out_dev, cm->count_dev, (u32)count, (u32)keep, by_score, reversed, one_pass, sel, (u32)keep, sel_count, cm->ws.sort_hist,
-                                      (u32)(cm->ws.sort_cap / 2048 + 2), cm->lc.num_cus * 2, st));
+        HIPCHK(fzb_launch_topk_select(cm->out_dev, cm->count_dev, (u32)count, (u32)keep, by_score, reversed, one_pass, sel, (u32)keep, sel_count, cm->ws.sort.hist,
+                                      (u32)(cm->ws.sort.cap / 2048 + 2), cm->lc.num_cus * 2, st));
         if (copy_forced || sc->device[g] != root) {  // the slot and its count pair travel to the root
             if (sc->device[g] == root) {
                 if (keep) HIPCHK(hipMemcpyAsync(m->out_dev + slot[g], sel, keep * sizeof(fzb_match_rec), hipMemcpyDeviceToDevice, st));
@@ -618,20 +612,20 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
         for (int k = 0; k < rs.n; k++) {
             const size_t g = g0 + (size_t)k;
             const bool local = !copy_forced && sc->device[g] == root;
-            rs.run[k] = local ? m->shard_clones[g]->ws.sort_tmp : m->out_dev + slot[g];
+            rs.run[k] = local ? m->shard_clones[g]->ws.sort.tmp : m->out_dev + slot[g];
             rs.count[k] = local ? m->shard_clones[g]->count_dev + 4 : m->top_words + 2 * g;
             rs.cap[k] = (u32)(slot[g + 1] - slot[g]);
         }
-        fzb_launch_topk_concat(rs, base, tot, m->ws.sort_tmp, (u32)cap, m->lc.num_cus * 2, st);
+        fzb_launch_topk_concat(rs, base, tot, m->ws.sort.tmp, (u32)cap, m->lc.num_cus * 2, st);
         base = tot;
         tot = tot == words ? words + 4 : words;
     }
     const size_t want = std::min(limit, cap);
-    const u32 ntiles_cap = (u32)(m->ws.sort_cap / 2048 + 2);
-    hipError_t e_sel = fzb_launch_topk_select(m->ws.sort_tmp, base, (u32)cap, (u32)want, by_score, reversed, one_pass, m->out_dev, (u32)want, words + 8, m->ws.sort_hist, ntiles_cap,
+    const u32 ntiles_cap = (u32)(m->ws.sort.cap / 2048 + 2);
+    hipError_t e_sel = fzb_launch_topk_select(m->ws.sort.tmp, base, (u32)cap, (u32)want, by_score, reversed, one_pass, m->out_dev, (u32)want, words + 8, m->ws.sort.hist, ntiles_cap,
                                               m->lc.num_cus * 2, st);
     if (e_sel != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_sel)));
-    fzb_launch_sort(m->out_dev, m->ws.sort_tmp, words + 8, m->ws.sort_hist, ntiles_cap, reversed, by_score, m->lc.num_cus * 2, st, one_pass ? 1 : 2);
+    fzb_launch_sort(m->out_dev, m->ws.sort.tmp, words + 8, m->ws.sort.hist, ntiles_cap, reversed, by_score, m->lc.num_cus * 2, st, one_pass ? 1 : 2);
     {
         hipError_t e_ = hipGetLastError();
         if (e_ != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_)));

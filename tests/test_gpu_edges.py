@@ -91,6 +91,45 @@ def test_set_pattern_and_set_config_requery_a_resident_corpus():
     assert m.match_list(cp).tolist() == O.Matcher("deadbe", lanes=(16, 16, 8)).match_packed(odata, ends).tolist()
 
 
+def test_every_synchronous_entry_point_interleaved_across_needle_changes():
+    """match_list, match_list_top, match_list_indices and match_list_top_indices take turns on ONE matcher and one resident corpus while
+    set_pattern / set_config walk it through every kind of needle (short, beyond 64 bytes, beyond 128, typos, unicode, empty, literal, the
+    first again): what has to survive a needle change is the union of what the four keep on the device - workspace, staging, trace and top
+    buffers, pinned count words and their guesses, the long needle's arrays.  Every result equals a freshly created matcher's; the
+    oracle's records at the short, the 130-byte and the unicode step."""
+    data, ends = synth.paths_corpus(b"linux", 2000, seed=21)
+    starts = np.concatenate([[0], ends[:-1]]).astype(np.int64)
+    hs = [data[int(a):int(b)].tobytes() for a, b in zip(starts, ends.astype(np.int64))]
+    long_path = b"out/Release/gen/chrome/browser/resources/settings/privacy_page/security_keys_subpage/security_keys_bio_enroll_dialog.html.rollup.js.map"
+    n70, n130 = long_path[:70], long_path[-130:]  # beyond the 64 bytes of the by-value needle, and beyond 128
+    hs += [b"//" + n70 + b"~", b"a/" + n130 + b"/z", b"x/" * 520 + b"linux_" + n70, "éa_ü/linux".encode(), "zz/éXaü.txt".encode(), "日本語/é/a/ü".encode()]
+    assert max(len(h) for h in hs) > 1024
+    cp = F.Corpus(hs)
+    base = dict(max_typos=0, pf_lanes=64)
+    walk = (("linux", base, True), (n70, base, False), (n130, base, True), ("linx", dict(base, max_typos=1), False), ("éaü", dict(base, max_typos=1), True), ("", dict(base, max_typos=1), False),
+            ("lin", dict(base, matching=F.Matching.Substring), False), ("linux", base, False))
+
+    def four(mt):
+        top, found = mt.match_list_top(cp, 5)
+        topi, foundi = mt.match_list_top_indices(cp, 5)
+        return mt.match_list(cp).tolist(), (top.tolist(), found), mt.match_list_indices(cp), (topi, foundi)
+
+    m = F.Matcher(walk[0][0], F.Config(**base))
+    cur = base
+    for step, (needle, cfg, with_oracle) in enumerate(walk):
+        if cfg != cur:
+            m.set_config(F.Config(**cfg))
+            cur = cfg
+        m.set_pattern(needle)
+        got, want = four(m), four(F.Matcher(needle, F.Config(**cfg)))
+        for name, g, w in zip(("match_list", "match_list_top", "match_list_indices", "match_list_top_indices"), got, want):
+            assert g == w, (step, needle, name)
+        assert got[1][1] == len(got[0]) == got[3][1] and got[1][0] == got[0][:5], (step, needle)
+        if with_oracle:
+            rec = O.Matcher(needle, lanes=(64, 64, 32), max_typos=cfg["max_typos"]).match_list(hs)
+            assert got[0] == rec.tolist() and len(rec) > 0, (step, needle)
+
+
 def test_corpus_beyond_4_gib_uses_64_bit_offsets():
     # 41 M haystacks of 112 bytes = 4.59 GB: end offsets and byte addresses no longer fit 32 bits.  Built on the device
     # (padded-16 layout = back-to-back rows since 112 % 16 == 0); checked against the oracle on three windows of the list,

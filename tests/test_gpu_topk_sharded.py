@@ -110,3 +110,21 @@ def test_a_shard_without_a_match_empty_patterns_and_tiny_lists(gather_mode):
                 want = O.Matcher("deadbe", sort=sort).match_list(hs)
                 for limit in (0, 1, 5):
                     assert_top(F.Matcher("deadbe", F.Config(sort=F.SortStrategy[sort], pf_lanes=64)).match_list_top_sharded(sc, limit), want, limit, (hs, ndev, sort))
+
+
+def test_sharded_top_across_a_needle_change(gather_mode):
+    """set_pattern between sharded top queries: the root keeps its staging, count words, peer decisions and report, the per-shard clones
+    follow the needle - every answer is the unsharded matcher's."""
+    have = F.device_count()
+    hs = ["deadbeef_%d" % i for i in range(300)] + ["nothing-%d" % i for i in range(700)]
+    sc = F.ShardedCorpus(hs, ndev=3, oversubscribe=3 > have)
+    cp = F.Corpus(hs)
+    cfg = F.Config(pf_lanes=64, sw_lanes=64)
+    m = F.Matcher("deadbeef", cfg)
+    for needle in ("deadbeef", "nothing", "deadbeef"):
+        m.set_pattern(needle)
+        want, want_found = F.Matcher(needle, cfg).match_list_top(cp, 50)
+        got, found = m.match_list_top_sharded(sc, 50)
+        assert found == want_found and found in (300, 700), needle
+        assert got.tolist() == want.tolist(), needle
+    assert m.shard_report().startswith("root device") and m.shard_report().count("shard ") == 3
