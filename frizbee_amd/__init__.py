@@ -124,6 +124,7 @@ SYMBOLS = [
     "fzb_corpus_reserve", "fzb_corpus_append", "fzb_corpus_truncate", "fzb_corpus_info", "fzb_debug_corpus_read",
     "fzb_corpus_remove", "fzb_corpus_remove_device", "fzb_corpus_replace", "fzb_corpus_edit_info",
     "fzb_match_list_top_indices", "fzb_match_list_top_indices_device", "fzb_matcher_reserve_top_indices", "fzb_multi_match_list_top_indices",
+    "fzb_multi_match_list_top_indices_device", "fzb_multi_match_list_top_indices_fused", "fzb_multi_matcher_reserve_top_indices",
     "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold",
 ]
 
@@ -228,6 +229,9 @@ def lib():
         l.fzb_match_list_top_indices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.fzb_matcher_reserve_top_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         l.fzb_multi_match_list_top_indices.argtypes = l.fzb_match_list_top_indices.argtypes
+        l.fzb_multi_match_list_top_indices_fused.argtypes = l.fzb_match_list_top_indices.argtypes
+        l.fzb_multi_match_list_top_indices_device.argtypes = l.fzb_match_list_top_indices_device.argtypes
+        l.fzb_multi_matcher_reserve_top_indices.argtypes = l.fzb_matcher_reserve_top_indices.argtypes
         l.fzb_corpus_signature_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         l.fzb_debug_needle_signature.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         l.fzb_debug_signature_threshold.argtypes = []
@@ -621,10 +625,22 @@ class MultiMatcher(_IterApi):
         return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
     def match_list_top_indices(self, haystacks, limit):
-        """(`match_list_indices(haystacks)[:limit]` with `index` = the corpus index, len of the full list) for the compiled patterns: a
-        host composition - `match_list_top`, then the matched-indices pass in list order over that head (see `Matcher.match_list_top_indices`)."""
+        """(`match_list_indices(haystacks)[:limit]` with `index` = the corpus index, len of the full list) for the compiled patterns, in one
+        fused device call with one host wait: the multi top stage, one traced pass per non-negated pattern over the head, the union of their
+        positions and the pack, all on the device (see `Matcher.match_list_top_indices`)."""
         cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
-        return _top_indices(lib().fzb_multi_match_list_top_indices, self.h, cp, limit)
+        return _top_indices(lib().fzb_multi_match_list_top_indices_fused, self.h, cp, limit)
+
+    def match_list_top_indices_device(self, corpus, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream=0):
+        """`match_list_top_indices` with the result left in HBM, asynchronous on `stream` (see `Matcher.match_list_top_indices_device`):
+        `positions_capacity` >= min(limit, len(corpus)) x U uint32, U = the needle bytes of the non-negated patterns together.  A matcher
+        without a compiled pattern is refused."""
+        _check(lib().fzb_multi_match_list_top_indices_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream))
+
+    def reserve_top_indices(self, corpus, limit, max_needle_bytes):
+        """After `reserve(corpus)`: no `match_list_top_indices` call with this `limit` or a smaller one allocates device memory, also after
+        `set_patterns` / `set_config` that add no pattern slot and keep every needle within `max_needle_bytes` bytes."""
+        _check(lib().fzb_multi_matcher_reserve_top_indices(self.h, corpus.h, limit, max_needle_bytes))
 
     def match_list_indices(self, haystacks, selection=None):
         """`Matcher::match_list_indices` over the compiled patterns (`match_one_indices_multi`, src/matcher/multi.rs:56-82); see

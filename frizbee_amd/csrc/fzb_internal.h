@@ -256,6 +256,10 @@ void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 
 size_t fzb_indices_pack_tile_words(size_t max_records);
 void fzb_launch_indices_pack(const fzb_match_rec* head, const u32* head_count, const fzb_match_rec* traced, const u32* traced_count, const u32* npos, const u32* pos, u32 stride,
                              fzb_indices_rec* out, u32 out_cap, u32* dense, u32 dense_cap, u32* dev_count, u32* tiles, u32 max_records, int grid, hipStream_t st);
+// the multi-pattern form's union step between the traced passes and the pack (indices_union.h: IUnionSrc, IUNION_BY_VALUE)
+struct IUnionSrc;
+void fzb_launch_multi_union(const fzb_match_rec* head, const u32* head_count, u32 max_records, const IUnionSrc* src, u32 P, const IUnionSrc* src_dev, u32* cursors, fzb_match_rec* out,
+                            u32* out_count, u32* npos_u, u32* pos_u, u32 U, int grid, hipStream_t st);
 // kernels_multi.hip
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st);
 void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u32* count_out, int grid, hipStream_t st);

@@ -2258,6 +2258,15 @@ static void multi_free_buffers(fzb_multi_matcher* mm) {
 }
 static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and pinned word the composition itself owns
     multi_free_buffers(mm);
+    for (void* p : {(void*)mm->top_head, (void*)mm->top_comb, (void*)mm->top_items, (void*)mm->top_npos_u, (void*)mm->top_tiles, (void*)mm->top_words, (void*)mm->top_pos_u,
+                    (void*)mm->union_src, (void*)mm->union_cursors, (void*)mm->top_packed, (void*)mm->top_dense})
+        if (p) (void)hipFree(p);
+    mm->top_head = mm->top_comb = nullptr;
+    mm->top_items = mm->top_npos_u = mm->top_tiles = mm->top_words = mm->top_pos_u = mm->union_cursors = mm->top_dense = nullptr;
+    mm->union_src = nullptr;
+    mm->top_packed = nullptr;
+    mm->top_cap = mm->top_pos_u_words = mm->union_src_cap = mm->union_cursor_words = mm->top_packed_cap = mm->top_dense_words = 0;
+    mm->union_src_host.clear();
     fzb_sort_release(mm->sort);
     fzb_out_release(*mm);
 }
@@ -2776,6 +2785,27 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
     return fzb_fetch_top(m->fetch_top, m->out_dev, m->count_dev, want, nullptr, out, out_len, out_found);
 }
 
+}  // extern "C"
+// The top stage of a `from_patterns` matcher on `st`: the composition over the n haystacks into the sort's second buffer (its pair in
+// raw_count), the selection of the best `want` and their ordering into `head` (room for `want` records; its pair - records, matches found -
+// in head_count).  Nothing is read back.
+static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n, size_t want, fzb_match_rec* head, u32* head_count, u32* raw_count, hipStream_t st) {
+    int rc;
+    if ((rc = fzb_sort_ensure(mm->sort, n))) return rc;
+    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st))) return rc;
+    const int sort = mm->config.sort;
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    const u32 ntiles_cap = (u32)(mm->sort.cap / 2048 + 2);
+    const int grid = mm->num_cus * 2;
+    // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
+    HIPCHK(fzb_launch_topk_select(mm->sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, 0, head, (u32)want, head_count, mm->sort.hist, ntiles_cap, grid, st));
+    fzb_launch_sort(head, mm->sort.tmp, head_count, mm->sort.hist, ntiles_cap, reversed, by_score, grid, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+extern "C" {
+
 int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -2785,18 +2815,7 @@ int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t 
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
     int rc;
-    if ((rc = fzb_out_ensure(*mm, want)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
-    u32* const raw_count = mm->count_dev + 4;
-    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, nullptr))) return rc;
-    const int sort = mm->config.sort;
-    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
-    const u32 ntiles_cap = (u32)(mm->sort.cap / 2048 + 2);
-    const int grid = mm->num_cus * 2;
-    // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
-    HIPCHK(fzb_launch_topk_select(mm->sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, 0, mm->out_dev, (u32)want, mm->count_dev, mm->sort.hist, ntiles_cap, grid, nullptr));
-    fzb_launch_sort(mm->out_dev, mm->sort.tmp, mm->count_dev, mm->sort.hist, ntiles_cap, reversed, by_score, grid, nullptr);
-    HIPCHK(hipGetLastError());
+    if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + 4, nullptr))) return rc;
     return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
 }
 
@@ -2829,6 +2848,14 @@ int ensure_top_indices_buffers(fzb_matcher* m, size_t want, size_t stride, bool 
     return fzb_grow_dev(&m->top_dense, &m->top_dense_words, want * stride, 1);
 }
 u32 trace_stride(const fzb_matcher* m) { return (u32)std::max(1, m->nd.nbytes); }  // position dwords per record: as indices_in_list_order
+// the traced scorer's matrices for heads of up to `want` records and needles of up to `stride` bytes: one (rows + 1) x TRACE_W slab per wave
+// of its grid; a needle of b bytes has at most b rows, and one the by-value NeedleDev holds at most FZB_MAX_ROWS (a longer needle's scratch
+// is its own: ensure_long_needle grows it on first use)
+int reserve_trace_cells(fzb_matcher* m, size_t want, size_t stride) {
+    NeedleDev probe = m->nd;
+    probe.rows = (int32_t)std::min<size_t>(stride, FZB_MAX_ROWS);
+    return ensure_trace_cells(m, fzb_trace_scratch_words(probe, traced_grid(m->lc.num_cus, want)));
+}
 
 // malloc'ed result of the *_indices entry points (fzb_match_indices_free): nrec records, npos positions, copied from `recs` / `pos`
 int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos, size_t npos, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
@@ -2844,6 +2871,72 @@ int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos
     *out = r;
     *out_len = nrec;
     *out_positions = p;
+    return FZB_OK;
+}
+
+// CompiledPatterns::Empty (an empty needle, no pattern): fzb_empty_pattern_top's rule - the first / last min(limit, n) indices, score 0 - and no
+// positions
+int empty_top_indices(size_t n, int sort, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    const size_t want = std::min(limit, n);
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    std::vector<fzb_match_indices> recs(want);
+    for (size_t i = 0; i < want; i++) recs[i] = fzb_match_indices{(uint32_t)(reversed ? n - 1 - i : i), 0, 0, 0, 0, 0};
+    if (out_found) *out_found = n;
+    return hand_over_indices(recs.data(), want, nullptr, 0, out, out_len, out_positions);
+}
+
+// The result of a fused query on the null stream -> the caller, with ONE wait for the four words (`words`), the records (`packed`) and the
+// packed positions (`dense`): a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind the words, filled or not (fzb_fetch_top's
+// rule), and so are its positions while they are no more than the records would be at that bound (256 KB); beyond, the copy takes the
+// previous result's size (*last_records, *last_positions) and a little more, and a result that outgrew it costs a second wait.
+// want / max_pos: the most records / positions the result can have.  `disagree`: what a raised inconsistency word means.
+int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32* dense, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions, const char* disagree,
+                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
+    const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(*last_records, want);
+    const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(*last_positions, max_pos);
+    u8* stage = (u8*)fzb_pinned_get(32 + grec * sizeof(fzb_match_indices) + gpos * 4);
+    if (!stage) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
+    const u32* const hw = (const u32*)stage;
+    const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + 32);
+    const u32* const hpos = (const u32*)(stage + 32 + grec * sizeof(fzb_match_indices));
+    hipError_t e = hipMemcpyAsync(stage, words, 16, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess) e = fzb_stream_wait(nullptr);
+    if (e != hipSuccess) {
+        fzb_pinned_put(stage);
+        return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
+    }
+    const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
+    if (hw[3]) {
+        const u32 why = hw[3];
+        fzb_pinned_put(stage);
+        return fail(FZB_ERR_HIP, std::string("internal: ") + disagree + " (" + ((why & 1u) ? "record count" : "a record's index, score or exact flag") + ")");
+    }
+    int rc = hand_over_indices(hrec, std::min(nrec, grec), hpos, std::min(npos, gpos), out, out_len, out_positions);
+    fzb_pinned_put(stage);
+    if (rc) return rc;
+    if (nrec > grec || npos > gpos) {  // the result outgrew the guess: the rest in a second copy, straight into the caller's arrays
+        fzb_match_indices* r = (fzb_match_indices*)realloc(*out, std::max<size_t>(nrec, 1) * sizeof(fzb_match_indices));
+        if (r) *out = r;
+        u32* p = r ? (u32*)realloc(*out_positions, std::max<size_t>(npos, 1) * 4) : nullptr;
+        if (p) *out_positions = p;
+        e = (r && p) ? hipSuccess : hipErrorOutOfMemory;
+        if (e == hipSuccess && nrec > grec) e = hipMemcpy(r + grec, (const fzb_match_indices*)packed + grec, (nrec - grec) * sizeof(fzb_match_indices), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && npos > gpos) e = hipMemcpy(p + gpos, dense + gpos, (npos - gpos) * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            fzb_match_indices_free(*out, *out_positions);
+            *out = nullptr;
+            *out_positions = nullptr;
+            *out_len = 0;
+            return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
+        }
+        *out_len = nrec;
+    }
+    *last_records = nrec;
+    *last_positions = npos;
+    if (out_found) *out_found = found;
     return FZB_OK;
 }
 }  // namespace
@@ -2891,69 +2984,15 @@ int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (m->empty) {  // fzb_empty_pattern_top's rule: the first / last min(limit, n) indices, score 0; no positions
-        const bool reversed = m->config.sort == FZB_SORT_INDEX_DESC || m->config.sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-        std::vector<fzb_match_indices> recs(want);
-        for (size_t i = 0; i < want; i++) recs[i] = fzb_match_indices{(uint32_t)(reversed ? n - 1 - i : i), 0, 0, 0, 0, 0};
-        if (out_found) *out_found = n;
-        return hand_over_indices(recs.data(), want, nullptr, 0, out, out_len, out_positions);
-    }
+    if (m->empty) return empty_top_indices(n, m->config.sort, limit, out, out_len, out_positions, out_found);
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     const size_t stride = trace_stride(m);
     int rc;
     if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
     u32* const words = m->top_idx_words + 4;
     if ((rc = fzb_match_list_top_indices_device(m, c, limit, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense, m->top_dense_words, words, nullptr))) return rc;
-    // ONE wait for the four words, the records and the packed positions: a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind
-    // the words, filled or not (fzb_fetch_top's rule), and so are its positions while they are no more than the records would be at that
-    // bound (256 KB); beyond, the copy takes the previous result's size and a little more, and a result that outgrew it costs a second wait
-    const size_t max_pos = want * stride;
-    auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
-    const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(m->top_last_records, want);
-    const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(m->top_last_positions, max_pos);
-    u8* stage = (u8*)fzb_pinned_get(32 + grec * sizeof(fzb_match_indices) + gpos * 4);
-    if (!stage) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
-    const u32* const hw = (const u32*)stage;
-    const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + 32);
-    const u32* const hpos = (const u32*)(stage + 32 + grec * sizeof(fzb_match_indices));
-    hipError_t e = hipMemcpyAsync(stage, words, 16, hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, m->top_packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, m->top_dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess) e = fzb_stream_wait(nullptr);
-    if (e != hipSuccess) {
-        fzb_pinned_put(stage);
-        return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
-    }
-    const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
-    if (hw[3]) {
-        const u32 why = hw[3];
-        fzb_pinned_put(stage);
-        return fail(FZB_ERR_HIP, std::string("internal: the traced pass disagrees with the top stage (") + ((why & 1u) ? "record count" : "a record's index, score or exact flag") + ")");
-    }
-    rc = hand_over_indices(hrec, std::min(nrec, grec), hpos, std::min(npos, gpos), out, out_len, out_positions);
-    fzb_pinned_put(stage);
-    if (rc) return rc;
-    if (nrec > grec || npos > gpos) {  // the result outgrew the guess: the rest in a second copy, straight into the caller's arrays
-        fzb_match_indices* r = (fzb_match_indices*)realloc(*out, std::max<size_t>(nrec, 1) * sizeof(fzb_match_indices));
-        if (r) *out = r;
-        u32* p = r ? (u32*)realloc(*out_positions, std::max<size_t>(npos, 1) * 4) : nullptr;
-        if (p) *out_positions = p;
-        e = (r && p) ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess && nrec > grec) e = hipMemcpy(r + grec, m->top_packed + grec, (nrec - grec) * sizeof(fzb_match_indices), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && npos > gpos) e = hipMemcpy(p + gpos, m->top_dense + gpos, (npos - gpos) * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            fzb_match_indices_free(*out, *out_positions);
-            *out = nullptr;
-            *out_positions = nullptr;
-            *out_len = 0;
-            return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
-        }
-        *out_len = nrec;
-    }
-    m->top_last_records = nrec;
-    m->top_last_positions = npos;
-    if (out_found) *out_found = found;
-    return FZB_OK;
+    return fetch_top_indices(words, m->top_packed, m->top_dense, want, want * stride, &m->top_last_records, &m->top_last_positions, "the traced pass disagrees with the top stage", out, out_len,
+                             out_positions, out_found);
 }
 
 // Sizes what fzb_matcher_reserve leaves to the first matched-indices query - item list, position counts, strided positions, the traced
@@ -2972,11 +3011,7 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
     // (the range workspace first: growing it releases every workspace buffer, the traced scorer's matrices included)
     if (!m->empty && (rc = ensure_workspace(m, n))) return rc;
     if ((rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
-    // the traced scorer's matrices: one (rows + 1) x TRACE_W slab per wave of its grid; a needle of b bytes has at most b rows, and one the
-    // by-value NeedleDev holds at most FZB_MAX_ROWS (a longer needle's scratch is its own: ensure_long_needle grows it on first use)
-    NeedleDev probe = m->nd;
-    probe.rows = (int32_t)std::min<size_t>(stride, FZB_MAX_ROWS);
-    return ensure_trace_cells(m, fzb_trace_scratch_words(probe, traced_grid(m->lc.num_cus, want)));
+    return reserve_trace_cells(m, want, stride);
 }
 
 // The `from_patterns` form, a host composition of the existing pieces: the multi top goes to the host, then the multi matched-indices
@@ -3014,6 +3049,150 @@ int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c,
         return fail(FZB_ERR_HIP, "internal: the matched-indices pass disagrees with the top stage");
     }
     return FZB_OK;
+}
+
+// ---- the `from_patterns` form fused on the device --------------------------------------------------------------------------------
+// The multi top stage leaves its sorted head in HBM (mm->top_head), k_top_items makes it ONE item list, every positive pattern's sub-matcher
+// runs the traced pipeline over that list into its own trace buffers (records in head order: every pattern accepts every haystack of the
+// head, which is what the composition selected), k_multi_union puts the patterns' records and positions together per head record
+// (indices_union.h: match_one_indices_multi, src/matcher/multi.rs:56-82) and the pack kernels write the caller's result while holding the
+// combined records to the head.  Negated patterns are not traced: the head holds no haystack they hit.  Nothing is read back in between.
+// CompiledPatterns::Single takes the same path with one source: its sub-matcher runs IndexAsc and owns neither sort buffers nor staging, so
+// the ordering is the multi top stage's here too.
+}  // extern "C"
+namespace {
+// positive patterns and U = the union's stride: every pattern's positions side by side
+size_t multi_union_stride(const fzb_multi_matcher* mm, size_t* positive) {
+    size_t U = 0, P = 0;
+    for (const auto& p : mm->patterns)
+        if (!p.negated) {
+            U += trace_stride(p.m);
+            P++;
+        }
+    if (positive) *positive = P;
+    return U;
+}
+// the composition's own buffers of a fused query: a head of up to `want` records, unions of U dwords, P sources; staging: the host form's too
+int ensure_multi_top_indices_buffers(fzb_multi_matcher* mm, size_t want, size_t U, size_t P, bool staging) {
+    int rc;
+    if (!mm->top_words) HIPCHK(dev_alloc((void**)&mm->top_words, 64));
+    if (!mm->top_head || !mm->top_comb || !mm->top_items || !mm->top_npos_u || !mm->top_tiles || mm->top_cap < want) {
+        mm->top_cap = 0;
+        if ((rc = fzb_dev_renew(&mm->top_head, want + 16)) || (rc = fzb_dev_renew(&mm->top_comb, want + 16)) || (rc = fzb_dev_renew(&mm->top_items, want + 4)) ||
+            (rc = fzb_dev_renew(&mm->top_npos_u, want + 4)) || (rc = fzb_dev_renew(&mm->top_tiles, fzb_indices_pack_tile_words(want))))
+            return rc;
+        mm->top_cap = want;
+    }
+    if ((rc = fzb_grow_dev(&mm->top_pos_u, &mm->top_pos_u_words, want * U, 1))) return rc;
+    if (P > IUNION_BY_VALUE) {
+        if (!mm->union_src || mm->union_src_cap < P) mm->union_src_host.clear();  // (a new array holds nothing yet)
+        if ((rc = fzb_grow_dev(&mm->union_src, &mm->union_src_cap, P)) || (rc = fzb_grow_dev(&mm->union_cursors, &mm->union_cursor_words, want * P, 1))) return rc;
+    }
+    if (!staging) return FZB_OK;
+    if ((rc = fzb_grow_dev(&mm->top_packed, &mm->top_packed_cap, want, 1))) return rc;
+    return fzb_grow_dev(&mm->top_dense, &mm->top_dense_words, want * U, 1);
+}
+bool same_union_src(const IUnionSrc& a, const IUnionSrc& b) { return a.rec == b.rec && a.count == b.count && a.npos == b.npos && a.pos == b.pos && a.stride == b.stride; }
+}  // namespace
+extern "C" {
+
+int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                            size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    if (!mm || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_indices_fused");
+    size_t P = 0;
+    const size_t U = multi_union_stride(mm, &P);
+    if (positions_capacity < want * U)
+        return fail(FZB_ERR_CAPACITY, "positions buffer smaller than min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(want * U));
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if ((u64)want * U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
+        return FZB_OK;
+    }
+    // every buffer first: the sources of the union are final before anything is launched
+    int rc;
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, false))) return rc;
+    std::vector<IUnionSrc> src;
+    src.reserve(P);
+    for (auto& p : mm->patterns) {
+        if (p.negated) continue;
+        fzb_matcher* m = p.m;
+        if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
+        src.push_back(IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0});
+    }
+    if (P > IUNION_BY_VALUE) {
+        bool same = mm->union_src_host.size() == P;
+        for (size_t i = 0; same && i < P; i++) same = same_union_src(mm->union_src_host[i], src[i]);
+        if (!same) {  // (a pattern or a buffer changed since the array was written: ahead of the first launch, ordered on the stream)
+            mm->union_src_host = src;
+            HIPCHK(hipMemcpyAsync(mm->union_src, mm->union_src_host.data(), P * sizeof(IUnionSrc), hipMemcpyHostToDevice, st));
+        }
+    }
+    u32* const head_count = mm->top_words;      // (records, matches found) of the head
+    u32* const comb_count = mm->top_words + 2;  // the combined traced pair
+    u32* const n_items = mm->top_words + 10;
+    if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 8, st))) return rc;
+    const int grid = mm->num_cus * 2;
+    fzb_launch_top_items(mm->top_head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
+    for (auto& p : mm->patterns) {
+        if (p.negated) continue;
+        fzb_matcher* m = p.m;
+        const TraceOut tr{m->trace_pos, m->trace_npos, trace_stride(m)};
+        if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
+    }
+    fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)P, mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, grid, st);
+    fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
+int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (mm->patterns.empty()) return empty_top_indices(n, mm->config.sort, limit, out, out_len, out_positions, out_found);  // CompiledPatterns::Empty
+    if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
+    size_t P = 0;
+    const size_t U = multi_union_stride(mm, &P);
+    if ((u64)want * U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    int rc;
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, true))) return rc;
+    u32* const words = mm->top_words + 4;
+    if ((rc = fzb_multi_match_list_top_indices_device(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr))) return rc;
+    return fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out,
+                             out_len, out_positions, out_found);
+}
+
+// fzb_matcher_reserve_top_indices for the composition: every sub-matcher slot (the spares too) gets the trace buffers and the traced scorer's
+// matrices for heads of up to min(limit, haystacks the corpus has room for) records and needles of up to max_needle_bytes bytes; the
+// composition gets its head, item list, combined records, the unions for U = slots x max_needle_bytes and the host form's staging.
+int fzb_multi_matcher_reserve_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, size_t max_needle_bytes) {
+    if (!mm || !c) return fail(FZB_ERR_INVALID, "null argument");
+    const size_t n = fzb_corpus_reserved_items(c);
+    const size_t want = std::min(limit, n);
+    if (want == 0) return FZB_OK;
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    std::vector<fzb_matcher*> slots;
+    for (auto& p : mm->patterns) slots.push_back(p.m);
+    slots.insert(slots.end(), mm->spare.begin(), mm->spare.end());
+    size_t stride = std::max<size_t>(max_needle_bytes, 1);
+    for (fzb_matcher* m : slots) stride = std::max<size_t>(stride, trace_stride(m));
+    const size_t U = slots.size() * stride;
+    if ((u64)want * U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    int rc;
+    for (fzb_matcher* m : slots)
+        if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false)) || (rc = reserve_trace_cells(m, want, stride))) return rc;
+    return ensure_multi_top_indices_buffers(mm, want, U, slots.size(), true);
 }
 
 void fzb_matches_free(fzb_match* p) {

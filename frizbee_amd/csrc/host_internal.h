@@ -11,6 +11,7 @@
 
 #include "../../include/frizbee_hip.h"
 #include "fzb_internal.h"
+#include "indices_union.h"
 #include "knobs.h"
 
 // error state of the calling thread (fzb_last_error) + the usual early return
@@ -217,6 +218,31 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     u64* bitmap = nullptr;
     u32* tile_counts = nullptr;
     SortBuffers sort{};  // ordering of the synchronous entry points
+    // fzb_multi_match_list_top_indices_device / _fused: for heads of up to `top_cap` records - the multi top stage's sorted head, the item
+    // list every positive pattern traces (one list, shared), the combined records and union lengths k_multi_union writes, the pack's tile
+    // sums; `top_words`: [0..1] head pair, [2..3] combined pair, [4..7] the host form's four result words, [8..9] the composition's pair,
+    // [10] the item list's length.  `top_pos_u`: the strided unions (U per record).  Beyond IUNION_BY_VALUE positive patterns the union
+    // kernel reads its sources from `union_src` (what it holds: `union_src_host`; written again only when a pattern or a buffer changed,
+    // ahead of the query's first launch) and keeps its cursors in `union_cursors`.  Then the host form's packed staging and what its
+    // previous result held, as MatcherState's.
+    fzb_match_rec* top_head = nullptr;
+    fzb_match_rec* top_comb = nullptr;
+    u32* top_items = nullptr;
+    u32* top_npos_u = nullptr;
+    u32* top_tiles = nullptr;
+    u32* top_words = nullptr;
+    size_t top_cap = 0;
+    u32* top_pos_u = nullptr;
+    size_t top_pos_u_words = 0;
+    IUnionSrc* union_src = nullptr;
+    size_t union_src_cap = 0;
+    std::vector<IUnionSrc> union_src_host;
+    u32* union_cursors = nullptr;
+    size_t union_cursor_words = 0;
+    fzb_indices_rec* top_packed = nullptr;
+    u32* top_dense = nullptr;
+    size_t top_packed_cap = 0, top_dense_words = 0;
+    size_t top_last_records = 0, top_last_positions = 0;
     // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]

@@ -13,8 +13,12 @@
 //   * a longer head takes three launches, as the selection stage does (kernels_topk.hip): per-tile sums, their exclusive scan (one wave),
 //     and the same scatter kernel with every tile starting at its scanned base.  No workgroup waits for another one, nothing is ordered by
 //     an atomic.
+// The multi-pattern form (fzb_multi_match_list_top_indices_device) traces every positive pattern over the one item list and puts a step
+// between those passes and the pack: k_multi_union merges the patterns' records and positions per head record (indices_union.h says how),
+// and the pack then sees one traced pass with a stride of U.
 #include "kernels_common.h"
 #include "indices_pack.h"
+#include "indices_union.h"
 
 #define IPACK_THREADS (IPACK_TILE / IPACK_SHARE)
 static_assert(IPACK_THREADS == 256, "four waves scan a tile");
@@ -158,6 +162,71 @@ __global__ __launch_bounds__(IPACK_THREADS) void k_ipack_scatter(const PackArgs 
         __syncthreads();  // (s_begin is written again by the next tile)
     }
     if (bad) a.dev_count[3] = bad;  // (k_top_items cleared it; every writer stores a non-zero word)
+}
+
+static_assert(sizeof(IUnionRec) == sizeof(fzb_match_rec) && offsetof(IUnionRec, score) == offsetof(fzb_match_rec, score) && offsetof(IUnionRec, exact) == offsetof(fzb_match_rec, exact),
+              "indices_union.h reads and writes fzb_match_rec");
+
+struct UnionArgs {
+    const fzb_match_rec* head;  // the sorted head, its pair (records, matches found) and the records it has room for
+    const u32* head_count;
+    u32 cap;
+    u32 P;                      // positive patterns
+    IUnionSrc src[IUNION_BY_VALUE];  // their traced passes (P <= IUNION_BY_VALUE) ..
+    const IUnionSrc* more;      // .. or all P of them in device memory, with P cursors per record of the head
+    u32* cursors;
+    fzb_match_rec* out;         // the combined records and their pair; per record the union's length and, at pos_u[k * U ..], the union
+    u32* out_count;
+    u32* npos_u;
+    u32* pos_u;
+    u32 U;
+};
+
+// One thread per head record: a few dependent loads per position, no reuse between threads - latency-bound glue between the traced passes and
+// the pack.  BY_VALUE: the sources are read from the argument block (wave-uniform scalar loads) and the cursors are the thread's own.
+template <bool BY_VALUE>
+__global__ __launch_bounds__(256) void k_multi_union(const UnionArgs a) {
+    const u32 n = min(a.head_count[0], a.cap);
+    const IUnionSrc* const src = BY_VALUE ? a.src : a.more;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.out_count[0] = iunion_count(src, a.P, a.head_count[0]);
+        a.out_count[1] = a.head_count[1];
+    }
+    for (u32 k = blockIdx.x * 256u + threadIdx.x; k < n; k += gridDim.x * 256u) {
+        const IUnionRec r = iunion_record(src, a.P, k, a.head[k].index);
+        fzb_match_rec o;
+        o.index = r.index;
+        o.score = r.score;
+        o.exact = r.exact;
+        o.valid = 0;
+        a.out[k] = o;
+        u32 own[IUNION_BY_VALUE];
+        u32* const cur = BY_VALUE ? own : a.cursors + (size_t)k * a.P;
+        a.npos_u[k] = iunion_merge(src, a.P, k, cur, a.pos_u + (size_t)k * a.U, a.U);
+    }
+}
+
+// src: P sources in host memory (copied into the argument block while P <= IUNION_BY_VALUE); src_dev / cursors: the same P sources and
+// max_records x P words in device memory, read only beyond that
+void fzb_launch_multi_union(const fzb_match_rec* head, const u32* head_count, u32 max_records, const IUnionSrc* src, u32 P, const IUnionSrc* src_dev, u32* cursors, fzb_match_rec* out,
+                            u32* out_count, u32* npos_u, u32* pos_u, u32 U, int grid, hipStream_t st) {
+    UnionArgs a{};
+    a.head = head;
+    a.head_count = head_count;
+    a.cap = max_records;
+    a.P = P;
+    const bool by_value = P <= IUNION_BY_VALUE;
+    for (u32 p = 0; by_value && p < P; p++) a.src[p] = src[p];
+    a.more = src_dev;
+    a.cursors = cursors;
+    a.out = out;
+    a.out_count = out_count;
+    a.npos_u = npos_u;
+    a.pos_u = pos_u;
+    a.U = U;
+    const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, (max_records + 255) / 256));
+    if (by_value) hipLaunchKernelGGL((k_multi_union<true>), dim3(g), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_multi_union<false>), dim3(g), dim3(256), 0, st, a);
 }
 
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st) {

@@ -449,9 +449,33 @@ int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, con
  * returns over the whole list for `Matcher::from_patterns` (src/matcher/mod.rs:234-275).  A HOST composition of the existing pieces:
  * fzb_multi_match_list_top brings the head to the host, fzb_multi_match_list_indices' implementation then runs in list order over that
  * selection and `index` is mapped back to the corpus index; the head is already in order, so nothing is re-ordered.  (The per-haystack
- * union of the patterns' positions stays host work; a device-fused multi form, the sharded and the RCCL forms are not built.) */
+ * union of the patterns' positions stays host work in this call; the sharded and the RCCL forms are not built.) */
 int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions,
                                      uint64_t* out_found);
+/* (The device-fused form of that call is fzb_multi_match_list_top_indices_fused below; the one above remains the portable host composition.)
+ *
+ * THE SAME QUERY FUSED ON THE DEVICE.  fzb_multi_match_list_top_indices_device is fzb_match_list_top_indices_device for a `from_patterns`
+ * matcher - same contract, same four count words (records written, matches found, positions written, 0 or why the passes disagree) - with
+ * positions_capacity >= min(limit, haystacks) x U, U = the sum over the NON-NEGATED patterns of max(1, needle bytes).  Asynchronous on
+ * `stream`, no host synchronisation: the multi top stage leaves its sorted head in HBM, one item list is made of it, every non-negated
+ * pattern runs the traced pipeline over that list (negated patterns are not traced: the head holds no haystack they hit), one kernel puts
+ * the patterns' records and positions together per head record - `match_one_indices_multi`, src/matcher/multi.rs:56-82: scores add with
+ * saturation, exact flags OR, positions merged descending without repeats - and the pack step of the single-needle form writes the result
+ * while holding the combined records to the head.  A matcher with no compiled pattern (CompiledPatterns::Empty) is refused with
+ * FZB_ERR_INVALID - the host form answers it -, an empty corpus zeroes the four words.  The sharded and the RCCL forms are not built. */
+int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                            size_t positions_capacity, uint32_t* dev_count, void* stream);
+/* The host form: the call above into the matcher's staging, then ONE wait for the words, the records and the positions (as
+ * fzb_match_list_top_indices).  Result and contract as fzb_multi_match_list_top_indices; a disagreement between the passes is FZB_ERR_HIP
+ * "internal: ...". */
+int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions,
+                                           uint64_t* out_found);
+/* After fzb_multi_matcher_reserve(mm, c) and this call, no fzb_multi_match_list_top_indices_fused / _device call with this `limit` or a
+ * smaller one allocates device memory - also across fzb_multi_matcher_set_patterns / _set_config that do not raise the number of compiled
+ * patterns above the slots held, while every needle has at most max_needle_bytes bytes.  Sizes the head, the item list, every slot's trace
+ * buffers and traced scorer's matrices (spare slots included), the unions for U = slots x max_needle_bytes and the host form's staging.
+ * The exceptions of fzb_matcher_reserve_top_indices apply (a needle beyond 64 bytes / 63 rows, another scoring or lane pair). */
+int fzb_multi_matcher_reserve_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, size_t max_needle_bytes);
 /* list-order forms (see fzb_match_list_into / fzb_match_list_indices_into): `Matcher::match_list_into` over CompiledPatterns
  * (src/matcher/mod.rs:373-392) with the result on the host, and what `match_iter` / `match_one` / `match_iter_indices` yield
  * (`match_one_multi`, `match_one_indices_multi`, src/matcher/multi.rs:29-82) */

@@ -361,14 +361,16 @@ class Matcher {  // src/matcher/mod.rs:77-222
 
     // The first min(limit, found) entries of `match_list_indices(&haystacks)` over the whole list (src/matcher/mod.rs:234-275; the
     // reference's caller truncates the Vec), `index` = the corpus index: fzb_match_list_top_indices - the top stage, a traced pass over its
-    // head and the packing of the positions in one device call with one host wait - or fzb_multi_match_list_top_indices (a host composition).
+    // head and the packing of the positions in one device call with one host wait - or fzb_multi_match_list_top_indices_fused, the same for
+    // `from_patterns` with one traced pass per non-negated pattern and the union of their positions on the device (the host composition
+    // fzb_multi_match_list_top_indices stays in the C ABI).
     std::vector<MatchIndices> match_list_top_indices(const Corpus& corpus, size_t limit, size_t* found = nullptr) {
         fzb_match_indices* out = nullptr;
         uint32_t* pos = nullptr;
         size_t n = 0;
         uint64_t f = 0;
         if (single_) check(fzb_match_list_top_indices(single_.get(), corpus.raw(), limit, &out, &n, &pos, &f));
-        else check(fzb_multi_match_list_top_indices(multi_.get(), corpus.raw(), limit, &out, &n, &pos, &f));
+        else check(fzb_multi_match_list_top_indices_fused(multi_.get(), corpus.raw(), limit, &out, &n, &pos, &f));
         if (found) *found = (size_t)f;
         std::vector<MatchIndices> v(n);
         for (size_t i = 0; i < n; i++)
@@ -378,16 +380,18 @@ class Matcher {  // src/matcher/mod.rs:77-222
     }
     template <typename Strings>
     std::vector<MatchIndices> match_list_top_indices(const Strings& haystacks, size_t limit, size_t* found = nullptr) { return match_list_top_indices(Corpus(haystacks), limit, found); }
-    // the same left in HBM, asynchronous on `stream` (single-pattern matchers): see fzb_match_list_top_indices_device for the four count words
+    // the same left in HBM, asynchronous on `stream`: see fzb_match_list_top_indices_device for the four count words, and
+    // fzb_multi_match_list_top_indices_device for the positions a `from_patterns` matcher needs room for
     void match_list_top_indices_device(const Corpus& corpus, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
                                        uint32_t* dev_count, void* stream = nullptr) {
-        if (!single_) throw Error(FZB_ERR_INVALID, "match_list_top_indices_device: single-pattern matchers only");
-        check(fzb_match_list_top_indices_device(single_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
+        if (single_) check(fzb_match_list_top_indices_device(single_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
+        else check(fzb_multi_match_list_top_indices_device(multi_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
     }
     // after reserve-ing the matcher for the corpus: no match_list_top_indices call with this limit or a smaller one, on a needle of up to
-    // max_needle_bytes bytes, allocates device memory (single-pattern matchers; a no-op for the host-composed multi-pattern form)
+    // max_needle_bytes bytes, allocates device memory (`from_patterns`: while set_patterns / set_config add no pattern slot)
     void reserve_top_indices(const Corpus& corpus, size_t limit, size_t max_needle_bytes) {
         if (single_) check(fzb_matcher_reserve_top_indices(single_.get(), corpus.raw(), limit, max_needle_bytes));
+        else check(fzb_multi_matcher_reserve_top_indices(multi_.get(), corpus.raw(), limit, max_needle_bytes));
     }
 
     // `match_list_indices(&haystacks)` (src/matcher/mod.rs:234-275; multi-pattern: match_one_indices_multi, multi.rs:56-82).

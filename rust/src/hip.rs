@@ -162,6 +162,11 @@ extern "C" {
     fn fzb_multi_match_list_top(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_multi_match_list_top_indices(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize, out_positions: *mut *mut u32,
                                         out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_indices_fused(mm: *mut c_void, c: *const c_void, limit: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
+                                              out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_indices_device(mm: *mut c_void, c: *const c_void, limit: usize, dev_out: *mut FzbMatchIndices, capacity: usize, dev_positions: *mut u32,
+                                               positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_multi_matcher_reserve_top_indices(mm: *mut c_void, c: *const c_void, limit: usize, max_needle_bytes: usize) -> c_int;
     fn fzb_multi_match_list_top_sharded(mm: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_multi_matcher_shard_report(mm: *const c_void) -> *const c_char;
 }
@@ -553,12 +558,36 @@ impl HipMultiMatcher {
         (v, found as usize)
     }
 
-    /// `MatcherHip::match_list_top_indices` for `from_patterns`: a host composition - the multi top, then the multi matched-indices pass in
-    /// list order over that head (already in order: nothing is re-ordered), `index` mapped back to the corpus index.
+    /// `MatcherHip::match_list_top_indices` for `from_patterns`, fused on the device with one host wait: the multi top stage, one traced
+    /// pass per non-negated pattern over its head, the union of their positions (`match_one_indices_multi`) and the pack.
     pub fn match_list_top_indices(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<MatchIndices>, usize) {
+        let (mut out, mut n, mut pos, mut found) = (std::ptr::null_mut(), 0usize, std::ptr::null_mut(), 0u64);
+        check(unsafe { fzb_multi_match_list_top_indices_fused(self.handle, corpus.handle, limit, &mut out, &mut n, &mut pos, &mut found) });
+        (take_indices(out, n, pos), found as usize)
+    }
+
+    /// The same as a host composition - the multi top, then the multi matched-indices pass in list order over that head (already in order:
+    /// nothing is re-ordered), `index` mapped back to the corpus index: P + 1 round trips, no device-side union.
+    pub fn match_list_top_indices_host_composed(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<MatchIndices>, usize) {
         let (mut out, mut n, mut pos, mut found) = (std::ptr::null_mut(), 0usize, std::ptr::null_mut(), 0u64);
         check(unsafe { fzb_multi_match_list_top_indices(self.handle, corpus.handle, limit, &mut out, &mut n, &mut pos, &mut found) });
         (take_indices(out, n, pos), found as usize)
+    }
+
+    /// `MatcherHip::match_list_top_indices_device` for `from_patterns`: `positions_capacity >= min(limit, len) x U`, U = the needle bytes of
+    /// the non-negated patterns together; four count words at `dev_count`.  Asynchronous on `stream`.
+    ///
+    /// # Safety
+    /// The three device pointers must be valid for the capacities given, on the device the corpus lives on.
+    pub unsafe fn match_list_top_indices_device(&mut self, corpus: &HipCorpus, limit: usize, dev_out: *mut c_void, capacity: usize, dev_positions: *mut u32,
+                                                positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) {
+        check(fzb_multi_match_list_top_indices_device(self.handle, corpus.handle, limit, dev_out as *mut FzbMatchIndices, capacity, dev_positions, positions_capacity, dev_count, stream));
+    }
+
+    /// After `reserve`: no `match_list_top_indices` call with this `limit` or a smaller one allocates device memory, also across
+    /// `set_patterns` / `set_config` that add no pattern slot and keep every needle within `max_needle_bytes` bytes.
+    pub fn reserve_top_indices(&mut self, corpus: &HipCorpus, limit: usize, max_needle_bytes: usize) {
+        check(unsafe { fzb_multi_matcher_reserve_top_indices(self.handle, corpus.handle, limit, max_needle_bytes) });
     }
 
     /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
