@@ -126,6 +126,7 @@ SYMBOLS = [
     "fzb_match_list_top_indices", "fzb_match_list_top_indices_device", "fzb_matcher_reserve_top_indices", "fzb_multi_match_list_top_indices",
     "fzb_multi_match_list_top_indices_device", "fzb_multi_match_list_top_indices_fused", "fzb_multi_matcher_reserve_top_indices",
     "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold",
+    "fzb_corpus_set_bias", "fzb_corpus_update_bias", "fzb_corpus_clear_bias", "fzb_corpus_bias_info",
 ]
 
 
@@ -236,6 +237,10 @@ def lib():
         l.fzb_debug_needle_signature.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         l.fzb_debug_signature_threshold.argtypes = []
         l.fzb_debug_signature_threshold.restype = C.c_uint32
+        l.fzb_corpus_set_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_update_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_clear_bias.argtypes = [C.c_void_p]
+        l.fzb_corpus_bias_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         _lib = l
     return _lib
 
@@ -363,7 +368,40 @@ class Corpus:
     INFO_FIELDS = ("items", "item_capacity", "bytes", "byte_capacity", "max_len", "uniform_len", "has_view", "view_nv", "outliers", "ends_u64", "regrows",
                    "h2d_bytes")
     DEBUG_ARRAYS = {"bytes": (0, np.uint8), "ends": (1, None), "vbytes": (2, np.uint8), "vgofs": (3, np.uint32), "vgnv": (4, np.uint8), "vlen": (5, np.uint16),
-                    "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32)}
+                    "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32), "bias": (9, np.int16)}
+
+    def set_bias(self, values):
+        """fzb_corpus_set_bias: one int16 per haystack (len(values) == len(self)), added to every record's score on the device before
+        anything selects or orders - reported score = clamp(score + bias[index], 0, 65535).  `None` = fzb_corpus_clear_bias: the corpus
+        answers as before any bias.  The bias belongs to the list: it survives set_pattern and follows append / truncate / remove / replace."""
+        if values is None:
+            _check(lib().fzb_corpus_clear_bias(self.h))
+            return
+        v = np.asarray(values)
+        if v.size and (v.min() < -32768 or v.max() > 32767):
+            raise FrizbeeError(1, "Corpus.set_bias: a bias is a signed 16-bit value")
+        v = np.ascontiguousarray(v, dtype=np.int16)
+        _check(lib().fzb_corpus_set_bias(self.h, v.ctypes.data if len(v) else None, len(v)))
+
+    def update_bias(self, indices, values):
+        """fzb_corpus_update_bias: bias[indices[k]] = values[k] (unique indices in range; what a picker does when a file is opened).  A
+        corpus without a bias gets an all-zero one first."""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        v = np.asarray(values)
+        if v.size and (v.min() < -32768 or v.max() > 32767):
+            raise FrizbeeError(1, "Corpus.update_bias: a bias is a signed 16-bit value")
+        v = np.ascontiguousarray(v, dtype=np.int16)
+        if len(ix) != len(v):
+            raise FrizbeeError(1, f"Corpus.update_bias: {len(ix)} indices for {len(v)} values")
+        _check(lib().fzb_corpus_update_bias(self.h, ix.ctypes.data if len(ix) else None, v.ctypes.data if len(v) else None, len(ix)))
+
+    BIAS_INFO_FIELDS = ("has_bias", "capacity", "bias_hi", "device_bytes")
+
+    def bias_info(self):
+        """fzb_corpus_bias_info as a dict (BIAS_INFO_FIELDS)."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_corpus_bias_info(self.h, out))
+        return dict(zip(self.BIAS_INFO_FIELDS, (int(x) for x in out)))
 
     def signature_info(self):
         """fzb_corpus_signature_info: (built, bytes) - whether the corpus has letter signatures and their size in device memory."""

@@ -251,6 +251,8 @@ void fzb_launch_concat_runs(const RunSet& rs, const u32* base_in, u32* total_out
 hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, u32 in_cap, u32 limit, int by_score, int desc, int one_pass, fzb_match_rec* out, u32 out_cap,
                             u32* out_count, u32* scratch, u32 ntiles_cap, int grid, hipStream_t st);
 void fzb_launch_topk_concat(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, hipStream_t st);
+// the corpus' score bias (score_bias.h) added to index-ordered records: haystack = first + (index - index_offset); the grid is sized from cap, trimmed by count[0]
+void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st);
 // kernels_indices.hip: the glue of the fused top + matched-positions query (item list from the sorted head; packing of the traced positions)
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st);
 size_t fzb_indices_pack_tile_words(size_t max_records);

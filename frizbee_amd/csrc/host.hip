@@ -27,6 +27,7 @@
 
 #include "host_internal.h"
 #include "sig_filter.h"
+#include "score_bias.h"
 
 namespace {
 #include "unicode_case_table.inc"
@@ -980,6 +981,8 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_bytes) (void)hipFree(c->own_bytes);
     if (c->own_ends) (void)hipFree(c->own_ends);
     if (c->own_sig) (void)hipFree(c->own_sig);
+    if (c->own_bias) (void)hipFree(c->own_bias);
+    if (c->bias_stage) (void)hipFree(c->bias_stage);
     for (void* q : c->own_view)
         if (q) (void)hipFree(q);
     for (void* q : {c->stage_raw, c->stage_ends, c->stage_tiles, c->stage_stats})
@@ -1162,6 +1165,50 @@ int fzb_out_ensure(OutStaging& o, size_t count) {  // device-side result of the 
     if (int rc = fzb_dev_renew(&o.out_dev, count + 16)) return rc;
     o.out_cap = count;
     if (!o.count_dev) HIPCHK(fzb_dev_alloc((void**)&o.count_dev, 64));
+    return FZB_OK;
+}
+
+// ---- the corpus' per-haystack score bias on the query path (score_bias.h; the corpus side is host_upload.hip) --------------------------
+// The ONE helper that launches k_bias_apply: index-ordered records (up to `cap`, count[0] written) of the range that starts at haystack
+// `first`, numbered from index_offset.  Called where such records are final and before anything selects or orders them; nothing is
+// launched for a corpus without a bias.
+static int apply_bias(const fzb_corpus* c, fzb_match_rec* recs, const u32* count, size_t cap, size_t first, uint32_t index_offset, int grid_max, hipStream_t st) {
+    const int16_t* bias = fzb_corpus_bias(c);
+    if (!bias || !cap) return FZB_OK;
+    fzb_launch_bias_apply(recs, count, (u32)std::min<size_t>(cap, 0xFFFFFFFFu), bias, c->dev.n, first, index_offset, grid_max, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+// "returns biased scores or refuses": the entry points that cannot add the bias say so instead of ignoring it
+int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead) {
+    if (!c || !fzb_corpus_bias(c)) return FZB_OK;
+    return fail(FZB_ERR_INVALID, std::string(call) + ": the corpus carries a score bias, which this call does not apply; use " + instead + ", or fzb_corpus_clear_bias first");
+}
+// entries [first, first + count) of the bias on the host (one device-to-host copy)
+static int fetch_bias(const fzb_corpus* c, size_t first, size_t count, std::vector<int16_t>& out) {
+    out.assign(count, 0);
+    if (count) HIPCHK(hipMemcpy(out.data(), fzb_corpus_bias(c) + first, count * sizeof(int16_t), hipMemcpyDeviceToHost));
+    return FZB_OK;
+}
+// CompiledPatterns::Empty (an empty needle, no pattern) over a BIASED corpus - the picker's empty prompt, "most frecent first": every haystack
+// of [first, first + count) matches with score clamp(bias, 0, 65535), and - unlike the reference's unsorted empty result - the list is ordered
+// per `sort` (reverse for the *Desc strategies, then the stable descending sort by score for the Score* ones), cut to `limit` records.
+// Host work: one copy of the bias and the host's stable sort.  *out: malloc'ed (fzb_matches_free); *out_found (optional) = count.
+static int biased_empty_list(const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    std::vector<int16_t> hb;
+    if (int rc = fetch_bias(c, first, count, hb)) return rc;
+    std::vector<fzb_match> recs(count);
+    for (size_t i = 0; i < count; i++) recs[i] = fzb_match{(uint32_t)(index_offset + i), (uint16_t)sbias_clamp_add(0, hb[i]), 0, 0};
+    if (sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC) std::reverse(recs.begin(), recs.end());
+    if (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC)
+        std::stable_sort(recs.begin(), recs.end(), [](const fzb_match& a, const fzb_match& b) { return a.score > b.score; });
+    const size_t keep = std::min(limit, count);
+    fzb_match* r = (fzb_match*)malloc(std::max<size_t>(keep, 1) * sizeof(fzb_match));
+    if (!r) return fail(FZB_ERR_INVALID, "out of memory");
+    if (keep) memcpy(r, recs.data(), keep * sizeof(fzb_match));
+    *out = r;
+    *out_len = keep;
+    if (out_found) *out_found = count;
     return FZB_OK;
 }
 extern "C" {
@@ -1781,7 +1828,9 @@ extern "C" {
 
 int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                           uint32_t* dev_count, void* stream) {
-    return run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
+    int rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
+    if (rc) return rc;
+    return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
 }
 
 int fzb_match_list_sorted_device(fzb_matcher* m, const fzb_corpus* c, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
@@ -1801,7 +1850,8 @@ int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, s
     int rc;
     // (the range workspace first: growing it releases every workspace buffer, the sort's included)
     if (!m->empty && count != 0 && ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, count, (hipStream_t)stream, true)))) return rc;
-    if ((rc = fzb_order_begin(m, m->empty || count == 0 ? 0 : cap, (fzb_match_rec*)dev_out, &plan))) return rc;
+    if ((rc = fzb_order_begin(m, m->empty || count == 0 ? 0 : cap, (fzb_match_rec*)dev_out, &plan, fzb_corpus_bias_hi(c)))) return rc;
+    // (the public call: the pipeline and, on a biased corpus, the bias pass over the index-ordered records - before anything orders them)
     rc = fzb_match_list_device(m, c, first, count, index_offset, (fzb_match*)plan.in, plan.via_tmp ? cap : capacity, dev_count, stream);
     if (rc) return rc;
     if (count == 0) return FZB_OK;
@@ -1815,15 +1865,17 @@ int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, s
 // read from device memory.  Producers: the pipeline (above), the concatenation of per-shard runs (host_shard.hip).
 // What `match_list`'s post-step does for this matcher: the ONE place that decides it (fzb_order_begin and the top-`limit` selection both ask here - a
 // `one_pass` that is wrongly true would make the selection read the low byte only)
-void fzb_order_flags(const fzb_matcher* m, bool* reversed, bool* by_score, bool* one_pass) {
+// bias_hi: the upper bound of the corpus' largest positive score bias (fzb_corpus_bias_hi; 0 for callers without a corpus)
+void fzb_order_flags(const fzb_matcher* m, u32 bias_hi, bool* reversed, bool* by_score, bool* one_pass) {
     const int sort = m->config.sort;
     *reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;          // src/matcher/mod.rs:215-217
     *by_score = sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;  // :218-220
     // one radix pass is enough when no score can reach 256 (Scoring::guard's bound on the matrix + the exact-match bonus added after it)
-    *one_pass = !m->sum_scores && !m->literal_mode && max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus < 256;
+    // - nor, on a biased corpus, the largest positive bias on top of it (score_bias.h)
+    *one_pass = !m->sum_scores && !m->literal_mode && sbias_one_pass(max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus, bias_hi);
 }
-int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p) {
-    fzb_order_flags(m, &p->reversed, &p->by_score, &p->one_pass);
+int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p, u32 bias_hi) {
+    fzb_order_flags(m, bias_hi, &p->reversed, &p->by_score, &p->one_pass);
     p->via_tmp = p->by_score && p->one_pass && cap != 0;
     p->in = dev_out;
     if (p->by_score) {
@@ -1959,6 +2011,7 @@ int fzb_match_list_into(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
         return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
     *out = nullptr;
     *out_len = 0;
+    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, first, count, index_offset, FZB_SORT_INDEX_ASC, count, out, out_len, nullptr);
     if (m->empty) {  // src/matcher/mod.rs:381-384
         fzb_match* r = (fzb_match*)malloc(std::max<size_t>(count, 1) * sizeof(fzb_match));
         if (!r) return fail(FZB_ERR_INVALID, "out of memory");
@@ -1993,6 +2046,7 @@ void fzb_radix_sort_matches(fzb_match* matches, size_t n) {  // src/sort.rs:6-40
 int fzb_match_list(fzb_matcher* m, const fzb_corpus* c, fzb_match** out, size_t* out_len) {
     if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     const int sort = m->config.sort;
+    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, 0, c->dev.n, 0, sort, c->dev.n, out, out_len, nullptr);  // the empty prompt: ordered by the bias
     if (m->empty) {  // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
         int rc = fzb_match_list_into(m, c, 0, c->dev.n, 0, out, out_len);
         if (rc) return rc;
@@ -2047,11 +2101,19 @@ int ensure_trace_buffers(fzb_matcher* m, size_t count, size_t pos_words) {
 
 // One pattern over the list, LIST order (match_list_indices_impl, algo.rs:196-227): recs[k].index = position in the list,
 // its positions appended to `positions`.  An empty needle matches everything with no positions.
-int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t count, std::vector<fzb_match_indices>& recs, std::vector<u32>& positions) {
+// biased: the corpus' score bias is added to the records (the single-pattern entry points; the multi composition sums its patterns' scores
+// and must not pass it)
+int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t count, std::vector<fzb_match_indices>& recs, std::vector<u32>& positions,
+                          bool biased = false) {
     recs.clear();
+    biased = biased && fzb_corpus_bias(c);
     if (m->empty) {
+        std::vector<int16_t> hb;
+        if (biased)
+            if (int rc_ = fetch_bias(c, 0, c->dev.n, hb)) return rc_;
         recs.resize(count);
-        for (size_t i = 0; i < count; i++) recs[i] = fzb_match_indices{(uint32_t)i, 0, 0, 0, (uint32_t)positions.size(), 0};
+        for (size_t i = 0; i < count; i++)
+            recs[i] = fzb_match_indices{(uint32_t)i, (uint16_t)(biased ? sbias_clamp_add(0, hb[selection ? selection[i] : i]) : 0), 0, 0, (uint32_t)positions.size(), 0};
         return FZB_OK;
     }
     if (!count) return FZB_OK;
@@ -2070,6 +2132,8 @@ int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* s
     const TraceOut tr{m->trace_pos, m->trace_npos, stride};
     int rc = run_pipeline(m, c, 0, count, 0, items_dev, n_items_dev, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr, &tr);
     if (rc) return rc;
+    // (records carry the corpus index here - first 0, index_offset 0 - whether they come from a selection or the whole list)
+    if (biased && (rc = apply_bias(c, m->out_dev, m->count_dev, std::min(m->out_cap, count), 0, 0, m->lc.num_cus * 2, nullptr))) return rc;
     u32 n = 0;
     HIPCHK(hipMemcpy(&n, m->count_dev, 4, hipMemcpyDeviceToHost));
     std::vector<fzb_match_rec> dev_recs(n);
@@ -2133,10 +2197,10 @@ static int match_list_indices_impl(fzb_matcher* m, const fzb_corpus* c, const ui
     if (rc) return rc;
     std::vector<fzb_match_indices> recs;
     std::vector<u32> positions;
-    rc = indices_in_list_order(m, c, selection, count, recs, positions);
+    rc = indices_in_list_order(m, c, selection, count, recs, positions, true);
     if (rc) return rc;
-    // CompiledPatterns::Empty returns before the score sort (mod.rs:237-246) - all scores are 0 anyway
-    return finish_indices(recs, positions, sort, !m->empty, out, out_len, out_positions, index_offset);
+    // CompiledPatterns::Empty returns before the score sort (mod.rs:237-246) - all scores are 0 anyway, unless the corpus carries a bias
+    return finish_indices(recs, positions, sort, !m->empty || fzb_corpus_bias(c), out, out_len, out_positions, index_offset);
 }
 
 int fzb_match_list_indices(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
@@ -2525,7 +2589,9 @@ int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, si
     return fzb_multi_match_list(mm, c, out, out_len);
 }
 
-int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+}  // extern "C"
+// the composition alone: the patterns' scores summed, no score bias
+static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                                 uint32_t* dev_count, void* stream) {
     if (!mm || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
@@ -2553,7 +2619,7 @@ int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
         HIPCHK(hipGetLastError());
         return FZB_OK;
     }
-    if (ps.size() == 1 && !ps[0].negated) return fzb_match_list_device(ps[0].m, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
+    if (ps.size() == 1 && !ps[0].negated) return run_pipeline(ps[0].m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
     if (int rc_ = multi_ensure_buffers(mm, count)) return rc_;
     // match_list_multi_into (src/matcher/multi.rs:84-152)
     size_t base = ps.size();
@@ -2562,7 +2628,7 @@ int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     int cur = 0;  // cand[cur] / counts[cur] = the candidates
     int rc;
     if (base != ps.size()) {
-        rc = fzb_match_list_device(ps[base].m, c, first, count, index_offset, (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], stream);
+        rc = run_pipeline(ps[base].m, c, first, count, index_offset, nullptr, nullptr, (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], stream);
         if (rc) return rc;
     } else {
         fzb_launch_identity_records(mm->cand[0], (u32)count, index_offset, &mm->counts[4 * 0], cus * 2, st);  // all patterns negated: every haystack is a candidate
@@ -2591,6 +2657,15 @@ int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
+extern "C" {
+
+// (on a biased corpus the bias is added ONCE per record, after the composition's sum; with no pattern every haystack's score is its bias)
+int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+                                uint32_t* dev_count, void* stream) {
+    int rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
+    if (rc) return rc;
+    return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
+}
 
 int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len) {
     if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
@@ -2603,7 +2678,8 @@ int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match**
     // Matcher::match_list (src/matcher/mod.rs:212-222): reverse, then the stable radix sort unless there is no pattern at all
     const int sort = mm->config.sort;
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    // (no pattern over a biased corpus - the empty prompt - IS ordered: the scores are the biases)
+    const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
     if ((reversed || by_score) && count) {
         if (by_score)
             if (int rc_ = fzb_sort_ensure(mm->sort, count)) return rc_;
@@ -2687,11 +2763,13 @@ static int multi_match_list_indices_impl(fzb_multi_matcher* mm, const fzb_corpus
 
 int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
                                  uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, mm ? mm->config.sort : 0, 0, out, out_len, out_positions);
 }
 
 int fzb_multi_match_list_indices_into(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, uint32_t index_offset,
                                       fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, FZB_SORT_INDEX_ASC, index_offset, out, out_len, out_positions);
 }
 
@@ -2758,10 +2836,11 @@ int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit,
     if ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, n, st, true)) || (rc = ensure_sort_buffers(m, n))) return rc;
     if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
     bool reversed, by_score, one_pass;
-    fzb_order_flags(m, &reversed, &by_score, &one_pass);
+    fzb_order_flags(m, fzb_corpus_bias_hi(c), &reversed, &by_score, &one_pass);
     Workspace& w = m->ws;
     u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
     if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort.tmp, n, raw_count, stream))) return rc;
+    if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
     const int grid = m->lc.num_cus * 2;
     HIPCHK(fzb_launch_topk_select(w.sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort.hist, ntiles_cap, grid, st));
@@ -2776,6 +2855,7 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
     *out_len = 0;
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
+    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, 0, n, 0, m->config.sort, limit, out, out_len, out_found);
     if (m->empty) return fzb_empty_pattern_top(n, m->config.sort, limit, out, out_len, out_found);
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
@@ -2795,7 +2875,7 @@ static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n,
     if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st))) return rc;
     const int sort = mm->config.sort;
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    const bool by_score = !mm->patterns.empty() && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
     const u32 ntiles_cap = (u32)(mm->sort.cap / 2048 + 2);
     const int grid = mm->num_cus * 2;
     // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
@@ -2876,7 +2956,16 @@ int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos
 
 // CompiledPatterns::Empty (an empty needle, no pattern): fzb_empty_pattern_top's rule - the first / last min(limit, n) indices, score 0 - and no
 // positions
-int empty_top_indices(size_t n, int sort, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (fzb_corpus_bias(c)) {  // the empty prompt over a biased corpus: the head of the list ordered by the bias
+        fzb_match* head = nullptr;
+        size_t nhead = 0;
+        if (int rc_ = biased_empty_list(c, 0, n, 0, sort, limit, &head, &nhead, out_found)) return rc_;
+        std::vector<fzb_match_indices> recs(nhead);
+        for (size_t i = 0; i < nhead; i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};
+        free(head);
+        return hand_over_indices(recs.data(), nhead, nullptr, 0, out, out_len, out_positions);
+    }
     const size_t want = std::min(limit, n);
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
     std::vector<fzb_match_indices> recs(want);
@@ -2970,6 +3059,8 @@ int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_
     const TraceOut tr{m->trace_pos, m->trace_npos, stride};
     // (grids from min(limit, n) on the host, trimmed by the item count on the device; want == 0 - limit 0 - clears the pair and launches nothing)
     if ((rc = run_pipeline(m, c, 0, want, 0, m->trace_sel, n_items, (fzb_match*)m->top_traced, want, traced_count, stream, &tr))) return rc;
+    // (the head's scores are biased: the traced records get the same pass, so the pack holds them to the head on the scores the caller sees)
+    if ((rc = apply_bias(c, m->top_traced, traced_count, want, 0, 0, grid, st))) return rc;
     fzb_launch_indices_pack(m->top_head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
                             dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top_tiles, (u32)want, grid, st);
     HIPCHK(hipGetLastError());
@@ -2984,7 +3075,7 @@ int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (m->empty) return empty_top_indices(n, m->config.sort, limit, out, out_len, out_positions, out_found);
+    if (m->empty) return empty_top_indices(c, n, m->config.sort, limit, out, out_len, out_positions, out_found);
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     const size_t stride = trace_stride(m);
     int rc;
@@ -3019,6 +3110,7 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
 // from the position in the selection to the corpus index.
 int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     *out = nullptr;
     *out_len = 0;
     *out_positions = nullptr;
@@ -3146,6 +3238,7 @@ int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_cor
         if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
     }
     fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)P, mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, grid, st);
+    if ((rc = apply_bias(c, mm->top_comb, comb_count, want, 0, 0, grid, st))) return rc;  // once, after the sum: as the head's records
     fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
                             dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
     HIPCHK(hipGetLastError());
@@ -3160,7 +3253,7 @@ int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corp
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (mm->patterns.empty()) return empty_top_indices(n, mm->config.sort, limit, out, out_len, out_positions, out_found);  // CompiledPatterns::Empty
+    if (mm->patterns.empty()) return empty_top_indices(c, n, mm->config.sort, limit, out, out_len, out_positions, out_found);  // CompiledPatterns::Empty
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     size_t P = 0;
     const size_t U = multi_union_stride(mm, &P);

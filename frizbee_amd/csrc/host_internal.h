@@ -51,6 +51,14 @@ struct fzb_corpus {
     void* own_sig = nullptr; // the letter signatures (CorpusDev::sig; also of a borrowed corpus: the library's own array), room for sig_cap_items haystacks
     u64 sig_cap_items = 0;
     int sig_device = -1;     // a borrowed corpus: the device the signatures were built on (where its bytes live)
+    // the per-haystack score bias (fzb_corpus_set_bias / _update_bias, score_bias.h): one int16 per haystack, room for bias_cap_items; every
+    // entry at or behind the list's length is ZERO, so appended haystacks start unbiased.  has_bias = the queries add it (clear keeps the array).
+    int16_t* own_bias = nullptr;
+    u64 bias_cap_items = 0;
+    bool has_bias = false;
+    u32 bias_hi = 0;         // upper bound of the largest positive entry (exact after set, never lowered by an update or an edit)
+    void* bias_stage = nullptr;  // landing place of fzb_corpus_update_bias' pairs (indices, then values), kept between calls
+    u64 bias_stage_pairs = 0;
     u64 regrows = 0;         // reallocations of the canonical arrays so far
     u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
     u64 edit_info[4] = {0, 0, 0, 0};  // the last successful fzb_corpus_remove / _replace (fzb_corpus_edit_info)
@@ -64,6 +72,9 @@ struct fzb_corpus {
 };
 // the haystacks a matcher's buffers are sized for: the list's length, or what fzb_corpus_reserve made room for
 inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c->cap_items > c->dev.n ? c->cap_items : c->dev.n); }
+// the corpus' score bias as the queries see it: nullptr / 0 without one
+inline const int16_t* fzb_corpus_bias(const fzb_corpus* c) { return c->has_bias ? c->own_bias : nullptr; }
+inline u32 fzb_corpus_bias_hi(const fzb_corpus* c) { return c->has_bias ? c->bias_hi : 0; }
 
 // A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
 // null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).
@@ -267,7 +278,8 @@ int fzb_fetch_records(FetchHint& h, const void* dev_records, const u32* dev_word
 inline int fzb_ensure_out_staging(fzb_matcher* m, size_t count) { return fzb_out_ensure(*m, count); }
 // top-`limit` queries (host.hip): the ordering flags of a matcher as fzb_order_begin decides them, the sort's buffers for `cap` records
 // (the selection stage's input and scratch), the one-wait copy of (count pair, <= max_records records), the no-pattern result
-void fzb_order_flags(const fzb_matcher* m, bool* reversed, bool* by_score, bool* one_pass);
+// (bias_hi: fzb_corpus_bias_hi of the corpus the records come from - 0 without a corpus)
+void fzb_order_flags(const fzb_matcher* m, u32 bias_hi, bool* reversed, bool* by_score, bool* one_pass);
 inline int fzb_ensure_sort_buffers(fzb_matcher* m, size_t cap) { return fzb_sort_ensure(m->ws.sort, cap); }
 int fzb_fetch_top(FetchHint& h, const void* dev_records, const u32* dev_words, size_t max_records, hipStream_t st, fzb_match** out, size_t* out_len, uint64_t* out_found);
 int fzb_empty_pattern_top(size_t n, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
@@ -276,7 +288,7 @@ struct OrderPlan {
     bool reversed, by_score, one_pass, via_tmp;
     fzb_match_rec* in;  // where the index-ordered records have to be written before fzb_order_finish
 };
-int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p);
+int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p, u32 bias_hi);
 int fzb_order_finish(fzb_matcher* m, const OrderPlan& p, fzb_match_rec* dev_out, const u32* dev_count, hipStream_t stream);
 // `Matcher::match_list` over the sub-range [first, first + count) of a corpus, records numbered from index_offset, ordered per
 // config.sort on the device (fzb_match_list_sorted_device = the whole corpus from 0)
@@ -299,5 +311,7 @@ int fzb_build_filter_view(fzb_corpus* c);     // host_upload.hip
 // corpus itself and synchronises.
 int fzb_sig_sync(fzb_corpus* c, u64 n_valid);
 int fzb_sig_sync_borrowed(fzb_corpus* c);
+// the refusal of an entry point that does not apply the corpus' score bias (host.hip): FZB_OK for an unbiased corpus
+int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

@@ -193,8 +193,10 @@ static int grow(fzb_match_rec** p, size_t* cap, size_t want) {
 // Every rank-local step runs BEFORE the count all-gather and a failure there travels in the status word: when any rank failed, every rank
 // returns that rank's error code, and none is left waiting inside the collective for a rank that has gone.
 using ProduceFn = std::function<int(fzb_match* run, size_t capacity, u32* words, hipStream_t stream)>;
-static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort, size_t n, uint32_t index_offset, fzb_shard_comm* c, int flags, const ProduceFn& produce,
-                         fzb_match** out, size_t* out_len) {
+// A shard that carries a score bias is a rank-local failure like any other (the root's merge orders by what the matchers produce): no rank returns
+// before the all-gather.
+static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort, size_t n, uint32_t index_offset, fzb_shard_comm* c, int flags, const fzb_corpus* shard,
+                         const char* call, const ProduceFn& produce, fzb_match** out, size_t* out_len) {
     const bool all = (flags & FZB_GATHER_ALL) != 0;
     const bool receiver = all || c->rank == 0;
     // 1. the rank-local steps: this rank's run (or, for Empty, nothing to score) and its words
@@ -209,7 +211,8 @@ static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort,
         else if ((u64)n + (u64)index_offset > 0xFFFFFFFFull)
             local = fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)n + index_offset) + " > 4294967295 (index offset: " +
                                                 std::to_string(index_offset) + ")");
-        else if (!empty && !(local = grow(&c->run, &c->run_cap, n)))
+        else if ((local = fzb_refuse_biased(shard, call, "a single-device call (fzb_match_list, fzb_match_list_top) on the rank that holds the list"))) {
+        } else if (!empty && !(local = grow(&c->run, &c->run_cap, n)))
             local = produce((fzb_match*)c->run, n ? n : 1, c->words, c->stream);
         if (local) local_msg = fzb_last_error();
     }
@@ -313,7 +316,7 @@ int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32
     int rc = rccl_begin(m, shard, c, flags, out, out_len, &api);
     if (rc) return rc;
     const size_t n = shard->dev.n;
-    return rccl_exchange(api, m, m->empty, m->config.sort, n, index_offset, c, flags, [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+    return rccl_exchange(api, m, m->empty, m->config.sort, n, index_offset, c, flags, shard, "fzb_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
         return fzb_match_list_device(m, shard, 0, n, index_offset, run, cap, words, st);
     }, out, out_len);
 }
@@ -326,7 +329,7 @@ int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* 
     fzb_matcher* order = nullptr;
     if ((rc = fzb_multi_order_host(mm, &order))) return rc;  // host memory only: cannot fail per rank
     const size_t n = shard->dev.n;
-    return rccl_exchange(api, order, mm->patterns.empty(), mm->config.sort, n, index_offset, c, flags, [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+    return rccl_exchange(api, order, mm->patterns.empty(), mm->config.sort, n, index_offset, c, flags, shard, "fzb_multi_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
         return fzb_multi_match_list_device(mm, shard, 0, n, index_offset, run, cap, words, st);
     }, out, out_len);
 }

@@ -146,7 +146,7 @@ static int merge_runs_on_device(fzb_matcher* m, const void* const* dev_runs, con
     if (!cap) return FZB_OK;
     if ((rc = fzb_ensure_out_staging(m, cap))) return rc;
     OrderPlan plan;
-    if ((rc = fzb_order_begin(m, cap, m->out_dev, &plan))) return rc;
+    if ((rc = fzb_order_begin(m, cap, m->out_dev, &plan, 0))) return rc;
     // count_dev: two blocks of four words, alternating between batches of FZB_MAX_RUNS runs - [0] records written so far, [1] matches
     // found, [2] "a run was truncated by its producer" (sticky: every batch writes into the same word)
     u32* words = m->count_dev;  // (every word read below is assigned by the concatenation launches: no clearing fill in the stream)
@@ -425,7 +425,7 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
     if (sc->n == 0) return FZB_OK;
     if ((rc = fzb_ensure_out_staging(m, sc->n))) return rc;
     OrderPlan plan;
-    if ((rc = fzb_order_begin(m, sc->n, m->out_dev, &plan))) return rc;
+    if ((rc = fzb_order_begin(m, sc->n, m->out_dev, &plan, 0))) return rc;
     fzb_match_rec* const gather = plan.in;  // the concatenation of the runs (the sort's second buffer when one radix pass orders it)
     if ((rc = shard_prepare(m, sc, root))) return rc;
     // How the runs reach the root.  PULL (every shard lives on the root device - one GPU holding several shards): the workers only enqueue
@@ -556,7 +556,7 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
     if ((rc = fzb_grow_dev(&m->top_words, &m->top_words_cap, 2 * ns))) return rc;
     if ((rc = shard_prepare(m, sc, root))) return rc;
     bool reversed, by_score, one_pass;
-    fzb_order_flags(m, &reversed, &by_score, &one_pass);  // the root's: a carrier of a multi matcher's runs does not know that scores are sums
+    fzb_order_flags(m, 0, &reversed, &by_score, &one_pass);  // the root's: a carrier of a multi matcher's runs does not know that scores are sums
     const bool copy_forced = fzb_knobs().shard_gather_copy;
     bool all_local = !copy_forced;
     for (size_t g = 0; g < ns; g++) all_local = all_local && sc->device[g] == root;

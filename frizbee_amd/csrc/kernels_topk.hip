@@ -13,6 +13,7 @@
 // returns, the scatter is a plain copy.  The record count lives in device memory; grids are sized by the caller from the capacity.
 #include "kernels_common.h"
 #include "topk_select.h"
+#include "score_bias.h"
 
 #define TOPK_TILE 2048
 // scratch layout (u32 words; the caller hands in the radix sort's histogram buffer, idle until the ordering step):
@@ -277,4 +278,34 @@ hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, 
     }
     hipLaunchKernelGGL(k_topk_scatter, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, by_score, out, out_cap, out_count, scratch, ntiles_cap);
     return hipGetLastError();
+}
+
+// ---- the corpus' per-haystack score bias (score_bias.h) ----------------------------------------------------------------------------
+// Between the scorers and the selection / ordering stage: record k of an index-ordered run belongs to haystack
+// first + (index - index_offset) of the corpus, and its score becomes clamp(score + bias[haystack], 0, 65535).  One thread per record,
+// grid-stride; the whole 8-byte record is loaded and stored back (two dwords where the caller's array is only 4-byte aligned); the records
+// come in index order, so the 2-byte gather is near-coalesced.  A record whose haystack lies outside the n_bias entries is left alone.
+__global__ __launch_bounds__(256) void k_bias_apply(fzb_match_rec* __restrict__ recs, const u32* __restrict__ count, u32 cap, const int16_t* __restrict__ bias, u64 n_bias, u64 first,
+                                                    u32 index_offset) {
+    const u32 n = min(count[0], cap);
+    const bool wide = ((uintptr_t)recs & 7u) == 0;
+    for (u32 i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        uint2 w;
+        if (wide) w = *(const uint2*)(recs + i);
+        else w = make_uint2(((const u32*)(recs + i))[0], ((const u32*)(recs + i))[1]);
+        const u64 h = first + (u64)(w.x - index_offset);
+        if (h >= n_bias) continue;
+        w.y = (w.y & 0xFFFF0000u) | sbias_clamp_add(w.y & 0xFFFFu, (int32_t)bias[h]);
+        if (wide) *(uint2*)(recs + i) = w;
+        else ((u32*)(recs + i))[1] = w.y;
+    }
+}
+
+// recs: up to `cap` index-ordered records, count[0] of them written; bias: the corpus' array of n_bias entries.  The grid is sized from
+// the capacity here and trimmed by the device-side count in the kernel.
+void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st) {
+    if (!cap || !n_bias) return;
+    const u32 blocks = (cap + 255u) / 256u, most = grid_max > 0 ? (u32)grid_max : 1u;
+    const int grid = (int)(blocks < most ? blocks : most);
+    hipLaunchKernelGGL(k_bias_apply, dim3(grid), dim3(256), 0, st, recs, count, cap, bias, n_bias, first, index_offset);
 }

@@ -12,7 +12,7 @@ import torch.distributed as dist
 
 import ctypes as C
 
-from . import MATCH_DTYPE, MultiMatcher, SortStrategy, _check, _take, k_merge_matches, lib, radix_sort_matches
+from . import MATCH_DTYPE, FrizbeeError, MultiMatcher, SortStrategy, _check, _take, k_merge_matches, lib, radix_sort_matches
 
 
 def shard_range(n_total, rank, world):
@@ -74,7 +74,11 @@ class ShardExchange:
     starts the transport on the backend's own stream (RCCL send/recv over the point-to-point xGMI links: the root
     receives its world-1 peers' buffers on separate links in parallel), and the next step's kernels overlap it.
     The capacity is agreed once, up front (`plan`), from a first measured count; a shard that later outgrows it is
-    reported by `collect`, never truncated silently."""
+    reported by `collect`, never truncated silently.
+
+    The exchange sees runs, not corpora: a shard that carries a score bias (`Corpus.set_bias`) must not be queried through it - the root's
+    merge orders by what the matcher alone can produce.  Show it the shard (`check_corpus(shard)`, or `ordered_query(..., corpus=shard)`) and
+    it raises; include/frizbee_hip.h states the rule for fzb_merge_shard_runs."""
 
     HEADER = 8
 
@@ -180,14 +184,25 @@ class ShardExchange:
         hdr = torch.stack([b[: self.HEADER] for b in self.recv[slot]]).cpu().numpy().view(np.uint32).reshape(self.world, 2)
         return int(hdr.max())
 
-    def ordered_query(self, run, matcher, slot=0, stream=None, copy=False, max_retries=6):
+    @staticmethod
+    def check_corpus(corpus):
+        """Raises for a shard that carries a score bias (`Corpus.set_bias`): the root combines the runs with fzb_merge_shard_runs, which
+        orders by what the matcher alone can produce - it knows nothing of a shard's bias.  Pass the shard to `ordered_query(corpus=...)`,
+        or call this before enqueueing a run into the exchange."""
+        if corpus is not None and corpus.bias_info()["has_bias"]:
+            raise FrizbeeError(1, "ShardExchange: the shard carries a score bias, which the exchange's merge does not apply; query the list on one device "
+                                  "(Matcher.match_list / match_list_top), or Corpus.set_bias(None) first")
+
+    def ordered_query(self, run, matcher, slot=0, stream=None, copy=False, max_retries=6, corpus=None):
         """One query, every rank together, the ordered list on the root (None elsewhere) - `match_list_parallel`'s result
         (src/matcher/parallel.rs:18-89) whatever the number of matches: `run(records_ptr, capacity, count_ptr)` enqueues this rank's
         pipeline (fzb_match_list_device with its global index_offset) into the exchange buffer; the runs are gathered to the root and
         combined there (`collect_merged`); then the root tells every rank, with ONE 8-byte broadcast, whether every shard's run fitted
         the exchange.  If one did not (its `matches found` exceeds the capacity: the capacity was planned from an earlier query), every rank
         re-sizes the exchange to 1.25 x the largest run and the query is repeated - a second query with more matches than the first can
-        never fail with FZB_ERR_CAPACITY or return a shorter list."""
+        never fail with FZB_ERR_CAPACITY or return a shorter list.  `corpus`: this rank's shard - a biased one raises (`check_corpus`) before
+        anything is enqueued."""
+        self.check_corpus(corpus)
         ctl_dev = torch.device("cpu") if (self.host_staged or self.device.type != "cuda") else self.device
         for _ in range(max_retries + 1):
             self.wait(slot)

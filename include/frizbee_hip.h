@@ -204,6 +204,55 @@ int fzb_corpus_replace(fzb_corpus* c, const uint32_t* indices, size_t n, const u
  * [2] = 1024-haystack tiles of the filter's view rebuilt, [3] = peak temporary device bytes. */
 int fzb_corpus_edit_info(const fzb_corpus* c, uint64_t out[4]);
 
+/* A PER-HAYSTACK SCORE BIAS, applied on the device.  Real pickers do not rank by the match score alone: they add a per-item term - frecency,
+ * "file is open", "modified in git", a penalty for vendored paths.  The reference has no such term: its `match_list` returns the whole Vec and
+ * the caller adds the term on the host and sorts again - which a top-`limit` call cannot serve, because selecting before the boost is added
+ * picks the wrong records.  Here the corpus keeps one int16 per haystack (bias[i] belongs to haystack i) and a record's reported score becomes
+ *     clamp(score + bias[i], 0, 65535)
+ * where `score` is what the library reports without a bias: the single pattern's score with the exact-match bonus, or the multi-pattern
+ * saturating sum (the bias is added ONCE per record, after the sum).  The add runs between the scorers and the selection / ordering stage
+ * (one short launch over the index-ordered records, frizbee_amd/csrc/score_bias.h), so the threshold, the selection, the radix sort and the
+ * pack of the positions all work on the ranking the user sees.  Nothing else changes: which haystacks match, `found`, `exact`, the matched
+ * positions, min_haystack_len and the prefilter are those of the unbiased query; a score biased down to 0 stays in the result.  Ordering is the
+ * reference's rule (src/matcher/mod.rs:215-221, src/sort.rs:6-40) over the biased scores: index order, reversed for the *Desc strategies, then
+ * the stable descending sort by score for the Score* strategies; fzb_match_list_top stays "the first min(limit, found) records of
+ * fzb_match_list".  A corpus without a bias takes exactly the launches it took before.
+ * The bias is a property of the LIST, not of a query: it survives fzb_matcher_set_pattern / fzb_multi_matcher_set_patterns untouched and stays
+ * in step with the editing family - fzb_corpus_reserve grows it with the item capacity, appended haystacks start at 0 (every entry at or
+ * behind the list's length is zero), fzb_corpus_truncate clears the cut entries, fzb_corpus_remove / _remove_device compact the kept entries on
+ * the device (2 bytes of scratch per haystack from the first removed one on, counted in fzb_corpus_edit_info's out[3]), fzb_corpus_replace
+ * leaves it alone: the index is the identity, a renamed path keeps its bias.  Shards (fzb_sharded_corpus) have no bias.
+ * Every entry point that takes an fzb_corpus either returns biased scores or refuses a biased corpus with FZB_ERR_INVALID (the message says
+ * "bias" and names the call to use instead); none ignores the bias silently.  Biased: fzb_match_list / _into / _device / _sorted_device /
+ * _parallel, fzb_match_list_top / _top_device, fzb_match_list_top_indices / _device, fzb_match_list_indices / _into, fzb_multi_match_list /
+ * _into / _device / _top / _parallel, fzb_multi_match_list_top_indices_fused / _device.  Refused: fzb_multi_match_list_indices / _indices_into,
+ * the composed fzb_multi_match_list_top_indices (use the fused form), fzb_match_list_parallel_rccl / fzb_multi_match_list_parallel_rccl (a
+ * biased shard is a rank-local failure that travels in the gathered status word like any other).
+ * fzb_merge_shard_runs takes runs, not a corpus: it orders by what the matcher alone can produce, so runs that fzb_match_list_device /
+ * fzb_multi_match_list_device wrote over a BIASED corpus must not be handed to it (their scores may pass the bound its single radix pass
+ * rests on); frizbee_amd.distributed.ShardExchange raises for a biased shard it is shown (check_corpus, ordered_query(corpus=...)).
+ * AN EMPTY NEEDLE / NO PATTERN over a biased corpus is the picker's empty prompt, "most frecent first": every haystack matches with score
+ * clamp(bias, 0, 65535) and - a DEPARTURE from the reference, whose empty result is never sorted - the list IS ordered by `config.sort`
+ * (fzb_match_list, _parallel, _into (index order), _top, _top_indices with no positions, and the multi forms; host work for the single
+ * matcher: one copy of the bias and the host's stable sort).  The _device forms keep refusing an empty needle.
+ * These are SET-UP calls under the editing family's rules: only for a corpus made by fzb_corpus_upload (a borrowed one gets FZB_ERR_INVALID),
+ * they wait for the device's outstanding work on entry and are complete on return, must not run concurrently with queries over the same
+ * corpus, and an error leaves the corpus as it was. */
+/* bias[i] = values[i] for every haystack: n must equal the corpus length (FZB_ERR_INVALID otherwise).  One host-to-device copy; the array is
+ * created on first use, sized for max(length, reserved items). */
+int fzb_corpus_set_bias(fzb_corpus* c, const int16_t* values, size_t n);
+/* Sparse set - what a picker does when a file is opened: bias[indices[k]] = values[k].  Checked on the host: an index >= the corpus length or a
+ * repeated index gives FZB_ERR_INVALID naming the position, nothing written.  One copy of the pairs and one scatter kernel (up to 4096 pairs
+ * allocate nothing once the corpus has a bias).  On a corpus without a bias an all-zero one is created first.  n == 0 is a no-op. */
+int fzb_corpus_update_bias(fzb_corpus* c, const uint32_t* indices, const int16_t* values, size_t n);
+/* the corpus answers exactly as before any bias (the array is kept for the next fzb_corpus_set_bias / _update_bias) */
+int fzb_corpus_clear_bias(fzb_corpus* c);
+/* out[0] = carries a bias (0/1), [1] = entries the array has room for, [2] = bias_hi: the host-side upper bound of the largest positive bias
+ * (exact after fzb_corpus_set_bias, max(old, new values) after fzb_corpus_update_bias, 0 after clear, never lowered by an edit) - while
+ * max matrix score + exact_match_bonus + bias_hi < 256 the ordering keeps its single radix pass and the selection its single histogram
+ * level -, [3] = device bytes (the array and the landing place of an update's pairs) */
+int fzb_corpus_bias_info(const fzb_corpus* c, uint64_t out[4]);
+
 /* `Matcher::match_list(&haystacks)` (src/matcher/mod.rs:212-222) = `match_list_into(.., offset 0)` ->
 * `Specialized::match_list::<TYPOS,UNICODE,_>` (src/matcher/algo.rs:78-103) and the reverse / `radix_sort_matches`
  * post-step (src/sort.rs:6-40), all on the GPU.  `*out` is malloc'd by the library
@@ -305,7 +354,7 @@ const char* fzb_matcher_shard_report(const fzb_matcher* m);
  * gather - frizbee_amd.distributed): run g = dev_runs[g], index-ordered records of shard g as fzb_match_list_device wrote them,
  * dev_counts[g] -> the two uint32 that call wrote in DEVICE memory (records written, matches found), run_caps[g] = the run's buffer size
  * in records (a run with matches found > run_caps[g] was truncated by its producer: FZB_ERR_CAPACITY, nothing merged); runs in ascending
- * shard order, all readable from the current device.  Concatenation + `match_list`'s ordering (src/matcher/mod.rs:215-221) on the device, on `stream`, then one copy to the
+ * shard order, all readable from the current device, none written over a corpus that carries a score bias (fzb_corpus_set_bias).  Concatenation + `match_list`'s ordering (src/matcher/mod.rs:215-221) on the device, on `stream`, then one copy to the
  * host = the list `match_list_parallel` returns (src/matcher/parallel.rs:66-87).  Free the result with fzb_matches_free. */
 int fzb_merge_shard_runs(fzb_matcher* m, const void* const* dev_runs, const uint32_t* const* dev_counts, const size_t* run_caps, size_t nruns, void* stream,
                          fzb_match** out, size_t* out_len);
@@ -564,7 +613,7 @@ int fzb_debug_device_allocs(uint64_t* out);
 
 /* test hook: copies one of the corpus' device arrays to the host - what: 0 = canonical bytes up to the padded size + the 96-byte tail,
  * 1 = end offsets (u32 or u64, fzb_corpus_info out[9]), 2 = vbytes, 3 = vgofs, 4 = vgnv, 5 = vlen, 6 = vperm, 7 = vlong (2..7: the
- * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
+ * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them), 9 = the score bias (int16 per haystack, nothing without one).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes);
 
 #ifdef __cplusplus

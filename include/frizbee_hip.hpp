@@ -220,6 +220,24 @@ class Corpus {
         check(fzb_corpus_edit_info(h_.get(), o));
         return EditInfo{o[0], o[1], o[2], o[3]};
     }
+    // A per-haystack score bias (fzb_corpus_set_bias and friends): one int16 per haystack, added on the device to every record's score before
+    // anything selects or orders - reported score = clamp(score + bias[index], 0, 65535).  It belongs to the list: it survives set_pattern
+    // and follows append / truncate / remove / replace.
+    void set_bias(const std::vector<int16_t>& values) { check(fzb_corpus_set_bias(h_.get(), values.data(), values.size())); }
+    // bias[indices[k]] = values[k] (unique indices in range); a corpus without a bias gets an all-zero one first
+    void update_bias(const std::vector<uint32_t>& indices, const std::vector<int16_t>& values) {
+        if (indices.size() != values.size()) throw Error(FZB_ERR_INVALID, "Corpus::update_bias: one value per index");
+        check(fzb_corpus_update_bias(h_.get(), indices.data(), values.data(), indices.size()));
+    }
+    void clear_bias() { check(fzb_corpus_clear_bias(h_.get())); }
+    struct BiasInfo {
+        uint64_t has_bias, capacity, bias_hi, device_bytes;
+    };
+    BiasInfo bias_info() const {
+        uint64_t o[4] = {};
+        check(fzb_corpus_bias_info(h_.get(), o));
+        return BiasInfo{o[0], o[1], o[2], o[3]};
+    }
 
   private:
     struct Del { void operator()(fzb_corpus* c) const { fzb_corpus_free(c); } };

@@ -99,6 +99,11 @@ extern "C" {
     fn fzb_corpus_remove_device(c: *mut c_void, dev_indices: *const c_void, stride_bytes: usize, dev_count: *const u32, max_count: usize) -> c_int;
     fn fzb_corpus_replace(c: *mut c_void, indices: *const u32, n: usize, bytes: *const u8, ends: *const u64) -> c_int;
     fn fzb_corpus_edit_info(c: *const c_void, out: *mut u64) -> c_int;
+    // a per-haystack score bias, added on the device before anything selects or orders: reported score = clamp(score + bias[index], 0, 65535)
+    fn fzb_corpus_set_bias(c: *mut c_void, values: *const i16, n: usize) -> c_int;
+    fn fzb_corpus_update_bias(c: *mut c_void, indices: *const u32, values: *const i16, n: usize) -> c_int;
+    fn fzb_corpus_clear_bias(c: *mut c_void) -> c_int;
+    fn fzb_corpus_bias_info(c: *const c_void, out: *mut u64) -> c_int;
     fn fzb_corpus_len(c: *const c_void) -> usize;
     fn fzb_match_list(m: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_match_list_into(m: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
@@ -241,6 +246,27 @@ impl HipCorpus {
     pub fn edit_info(&self) -> [u64; 4] {
         let mut out = [0u64; 4];
         check(unsafe { fzb_corpus_edit_info(self.handle, out.as_mut_ptr()) });
+        out
+    }
+    /// One `i16` per haystack (`values.len()` = the list's length), added to every record's score on the device before the selection and
+    /// the ordering: what a picker's frecency / "file is open" boost needs for `match_list_top` to pick the records the user sees.  The
+    /// bias belongs to the list: it survives `set_pattern` and follows `append` / `truncate` / `remove` / `replace`.
+    pub fn set_bias(&mut self, values: &[i16]) {
+        check(unsafe { fzb_corpus_set_bias(self.handle, values.as_ptr(), values.len()) });
+    }
+    /// `bias[indices[k]] = values[k]` (unique indices in range); a corpus without a bias gets an all-zero one first.
+    pub fn update_bias(&mut self, indices: &[u32], values: &[i16]) {
+        assert_eq!(indices.len(), values.len(), "one value per index");
+        check(unsafe { fzb_corpus_update_bias(self.handle, indices.as_ptr(), values.as_ptr(), indices.len()) });
+    }
+    /// The corpus answers exactly as before any bias.
+    pub fn clear_bias(&mut self) {
+        check(unsafe { fzb_corpus_clear_bias(self.handle) });
+    }
+    /// [carries a bias (0/1), entries the array has room for, upper bound of the largest positive bias, device bytes].
+    pub fn bias_info(&self) -> [u64; 4] {
+        let mut out = [0u64; 4];
+        check(unsafe { fzb_corpus_bias_info(self.handle, out.as_mut_ptr()) });
         out
     }
 }
