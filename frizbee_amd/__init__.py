@@ -127,6 +127,7 @@ SYMBOLS = [
     "fzb_multi_match_list_top_indices_device", "fzb_multi_match_list_top_indices_fused", "fzb_multi_matcher_reserve_top_indices",
     "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold",
     "fzb_corpus_set_bias", "fzb_corpus_update_bias", "fzb_corpus_clear_bias", "fzb_corpus_bias_info",
+    "fzb_corpus_set_tags", "fzb_corpus_update_tags", "fzb_corpus_clear_tags", "fzb_corpus_set_scope", "fzb_corpus_scope_info",
 ]
 
 
@@ -241,6 +242,11 @@ def lib():
         l.fzb_corpus_update_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         l.fzb_corpus_clear_bias.argtypes = [C.c_void_p]
         l.fzb_corpus_bias_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_corpus_set_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_update_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_corpus_clear_tags.argtypes = [C.c_void_p]
+        l.fzb_corpus_set_scope.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16]
+        l.fzb_corpus_scope_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         _lib = l
     return _lib
 
@@ -368,7 +374,7 @@ class Corpus:
     INFO_FIELDS = ("items", "item_capacity", "bytes", "byte_capacity", "max_len", "uniform_len", "has_view", "view_nv", "outliers", "ends_u64", "regrows",
                    "h2d_bytes")
     DEBUG_ARRAYS = {"bytes": (0, np.uint8), "ends": (1, None), "vbytes": (2, np.uint8), "vgofs": (3, np.uint32), "vgnv": (4, np.uint8), "vlen": (5, np.uint16),
-                    "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32), "bias": (9, np.int16)}
+                    "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32), "bias": (9, np.int16), "tags": (10, np.uint16)}
 
     def set_bias(self, values):
         """fzb_corpus_set_bias: one int16 per haystack (len(values) == len(self)), added to every record's score on the device before
@@ -402,6 +408,54 @@ class Corpus:
         out = (C.c_uint64 * 4)()
         _check(lib().fzb_corpus_bias_info(self.h, out))
         return dict(zip(self.BIAS_INFO_FIELDS, (int(x) for x in out)))
+
+    @staticmethod
+    def _tags16(values, who):
+        v = np.asarray(values)
+        if v.size and (v.dtype.kind not in "iub" or v.min() < 0 or v.max() > 65535):
+            raise FrizbeeError(1, f"{who}: tags are 16 caller-defined bits (0 .. 65535)")
+        return np.ascontiguousarray(v, dtype=np.uint16)
+
+    def set_tags(self, values):
+        """fzb_corpus_set_tags: one uint16 of caller-defined bits per haystack (len(values) == len(self)).  Together with `set_scope` they
+        decide which haystacks a query sees.  The tags belong to the list: they survive set_pattern and follow append (new haystacks: tag
+        0) / truncate / remove / replace."""
+        v = self._tags16(values, "Corpus.set_tags")
+        _check(lib().fzb_corpus_set_tags(self.h, v.ctypes.data if len(v) else None, len(v)))
+
+    def update_tags(self, indices, values):
+        """fzb_corpus_update_tags: tags[indices[k]] = values[k] (unique indices in range).  A corpus without tags gets an all-zero array first."""
+        ix = np.asarray(indices)
+        if ix.size and (ix.min() < 0 or ix.max() > 0xFFFFFFFF):
+            raise FrizbeeError(1, "Corpus.update_tags: an index is an unsigned 32-bit value")
+        ix = np.ascontiguousarray(ix, dtype=np.uint32)
+        v = self._tags16(values, "Corpus.update_tags")
+        if len(ix) != len(v):
+            raise FrizbeeError(1, f"Corpus.update_tags: {len(ix)} indices for {len(v)} values")
+        _check(lib().fzb_corpus_update_tags(self.h, ix.ctypes.data if len(ix) else None, v.ctypes.data if len(v) else None, len(ix)))
+
+    def clear_tags(self):
+        """fzb_corpus_clear_tags: every tag 0 and the scope (0, 0) - the corpus answers as before any tags."""
+        _check(lib().fzb_corpus_clear_tags(self.h))
+
+    def set_scope(self, require=0, exclude=0):
+        """fzb_corpus_set_scope: haystack i is visible iff (tags[i] & require) == require and (tags[i] & exclude) == 0; a query returns what
+        it returns over the visible haystacks alone, every index that of the full list.  Host only - two words, no device work: the
+        "toggle ignored files" keystroke.  (0, 0) is no scope."""
+        for name, v in (("require", require), ("exclude", exclude)):
+            if not 0 <= int(v) <= 65535:
+                raise FrizbeeError(1, f"Corpus.set_scope: {name} is a 16-bit mask (0 .. 65535)")
+        _check(lib().fzb_corpus_set_scope(self.h, int(require), int(exclude)))
+
+    SCOPE_INFO_FIELDS = ("active", "capacity", "scope", "device_bytes")
+
+    def scope_info(self):
+        """fzb_corpus_scope_info as a dict (SCOPE_INFO_FIELDS), with `require` and `exclude` taken apart from the packed `scope` word."""
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_corpus_scope_info(self.h, out))
+        d = dict(zip(self.SCOPE_INFO_FIELDS, (int(x) for x in out)))
+        d["require"], d["exclude"] = d["scope"] & 0xFFFF, d["scope"] >> 16
+        return d
 
     def signature_info(self):
         """fzb_corpus_signature_info: (built, bytes) - whether the corpus has letter signatures and their size in device memory."""

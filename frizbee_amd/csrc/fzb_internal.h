@@ -253,6 +253,10 @@ hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, 
 void fzb_launch_topk_concat(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, hipStream_t st);
 // the corpus' score bias (score_bias.h) added to index-ordered records: haystack = first + (index - index_offset); the grid is sized from cap, trimmed by count[0]
 void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st);
+// the corpus' visibility scope (scope.h): the records of hidden haystacks dropped from count[0] index-ordered records (at most cap) into a DIFFERENT
+// buffer of `capacity` records - flag pass + stable compaction; count_out = (written, found); bitmap: 16 words per 1024 records of cap, tile_counts: one
+void fzb_launch_scope_drop(const fzb_match_rec* recs, const u32* count, u32 cap, const uint16_t* tags, u64 n_tags, u64 first, u32 index_offset, u32 require, u32 exclude, u64* bitmap,
+                           u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st);
 // kernels_indices.hip: the glue of the fused top + matched-positions query (item list from the sorted head; packing of the traced positions)
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st);
 size_t fzb_indices_pack_tile_words(size_t max_records);

@@ -28,6 +28,7 @@
 #include "host_internal.h"
 #include "sig_filter.h"
 #include "score_bias.h"
+#include "scope.h"
 
 namespace {
 #include "unicode_case_table.inc"
@@ -234,6 +235,18 @@ void fzb_sort_release(SortBuffers& s) {
     if (s.hist) (void)hipFree(s.hist);
     s = SortBuffers{};
 }
+int fzb_scope_ensure(ScopeScratch& s, size_t count) {
+    const size_t tiles = (count + SCOPE_TILE - 1) / SCOPE_TILE;
+    int rc;
+    if ((rc = fzb_grow_dev(&s.recs, &s.recs_cap, count, 16)) || (rc = fzb_grow_dev(&s.bitmap, &s.bitmap_words, tiles * SCOPE_WORDS, 1)) || (rc = fzb_grow_dev(&s.tiles, &s.tiles_cap, tiles, 1)))
+        return rc;
+    return fzb_grow_dev(&s.words, &s.words_cap, 16);
+}
+void fzb_scope_release(ScopeScratch& s) {
+    for (void* p : {(void*)s.recs, (void*)s.bitmap, (void*)s.tiles, (void*)s.words})
+        if (p) (void)hipFree(p);
+    s = ScopeScratch{};
+}
 void fzb_out_release(OutStaging& o) {
     if (o.out_dev) (void)hipFree(o.out_dev);
     if (o.count_dev) (void)hipFree(o.count_dev);
@@ -245,6 +258,7 @@ void fzb_out_release(OutStaging& o) {
 static void release_state(MatcherState& s) {
     free_workspace(s.ws);
     fzb_out_release(s);
+    fzb_scope_release(s.scope);
     for (void* p : {(void*)s.top_words, (void*)s.trace_sel, (void*)s.trace_pos, (void*)s.trace_npos, (void*)s.top_head, (void*)s.top_traced, (void*)s.top_idx_words, (void*)s.top_tiles,
                     (void*)s.top_packed, (void*)s.top_dense, s.long_blob_dev, (void*)s.long_scratch})
         if (p) (void)hipFree(p);
@@ -983,6 +997,7 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_sig) (void)hipFree(c->own_sig);
     if (c->own_bias) (void)hipFree(c->own_bias);
     if (c->bias_stage) (void)hipFree(c->bias_stage);
+    if (c->own_tags) (void)hipFree(c->own_tags);
     for (void* q : c->own_view)
         if (q) (void)hipFree(q);
     for (void* q : {c->stage_raw, c->stage_ends, c->stage_tiles, c->stage_stats})
@@ -1179,6 +1194,33 @@ static int apply_bias(const fzb_corpus* c, fzb_match_rec* recs, const u32* count
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
+// ---- the corpus' visibility scope on the query path (scope.h) ------------------------------------------------------------------------
+// A query over a corpus with an active scope: the producer (the pipeline, the multi-pattern composition) writes its index-ordered records
+// into the matcher's ScopeScratch - room for one per haystack of the range, its pair in scratch.words - and apply_terms applies the LIST's
+// terms to them: drop the records of hidden haystacks (flag pass + stable compaction into the caller's array of `capacity` records,
+// dev_count = (written, visible matches)), then add the bias.  The ONE helper that launches the drop; a corpus without an active scope never
+// gets here and takes the launches it took before.
+static int apply_terms(const fzb_corpus* c, ScopeScratch& sc, size_t count, fzb_match_rec* dev_out, size_t capacity, u32* dev_count, size_t first, uint32_t index_offset, int grid_max,
+                       hipStream_t st) {
+    const u32 cap32 = (u32)std::min<size_t>(capacity, 0xFFFFFFFFu);
+    fzb_launch_scope_drop(sc.recs, sc.words, (u32)count, c->own_tags, c->dev.n, first, index_offset, c->scope_require, c->scope_exclude, sc.bitmap, sc.tiles, dev_out, cap32, dev_count,
+                          grid_max, st);
+    HIPCHK(hipGetLastError());
+    return apply_bias(c, dev_out, dev_count, std::min(capacity, count), first, index_offset, grid_max, st);
+}
+// "honours the scope or refuses": the entry points that cannot drop the hidden haystacks say so instead of ignoring the scope
+int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead) {
+    if (!c || !fzb_corpus_scoped(c)) return FZB_OK;
+    return fail(FZB_ERR_INVALID, std::string(call) + ": the corpus has an active scope, which this call does not apply; use " + instead + ", or fzb_corpus_set_scope(c, 0, 0) first");
+}
+// entries [first, first + count) of the tags on the host (one device-to-host copy)
+static int fetch_tags(const fzb_corpus* c, size_t first, size_t count, std::vector<uint16_t>& out) {
+    out.assign(count, 0);
+    if (count) HIPCHK(hipMemcpy(out.data(), c->own_tags + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return FZB_OK;
+}
+// the list's terms, if any: what makes an empty needle's result more than "every index, score 0"
+static bool corpus_terms(const fzb_corpus* c) { return fzb_corpus_bias(c) || fzb_corpus_scoped(c); }
 // "returns biased scores or refuses": the entry points that cannot add the bias say so instead of ignoring it
 int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead) {
     if (!c || !fzb_corpus_bias(c)) return FZB_OK;
@@ -1194,13 +1236,24 @@ static int fetch_bias(const fzb_corpus* c, size_t first, size_t count, std::vect
 // of [first, first + count) matches with score clamp(bias, 0, 65535), and - unlike the reference's unsorted empty result - the list is ordered
 // per `sort` (reverse for the *Desc strategies, then the stable descending sort by score for the Score* ones), cut to `limit` records.
 // Host work: one copy of the bias and the host's stable sort.  *out: malloc'ed (fzb_matches_free); *out_found (optional) = count.
+// Over a corpus with an active SCOPE (with or without a bias) only the visible haystacks of the range are listed, each under its index in the
+// full list (index_offset + (i - first)), and *out_found counts those; without a bias the scores are 0 and the reference's rule holds: reversed
+// for the *Desc strategies, never sorted.  Host work: one copy of the tags, as of the bias.
 static int biased_empty_list(const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, int sort, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
     std::vector<int16_t> hb;
-    if (int rc = fetch_bias(c, first, count, hb)) return rc;
-    std::vector<fzb_match> recs(count);
-    for (size_t i = 0; i < count; i++) recs[i] = fzb_match{(uint32_t)(index_offset + i), (uint16_t)sbias_clamp_add(0, hb[i]), 0, 0};
+    std::vector<uint16_t> ht;
+    const bool biased = fzb_corpus_bias(c) != nullptr, scoped = fzb_corpus_scoped(c);
+    if (biased)
+        if (int rc = fetch_bias(c, first, count, hb)) return rc;
+    if (scoped)
+        if (int rc = fetch_tags(c, first, count, ht)) return rc;
+    std::vector<fzb_match> recs;
+    recs.reserve(count);
+    for (size_t i = 0; i < count; i++)
+        if (!scoped || scope_visible(ht[i], c->scope_require, c->scope_exclude)) recs.push_back(fzb_match{(uint32_t)(index_offset + i), (uint16_t)(biased ? sbias_clamp_add(0, hb[i]) : 0), 0, 0});
+    count = recs.size();
     if (sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC) std::reverse(recs.begin(), recs.end());
-    if (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC)
+    if (biased && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC))
         std::stable_sort(recs.begin(), recs.end(), [](const fzb_match& a, const fzb_match& b) { return a.score > b.score; });
     const size_t keep = std::min(limit, count);
     fzb_match* r = (fzb_match*)malloc(std::max<size_t>(keep, 1) * sizeof(fzb_match));
@@ -1790,6 +1843,7 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (rc) return rc;
     rc = ensure_workspace(m, n);
     if (rc) return rc;
+    if (c->own_tags && (rc = fzb_scope_ensure(m->scope, n))) return rc;  // a corpus that carries tags: toggling its scope between queries allocates nothing
     const bool no_wide = n == c->dev.n && c->dev.max_len != 0 && c->dev.max_len <= (u32)m->lc.sw_lanes;
     if (!m->long_needle && !m->literal_mode && !m->nd.unicode && !no_wide && ((rc = ensure_dp_scratch(m, m->lc.num_cus * 4)) || (rc = ensure_aux_stream(m)))) return rc;
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && fzb_knobs().unicode_multi != 0 && (rc = ensure_dp_scratch(m, m->lc.num_cus * 2))) return rc;
@@ -1828,7 +1882,13 @@ extern "C" {
 
 int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                           uint32_t* dev_count, void* stream) {
-    int rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
+    int rc;
+    if (m && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the pipeline into the scratch, then the list's terms: drop, then bias
+        if ((rc = fzb_scope_ensure(m->scope, count))) return rc;
+        if ((rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, (fzb_match*)m->scope.recs, count, m->scope.words, stream))) return rc;
+        return apply_terms(c, m->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
+    }
+    rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
     if (rc) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
 }
@@ -2011,7 +2071,7 @@ int fzb_match_list_into(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
         return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
     *out = nullptr;
     *out_len = 0;
-    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, first, count, index_offset, FZB_SORT_INDEX_ASC, count, out, out_len, nullptr);
+    if (m->empty && corpus_terms(c)) return biased_empty_list(c, first, count, index_offset, FZB_SORT_INDEX_ASC, count, out, out_len, nullptr);
     if (m->empty) {  // src/matcher/mod.rs:381-384
         fzb_match* r = (fzb_match*)malloc(std::max<size_t>(count, 1) * sizeof(fzb_match));
         if (!r) return fail(FZB_ERR_INVALID, "out of memory");
@@ -2046,7 +2106,7 @@ void fzb_radix_sort_matches(fzb_match* matches, size_t n) {  // src/sort.rs:6-40
 int fzb_match_list(fzb_matcher* m, const fzb_corpus* c, fzb_match** out, size_t* out_len) {
     if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     const int sort = m->config.sort;
-    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, 0, c->dev.n, 0, sort, c->dev.n, out, out_len, nullptr);  // the empty prompt: ordered by the bias
+    if (m->empty && corpus_terms(c)) return biased_empty_list(c, 0, c->dev.n, 0, sort, c->dev.n, out, out_len, nullptr);  // the empty prompt: the visible haystacks, ordered by the bias
     if (m->empty) {  // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
         int rc = fzb_match_list_into(m, c, 0, c->dev.n, 0, out, out_len);
         if (rc) return rc;
@@ -2205,11 +2265,13 @@ static int match_list_indices_impl(fzb_matcher* m, const fzb_corpus* c, const ui
 
 int fzb_match_list_indices(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
                            uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_scoped(c, "fzb_match_list_indices", "fzb_match_list_top_indices")) return rc_;
     return match_list_indices_impl(m, c, selection, n_selection, m ? m->config.sort : 0, 0, out, out_len, out_positions);
 }
 
 int fzb_match_list_indices_into(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, uint32_t index_offset, fzb_match_indices** out,
                                 size_t* out_len, uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_scoped(c, "fzb_match_list_indices_into", "fzb_match_list_top_indices")) return rc_;
     return match_list_indices_impl(m, c, selection, n_selection, FZB_SORT_INDEX_ASC, index_offset, out, out_len, out_positions);
 }
 
@@ -2333,6 +2395,7 @@ static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and p
     mm->union_src_host.clear();
     fzb_sort_release(mm->sort);
     fzb_out_release(*mm);
+    fzb_scope_release(mm->scope);
 }
 
 // the composition's buffers for ranges of up to `count` haystacks
@@ -2552,6 +2615,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     for (fzb_matcher* m : mm->spare)
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
+    if (c->own_tags && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags: the composition's records ahead of the drop)
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
     if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
     return FZB_OK;
@@ -2662,7 +2726,13 @@ extern "C" {
 // (on a biased corpus the bias is added ONCE per record, after the composition's sum; with no pattern every haystack's score is its bias)
 int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                                 uint32_t* dev_count, void* stream) {
-    int rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
+    int rc;
+    if (mm && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the composition into the scratch (with no pattern: identity records), then drop, then bias
+        if ((rc = fzb_scope_ensure(mm->scope, count))) return rc;
+        if ((rc = multi_compose_device(mm, c, first, count, index_offset, (fzb_match*)mm->scope.recs, count, mm->scope.words, stream))) return rc;
+        return apply_terms(c, mm->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
+    }
+    rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
     if (rc) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
 }
@@ -2764,12 +2834,14 @@ static int multi_match_list_indices_impl(fzb_multi_matcher* mm, const fzb_corpus
 int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
                                  uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, mm ? mm->config.sort : 0, 0, out, out_len, out_positions);
 }
 
 int fzb_multi_match_list_indices_into(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, uint32_t index_offset,
                                       fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, FZB_SORT_INDEX_ASC, index_offset, out, out_len, out_positions);
 }
 
@@ -2839,8 +2911,13 @@ int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit,
     fzb_order_flags(m, fzb_corpus_bias_hi(c), &reversed, &by_score, &one_pass);
     Workspace& w = m->ws;
     u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
-    if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort.tmp, n, raw_count, stream))) return rc;
-    if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
+    if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
+        if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)m->scope.recs, n, m->scope.words, stream))) return rc;
+        if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st))) return rc;
+    } else {
+        if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort.tmp, n, raw_count, stream))) return rc;
+        if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
+    }
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
     const int grid = m->lc.num_cus * 2;
     HIPCHK(fzb_launch_topk_select(w.sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort.hist, ntiles_cap, grid, st));
@@ -2855,7 +2932,7 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
     *out_len = 0;
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
-    if (m->empty && fzb_corpus_bias(c)) return biased_empty_list(c, 0, n, 0, m->config.sort, limit, out, out_len, out_found);
+    if (m->empty && corpus_terms(c)) return biased_empty_list(c, 0, n, 0, m->config.sort, limit, out, out_len, out_found);
     if (m->empty) return fzb_empty_pattern_top(n, m->config.sort, limit, out, out_len, out_found);
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
@@ -2957,7 +3034,7 @@ int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos
 // CompiledPatterns::Empty (an empty needle, no pattern): fzb_empty_pattern_top's rule - the first / last min(limit, n) indices, score 0 - and no
 // positions
 int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
-    if (fzb_corpus_bias(c)) {  // the empty prompt over a biased corpus: the head of the list ordered by the bias
+    if (corpus_terms(c)) {  // the empty prompt over a biased or scoped corpus: the head of the visible list, ordered by the bias
         fzb_match* head = nullptr;
         size_t nhead = 0;
         if (int rc_ = biased_empty_list(c, 0, n, 0, sort, limit, &head, &nhead, out_found)) return rc_;
@@ -3111,6 +3188,7 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
 int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     *out = nullptr;
     *out_len = 0;
     *out_positions = nullptr;

@@ -59,6 +59,12 @@ struct fzb_corpus {
     u32 bias_hi = 0;         // upper bound of the largest positive entry (exact after set, never lowered by an update or an edit)
     void* bias_stage = nullptr;  // landing place of fzb_corpus_update_bias' pairs (indices, then values), kept between calls
     u64 bias_stage_pairs = 0;
+    // the per-haystack tags and the visibility scope (fzb_corpus_set_tags / _set_scope, scope.h): one uint16 of caller-defined bits per
+    // haystack beside the bias, under the same invariant (every entry at or behind the list's length is ZERO); the scope is two host words
+    // that travel as kernel arguments - haystack i is visible iff (tags[i] & require) == require && (tags[i] & exclude) == 0
+    uint16_t* own_tags = nullptr;
+    u64 tags_cap_items = 0;
+    u32 scope_require = 0, scope_exclude = 0;
     u64 regrows = 0;         // reallocations of the canonical arrays so far
     u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
     u64 edit_info[4] = {0, 0, 0, 0};  // the last successful fzb_corpus_remove / _replace (fzb_corpus_edit_info)
@@ -75,6 +81,8 @@ inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c
 // the corpus' score bias as the queries see it: nullptr / 0 without one
 inline const int16_t* fzb_corpus_bias(const fzb_corpus* c) { return c->has_bias ? c->own_bias : nullptr; }
 inline u32 fzb_corpus_bias_hi(const fzb_corpus* c) { return c->has_bias ? c->bias_hi : 0; }
+// an active scope: (0, 0) is no scope, and a corpus without one takes the launches it took before tags existed
+inline bool fzb_corpus_scoped(const fzb_corpus* c) { return c->own_tags && (c->scope_require | c->scope_exclude) != 0; }
 
 // A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
 // null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).
@@ -111,6 +119,24 @@ struct OutStaging {
 };
 int fzb_out_ensure(OutStaging& o, size_t count);  // host.hip
 void fzb_out_release(OutStaging& o);
+
+// The scratch of a query over a corpus with an active scope (scope.h; host.hip's apply_terms), of either matcher type: the producer - the
+// pipeline, the multi-pattern composition - writes its index-ordered records here, one per haystack of the range at most, so nothing is
+// truncated ahead of the drop and `found` stays exact; `words` = its count pair; bitmap / tiles = the flag pass' words and per-tile counts.
+// Grown through fzb_grow_dev, touched only while the scope is active, sized ahead by fzb_matcher_reserve / fzb_multi_matcher_reserve on a
+// corpus that carries tags.
+struct ScopeScratch {
+    fzb_match_rec* recs = nullptr;
+    size_t recs_cap = 0;
+    u64* bitmap = nullptr;
+    size_t bitmap_words = 0;
+    u32* tiles = nullptr;
+    size_t tiles_cap = 0;
+    u32* words = nullptr;
+    size_t words_cap = 0;
+};
+int fzb_scope_ensure(ScopeScratch& s, size_t count);  // host.hip
+void fzb_scope_release(ScopeScratch& s);
 
 // A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle
 // (host.hip) computes all of it and makes no HIP call.  fzb_matcher_set_pattern / _set_config replace it as a whole.
@@ -204,6 +230,7 @@ struct MatcherState : OutStaging {
     // sharded top-`limit` queries, on the root: the count pairs of the shards whose selected runs are copied (two words per shard)
     u32* top_words = nullptr;
     size_t top_words_cap = 0;  // in words
+    ScopeScratch scope;        // queries over a corpus with an active scope: the pipeline's records ahead of the drop
 };
 
 struct fzb_matcher : CompiledNeedle, MatcherState {};
@@ -257,6 +284,7 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
+    ScopeScratch scope;  // queries over a corpus with an active scope: the composition's records ahead of the drop
     fzb_matcher* order = nullptr;
     std::vector<fzb_multi_matcher*> shard_clones;
     std::vector<int> shard_devices;
@@ -313,5 +341,7 @@ int fzb_sig_sync(fzb_corpus* c, u64 n_valid);
 int fzb_sig_sync_borrowed(fzb_corpus* c);
 // the refusal of an entry point that does not apply the corpus' score bias (host.hip): FZB_OK for an unbiased corpus
 int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead);
+// the same rule for the visibility scope: an entry point honours an active scope or refuses it (FZB_OK without one)
+int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

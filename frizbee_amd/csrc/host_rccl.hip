@@ -212,6 +212,7 @@ static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort,
             local = fzb_fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)n + index_offset) + " > 4294967295 (index offset: " +
                                                 std::to_string(index_offset) + ")");
         else if ((local = fzb_refuse_biased(shard, call, "a single-device call (fzb_match_list, fzb_match_list_top) on the rank that holds the list"))) {
+        } else if ((local = fzb_refuse_scoped(shard, call, "a single-device call (fzb_match_list, fzb_match_list_top) on the rank that holds the list"))) {
         } else if (!empty && !(local = grow(&c->run, &c->run_cap, n)))
             local = produce((fzb_match*)c->run, n ? n : 1, c->words, c->stream);
         if (local) local_msg = fzb_last_error();

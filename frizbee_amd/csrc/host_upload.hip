@@ -990,7 +990,9 @@ hipError_t bias_create(fzb_corpus* c, u64 stage_pairs) {
 }
 
 // sparse "set": bias[idx[k]] = val[k]; the indices are unique (checked on the host), so no two threads write one entry
-__global__ __launch_bounds__(UP_THREADS) void k_bias_scatter(const u32* __restrict__ idx, const int16_t* __restrict__ val, u64 n_pairs, int16_t* __restrict__ bias, u64 len) {
+// (V: int16_t for the bias, uint16_t for the tags - both arrays are 2 bytes per haystack)
+template <typename V>
+__global__ __launch_bounds__(UP_THREADS) void k_bias_scatter(const u32* __restrict__ idx, const V* __restrict__ val, u64 n_pairs, V* __restrict__ bias, u64 len) {
     const u64 stride = (u64)gridDim.x * UP_THREADS;
     for (u64 k = (u64)blockIdx.x * UP_THREADS + threadIdx.x; k < n_pairs; k += stride) {
         const u32 i = idx[k];
@@ -1002,8 +1004,10 @@ __global__ __launch_bounds__(UP_THREADS) void k_bias_scatter(const u32* __restri
 // wave per 64 haystacks.  A haystack whose bit of the pass' bitmap is clear is kept: its rank inside the wave from the wave's ballot, the
 // waves' totals through LDS, the tile's base = the pass' scanned per-tile kept count.  Written to scratch (a removal moves entries towards
 // lower indices, into tiles another workgroup may not have read yet); the copy into place is a separate, stream-ordered step.
-__global__ __launch_bounds__(SBIAS_TILE) void k_bias_compact(const int16_t* __restrict__ bias, const u32* __restrict__ bitmap, const u64* __restrict__ tile_cnt, u64 n, u64 i0,
-                                                             int16_t* __restrict__ out, u64 out_cap) {
+// The tags array (scope.h) goes through the same kernel: V as for k_bias_scatter.
+template <typename V>
+__global__ __launch_bounds__(SBIAS_TILE) void k_bias_compact(const V* __restrict__ bias, const u32* __restrict__ bitmap, const u64* __restrict__ tile_cnt, u64 n, u64 i0,
+                                                             V* __restrict__ out, u64 out_cap) {
     __shared__ u32 s_total[SBIAS_WAVES];
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 t0 = i0 + (u64)blockIdx.x * SBIAS_TILE;
@@ -1012,6 +1016,32 @@ __global__ __launch_bounds__(SBIAS_TILE) void k_bias_compact(const int16_t* __re
     if (lane == 0) s_total[wave] = (u32)__popcll(mask);
     __syncthreads();
     if (kept) sbias_tile_place(bias, t0, wave, lane, mask, s_total, tile_cnt[blockIdx.x], out, out_cap);
+}
+
+// ---- the per-haystack tags in step with the list (scope.h; the query side is host.hip's apply_terms) ---------------------------------
+// The array lives beside the bias and obeys its invariant: every entry at or behind the list's length is ZERO, so appended haystacks
+// start with tag 0.  Room for `items` entries; what is resident moves device to device.  On an error nothing has changed.
+hipError_t tags_ensure_room(fzb_corpus* c, u64 items) {
+    if (c->own_tags && c->tags_cap_items >= items) return hipSuccess;
+    void* p = nullptr;
+    const u64 cap = std::max<u64>(items, 8);
+    hipError_t e = fzb_dev_alloc(&p, cap * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMemset(p, 0, cap * sizeof(uint16_t));
+    if (e == hipSuccess && c->own_tags && c->dev.n) e = hipMemcpy(p, c->own_tags, c->dev.n * sizeof(uint16_t), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        if (p) (void)hipFree(p);
+        return e;
+    }
+    if (c->own_tags) (void)hipFree(c->own_tags);
+    c->own_tags = (uint16_t*)p;
+    c->tags_cap_items = cap;
+    return hipSuccess;
+}
+// the array (all zero on first use, sized for max(len, reserved items)) and the landing place of an update's pairs (shared with the bias)
+hipError_t tags_create(fzb_corpus* c, u64 stage_pairs) {
+    hipError_t e = tags_ensure_room(c, std::max(c->dev.n, c->cap_items));
+    if (e == hipSuccess) e = bias_stage_ensure(c, stage_pairs);  // (as bias_create: up to BIAS_STAGE_MIN_PAIRS pairs of a later update allocate nothing)
+    return e;
 }
 
 }  // namespace
@@ -1059,7 +1089,7 @@ int fzb_corpus_update_bias(fzb_corpus* c, const uint32_t* indices, const int16_t
     if (e == hipSuccess) e = hipMemcpy(c->bias_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_bias: ") + hipGetErrorString(e));
     const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
-    hipLaunchKernelGGL(k_bias_scatter, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->bias_stage, (const int16_t*)((const u8*)c->bias_stage + n * 4), (u64)n, c->own_bias,
+    hipLaunchKernelGGL(k_bias_scatter<int16_t>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->bias_stage, (const int16_t*)((const u8*)c->bias_stage + n * 4), (u64)n, c->own_bias,
                        c->dev.n);
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
@@ -1092,6 +1122,85 @@ int fzb_corpus_bias_info(const fzb_corpus* c, uint64_t out[4]) {
     return FZB_OK;
 }
 
+int fzb_corpus_set_tags(fzb_corpus* c, const uint16_t* values, size_t n) {
+    if (!c || (n && !values)) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    int rc = grow_begin(c, "fzb_corpus_set_tags");
+    if (rc) return rc;
+    if ((u64)n != c->dev.n)
+        return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_set_tags: " + std::to_string(n) + " values for the corpus' " + std::to_string(c->dev.n) + " haystacks (one per haystack)");
+    hipError_t e = tags_create(c, 0);
+    if (e == hipSuccess && n) e = hipMemcpy(c->own_tags, values, n * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_set_tags: ") + hipGetErrorString(e));
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
+}
+
+int fzb_corpus_update_tags(fzb_corpus* c, const uint32_t* indices, const uint16_t* values, size_t n) {
+    if (!c || (n && (!indices || !values))) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    int rc = grow_begin(c, "fzb_corpus_update_tags");
+    if (rc) return rc;
+    if (!n) return FZB_OK;
+    for (size_t k = 0; k < n; k++)
+        if (indices[k] >= c->dev.n)
+            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_tags: index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " +
+                                                 std::to_string(c->dev.n) + " haystacks");
+    std::vector<u32> order(n);
+    for (size_t k = 0; k < n; k++) order[k] = (u32)k;
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return indices[a] != indices[b] ? indices[a] < indices[b] : a < b; });
+    for (size_t k = 1; k < n; k++)
+        if (indices[order[k]] == indices[order[k - 1]])
+            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_tags: haystack " + std::to_string(indices[order[k]]) + " is named twice (positions " + std::to_string(order[k - 1]) + " and " +
+                                                 std::to_string(order[k]) + ")");
+    // the pairs travel in one copy: n indices, then n values
+    std::vector<u8> pairs(n * 6);
+    memcpy(pairs.data(), indices, n * 4);
+    memcpy(pairs.data() + n * 4, values, n * 2);
+    hipError_t e = tags_create(c, n);  // (a corpus without tags: an all-zero array first)
+    if (e == hipSuccess) e = hipMemcpy(c->bias_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_tags: ") + hipGetErrorString(e));
+    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
+    hipLaunchKernelGGL(k_bias_scatter<uint16_t>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->bias_stage, (const uint16_t*)((const u8*)c->bias_stage + n * 4), (u64)n,
+                       c->own_tags, c->dev.n);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_tags (scatter): ") + hipGetErrorString(e));
+    return FZB_OK;
+}
+
+int fzb_corpus_clear_tags(fzb_corpus* c) {
+    int rc = grow_begin(c, "fzb_corpus_clear_tags");
+    if (rc) return rc;
+    if (c->own_tags) {  // (complete on return, and the scope changes only then)
+        HIPCHK(hipMemset(c->own_tags, 0, c->tags_cap_items * sizeof(uint16_t)));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    c->scope_require = c->scope_exclude = 0;
+    return FZB_OK;
+}
+
+int fzb_corpus_set_scope(fzb_corpus* c, uint16_t require, uint16_t exclude) {
+    if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    if (!c->own_tags) {  // the first scope of a corpus without tags: an all-zero array, under the set-up calls' rules
+        int rc = grow_begin(c, "fzb_corpus_set_scope");
+        if (rc) return rc;
+        const hipError_t e = tags_create(c, 0);
+        if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_set_scope: ") + hipGetErrorString(e));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    c->scope_require = require;  // host only: the two words travel as kernel arguments of the next query
+    c->scope_exclude = exclude;
+    return FZB_OK;
+}
+
+int fzb_corpus_scope_info(const fzb_corpus* c, uint64_t out[4]) {
+    if (!c || !out) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    out[0] = fzb_corpus_scoped(c) ? 1 : 0;
+    out[1] = c->own_tags ? c->tags_cap_items : 0;
+    out[2] = (u64)c->scope_require | ((u64)c->scope_exclude << 16);
+    out[3] = c->own_tags ? c->tags_cap_items * sizeof(uint16_t) : 0;
+    return FZB_OK;
+}
+
 int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
     int rc = grow_begin(c, "fzb_corpus_reserve");
     if (rc) return rc;
@@ -1106,6 +1215,7 @@ int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
     if (e == hipSuccess) e = stage_ensure_room(c, c->cap_items - c->dev.n, c->cap_bytes - c->dev.total_bytes);
     if (e == hipSuccess) e = ensure_tiles_scratch(c, up_tiles(c->cap_items) + 1);
     if (e == hipSuccess && c->own_bias) e = bias_ensure_room(c, c->cap_items);  // the bias follows the item capacity: appends within the room allocate nothing
+    if (e == hipSuccess && c->own_tags) e = tags_ensure_room(c, c->cap_items);  // and so do the tags
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_reserve: ") + hipGetErrorString(e));
     if (!fzb_knobs().no_filter_view) {
         const u64 live_units = c->dev.vbytes ? c->view_units : 0;
@@ -1156,6 +1266,7 @@ int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_o
     e = canon_ensure_room(c, n_old + n_new, total, true);
     // (the bias array regrows with the items, device to device; the new haystacks' entries are zero by the invariant)
     if (e == hipSuccess && c->own_bias) e = bias_ensure_room(c, std::max<u64>(n_old + n_new, c->cap_items));
+    if (e == hipSuccess && c->own_tags) e = tags_ensure_room(c, std::max<u64>(n_old + n_new, c->cap_items));  // (the tags too: new haystacks start with tag 0)
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_append (room for the batch): ") + hipGetErrorString(e));
     batch_lay_out((const u8*)c->stage_raw, (const u64*)c->stage_ends, n_new, 0, (const u64*)c->stage_tiles, (u8*)c->own_bytes, used, c->own_ends, n_old, c->dev.ends_u64 != 0, true);
     c->h2d_bytes += raw + (u64)n_new * 8;
@@ -1191,6 +1302,7 @@ int fzb_corpus_truncate(fzb_corpus* c, size_t n) {
     if (old_used > used) HIPCHK(hipMemsetAsync((u8*)c->own_bytes + used, 0, old_used - used, nullptr));  // gaps and tail are zero
     hipError_t e = measure_resident(c, n);
     if (e == hipSuccess && c->own_bias && c->has_bias) e = hipMemsetAsync(c->own_bias + n, 0, (c->dev.n - n) * sizeof(int16_t), nullptr);  // the cut haystacks' biases
+    if (e == hipSuccess && c->own_tags) e = hipMemsetAsync(c->own_tags + n, 0, (c->dev.n - n) * sizeof(uint16_t), nullptr);  // and their tags
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_truncate: ") + hipGetErrorString(e));
     c->dev.n = n;
     c->dev.total_bytes = used + 96;
@@ -1246,6 +1358,7 @@ int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t 
         case 7: src = c->dev.vlong; bytes = view ? (size_t)c->dev.n_long * 4 : 0; break;
         case 8: src = c->dev.sig; bytes = c->dev.sig ? (size_t)n * 4 : 0; break;
         case 9: src = c->own_bias; bytes = c->has_bias ? (size_t)n * sizeof(int16_t) : 0; break;
+        case 10: src = c->own_tags; bytes = c->own_tags ? (size_t)n * sizeof(uint16_t) : 0; break;
         default: return fzb_fail(FZB_ERR_INVALID, "fzb_debug_corpus_read: unknown array " + std::to_string(what));
     }
     *out_bytes = bytes;
@@ -1602,10 +1715,12 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     u8* aux = nullptr;
     u8* work = nullptr;
     int16_t* bias_work = nullptr;  // a removal on a biased corpus: the kept biases of the suffix pass through here
+    uint16_t* tags_work = nullptr;  // ... on a corpus with tags: the kept tags
     auto done = [&](int rc) {
         if (aux) (void)hipFree(aux);
         if (work) (void)hipFree(work);
         if (bias_work) (void)hipFree(bias_work);
+        if (tags_work) (void)hipFree(tags_work);
         return rc;
     };
     auto hip_fail = [&](hipError_t e, const char* where) { return done(fzb_fail(FZB_ERR_HIP, what + " (" + where + "): " + hipGetErrorString(e))); };
@@ -1656,6 +1771,11 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
         e = fzb_dev_alloc((void**)&bias_work, bias_work_bytes);
         if (e != hipSuccess) { bias_work = nullptr; return hip_fail(e, "scratch for the score bias"); }
     }
+    const u64 tags_work_bytes = (!replace && c->own_tags) ? round_up((n - i0) * sizeof(uint16_t), 16) : 0;  // 2 bytes per suffix haystack, as the bias
+    if (tags_work_bytes) {
+        e = fzb_dev_alloc((void**)&tags_work, tags_work_bytes);
+        if (e != hipSuccess) { tags_work = nullptr; return hip_fail(e, "scratch for the tags"); }
+    }
     if (total > c->cap_bytes) {
         e = canon_ensure_room(c, n_new, total, true);
         if (e != hipSuccess) return hip_fail(e, "room for the new content");
@@ -1677,10 +1797,16 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     const bool had_view = c->dev.vbytes != nullptr;
     if (e == hipSuccess) e = measure_resident(c, n_new);
     if (e == hipSuccess && bias_work) {  // the kept entries from i0 on, compacted through scratch, copied into place, the freed tail cleared (a replace keeps every bias where it is)
-        hipLaunchKernelGGL(k_bias_compact, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const int16_t*)c->own_bias, (const u32*)d_bitmap, (const u64*)d_tc, n, i0, bias_work,
+        hipLaunchKernelGGL(k_bias_compact<int16_t>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const int16_t*)c->own_bias, (const u32*)d_bitmap, (const u64*)d_tc, n, i0, bias_work,
                            n - i0);
         if (st.new_items) e = hipMemcpyAsync(c->own_bias + i0, bias_work, st.new_items * sizeof(int16_t), hipMemcpyDeviceToDevice, nullptr);
         if (e == hipSuccess && n > n_new) e = hipMemsetAsync(c->own_bias + n_new, 0, (n - n_new) * sizeof(int16_t), nullptr);
+    }
+    if (e == hipSuccess && tags_work) {  // the tags through the same pass (a replace keeps every tag where it is)
+        hipLaunchKernelGGL(k_bias_compact<uint16_t>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const uint16_t*)c->own_tags, (const u32*)d_bitmap, (const u64*)d_tc, n, i0,
+                           tags_work, n - i0);
+        if (st.new_items) e = hipMemcpyAsync(c->own_tags + i0, tags_work, st.new_items * sizeof(uint16_t), hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess && n > n_new) e = hipMemsetAsync(c->own_tags + n_new, 0, (n - n_new) * sizeof(uint16_t), nullptr);
     }
     if (e != hipSuccess) return hip_fail(e, "layout");
     c->dev.n = n_new;
@@ -1696,7 +1822,7 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     c->edit_info[0] = i0;
     c->edit_info[1] = st.new_bytes + (old_used > new_used ? old_used - new_used : 0) + st.new_items * esz;
     c->edit_info[2] = c->dev.vbytes ? up_tiles(n_new) - (had_view ? std::min(i0, n_new) / UP_TILE : 0) : 0;
-    c->edit_info[3] = aux_bytes + work_bytes + bias_work_bytes;
+    c->edit_info[3] = aux_bytes + work_bytes + bias_work_bytes + tags_work_bytes;
     return done(FZB_OK);
 }
 

@@ -1,0 +1,71 @@
+// Per-haystack tags and the visibility scope of a resident corpus: the predicate and the arithmetic of the drop pass, as plain functions
+// for the device AND the host (kernels_topk.hip calls them; tests/kernel_host/scope_host.cpp compiles them for the CPU and
+// tests/test_scope_host.py fuzzes them against numpy).
+//
+// The reference has no such term: a picker filters its list ("hide ignored files", "only this folder") before it hands it to `match_list`.
+// Here the corpus keeps one uint16 of caller-defined bits per haystack and a scope (require, exclude); haystack i is visible iff
+//   (tags[i] & require) == require  &&  (tags[i] & exclude) == 0
+// and a query over a scoped corpus returns what it returns over the visible haystacks alone, every index mapped back to the full list.
+// The drop runs between the scorers and the bias / selection / ordering stage, over index-ordered records, in two launches:
+//   * the flag pass (k_scope_flag): scope_tile_keeps per record - the wave's kept mask is a ballot on the device, a loop over the lanes
+//     on the host -, one 64-bit word per 64 records and one kept count per 1024-record tile;
+//   * the compaction (k_scope_compact): a workgroup owns the run of tiles scope_block_tiles gives it, the kept records in front of the
+//     run are the sum of the earlier tiles' counts, inside a tile a record's place is scope_place - no atomics, nothing ordered between
+//     workgroups, never in place.  scope_counts is the (written, found) pair the last workgroup publishes.
+// The kernels and the host walk call the SAME functions; only the ballot, the shuffles and the barriers between them differ.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define FZB_SCOPE_FN __host__ __device__ __forceinline__
+#else
+#define FZB_SCOPE_FN inline
+#endif
+
+#define SCOPE_TILE 1024  // records per tile of the drop pass: the tile of every bitmap + per-tile count pair here (FZB_TILE)
+#define SCOPE_WORDS (SCOPE_TILE / 64)
+
+// a record as the drop pass sees it: the haystack's index, then score / exact / valid - moved as a whole, never looked into
+struct scope_rec {
+    uint32_t index, rest;
+};
+
+// the scope as the kernels take it: two words that travel as kernel arguments
+FZB_SCOPE_FN bool scope_visible(uint32_t tag, uint32_t require, uint32_t exclude) { return (tag & require) == require && (tag & exclude) == 0; }
+
+// the tag of the haystack a record belongs to: record index -> haystack first + (index - index_offset) of the corpus; a haystack outside
+// the n_tags entries has tag 0 (the array's invariant: every entry at or behind the list's length is zero)
+FZB_SCOPE_FN uint32_t scope_tag_of(const uint16_t* tags, uint64_t n_tags, uint64_t first, uint32_t index_offset, uint32_t index) {
+    const uint64_t h = first + (uint64_t)(uint32_t)(index - index_offset);
+    return h < n_tags ? tags[h] : 0u;
+}
+
+// ---- the flag pass: slot (0 .. SCOPE_TILE - 1) of tile `tile` of a list of n records ----
+FZB_SCOPE_FN bool scope_tile_keeps(const scope_rec* recs, uint64_t n, uint64_t tile, uint32_t slot, const uint16_t* tags, uint64_t n_tags, uint64_t first, uint32_t index_offset,
+                                   uint32_t require, uint32_t exclude) {
+    const uint64_t j = tile * SCOPE_TILE + slot;
+    return j < n && scope_visible(scope_tag_of(tags, n_tags, first, index_offset, recs[j].index), require, exclude);
+}
+
+// ---- the compaction ----
+// workgroup `block` of `grid` owns the tiles [*t0, *t1) of ntiles: a contiguous run, so that what lies in front of it is a prefix
+FZB_SCOPE_FN void scope_block_tiles(uint32_t ntiles, uint32_t grid, uint32_t block, uint32_t* t0, uint32_t* t1) {
+    const uint32_t per = (ntiles + grid - 1) / grid;
+    const uint64_t a = (uint64_t)block * per;
+    *t0 = a < ntiles ? (uint32_t)a : ntiles;
+    *t1 = (uint64_t)*t0 + per < ntiles ? *t0 + per : ntiles;
+}
+// the place of the record at bit `lane` of a kept word: kept records in front of the tile + in front of the word inside the tile + in
+// front of the lane inside the word
+FZB_SCOPE_FN uint32_t scope_place(uint32_t tile_base, uint32_t word_base, uint64_t bits, uint32_t lane) {
+    return tile_base + word_base + (uint32_t)__builtin_popcountll(bits & (((uint64_t)1 << lane) - 1));
+}
+// a kept record goes to its place unless the destination has no room for it (the first `capacity` kept records are written)
+FZB_SCOPE_FN void scope_store(scope_rec* out, uint32_t capacity, uint32_t place, const scope_rec* in, uint64_t j) {
+    if (place < capacity) out[place] = in[j];
+}
+// what the caller reads: [0] = records written = min(kept, capacity), [1] = kept = the visible matches (> capacity: the list was cut)
+FZB_SCOPE_FN void scope_counts(uint32_t kept, uint32_t capacity, uint32_t* pair) {
+    pair[0] = kept < capacity ? kept : capacity;
+    pair[1] = kept;
+}

@@ -55,7 +55,9 @@ FZB_SBIAS_FN bool sbias_tile_keeps(const uint32_t* bitmap, uint64_t n, uint64_t 
 }
 // step 2, every KEPT lane, once every wave's total is known: the value goes to tile_base + kept in front of my wave + kept in front of my
 // lane; out has room for out_cap entries (the suffix' length: a place beyond it cannot occur and is never written)
-FZB_SBIAS_FN void sbias_tile_place(const int16_t* values, uint64_t t0, uint32_t wave, uint32_t lane, uint64_t kept_mask, const uint32_t* wave_totals, uint64_t tile_base, int16_t* out,
+// (V: the array's 2-byte value type - int16_t for the bias, uint16_t for the corpus' tags, which follow a removal through the same pass)
+template <typename V>
+FZB_SBIAS_FN void sbias_tile_place(const V* values, uint64_t t0, uint32_t wave, uint32_t lane, uint64_t kept_mask, const uint32_t* wave_totals, uint64_t tile_base, V* out,
                                    uint64_t out_cap) {
     const uint64_t dst = tile_base + sbias_wave_base(wave_totals, wave) + sbias_lane_rank(kept_mask, lane);
     if (dst < out_cap) out[dst] = values[t0 + (uint64_t)wave * 64 + lane];

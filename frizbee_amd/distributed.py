@@ -192,6 +192,9 @@ class ShardExchange:
         if corpus is not None and corpus.bias_info()["has_bias"]:
             raise FrizbeeError(1, "ShardExchange: the shard carries a score bias, which the exchange's merge does not apply; query the list on one device "
                                   "(Matcher.match_list / match_list_top), or Corpus.set_bias(None) first")
+        if corpus is not None and corpus.scope_info()["active"]:  # (tags and scopes belong to single-device lists: shards have none)
+            raise FrizbeeError(1, "ShardExchange: the shard has an active scope, which the exchange does not apply; query the list on one device "
+                                  "(Matcher.match_list / match_list_top), or Corpus.set_scope(0, 0) first")
 
     def ordered_query(self, run, matcher, slot=0, stream=None, copy=False, max_retries=6, corpus=None):
         """One query, every rank together, the ordered list on the root (None elsewhere) - `match_list_parallel`'s result

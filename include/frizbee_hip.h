@@ -253,6 +253,58 @@ int fzb_corpus_clear_bias(fzb_corpus* c);
  * level -, [3] = device bytes (the array and the landing place of an update's pairs) */
 int fzb_corpus_bias_info(const fzb_corpus* c, uint64_t out[4]);
 
+/* PER-HAYSTACK TAGS AND A VISIBILITY SCOPE, applied on the device.  The other per-item term every picker has is a filter: "hide git-ignored
+ * files", "hide hidden files", "only tracked files", "not under vendor/", "only this workspace folder".  A corpus the library owns can carry
+ * one uint16 of TAGS per haystack - 16 caller-defined bits - and a SCOPE, a pair (require, exclude) of uint16 masks.  Haystack i is visible iff
+ *     (tags[i] & require) == require  &&  (tags[i] & exclude) == 0
+ * (a bit in both masks hides every haystack).  The contract is one sentence:
+ *     A query over a scoped corpus returns what the same query returns over a fzb_corpus_upload of the visible haystacks alone, in their
+ *     order, with every `index` mapped back to the haystack's index in the full list.
+ * The map is monotone, so the reference's ordering rule (reverse for the *Desc strategies, then the stable descending sort by score:
+ * src/matcher/mod.rs:215-221, src/sort.rs:6-40) and the tie-breaks at the cut of a top-`limit` call are preserved; `found` counts visible
+ * matches only; scores, `exact` and the matched positions of a visible haystack are untouched; a score bias, when present, is added as before,
+ * to the visible records; the range forms number the visible haystacks of the range, index = index_offset + (i - first).  The records of
+ * hidden haystacks are dropped between the scorers (or the multi-pattern composition) and the bias / selection / ordering stage: a flag pass
+ * and a stable compaction over the index-ordered records (frizbee_amd/csrc/scope.h; two short launches), ahead of which the records go to a
+ * scratch of the matcher's with room for one per haystack, so `found` over a scoped corpus is always exact.  The _device forms write
+ * dev_count[0] = min(visible matches, capacity), dev_count[1] = visible matches, and the first `capacity` of them.
+ * The tags are a property of the LIST, like the bias: they survive fzb_matcher_set_pattern / fzb_multi_matcher_set_patterns and follow the
+ * editing family under the bias' invariant (every entry at or behind the list's length is zero) - fzb_corpus_reserve grows the array with the
+ * item capacity, appended haystacks start with tag 0, fzb_corpus_truncate clears the cut entries, fzb_corpus_remove / _remove_device compact
+ * the kept entries through the bias' pass (2 more bytes of scratch per haystack from the first removed one on, counted in
+ * fzb_corpus_edit_info's out[3]), fzb_corpus_replace leaves them alone.  Changing the SCOPE is host-only: two words that travel as kernel
+ * arguments, no device work, no allocation - the "toggle ignored files" keystroke.  A scope of (0, 0) is no scope, and a corpus without an
+ * active scope, with or without tags, takes exactly the launches and allocations it took before.  After fzb_matcher_reserve /
+ * fzb_multi_matcher_reserve on a corpus that carries tags no scoped query allocates device memory.  Shards (fzb_sharded_corpus) have no tags.
+ * Every entry point that takes an fzb_corpus either HONOURS an active scope or REFUSES it with FZB_ERR_INVALID (the message says "scope" and
+ * names the call to use instead); none ignores the scope.  Honoured: fzb_match_list / _into / _device / _sorted_device / _parallel,
+ * fzb_match_list_top / _top_device, fzb_match_list_top_indices / _device, fzb_multi_match_list / _into / _device / _top / _parallel,
+ * fzb_multi_match_list_top_indices_fused / _device - an empty needle and an empty pattern list included (the picker's empty prompt with
+ * "hide ignored" switched on: the visible haystacks, score 0 or the clamped bias; host work for the single matcher: one copy of the tags).
+ * Refused: the list-order matched-indices forms fzb_match_list_indices / _indices_into and fzb_multi_match_list_indices / _indices_into (use
+ * the top-`limit` forms with positions), the composed fzb_multi_match_list_top_indices (use the fused form), fzb_match_list_parallel_rccl /
+ * fzb_multi_match_list_parallel_rccl (a scoped shard is a rank-local failure that travels in the gathered status word like any other);
+ * frizbee_amd.distributed.ShardExchange raises for a scoped shard it is shown (check_corpus).
+ * These are SET-UP calls under the bias' rules: only for a corpus made by fzb_corpus_upload (a borrowed one gets FZB_ERR_INVALID), they wait
+ * for the device's outstanding work on entry and are complete on return, must not run concurrently with queries over the same corpus, and an
+ * error leaves the corpus as it was. */
+/* tags[i] = values[i] for every haystack: n must equal the corpus length (FZB_ERR_INVALID otherwise).  One host-to-device copy; the array is
+ * created on first use, sized for max(length, reserved items).  The scope stays as it is. */
+int fzb_corpus_set_tags(fzb_corpus* c, const uint16_t* values, size_t n);
+/* Sparse set: tags[indices[k]] = values[k].  Checked on the host: an index >= the corpus length or a repeated index gives FZB_ERR_INVALID
+ * naming the position, nothing written.  One copy of the pairs (through the landing place fzb_corpus_update_bias uses) and one scatter
+ * kernel (up to 4096 pairs allocate nothing once the corpus carries tags).  On a corpus without tags an all-zero array is created first.
+ * n == 0 is a no-op. */
+int fzb_corpus_update_tags(fzb_corpus* c, const uint32_t* indices, const uint16_t* values, size_t n);
+/* all tags 0 and the scope (0, 0): the corpus answers as before any tags; the array is kept */
+int fzb_corpus_clear_tags(fzb_corpus* c);
+/* The scope of the queries that follow.  Host only; on a corpus without tags an all-zero array is created first (that once is a set-up call as
+ * above).  (0, 0) switches the scope off. */
+int fzb_corpus_set_scope(fzb_corpus* c, uint16_t require, uint16_t exclude);
+/* out[0] = a scope is active (0/1), [1] = entries the tags array has room for (0: the corpus carries no tags), [2] = require | exclude << 16,
+ * [3] = device bytes of the array (the landing place of an update's pairs is shared with the bias and counted in fzb_corpus_bias_info) */
+int fzb_corpus_scope_info(const fzb_corpus* c, uint64_t out[4]);
+
 /* `Matcher::match_list(&haystacks)` (src/matcher/mod.rs:212-222) = `match_list_into(.., offset 0)` ->
 * `Specialized::match_list::<TYPOS,UNICODE,_>` (src/matcher/algo.rs:78-103) and the reverse / `radix_sort_matches`
  * post-step (src/sort.rs:6-40), all on the GPU.  `*out` is malloc'd by the library
@@ -613,7 +665,7 @@ int fzb_debug_device_allocs(uint64_t* out);
 
 /* test hook: copies one of the corpus' device arrays to the host - what: 0 = canonical bytes up to the padded size + the 96-byte tail,
  * 1 = end offsets (u32 or u64, fzb_corpus_info out[9]), 2 = vbytes, 3 = vgofs, 4 = vgnv, 5 = vlen, 6 = vperm, 7 = vlong (2..7: the
- * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them), 9 = the score bias (int16 per haystack, nothing without one).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
+ * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them), 9 = the score bias (int16 per haystack, nothing without one), 10 = the tags (uint16 per haystack, nothing when the corpus has none).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes);
 
 #ifdef __cplusplus

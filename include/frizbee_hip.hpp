@@ -238,6 +238,26 @@ class Corpus {
         check(fzb_corpus_bias_info(h_.get(), o));
         return BiasInfo{o[0], o[1], o[2], o[3]};
     }
+    // Per-haystack tags and a visibility scope (fzb_corpus_set_tags and friends): one uint16 of caller-defined bits per haystack; haystack i
+    // is visible iff (tags[i] & require) == require && (tags[i] & exclude) == 0, and a query returns what it returns over the visible
+    // haystacks alone, every index that of the full list.  The tags belong to the list; set_scope is host-only (the toggle keystroke).
+    void set_tags(const std::vector<uint16_t>& values) { check(fzb_corpus_set_tags(h_.get(), values.data(), values.size())); }
+    void update_tags(const std::vector<uint32_t>& indices, const std::vector<uint16_t>& values) {
+        if (indices.size() != values.size()) throw Error(FZB_ERR_INVALID, "Corpus::update_tags: one value per index");
+        check(fzb_corpus_update_tags(h_.get(), indices.data(), values.data(), indices.size()));
+    }
+    void clear_tags() { check(fzb_corpus_clear_tags(h_.get())); }
+    void set_scope(uint16_t require = 0, uint16_t exclude = 0) { check(fzb_corpus_set_scope(h_.get(), require, exclude)); }
+    struct ScopeInfo {
+        uint64_t active, capacity, scope, device_bytes;
+        uint16_t require() const { return (uint16_t)(scope & 0xFFFF); }
+        uint16_t exclude() const { return (uint16_t)(scope >> 16); }
+    };
+    ScopeInfo scope_info() const {
+        uint64_t o[4] = {};
+        check(fzb_corpus_scope_info(h_.get(), o));
+        return ScopeInfo{o[0], o[1], o[2], o[3]};
+    }
 
   private:
     struct Del { void operator()(fzb_corpus* c) const { fzb_corpus_free(c); } };

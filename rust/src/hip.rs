@@ -104,6 +104,12 @@ extern "C" {
     fn fzb_corpus_update_bias(c: *mut c_void, indices: *const u32, values: *const i16, n: usize) -> c_int;
     fn fzb_corpus_clear_bias(c: *mut c_void) -> c_int;
     fn fzb_corpus_bias_info(c: *const c_void, out: *mut u64) -> c_int;
+    // per-haystack tags and a visibility scope: haystack i is visible iff (tags[i] & require) == require && (tags[i] & exclude) == 0
+    fn fzb_corpus_set_tags(c: *mut c_void, values: *const u16, n: usize) -> c_int;
+    fn fzb_corpus_update_tags(c: *mut c_void, indices: *const u32, values: *const u16, n: usize) -> c_int;
+    fn fzb_corpus_clear_tags(c: *mut c_void) -> c_int;
+    fn fzb_corpus_set_scope(c: *mut c_void, require: u16, exclude: u16) -> c_int;
+    fn fzb_corpus_scope_info(c: *const c_void, out: *mut u64) -> c_int;
     fn fzb_corpus_len(c: *const c_void) -> usize;
     fn fzb_match_list(m: *mut c_void, c: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_match_list_into(m: *mut c_void, c: *const c_void, first: usize, count: usize, index_offset: u32, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
@@ -267,6 +273,31 @@ impl HipCorpus {
     pub fn bias_info(&self) -> [u64; 4] {
         let mut out = [0u64; 4];
         check(unsafe { fzb_corpus_bias_info(self.handle, out.as_mut_ptr()) });
+        out
+    }
+    /// One `u16` of caller-defined bits per haystack (`values.len()` = the list's length).  With `set_scope` they decide which haystacks
+    /// a query sees.  The tags belong to the list: they survive `set_pattern` and follow `append` / `truncate` / `remove` / `replace`.
+    pub fn set_tags(&mut self, values: &[u16]) {
+        check(unsafe { fzb_corpus_set_tags(self.handle, values.as_ptr(), values.len()) });
+    }
+    /// `tags[indices[k]] = values[k]` (unique indices in range); a corpus without tags gets an all-zero array first.
+    pub fn update_tags(&mut self, indices: &[u32], values: &[u16]) {
+        assert_eq!(indices.len(), values.len(), "one value per index");
+        check(unsafe { fzb_corpus_update_tags(self.handle, indices.as_ptr(), values.as_ptr(), indices.len()) });
+    }
+    /// Every tag 0 and the scope (0, 0).
+    pub fn clear_tags(&mut self) {
+        check(unsafe { fzb_corpus_clear_tags(self.handle) });
+    }
+    /// Haystack `i` is visible iff `(tags[i] & require) == require && (tags[i] & exclude) == 0`; a query returns what it returns over the
+    /// visible haystacks alone, every index that of the full list.  Host only: the "toggle ignored files" keystroke.  `(0, 0)` is no scope.
+    pub fn set_scope(&mut self, require: u16, exclude: u16) {
+        check(unsafe { fzb_corpus_set_scope(self.handle, require, exclude) });
+    }
+    /// [scope active (0/1), entries the tags array has room for, require | exclude << 16, device bytes].
+    pub fn scope_info(&self) -> [u64; 4] {
+        let mut out = [0u64; 4];
+        check(unsafe { fzb_corpus_scope_info(self.handle, out.as_mut_ptr()) });
         out
     }
 }
