@@ -389,17 +389,20 @@ class Corpus:
         v = np.ascontiguousarray(v, dtype=np.int16)
         _check(lib().fzb_corpus_set_bias(self.h, v.ctypes.data if len(v) else None, len(v)))
 
+    def _update_column(self, fn, who, indices, v):
+        """the sparse update of either column: `v` = the values, already in the column's dtype"""
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        if len(ix) != len(v):
+            raise FrizbeeError(1, f"{who}: {len(ix)} indices for {len(v)} values")
+        _check(fn(self.h, ix.ctypes.data if len(ix) else None, v.ctypes.data if len(v) else None, len(ix)))
+
     def update_bias(self, indices, values):
         """fzb_corpus_update_bias: bias[indices[k]] = values[k] (unique indices in range; what a picker does when a file is opened).  A
         corpus without a bias gets an all-zero one first."""
-        ix = np.ascontiguousarray(indices, dtype=np.uint32)
         v = np.asarray(values)
         if v.size and (v.min() < -32768 or v.max() > 32767):
             raise FrizbeeError(1, "Corpus.update_bias: a bias is a signed 16-bit value")
-        v = np.ascontiguousarray(v, dtype=np.int16)
-        if len(ix) != len(v):
-            raise FrizbeeError(1, f"Corpus.update_bias: {len(ix)} indices for {len(v)} values")
-        _check(lib().fzb_corpus_update_bias(self.h, ix.ctypes.data if len(ix) else None, v.ctypes.data if len(v) else None, len(ix)))
+        self._update_column(lib().fzb_corpus_update_bias, "Corpus.update_bias", indices, np.ascontiguousarray(v, dtype=np.int16))
 
     BIAS_INFO_FIELDS = ("has_bias", "capacity", "bias_hi", "device_bytes")
 
@@ -428,11 +431,7 @@ class Corpus:
         ix = np.asarray(indices)
         if ix.size and (ix.min() < 0 or ix.max() > 0xFFFFFFFF):
             raise FrizbeeError(1, "Corpus.update_tags: an index is an unsigned 32-bit value")
-        ix = np.ascontiguousarray(ix, dtype=np.uint32)
-        v = self._tags16(values, "Corpus.update_tags")
-        if len(ix) != len(v):
-            raise FrizbeeError(1, f"Corpus.update_tags: {len(ix)} indices for {len(v)} values")
-        _check(lib().fzb_corpus_update_tags(self.h, ix.ctypes.data if len(ix) else None, v.ctypes.data if len(v) else None, len(ix)))
+        self._update_column(lib().fzb_corpus_update_tags, "Corpus.update_tags", ix, self._tags16(values, "Corpus.update_tags"))
 
     def clear_tags(self):
         """fzb_corpus_clear_tags: every tag 0 and the scope (0, 0) - the corpus answers as before any tags."""

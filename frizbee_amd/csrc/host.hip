@@ -995,9 +995,9 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_bytes) (void)hipFree(c->own_bytes);
     if (c->own_ends) (void)hipFree(c->own_ends);
     if (c->own_sig) (void)hipFree(c->own_sig);
-    if (c->own_bias) (void)hipFree(c->own_bias);
-    if (c->bias_stage) (void)hipFree(c->bias_stage);
-    if (c->own_tags) (void)hipFree(c->own_tags);
+    fzb_column_release(c->bias);
+    fzb_column_release(c->tags);
+    if (c->pair_stage) (void)hipFree(c->pair_stage);
     for (void* q : c->own_view)
         if (q) (void)hipFree(q);
     for (void* q : {c->stage_raw, c->stage_ends, c->stage_tiles, c->stage_stats})
@@ -1203,7 +1203,7 @@ static int apply_bias(const fzb_corpus* c, fzb_match_rec* recs, const u32* count
 static int apply_terms(const fzb_corpus* c, ScopeScratch& sc, size_t count, fzb_match_rec* dev_out, size_t capacity, u32* dev_count, size_t first, uint32_t index_offset, int grid_max,
                        hipStream_t st) {
     const u32 cap32 = (u32)std::min<size_t>(capacity, 0xFFFFFFFFu);
-    fzb_launch_scope_drop(sc.recs, sc.words, (u32)count, c->own_tags, c->dev.n, first, index_offset, c->scope_require, c->scope_exclude, sc.bitmap, sc.tiles, dev_out, cap32, dev_count,
+    fzb_launch_scope_drop(sc.recs, sc.words, (u32)count, c->tags.data, c->dev.n, first, index_offset, c->scope_require, c->scope_exclude, sc.bitmap, sc.tiles, dev_out, cap32, dev_count,
                           grid_max, st);
     HIPCHK(hipGetLastError());
     return apply_bias(c, dev_out, dev_count, std::min(capacity, count), first, index_offset, grid_max, st);
@@ -1213,12 +1213,6 @@ int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead
     if (!c || !fzb_corpus_scoped(c)) return FZB_OK;
     return fail(FZB_ERR_INVALID, std::string(call) + ": the corpus has an active scope, which this call does not apply; use " + instead + ", or fzb_corpus_set_scope(c, 0, 0) first");
 }
-// entries [first, first + count) of the tags on the host (one device-to-host copy)
-static int fetch_tags(const fzb_corpus* c, size_t first, size_t count, std::vector<uint16_t>& out) {
-    out.assign(count, 0);
-    if (count) HIPCHK(hipMemcpy(out.data(), c->own_tags + first, count * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return FZB_OK;
-}
 // the list's terms, if any: what makes an empty needle's result more than "every index, score 0"
 static bool corpus_terms(const fzb_corpus* c) { return fzb_corpus_bias(c) || fzb_corpus_scoped(c); }
 // "returns biased scores or refuses": the entry points that cannot add the bias say so instead of ignoring it
@@ -1226,10 +1220,11 @@ int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead
     if (!c || !fzb_corpus_bias(c)) return FZB_OK;
     return fail(FZB_ERR_INVALID, std::string(call) + ": the corpus carries a score bias, which this call does not apply; use " + instead + ", or fzb_corpus_clear_bias first");
 }
-// entries [first, first + count) of the bias on the host (one device-to-host copy)
-static int fetch_bias(const fzb_corpus* c, size_t first, size_t count, std::vector<int16_t>& out) {
+// entries [first, first + count) of one of the corpus' columns on the host (one device-to-host copy)
+template <typename V>
+static int fetch_column(const V* col, size_t first, size_t count, std::vector<V>& out) {
     out.assign(count, 0);
-    if (count) HIPCHK(hipMemcpy(out.data(), fzb_corpus_bias(c) + first, count * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (count) HIPCHK(hipMemcpy(out.data(), col + first, count * sizeof(V), hipMemcpyDeviceToHost));
     return FZB_OK;
 }
 // CompiledPatterns::Empty (an empty needle, no pattern) over a BIASED corpus - the picker's empty prompt, "most frecent first": every haystack
@@ -1244,9 +1239,9 @@ static int biased_empty_list(const fzb_corpus* c, size_t first, size_t count, ui
     std::vector<uint16_t> ht;
     const bool biased = fzb_corpus_bias(c) != nullptr, scoped = fzb_corpus_scoped(c);
     if (biased)
-        if (int rc = fetch_bias(c, first, count, hb)) return rc;
+        if (int rc = fetch_column(fzb_corpus_bias(c), first, count, hb)) return rc;
     if (scoped)
-        if (int rc = fetch_tags(c, first, count, ht)) return rc;
+        if (int rc = fetch_column(c->tags.data, first, count, ht)) return rc;
     std::vector<fzb_match> recs;
     recs.reserve(count);
     for (size_t i = 0; i < count; i++)
@@ -1843,7 +1838,7 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (rc) return rc;
     rc = ensure_workspace(m, n);
     if (rc) return rc;
-    if (c->own_tags && (rc = fzb_scope_ensure(m->scope, n))) return rc;  // a corpus that carries tags: toggling its scope between queries allocates nothing
+    if (c->tags.data && (rc = fzb_scope_ensure(m->scope, n))) return rc;  // a corpus that carries tags: toggling its scope between queries allocates nothing
     const bool no_wide = n == c->dev.n && c->dev.max_len != 0 && c->dev.max_len <= (u32)m->lc.sw_lanes;
     if (!m->long_needle && !m->literal_mode && !m->nd.unicode && !no_wide && ((rc = ensure_dp_scratch(m, m->lc.num_cus * 4)) || (rc = ensure_aux_stream(m)))) return rc;
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && fzb_knobs().unicode_multi != 0 && (rc = ensure_dp_scratch(m, m->lc.num_cus * 2))) return rc;
@@ -2170,7 +2165,7 @@ int indices_in_list_order(fzb_matcher* m, const fzb_corpus* c, const uint32_t* s
     if (m->empty) {
         std::vector<int16_t> hb;
         if (biased)
-            if (int rc_ = fetch_bias(c, 0, c->dev.n, hb)) return rc_;
+            if (int rc_ = fetch_column(fzb_corpus_bias(c), 0, c->dev.n, hb)) return rc_;
         recs.resize(count);
         for (size_t i = 0; i < count; i++)
             recs[i] = fzb_match_indices{(uint32_t)i, (uint16_t)(biased ? sbias_clamp_add(0, hb[selection ? selection[i] : i]) : 0), 0, 0, (uint32_t)positions.size(), 0};
@@ -2615,7 +2610,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     for (fzb_matcher* m : mm->spare)
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
-    if (c->own_tags && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags: the composition's records ahead of the drop)
+    if (c->tags.data && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags: the composition's records ahead of the drop)
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
     if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
     return FZB_OK;

@@ -30,6 +30,22 @@ inline hipError_t fzb_dev_alloc(void** p, size_t bytes) {
     return hipMalloc(p, bytes ? bytes : 16);
 }
 
+// A per-haystack side array ("column") of a corpus the library uploaded: one V per haystack beside the end offsets, room for cap_items
+// (host_upload.hip keeps it in step with the list).  Every entry at or behind the list's length is ZERO, so appended
+// haystacks start at 0; the capacity follows the corpus' cap_items once the array exists.  live = the editing family maintains the column:
+// a truncate clears its cut entries, a removal compacts it, a regrow copies it.  A column that is not live is all zero, if it exists at all.
+template <typename V>
+struct ItemColumn {
+    V* data = nullptr;
+    u64 cap_items = 0;
+    bool live = false;
+};
+template <typename V>
+inline void fzb_column_release(ItemColumn<V>& col) {
+    if (col.data) (void)hipFree(col.data);
+    col = ItemColumn<V>{};
+}
+
 struct fzb_corpus {
     CorpusDev dev{};
     void* own_bytes = nullptr;
@@ -51,20 +67,17 @@ struct fzb_corpus {
     void* own_sig = nullptr; // the letter signatures (CorpusDev::sig; also of a borrowed corpus: the library's own array), room for sig_cap_items haystacks
     u64 sig_cap_items = 0;
     int sig_device = -1;     // a borrowed corpus: the device the signatures were built on (where its bytes live)
-    // the per-haystack score bias (fzb_corpus_set_bias / _update_bias, score_bias.h): one int16 per haystack, room for bias_cap_items; every
-    // entry at or behind the list's length is ZERO, so appended haystacks start unbiased.  has_bias = the queries add it (clear keeps the array).
-    int16_t* own_bias = nullptr;
-    u64 bias_cap_items = 0;
-    bool has_bias = false;
+    // the two columns (ItemColumn above) and what is specific to each:
+    // the score bias (fzb_corpus_set_bias / _update_bias, score_bias.h) is live while the queries add it - from set / update to clear,
+    // which keeps the array, zeroed; the tags (fzb_corpus_set_tags / _update_tags / _set_scope, scope.h) are live from the moment they
+    // exist and stay so after a clear.  The scope is two host words that travel as kernel arguments - haystack i is visible iff
+    // (tags[i] & require) == require && (tags[i] & exclude) == 0.
+    ItemColumn<int16_t> bias;
     u32 bias_hi = 0;         // upper bound of the largest positive entry (exact after set, never lowered by an update or an edit)
-    void* bias_stage = nullptr;  // landing place of fzb_corpus_update_bias' pairs (indices, then values), kept between calls
-    u64 bias_stage_pairs = 0;
-    // the per-haystack tags and the visibility scope (fzb_corpus_set_tags / _set_scope, scope.h): one uint16 of caller-defined bits per
-    // haystack beside the bias, under the same invariant (every entry at or behind the list's length is ZERO); the scope is two host words
-    // that travel as kernel arguments - haystack i is visible iff (tags[i] & require) == require && (tags[i] & exclude) == 0
-    uint16_t* own_tags = nullptr;
-    u64 tags_cap_items = 0;
+    ItemColumn<uint16_t> tags;
     u32 scope_require = 0, scope_exclude = 0;
+    void* pair_stage = nullptr;  // landing place of an update's pairs, of either column (indices, then values), kept between calls
+    u64 pair_stage_cap = 0;      // in pairs
     u64 regrows = 0;         // reallocations of the canonical arrays so far
     u64 h2d_bytes = 0;       // bytes copied host to device so far (haystack bytes + 8 per offset)
     u64 edit_info[4] = {0, 0, 0, 0};  // the last successful fzb_corpus_remove / _replace (fzb_corpus_edit_info)
@@ -79,10 +92,10 @@ struct fzb_corpus {
 // the haystacks a matcher's buffers are sized for: the list's length, or what fzb_corpus_reserve made room for
 inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c->cap_items > c->dev.n ? c->cap_items : c->dev.n); }
 // the corpus' score bias as the queries see it: nullptr / 0 without one
-inline const int16_t* fzb_corpus_bias(const fzb_corpus* c) { return c->has_bias ? c->own_bias : nullptr; }
-inline u32 fzb_corpus_bias_hi(const fzb_corpus* c) { return c->has_bias ? c->bias_hi : 0; }
+inline const int16_t* fzb_corpus_bias(const fzb_corpus* c) { return c->bias.live ? c->bias.data : nullptr; }
+inline u32 fzb_corpus_bias_hi(const fzb_corpus* c) { return c->bias.live ? c->bias_hi : 0; }
 // an active scope: (0, 0) is no scope, and a corpus without one takes the launches it took before tags existed
-inline bool fzb_corpus_scoped(const fzb_corpus* c) { return c->own_tags && (c->scope_require | c->scope_exclude) != 0; }
+inline bool fzb_corpus_scoped(const fzb_corpus* c) { return c->tags.data && (c->scope_require | c->scope_exclude) != 0; }
 
 // A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
 // null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).

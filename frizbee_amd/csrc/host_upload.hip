@@ -948,66 +948,73 @@ hipError_t stage_ensure_room(fzb_corpus* c, u64 items, u64 raw) {
     return e;
 }
 
-// ---- the per-haystack score bias in step with the list (score_bias.h; the query side is host.hip's apply_bias) ----------------------
-// Invariant, as for the bytes: every entry at or behind the list's length is ZERO (the array is cleared when allocated, by truncate, by a
-// removal's freed tail and by clear), so appended haystacks start unbiased and a corpus without a bias keeps an all-zero array, if any.
-static_assert(SBIAS_TILE == UP_TILE, "k_bias_compact walks the edit pass' tiles");
-constexpr u64 BIAS_STAGE_MIN_PAIRS = 4096;  // pairs fzb_corpus_update_bias stages without another allocation once the bias exists
+// ---- the per-haystack columns in step with the list: the score bias (score_bias.h; query side: host.hip's apply_bias) and the tags --------
+// (scope.h; host.hip's apply_terms).  One set of rules (ItemColumn, host_internal.h), written once for both.  Invariant, as for the bytes:
+// every entry at or behind the list's length is ZERO (the array is cleared when allocated, by truncate, by a removal's freed tail and by
+// clear), so appended haystacks start at 0 and a column that is not live keeps an all-zero array, if any.
+static_assert(SBIAS_TILE == UP_TILE, "k_col_compact walks the edit pass' tiles");
+constexpr u64 PAIR_STAGE_MIN_PAIRS = 4096;  // pairs an update stages without another allocation once a column exists
 
-// room for `items` entries; what is resident moves device to device.  On an error nothing has changed.
-hipError_t bias_ensure_room(fzb_corpus* c, u64 items) {
-    if (c->own_bias && c->bias_cap_items >= items) return hipSuccess;
+// room for `items` entries; the first n of a live column move device to device.  On an error nothing has changed.
+template <typename V>
+hipError_t col_ensure_room(ItemColumn<V>& col, u64 n, u64 items) {
+    if (col.data && col.cap_items >= items) return hipSuccess;
     void* p = nullptr;
     const u64 cap = std::max<u64>(items, 8);
-    hipError_t e = fzb_dev_alloc(&p, cap * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMemset(p, 0, cap * sizeof(int16_t));
-    if (e == hipSuccess && c->own_bias && c->has_bias && c->dev.n) e = hipMemcpy(p, c->own_bias, c->dev.n * sizeof(int16_t), hipMemcpyDeviceToDevice);
+    hipError_t e = fzb_dev_alloc(&p, cap * sizeof(V));
+    if (e == hipSuccess) e = hipMemset(p, 0, cap * sizeof(V));
+    if (e == hipSuccess && col.live && n) e = hipMemcpy(p, col.data, n * sizeof(V), hipMemcpyDeviceToDevice);
     if (e != hipSuccess) {
         if (p) (void)hipFree(p);
         return e;
     }
-    if (c->own_bias) (void)hipFree(c->own_bias);
-    c->own_bias = (int16_t*)p;
-    c->bias_cap_items = cap;
+    if (col.data) (void)hipFree(col.data);
+    col.data = (V*)p;
+    col.cap_items = cap;
     return hipSuccess;
 }
-hipError_t bias_stage_ensure(fzb_corpus* c, u64 pairs) {
-    if (c->bias_stage && c->bias_stage_pairs >= pairs) return hipSuccess;
+// a column that exists follows the item capacity (reserve, append): appends within the room allocate nothing
+template <typename V>
+hipError_t col_follow(fzb_corpus* c, ItemColumn<V>& col, u64 items) {
+    return col.data ? col_ensure_room(col, c->dev.n, items) : hipSuccess;
+}
+hipError_t pair_stage_ensure(fzb_corpus* c, u64 pairs) {
+    if (c->pair_stage && c->pair_stage_cap >= pairs) return hipSuccess;
     void* p = nullptr;
-    const u64 cap = std::max(pairs, BIAS_STAGE_MIN_PAIRS);
+    const u64 cap = std::max(pairs, PAIR_STAGE_MIN_PAIRS);
     const hipError_t e = fzb_dev_alloc(&p, cap * 6);
     if (e != hipSuccess) return e;
-    if (c->bias_stage) (void)hipFree(c->bias_stage);
-    c->bias_stage = p;
-    c->bias_stage_pairs = cap;
+    if (c->pair_stage) (void)hipFree(c->pair_stage);
+    c->pair_stage = p;
+    c->pair_stage_cap = cap;
     return hipSuccess;
 }
 // the array (all zero on first use, sized for max(len, reserved items)) and the landing place of an update's pairs
-hipError_t bias_create(fzb_corpus* c, u64 stage_pairs) {
-    hipError_t e = bias_ensure_room(c, std::max(c->dev.n, c->cap_items));
-    if (e == hipSuccess) e = bias_stage_ensure(c, stage_pairs);
+template <typename V>
+hipError_t col_create(fzb_corpus* c, ItemColumn<V>& col, u64 stage_pairs) {
+    hipError_t e = col_ensure_room(col, c->dev.n, std::max(c->dev.n, c->cap_items));
+    if (e == hipSuccess) e = pair_stage_ensure(c, stage_pairs);
     return e;
 }
 
-// sparse "set": bias[idx[k]] = val[k]; the indices are unique (checked on the host), so no two threads write one entry
-// (V: int16_t for the bias, uint16_t for the tags - both arrays are 2 bytes per haystack)
+// sparse "set": col[idx[k]] = val[k]; the indices are unique (checked on the host), so no two threads write one entry
+// (V: the column's 2-byte value type - int16_t for the bias, uint16_t for the tags)
 template <typename V>
-__global__ __launch_bounds__(UP_THREADS) void k_bias_scatter(const u32* __restrict__ idx, const V* __restrict__ val, u64 n_pairs, V* __restrict__ bias, u64 len) {
+__global__ __launch_bounds__(UP_THREADS) void k_col_scatter(const u32* __restrict__ idx, const V* __restrict__ val, u64 n_pairs, V* __restrict__ col, u64 len) {
     const u64 stride = (u64)gridDim.x * UP_THREADS;
     for (u64 k = (u64)blockIdx.x * UP_THREADS + threadIdx.x; k < n_pairs; k += stride) {
         const u32 i = idx[k];
-        if (i < len) bias[i] = val[k];
+        if (i < len) col[i] = val[k];
     }
 }
 
-// The remove compaction of the bias array: one workgroup per 1024-haystack SOURCE tile of the suffix from i0 on (the edit pass' tiles), a
+// The remove compaction of a column: one workgroup per 1024-haystack SOURCE tile of the suffix from i0 on (the edit pass' tiles), a
 // wave per 64 haystacks.  A haystack whose bit of the pass' bitmap is clear is kept: its rank inside the wave from the wave's ballot, the
 // waves' totals through LDS, the tile's base = the pass' scanned per-tile kept count.  Written to scratch (a removal moves entries towards
 // lower indices, into tiles another workgroup may not have read yet); the copy into place is a separate, stream-ordered step.
-// The tags array (scope.h) goes through the same kernel: V as for k_bias_scatter.
 template <typename V>
-__global__ __launch_bounds__(SBIAS_TILE) void k_bias_compact(const V* __restrict__ bias, const u32* __restrict__ bitmap, const u64* __restrict__ tile_cnt, u64 n, u64 i0,
-                                                             V* __restrict__ out, u64 out_cap) {
+__global__ __launch_bounds__(SBIAS_TILE) void k_col_compact(const V* __restrict__ col, const u32* __restrict__ bitmap, const u64* __restrict__ tile_cnt, u64 n, u64 i0,
+                                                            V* __restrict__ out, u64 out_cap) {
     __shared__ u32 s_total[SBIAS_WAVES];
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 t0 = i0 + (u64)blockIdx.x * SBIAS_TILE;
@@ -1015,33 +1022,61 @@ __global__ __launch_bounds__(SBIAS_TILE) void k_bias_compact(const V* __restrict
     const u64 mask = __ballot(kept);
     if (lane == 0) s_total[wave] = (u32)__popcll(mask);
     __syncthreads();
-    if (kept) sbias_tile_place(bias, t0, wave, lane, mask, s_total, tile_cnt[blockIdx.x], out, out_cap);
+    if (kept) sbias_tile_place(col, t0, wave, lane, mask, s_total, tile_cnt[blockIdx.x], out, out_cap);
 }
 
-// ---- the per-haystack tags in step with the list (scope.h; the query side is host.hip's apply_terms) ---------------------------------
-// The array lives beside the bias and obeys its invariant: every entry at or behind the list's length is ZERO, so appended haystacks
-// start with tag 0.  Room for `items` entries; what is resident moves device to device.  On an error nothing has changed.
-hipError_t tags_ensure_room(fzb_corpus* c, u64 items) {
-    if (c->own_tags && c->tags_cap_items >= items) return hipSuccess;
-    void* p = nullptr;
-    const u64 cap = std::max<u64>(items, 8);
-    hipError_t e = fzb_dev_alloc(&p, cap * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMemset(p, 0, cap * sizeof(uint16_t));
-    if (e == hipSuccess && c->own_tags && c->dev.n) e = hipMemcpy(p, c->own_tags, c->dev.n * sizeof(uint16_t), hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        if (p) (void)hipFree(p);
-        return e;
-    }
-    if (c->own_tags) (void)hipFree(c->own_tags);
-    c->own_tags = (uint16_t*)p;
-    c->tags_cap_items = cap;
-    return hipSuccess;
+// ---- the set-up calls of a column, behind the entry point's argument checks and grow_begin; `what` = the public call, for the messages ----
+// one value per haystack, from the host; complete on return
+template <typename V>
+int col_set(fzb_corpus* c, ItemColumn<V>& col, const char* what, const V* values, size_t n) {
+    if ((u64)n != c->dev.n)
+        return fzb_fail(FZB_ERR_INVALID, std::string(what) + ": " + std::to_string(n) + " values for the corpus' " + std::to_string(c->dev.n) + " haystacks (one per haystack)");
+    hipError_t e = col_create(c, col, 0);
+    if (e == hipSuccess && n) e = hipMemcpy(col.data, values, n * sizeof(V), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
 }
-// the array (all zero on first use, sized for max(len, reserved items)) and the landing place of an update's pairs (shared with the bias)
-hipError_t tags_create(fzb_corpus* c, u64 stage_pairs) {
-    hipError_t e = tags_ensure_room(c, std::max(c->dev.n, c->cap_items));
-    if (e == hipSuccess) e = bias_stage_ensure(c, stage_pairs);  // (as bias_create: up to BIAS_STAGE_MIN_PAIRS pairs of a later update allocate nothing)
-    return e;
+// col[indices[k]] = values[k] for n > 0 unique indices in range (a column that does not exist yet: an all-zero one first); complete on return
+template <typename V>
+int col_update(fzb_corpus* c, ItemColumn<V>& col, const std::string& what, const uint32_t* indices, const V* values, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (indices[k] >= c->dev.n)
+            return fzb_fail(FZB_ERR_INVALID, what + ": index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " + std::to_string(c->dev.n) +
+                                                 " haystacks");
+    std::vector<u32> order(n);
+    for (size_t k = 0; k < n; k++) order[k] = (u32)k;
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return indices[a] != indices[b] ? indices[a] < indices[b] : a < b; });
+    for (size_t k = 1; k < n; k++)
+        if (indices[order[k]] == indices[order[k - 1]])
+            return fzb_fail(FZB_ERR_INVALID, what + ": haystack " + std::to_string(indices[order[k]]) + " is named twice (positions " + std::to_string(order[k - 1]) + " and " +
+                                                 std::to_string(order[k]) + ")");
+    // the pairs travel in one copy: n indices, then n values
+    std::vector<u8> pairs(n * 6);
+    memcpy(pairs.data(), indices, n * 4);
+    memcpy(pairs.data() + n * 4, values, n * 2);
+    hipError_t e = col_create(c, col, n);
+    if (e == hipSuccess) e = hipMemcpy(c->pair_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, what + ": " + hipGetErrorString(e));
+    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
+    hipLaunchKernelGGL(k_col_scatter<V>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->pair_stage, (const V*)((const u8*)c->pair_stage + n * 4), (u64)n, col.data, c->dev.n);
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, what + " (scatter): " + hipGetErrorString(e));
+    return FZB_OK;
+}
+// a live column back to all zero, the allocation kept; complete on return, and the caller's flags change only then
+template <typename V>
+int col_clear(ItemColumn<V>& col) {
+    if (!col.live) return FZB_OK;
+    HIPCHK(hipMemset(col.data, 0, col.cap_items * sizeof(V)));
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
+}
+// truncate: the entries of the cut haystacks [n, n_old)
+template <typename V>
+hipError_t col_truncate(ItemColumn<V>& col, u64 n_old, u64 n) {
+    return col.live ? hipMemsetAsync(col.data + n, 0, (n_old - n) * sizeof(V), nullptr) : hipSuccess;
 }
 
 }  // namespace
@@ -1051,139 +1086,80 @@ extern "C" {
 int fzb_corpus_set_bias(fzb_corpus* c, const int16_t* values, size_t n) {
     if (!c || (n && !values)) return fzb_fail(FZB_ERR_INVALID, "null argument");
     int rc = grow_begin(c, "fzb_corpus_set_bias");
+    if (!rc) rc = col_set(c, c->bias, "fzb_corpus_set_bias", values, n);
     if (rc) return rc;
-    if ((u64)n != c->dev.n)
-        return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_set_bias: " + std::to_string(n) + " values for the corpus' " + std::to_string(c->dev.n) + " haystacks (one per haystack)");
-    hipError_t e = bias_create(c, 0);
-    if (e == hipSuccess && n) e = hipMemcpy(c->own_bias, values, n * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_set_bias: ") + hipGetErrorString(e));
-    HIPCHK(hipDeviceSynchronize());
     int32_t hi = 0;
     for (size_t k = 0; k < n; k++) hi = std::max<int32_t>(hi, values[k]);
     c->bias_hi = (u32)hi;
-    c->has_bias = true;
+    c->bias.live = true;
     return FZB_OK;
 }
 
 int fzb_corpus_update_bias(fzb_corpus* c, const uint32_t* indices, const int16_t* values, size_t n) {
     if (!c || (n && (!indices || !values))) return fzb_fail(FZB_ERR_INVALID, "null argument");
     int rc = grow_begin(c, "fzb_corpus_update_bias");
-    if (rc) return rc;
-    if (!n) return FZB_OK;
-    for (size_t k = 0; k < n; k++)
-        if (indices[k] >= c->dev.n)
-            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_bias: index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " +
-                                                 std::to_string(c->dev.n) + " haystacks");
-    std::vector<u32> order(n);
-    for (size_t k = 0; k < n; k++) order[k] = (u32)k;
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return indices[a] != indices[b] ? indices[a] < indices[b] : a < b; });
-    for (size_t k = 1; k < n; k++)
-        if (indices[order[k]] == indices[order[k - 1]])
-            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_bias: haystack " + std::to_string(indices[order[k]]) + " is named twice (positions " + std::to_string(order[k - 1]) + " and " +
-                                                 std::to_string(order[k]) + ")");
-    // the pairs travel in one copy: n indices, then n values
-    std::vector<u8> pairs(n * 6);
-    memcpy(pairs.data(), indices, n * 4);
-    memcpy(pairs.data() + n * 4, values, n * 2);
-    hipError_t e = bias_create(c, n);  // (a corpus without a bias: an all-zero one first)
-    if (e == hipSuccess) e = hipMemcpy(c->bias_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_bias: ") + hipGetErrorString(e));
-    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
-    hipLaunchKernelGGL(k_bias_scatter<int16_t>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->bias_stage, (const int16_t*)((const u8*)c->bias_stage + n * 4), (u64)n, c->own_bias,
-                       c->dev.n);
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_bias (scatter): ") + hipGetErrorString(e));
-    int32_t hi = c->has_bias ? (int32_t)c->bias_hi : 0;
+    if (rc || !n) return rc;
+    if ((rc = col_update(c, c->bias, "fzb_corpus_update_bias", indices, values, n))) return rc;
+    int32_t hi = c->bias.live ? (int32_t)c->bias_hi : 0;
     for (size_t k = 0; k < n; k++) hi = std::max<int32_t>(hi, values[k]);
     c->bias_hi = (u32)hi;
-    c->has_bias = true;
+    c->bias.live = true;
     return FZB_OK;
 }
 
 int fzb_corpus_clear_bias(fzb_corpus* c) {
     int rc = grow_begin(c, "fzb_corpus_clear_bias");
+    if (!rc) rc = col_clear(c->bias);
     if (rc) return rc;
-    if (c->own_bias && c->has_bias) {  // (the invariant of an array without a bias: all zero; complete on return, and the flags change only then)
-        HIPCHK(hipMemset(c->own_bias, 0, c->bias_cap_items * sizeof(int16_t)));
-        HIPCHK(hipDeviceSynchronize());
-    }
-    c->has_bias = false;
+    c->bias.live = false;  // (the array stays, all zero: the invariant of a column that is not live)
     c->bias_hi = 0;
     return FZB_OK;
 }
 
 int fzb_corpus_bias_info(const fzb_corpus* c, uint64_t out[4]) {
     if (!c || !out) return fzb_fail(FZB_ERR_INVALID, "null argument");
-    out[0] = c->has_bias ? 1 : 0;
-    out[1] = c->own_bias ? c->bias_cap_items : 0;
-    out[2] = c->has_bias ? c->bias_hi : 0;
-    out[3] = (c->own_bias ? c->bias_cap_items * sizeof(int16_t) : 0) + (c->bias_stage ? c->bias_stage_pairs * 6 : 0);
+    out[0] = c->bias.live ? 1 : 0;
+    out[1] = c->bias.cap_items;
+    out[2] = fzb_corpus_bias_hi(c);
+    out[3] = c->bias.cap_items * sizeof(int16_t) + c->pair_stage_cap * 6;
     return FZB_OK;
+}
+
+// the tags are live from the moment their array exists, whatever became of the call that allocated it
+static int tags_made(fzb_corpus* c, int rc) {
+    c->tags.live = c->tags.data != nullptr;
+    return rc;
 }
 
 int fzb_corpus_set_tags(fzb_corpus* c, const uint16_t* values, size_t n) {
     if (!c || (n && !values)) return fzb_fail(FZB_ERR_INVALID, "null argument");
     int rc = grow_begin(c, "fzb_corpus_set_tags");
     if (rc) return rc;
-    if ((u64)n != c->dev.n)
-        return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_set_tags: " + std::to_string(n) + " values for the corpus' " + std::to_string(c->dev.n) + " haystacks (one per haystack)");
-    hipError_t e = tags_create(c, 0);
-    if (e == hipSuccess && n) e = hipMemcpy(c->own_tags, values, n * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_set_tags: ") + hipGetErrorString(e));
-    HIPCHK(hipDeviceSynchronize());
-    return FZB_OK;
+    return tags_made(c, col_set(c, c->tags, "fzb_corpus_set_tags", values, n));
 }
 
 int fzb_corpus_update_tags(fzb_corpus* c, const uint32_t* indices, const uint16_t* values, size_t n) {
     if (!c || (n && (!indices || !values))) return fzb_fail(FZB_ERR_INVALID, "null argument");
     int rc = grow_begin(c, "fzb_corpus_update_tags");
-    if (rc) return rc;
-    if (!n) return FZB_OK;
-    for (size_t k = 0; k < n; k++)
-        if (indices[k] >= c->dev.n)
-            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_tags: index " + std::to_string(indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " +
-                                                 std::to_string(c->dev.n) + " haystacks");
-    std::vector<u32> order(n);
-    for (size_t k = 0; k < n; k++) order[k] = (u32)k;
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return indices[a] != indices[b] ? indices[a] < indices[b] : a < b; });
-    for (size_t k = 1; k < n; k++)
-        if (indices[order[k]] == indices[order[k - 1]])
-            return fzb_fail(FZB_ERR_INVALID, "fzb_corpus_update_tags: haystack " + std::to_string(indices[order[k]]) + " is named twice (positions " + std::to_string(order[k - 1]) + " and " +
-                                                 std::to_string(order[k]) + ")");
-    // the pairs travel in one copy: n indices, then n values
-    std::vector<u8> pairs(n * 6);
-    memcpy(pairs.data(), indices, n * 4);
-    memcpy(pairs.data() + n * 4, values, n * 2);
-    hipError_t e = tags_create(c, n);  // (a corpus without tags: an all-zero array first)
-    if (e == hipSuccess) e = hipMemcpy(c->bias_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_tags: ") + hipGetErrorString(e));
-    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
-    hipLaunchKernelGGL(k_bias_scatter<uint16_t>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->bias_stage, (const uint16_t*)((const u8*)c->bias_stage + n * 4), (u64)n,
-                       c->own_tags, c->dev.n);
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_update_tags (scatter): ") + hipGetErrorString(e));
-    return FZB_OK;
+    if (rc || !n) return rc;
+    return tags_made(c, col_update(c, c->tags, "fzb_corpus_update_tags", indices, values, n));
 }
 
 int fzb_corpus_clear_tags(fzb_corpus* c) {
     int rc = grow_begin(c, "fzb_corpus_clear_tags");
+    if (!rc) rc = col_clear(c->tags);
     if (rc) return rc;
-    if (c->own_tags) {  // (complete on return, and the scope changes only then)
-        HIPCHK(hipMemset(c->own_tags, 0, c->tags_cap_items * sizeof(uint16_t)));
-        HIPCHK(hipDeviceSynchronize());
-    }
-    c->scope_require = c->scope_exclude = 0;
+    c->scope_require = c->scope_exclude = 0;  // (the scope changes only once the tags are zero)
     return FZB_OK;
 }
 
 int fzb_corpus_set_scope(fzb_corpus* c, uint16_t require, uint16_t exclude) {
     if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
-    if (!c->own_tags) {  // the first scope of a corpus without tags: an all-zero array, under the set-up calls' rules
+    if (!c->tags.data) {  // the first scope of a corpus without tags: an all-zero array, under the set-up calls' rules
         int rc = grow_begin(c, "fzb_corpus_set_scope");
         if (rc) return rc;
-        const hipError_t e = tags_create(c, 0);
+        const hipError_t e = col_create(c, c->tags, 0);
+        tags_made(c, 0);
         if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_set_scope: ") + hipGetErrorString(e));
         HIPCHK(hipDeviceSynchronize());
     }
@@ -1195,9 +1171,9 @@ int fzb_corpus_set_scope(fzb_corpus* c, uint16_t require, uint16_t exclude) {
 int fzb_corpus_scope_info(const fzb_corpus* c, uint64_t out[4]) {
     if (!c || !out) return fzb_fail(FZB_ERR_INVALID, "null argument");
     out[0] = fzb_corpus_scoped(c) ? 1 : 0;
-    out[1] = c->own_tags ? c->tags_cap_items : 0;
+    out[1] = c->tags.cap_items;
     out[2] = (u64)c->scope_require | ((u64)c->scope_exclude << 16);
-    out[3] = c->own_tags ? c->tags_cap_items * sizeof(uint16_t) : 0;
+    out[3] = c->tags.cap_items * sizeof(uint16_t);
     return FZB_OK;
 }
 
@@ -1214,8 +1190,8 @@ int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
     // a batch may be as large as the room: its landing place, and - unless FZB_FILTER_VIEW=0 - the view's arrays, are sized for that
     if (e == hipSuccess) e = stage_ensure_room(c, c->cap_items - c->dev.n, c->cap_bytes - c->dev.total_bytes);
     if (e == hipSuccess) e = ensure_tiles_scratch(c, up_tiles(c->cap_items) + 1);
-    if (e == hipSuccess && c->own_bias) e = bias_ensure_room(c, c->cap_items);  // the bias follows the item capacity: appends within the room allocate nothing
-    if (e == hipSuccess && c->own_tags) e = tags_ensure_room(c, c->cap_items);  // and so do the tags
+    if (e == hipSuccess) e = col_follow(c, c->bias, c->cap_items);  // the columns follow the item capacity: appends within the room allocate nothing
+    if (e == hipSuccess) e = col_follow(c, c->tags, c->cap_items);
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_reserve: ") + hipGetErrorString(e));
     if (!fzb_knobs().no_filter_view) {
         const u64 live_units = c->dev.vbytes ? c->view_units : 0;
@@ -1264,9 +1240,9 @@ int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_o
     if (!c->dev.ends_u64 && total > 0xFFFFFFF0ull)
         return fzb_fail(FZB_ERR_CAPACITY, "fzb_corpus_append: the batch takes the padded list to 4 GiB, beyond this corpus' 32-bit end offsets; upload such a list in one piece");
     e = canon_ensure_room(c, n_old + n_new, total, true);
-    // (the bias array regrows with the items, device to device; the new haystacks' entries are zero by the invariant)
-    if (e == hipSuccess && c->own_bias) e = bias_ensure_room(c, std::max<u64>(n_old + n_new, c->cap_items));
-    if (e == hipSuccess && c->own_tags) e = tags_ensure_room(c, std::max<u64>(n_old + n_new, c->cap_items));  // (the tags too: new haystacks start with tag 0)
+    // (the columns regrow with the items, device to device; the new haystacks' entries are zero by the invariant)
+    if (e == hipSuccess) e = col_follow(c, c->bias, std::max<u64>(n_old + n_new, c->cap_items));
+    if (e == hipSuccess) e = col_follow(c, c->tags, std::max<u64>(n_old + n_new, c->cap_items));
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_append (room for the batch): ") + hipGetErrorString(e));
     batch_lay_out((const u8*)c->stage_raw, (const u64*)c->stage_ends, n_new, 0, (const u64*)c->stage_tiles, (u8*)c->own_bytes, used, c->own_ends, n_old, c->dev.ends_u64 != 0, true);
     c->h2d_bytes += raw + (u64)n_new * 8;
@@ -1301,8 +1277,8 @@ int fzb_corpus_truncate(fzb_corpus* c, size_t n) {
     const u64 old_used = c->dev.total_bytes - 96;
     if (old_used > used) HIPCHK(hipMemsetAsync((u8*)c->own_bytes + used, 0, old_used - used, nullptr));  // gaps and tail are zero
     hipError_t e = measure_resident(c, n);
-    if (e == hipSuccess && c->own_bias && c->has_bias) e = hipMemsetAsync(c->own_bias + n, 0, (c->dev.n - n) * sizeof(int16_t), nullptr);  // the cut haystacks' biases
-    if (e == hipSuccess && c->own_tags) e = hipMemsetAsync(c->own_tags + n, 0, (c->dev.n - n) * sizeof(uint16_t), nullptr);  // and their tags
+    if (e == hipSuccess) e = col_truncate(c->bias, c->dev.n, n);  // the cut haystacks' biases and tags
+    if (e == hipSuccess) e = col_truncate(c->tags, c->dev.n, n);
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_truncate: ") + hipGetErrorString(e));
     c->dev.n = n;
     c->dev.total_bytes = used + 96;
@@ -1357,8 +1333,8 @@ int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t 
         case 6: src = c->dev.vperm; bytes = view ? (size_t)n * 2 : 0; break;
         case 7: src = c->dev.vlong; bytes = view ? (size_t)c->dev.n_long * 4 : 0; break;
         case 8: src = c->dev.sig; bytes = c->dev.sig ? (size_t)n * 4 : 0; break;
-        case 9: src = c->own_bias; bytes = c->has_bias ? (size_t)n * sizeof(int16_t) : 0; break;
-        case 10: src = c->own_tags; bytes = c->own_tags ? (size_t)n * sizeof(uint16_t) : 0; break;
+        case 9: src = c->bias.data; bytes = c->bias.live ? (size_t)n * sizeof(int16_t) : 0; break;
+        case 10: src = c->tags.data; bytes = c->tags.live ? (size_t)n * sizeof(uint16_t) : 0; break;
         default: return fzb_fail(FZB_ERR_INVALID, "fzb_debug_corpus_read: unknown array " + std::to_string(what));
     }
     *out_bytes = bytes;
@@ -1703,6 +1679,36 @@ struct EditRequest {
     u64 batch_h2d = 0;
 };
 
+// A removal's scratch of one column: the kept entries of the suffix from i0 on pass through it, 2 bytes per suffix haystack.  A replace keeps
+// every entry where it is (the index map is the identity) and a column that is not live is all zero: neither needs any.
+template <typename V>
+struct ColScratch {
+    V* work = nullptr;
+    u64 bytes = 0;
+};
+template <typename V>
+u64 col_scratch_bytes(const ItemColumn<V>& col, bool replace, u64 suffix) {
+    return (!replace && col.live) ? round_up(suffix * sizeof(V), 16) : 0;
+}
+template <typename V>
+hipError_t col_scratch_alloc(ColScratch<V>& s, u64 bytes) {
+    if (!bytes) return hipSuccess;
+    const hipError_t e = fzb_dev_alloc((void**)&s.work, bytes);
+    if (e == hipSuccess) s.bytes = bytes;
+    else s.work = nullptr;
+    return e;
+}
+// the kept entries from i0 on, compacted through the scratch, copied into place, the freed tail [n_new, n) cleared
+template <typename V>
+hipError_t col_compact(ItemColumn<V>& col, const ColScratch<V>& s, const u32* bitmap, const u64* tile_cnt, u64 tiles, u64 n, u64 i0, u64 n_new) {
+    if (!s.work) return hipSuccess;
+    hipLaunchKernelGGL(k_col_compact<V>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const V*)col.data, bitmap, tile_cnt, n, i0, s.work, n - i0);
+    hipError_t e = hipSuccess;
+    if (n_new > i0) e = hipMemcpyAsync(col.data + i0, s.work, (n_new - i0) * sizeof(V), hipMemcpyDeviceToDevice, nullptr);
+    if (e == hipSuccess && n > n_new) e = hipMemsetAsync(col.data + n_new, 0, (n - n_new) * sizeof(V), nullptr);
+    return e;
+}
+
 // grow_begin has passed.  Everything up to canon_ensure_room only reads the corpus: an error before it leaves nothing to undo.
 int edit_run(fzb_corpus* c, const EditRequest& rq) {
     const std::string what = rq.what;
@@ -1714,13 +1720,13 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     const u64 off_rk = off_idx + (rq.host_idx ? round_up(rq.max_count * 4, 8) : 0), aux_bytes = off_rk + (replace ? rq.max_count * 4 : 0);
     u8* aux = nullptr;
     u8* work = nullptr;
-    int16_t* bias_work = nullptr;  // a removal on a biased corpus: the kept biases of the suffix pass through here
-    uint16_t* tags_work = nullptr;  // ... on a corpus with tags: the kept tags
+    ColScratch<int16_t> bias_tmp;  // a removal on a corpus with live columns
+    ColScratch<uint16_t> tags_tmp;
     auto done = [&](int rc) {
         if (aux) (void)hipFree(aux);
         if (work) (void)hipFree(work);
-        if (bias_work) (void)hipFree(bias_work);
-        if (tags_work) (void)hipFree(tags_work);
+        if (bias_tmp.work) (void)hipFree(bias_tmp.work);
+        if (tags_tmp.work) (void)hipFree(tags_tmp.work);
         return rc;
     };
     auto hip_fail = [&](hipError_t e, const char* where) { return done(fzb_fail(FZB_ERR_HIP, what + " (" + where + "): " + hipGetErrorString(e))); };
@@ -1766,16 +1772,8 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
         if (!out_b) out_b = work;
         if (!out_e) out_e = work + work_b;
     }
-    const u64 bias_work_bytes = (!replace && c->has_bias) ? round_up((n - i0) * sizeof(int16_t), 16) : 0;  // 2 bytes per suffix haystack
-    if (bias_work_bytes) {
-        e = fzb_dev_alloc((void**)&bias_work, bias_work_bytes);
-        if (e != hipSuccess) { bias_work = nullptr; return hip_fail(e, "scratch for the score bias"); }
-    }
-    const u64 tags_work_bytes = (!replace && c->own_tags) ? round_up((n - i0) * sizeof(uint16_t), 16) : 0;  // 2 bytes per suffix haystack, as the bias
-    if (tags_work_bytes) {
-        e = fzb_dev_alloc((void**)&tags_work, tags_work_bytes);
-        if (e != hipSuccess) { tags_work = nullptr; return hip_fail(e, "scratch for the tags"); }
-    }
+    if ((e = col_scratch_alloc(bias_tmp, col_scratch_bytes(c->bias, replace, n - i0))) != hipSuccess) return hip_fail(e, "scratch for the score bias");
+    if ((e = col_scratch_alloc(tags_tmp, col_scratch_bytes(c->tags, replace, n - i0))) != hipSuccess) return hip_fail(e, "scratch for the tags");
     if (total > c->cap_bytes) {
         e = canon_ensure_room(c, n_new, total, true);
         if (e != hipSuccess) return hip_fail(e, "room for the new content");
@@ -1796,18 +1794,8 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     if (e == hipSuccess && old_used > new_used) e = hipMemsetAsync((u8*)c->own_bytes + new_used, 0, old_used - new_used, nullptr);  // gaps and tail are zero
     const bool had_view = c->dev.vbytes != nullptr;
     if (e == hipSuccess) e = measure_resident(c, n_new);
-    if (e == hipSuccess && bias_work) {  // the kept entries from i0 on, compacted through scratch, copied into place, the freed tail cleared (a replace keeps every bias where it is)
-        hipLaunchKernelGGL(k_bias_compact<int16_t>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const int16_t*)c->own_bias, (const u32*)d_bitmap, (const u64*)d_tc, n, i0, bias_work,
-                           n - i0);
-        if (st.new_items) e = hipMemcpyAsync(c->own_bias + i0, bias_work, st.new_items * sizeof(int16_t), hipMemcpyDeviceToDevice, nullptr);
-        if (e == hipSuccess && n > n_new) e = hipMemsetAsync(c->own_bias + n_new, 0, (n - n_new) * sizeof(int16_t), nullptr);
-    }
-    if (e == hipSuccess && tags_work) {  // the tags through the same pass (a replace keeps every tag where it is)
-        hipLaunchKernelGGL(k_bias_compact<uint16_t>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const uint16_t*)c->own_tags, (const u32*)d_bitmap, (const u64*)d_tc, n, i0,
-                           tags_work, n - i0);
-        if (st.new_items) e = hipMemcpyAsync(c->own_tags + i0, tags_work, st.new_items * sizeof(uint16_t), hipMemcpyDeviceToDevice, nullptr);
-        if (e == hipSuccess && n > n_new) e = hipMemsetAsync(c->own_tags + n_new, 0, (n - n_new) * sizeof(uint16_t), nullptr);
-    }
+    if (e == hipSuccess) e = col_compact(c->bias, bias_tmp, d_bitmap, d_tc, tiles, n, i0, n_new);
+    if (e == hipSuccess) e = col_compact(c->tags, tags_tmp, d_bitmap, d_tc, tiles, n, i0, n_new);
     if (e != hipSuccess) return hip_fail(e, "layout");
     c->dev.n = n_new;
     c->dev.total_bytes = total;
@@ -1822,7 +1810,7 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     c->edit_info[0] = i0;
     c->edit_info[1] = st.new_bytes + (old_used > new_used ? old_used - new_used : 0) + st.new_items * esz;
     c->edit_info[2] = c->dev.vbytes ? up_tiles(n_new) - (had_view ? std::min(i0, n_new) / UP_TILE : 0) : 0;
-    c->edit_info[3] = aux_bytes + work_bytes + bias_work_bytes + tags_work_bytes;
+    c->edit_info[3] = aux_bytes + work_bytes + bias_tmp.bytes + tags_tmp.bytes;
     return done(FZB_OK);
 }
 

@@ -8,7 +8,7 @@
 // between the scorers and the selection / ordering stage, so the top-`limit` calls select on the ranking the user sees.
 //   * sbias_clamp_add     the add;
 //   * sbias_one_pass      whether the ordering may still take one radix pass / one histogram level: no biased score can reach 256;
-//   * sbias_tile_keeps / sbias_tile_place   the per-tile body of the remove compaction of the bias array (host_upload.hip, k_bias_compact):
+//   * sbias_tile_keeps / sbias_tile_place   the per-tile body of the remove compaction of a per-haystack column (host_upload.hip, k_col_compact):
 //     one workgroup per 1024-haystack source tile, a wave per 64 haystacks; a haystack is kept when it lies inside the list and its bit of
 //     the pass' bitmap is clear, its rank inside the wave comes from the wave's kept mask (a ballot on the device, a loop over the lanes
 //     on the host), the waves' totals go through LDS, and the tile's base is the scanned per-tile kept count - no atomics, nothing ordered

@@ -114,7 +114,7 @@ def test_remove_a_whole_tile_and_through_remove_device():
 
 
 def test_remove_over_many_tiles():
-    """twelve source tiles from a non-tile-aligned, mid-word first index: every workgroup of k_bias_compact lands at its scanned base"""
+    """twelve source tiles from a non-tile-aligned, mid-word first index: every workgroup of k_col_compact lands at its scanned base"""
     model = make_model(12_000, seed=77)
     cp, fm = upload(model), matcher()
     rng = np.random.default_rng(77)
