@@ -125,7 +125,7 @@ SYMBOLS = [
     "fzb_corpus_remove", "fzb_corpus_remove_device", "fzb_corpus_replace", "fzb_corpus_edit_info",
     "fzb_match_list_top_indices", "fzb_match_list_top_indices_device", "fzb_matcher_reserve_top_indices", "fzb_multi_match_list_top_indices",
     "fzb_multi_match_list_top_indices_device", "fzb_multi_match_list_top_indices_fused", "fzb_multi_matcher_reserve_top_indices",
-    "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold",
+    "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold", "fzb_debug_set_filter_grid",
     "fzb_corpus_set_bias", "fzb_corpus_update_bias", "fzb_corpus_clear_bias", "fzb_corpus_bias_info",
     "fzb_corpus_set_tags", "fzb_corpus_update_tags", "fzb_corpus_clear_tags", "fzb_corpus_set_scope", "fzb_corpus_scope_info",
 ]
@@ -238,6 +238,8 @@ def lib():
         l.fzb_debug_needle_signature.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         l.fzb_debug_signature_threshold.argtypes = []
         l.fzb_debug_signature_threshold.restype = C.c_uint32
+        l.fzb_debug_set_filter_grid.argtypes = [C.c_int]
+        l.fzb_debug_set_filter_grid.restype = None
         l.fzb_corpus_set_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         l.fzb_corpus_update_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         l.fzb_corpus_clear_bias.argtypes = [C.c_void_p]

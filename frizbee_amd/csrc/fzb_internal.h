@@ -135,6 +135,7 @@ struct Workspace {
     u32* tile_counts2;
     u32* items2;        // local haystack index of kept survivor
     u32* win2;          // its window
+    u32* seg_counts;    // FZB_SEG_MAX words behind the counter block (same allocation): survivors per segment of a filter that lists its own (seg_list.h)
     u32* counters;      // [0]=filter survivors [1]=kept by the lane-exact prefilter [2]=output base of the NEXT chunk [3]=multi-chunk queue length [4]=greedy (>1024 B) queue length
                         // [5]=marginal survivors (LCS == need) [6]=of those, rejected by the lane-exact decision
     u64* bitmap_m;      // typo fast path: "accepted with nothing to spare" bits, their tile counts, the list of those haystacks,
@@ -200,13 +201,24 @@ struct RejectOut {
     u32* count;
 };
 
+// The segmented survivor list (seg_list.h): what k1_dfa_sig writes when it lists its own survivors, and what k2b_dp_short reads instead of
+// (items, *n_items_ptr).  nseg = the filter's grid (<= FZB_SEG_MAX), stride = tiles per run x FZB_TILE; total_out = counters[0].
+struct SegList {
+    u32* list;
+    u32* counts;
+    u32 nseg, stride;
+    u32* total_out;
+};
+
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 // kernels_filter.hip
 void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* table, const u8* dfa, u32 dead, int rows, int mode, int need, u32 min_len,
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m = nullptr, u32* tile_counts_m = nullptr,
                        u64* reject_bits = nullptr, u32* tile_rejects = nullptr, int nul_safe = 0, int acc_lo = -1, const u8* cdfa = nullptr, u32 cdfa_bytes = 0,
-                       int cdfa_K = 0, int cdfa_G = 0, u32 needle_sig = 0, int sig_ok = 0);  // sig_ok: the needle is eligible for the signature form (sig_filter.h)
+                       int cdfa_K = 0, int cdfa_G = 0, u32 needle_sig = 0, int sig_ok = 0,  // sig_ok: the needle is eligible for the signature form (sig_filter.h)
+                       const SegList* seg = nullptr);  // seg (only where fzb_filter_sig_applies): grid = seg->nseg, the kernel also lists its survivors
+bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int sig_ok);  // fzb_launch_filter takes k1_dfa_sig
 void fzb_launch_scan_rejects(const u32* tile_rejects, u32 ntiles, const u32* reject_count, u32* rej_prefix, hipStream_t st);
 void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st);  // the 16-word counter block: [0] = n0, the rest 0
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,
@@ -221,7 +233,7 @@ void fzb_launch_window(const CorpusDev& c, u64 first, const u32* surv_idx, const
 // kernels_dp.hip
 void fzb_launch_dp(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* win, const u32* n_items_ptr, const NeedleDev& nd,
                    int sw_lanes, int mode, int wmode, int pad_ok, fzb_match_rec* out, u32 capacity, u32* dev_count, u32* overflow, u32 qcap, u32* counters, int grid, hipStream_t st,
-                   const RejectOut* rejects = nullptr);
+                   const RejectOut* rejects = nullptr, const SegList* seg = nullptr);  // seg: k2b_dp_short over the segmented list (items / n_items_ptr unused)
 bool fzb_dp_short_applies(const CorpusDev& c, int sw_lanes, int mode);
 void fzb_launch_compact1_classify(const CorpusDev& c, u64 first, const u64* bitmap, const u32* tile_counts, u32 n_items, u32* out_idx, u32* total_out, const NeedleDev& nd, int sw_lanes,
                                   int wmode, u32 capacity, u32* dev_count, u32* overflow, u32 qcap, u32* counters, u32* win_out, u32* lists, u32 list_stride, int grid, hipStream_t st,

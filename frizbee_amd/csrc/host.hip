@@ -29,6 +29,7 @@
 #include "sig_filter.h"
 #include "score_bias.h"
 #include "scope.h"
+#include "seg_list.h"
 
 namespace {
 #include "unicode_case_table.inc"
@@ -183,6 +184,7 @@ FzbKnobs parse_knobs() {
     k.no_cdfa = set("FZB_NO_CDFA");
     k.no_dp_classes = set("FZB_NO_DP_CLASSES");
     k.no_fused_classify = set("FZB_NO_FUSED_CLASSIFY");
+    k.no_seg_list = on("FZB_NO_SEG_LIST");
     k.no_dp_cfm = set("FZB_NO_DP_CFM");
     k.no_dp_cfu = set("FZB_NO_DP_CFU");
     k.unicode_multi = num("FZB_UNICODE_MULTI", -1);
@@ -1095,7 +1097,10 @@ static int ensure_workspace(fzb_matcher* m, size_t count, hipStream_t st = nullp
     HIPCHK(dev_alloc((void**)&w.tile_counts, ntiles * 4));
     HIPCHK(dev_alloc((void**)&w.surv_idx, cap * 4));
     HIPCHK(dev_alloc((void**)&w.overflow, cap * 16));
-    HIPCHK(dev_alloc((void**)&w.counters, 64));
+    // (the counter block, and behind it the segment counts of a filter that lists its own survivors: seg_list.h)
+    HIPCHK(dev_alloc((void**)&w.counters, 64 + FZB_SEG_MAX * 4));
+    w.seg_counts = w.counters + 16;
+    static_assert(FZB_UNICODE_FWD_CAP >= FZB_TILE, "surv_idx holds the range rounded up to a tile: the segmented list's reach");
     // (room for any needle's automata: short needles 64 states, a long needle's subsequence DFA up to 201, unicode <= 255 + 1, LCS <= 226)
     HIPCHK(dev_alloc((void**)&w.tables_blob, TB_TOTAL));
     HIPCHK(hipHostMalloc((void**)&w.tables_host, TB_TOTAL, hipHostMallocDefault));
@@ -1426,6 +1431,8 @@ struct Pipe {
     const u32* n_items_ptr = nullptr;
     int wmode = 0;
     bool classified = false;  // the compaction launch classified its survivors too (k_compact1_classify): pipe_score_ascii starts at the class scorers
+    bool segmented = false;   // the signature filter listed its survivors itself (seg): no compaction ran, p.items is not a dense list
+    SegList seg{};
 };
 #define FZB_STAGE(name)                                                                                        \
     do {                                                                                                       \
@@ -1505,6 +1512,15 @@ static int pipe_typo_fast_path(Pipe& p) {
 // compaction when the stream stage was a superset].  Leaves p.items / p.win / p.n_items_ptr / p.wmode for the scorers.
 static bool ascii_split_classes(const fzb_matcher* m, const CorpusDev& cd);
 static u32 pipe_qcap(const Pipe& p);
+static int g_debug_filter_grid = 0;  // fzb_debug_set_filter_grid
+// The two-launch form (the filter lists its survivors, k2b_dp_short reads the segmented list): a contiguous range, k1_dfa_sig as the filter,
+// k2b_dp_short with inline windows as the scorer (pipe_score_ascii's choice, restated), no matched positions, FZB_NO_SEG_LIST unset.
+static bool pipe_seg_applies(const Pipe& p) {
+    const fzb_matcher* m = p.m;
+    const LaunchCfg& lc = m->lc;
+    return !p.items_in && !p.trace && !fzb_knobs().no_seg_list && !m->nd.unicode && m->sig_eligible && lc.filter_mode == 1 && lc.filter_exact && lc.window_mode == 1 && lc.cf_ok &&
+           fzb_filter_sig_applies(p.cd, 1, m->needle_sig, 1) && fzb_dp_short_applies(p.cd, lc.sw_lanes, 2);
+}
 static int pipe_filter_stage(Pipe& p) {
     fzb_matcher* m = p.m;
     Workspace& w = m->ws;
@@ -1543,6 +1559,23 @@ static int pipe_filter_stage(Pipe& p) {
         FZB_STAGE("compact1");
         p.items = w.surv_idx;
         exact_wmode = 1;
+    } else if (pipe_seg_applies(p)) {
+        // 0-typo ASCII query over a short list with signatures, scored by k2b_dp_short: the filter lists the survivors of each workgroup's run of
+        // tiles itself and the scorer reads that segmented list (seg_list.h) - two launches, no k_compact1
+        const u32 ntiles = (p.cnt + FZB_TILE - 1) / FZB_TILE;
+        u32 grid = std::min<u32>(std::min<u32>((u32)p.cus * 8u, FZB_SEG_MAX), ntiles);
+        if (g_debug_filter_grid > 0) grid = std::min<u32>(grid, (u32)g_debug_filter_grid);
+        grid = std::max<u32>(grid, 1u);
+        const u32 stride = seg_tiles_per_run(ntiles, grid) * FZB_TILE;
+        if ((size_t)ntiles * FZB_TILE > w.cap_items) return fail(FZB_ERR_INVALID, "internal: the survivor list does not hold the range rounded up to a tile");
+        p.seg = SegList{w.surv_idx, w.seg_counts, grid, stride, &cnt_c[0]};
+        p.segmented = true;
+        FZB_PEV(2);
+        fzb_launch_filter(p.cd, p.first, p.cnt, w.table, w.dfa, lc.dead_byte, nd.rows, 1, need, (u32)nd.min_haystack_len, w.bitmap, w.tile_counts, w.counters, (int)grid, p.st, nullptr, nullptr,
+                          nullptr, nullptr, lc.pad_ok, -1, nullptr, 0, 0, 0, m->needle_sig, 1, &p.seg);
+        FZB_PEV(3);
+        FZB_STAGE("filter(lists its survivors)");
+        p.items = w.surv_idx;
     } else {
         FZB_PEV(2);
         if (lc.filter_mode == 2 && m->lcs_states)  // typo configurations: the LCS automaton in the streaming DFA kernels (short and ragged lists)
@@ -1715,6 +1748,7 @@ static int pipe_score_ascii(Pipe& p) {
     if (!no_wide && (rc = ensure_dp_scratch(m, mgrid))) return rc;  // first use only (or fzb_matcher_reserve)
     const int split = classes && !no_wide && mmode == 2;  // multi-chunk windows as k2w_classify's tail-class lists (needs dp_cfm.h's form; cf_ok includes pad_ok) == ascii_split_classes()
     if (p.classified && !split) return fail(FZB_ERR_INVALID, "internal: the compaction classified a list whose scorers do not take class lists");
+    if (p.segmented && (classes || !lc.cf_ok || !fzb_dp_short_applies(cd, lc.sw_lanes, 2))) return fail(FZB_ERR_INVALID, "internal: a segmented survivor list in front of a scorer that reads a dense one");
     bool fork = classes && !no_wide && !split;
     if (fork && ensure_aux_stream(m) != FZB_OK) {  // no second stream: everything on the caller's stream (the error text is dropped with the fallback)
         fork = false;
@@ -1729,7 +1763,8 @@ static int pipe_score_ascii(Pipe& p) {
         fzb_launch_dp_classes(cd, p.first, p.index_offset, p.items, p.win, p.n_items_ptr, nd, lc.sw_lanes, p.wmode, p.out, p.cap32, p.dev_count, w.overflow, qcap, cnt_c, w.cls_win, w.cls_lists,
                               (u32)w.cap_cls, cus, p.st, fork ? 1 : 0, 0);
     else
-        fzb_launch_dp(cd, p.first, p.index_offset, p.items, p.win, p.n_items_ptr, nd, lc.sw_lanes, lc.cf_ok ? 2 : lc.bias_ok ? 1 : 0, p.wmode, lc.pad_ok, p.out, p.cap32, p.dev_count, w.overflow, qcap, cnt_c, cus, p.st);
+        fzb_launch_dp(cd, p.first, p.index_offset, p.items, p.win, p.n_items_ptr, nd, lc.sw_lanes, lc.cf_ok ? 2 : lc.bias_ok ? 1 : 0, p.wmode, lc.pad_ok, p.out, p.cap32, p.dev_count, w.overflow, qcap, cnt_c, cus, p.st,
+                      nullptr, p.segmented ? &p.seg : nullptr);
     FZB_STAGE("dp");
     if (fork) {  // the queued multi-chunk windows on the second stream beside the three class launches (both start from the classifier's output, disjoint records)
         HIPCHK(hipEventRecord(m->ev_fork, p.st));
@@ -3518,6 +3553,9 @@ int fzb_debug_needle_signature(const fzb_matcher* m, uint32_t* out_mask, int* ou
     return FZB_OK;
 }
 uint32_t fzb_debug_signature_threshold(void) { return std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE); }
+// Test hook: caps the grid of a filter that lists its own survivors (0 = the default, 8 workgroups per CU), so that a small list gets runs of
+// several tiles, a short last run and empty trailing segments.
+void fzb_debug_set_filter_grid(int grid) { g_debug_filter_grid = grid > 0 ? grid : 0; }
 
 int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len, int32_t* out_kg) {
     if (out_kg) { out_kg[0] = m ? m->cdfa_K : 0; out_kg[1] = m ? m->cdfa_G : 0; }

@@ -17,7 +17,9 @@
 #include "dp_cfm.h"
 #include "dp_quad.h"
 #include "compact1.h"
+#include "seg_list.h"
 #include <cstdlib>
+#include <type_traits>
 
 // MODE 0: literal gap scan (the bias could overflow u16), 1: biased scan (dp_body.h).  (dp_cf.h's form of this per-wave kernel - rounds 2-5 -
 // only ever ran behind FZB_NO_DP_CLASSES once the classified path existed and left with round 6's prune.)
@@ -137,6 +139,10 @@ __global__ __launch_bounds__(128, 2) void k2b_dp(const u8* __restrict__ bytes, c
 // 0-typo window comes from one merged flag word per needle byte and the per-lane bonuses from two small LDS tables.  No
 // queues (nothing can be wider than a chunk) and a third of the registers of the general kernel: four waves per SIMD.
 // Chosen by fzb_launch_dp when LaunchCfg::cf_ok and CorpusDev::max_len allow; otherwise k2b_dp runs.
+// SEG: the survivors come as the signature filter's SEGMENTED list (seg_list.h) instead of a dense one behind a compaction launch.  Every
+// workgroup loads the <= 2048 segment counts (16 per thread, one round trip, in flight while the bonus tables are built), scans them into an
+// exclusive prefix in LDS, takes M from the total, and load_item(j) finds j's segment by bisection of that prefix.  The output position stays
+// j, so records stay index-ordered; pipeline, priorities and dev_count are as in the dense form, whose instantiations do not change.
 // ---------------------------------------------------------------------------------------------------------------
 #ifdef FZB_DP_TIMING
 // Debug build only (make TIMING=1 -> libfrizbee_hip_timing.so, tools/exp_dp_timing.py): per wave, the constant 100 MHz counter
@@ -155,18 +161,59 @@ extern "C" int fzb_debug_dp_timing(unsigned long long* host_out) { return (int)h
 #define FZB_TIMING_BEGIN
 #define FZB_TIMING_END
 #endif
-template <int SWL, bool UPPER>
+struct SegNone {};
+template <int SWL, bool UPPER, bool SEG = false>
 __global__ __launch_bounds__(128, 4) void k2b_dp_short(const u8* __restrict__ bytes, const EndsAny ends, u64 first, u32 index_offset,
                                                     const u32* __restrict__ items, const u32* __restrict__ win, const u32* __restrict__ n_items_ptr,
                                                     const NeedleDev nd, int wmode, fzb_match_rec* __restrict__ out, u32 capacity, u32* __restrict__ dev_count,
-                                                    RejectOut rej, u32* __restrict__ kept_out, u32 ulen) {
+                                                    RejectOut rej, u32* __restrict__ kept_out, u32 ulen, std::conditional_t<SEG, SegList, SegNone> seg) {
     FZB_TIMING_BEGIN
     __shared__ CfTables tab;
     __shared__ u8 fl[256];
+    __shared__ u32 seg_pre[SEG ? FZB_SEG_MAX : 1u];  // exclusive prefix of the segment counts; entries at and beyond nseg hold the total
+    __shared__ u32 seg_wsum[2];
+    u32 sc[16];  // SEG: the thread's sixteen counts
+    if constexpr (SEG) {
+        const uint4* c4 = (const uint4*)seg.counts;  // (the array has FZB_SEG_MAX words whatever nseg is)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const u32 i0 = 16u * threadIdx.x + 4u * k;
+            const uint4 v = i0 < seg.nseg ? c4[4 * threadIdx.x + k] : make_uint4(0, 0, 0, 0);
+            sc[4 * k] = v.x;
+            sc[4 * k + 1] = i0 + 1 < seg.nseg ? v.y : 0u;
+            sc[4 * k + 2] = i0 + 2 < seg.nseg ? v.z : 0u;
+            sc[4 * k + 3] = i0 + 3 < seg.nseg ? v.w : 0u;
+        }
+    }
     cf_build_tables<UPPER>(nd, tab);
     if (wmode == 3) cf_build_typo_table(nd, fl);
+    u32 seg_incl = 0, seg_tot = 0;
+    if constexpr (SEG) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) seg_tot += sc[k];
+        seg_incl = seg_tot;
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 v = __shfl_up(seg_incl, off);
+            if ((threadIdx.x & 63) >= (u32)off) seg_incl += v;
+        }
+        if ((threadIdx.x & 63) == 63) seg_wsum[threadIdx.x >> 6] = seg_incl;
+    }
     __syncthreads();
-    const u32 M = __builtin_amdgcn_readfirstlane(*n_items_ptr);  // wave-uniform: keeps the loop control on the scalar unit
+    u32 M_;
+    if constexpr (SEG) {
+        u32 run = (threadIdx.x >= 64 ? seg_wsum[0] : 0u) + seg_incl - seg_tot;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            seg_pre[16 * threadIdx.x + k] = run;
+            run += sc[k];
+        }
+        M_ = seg_wsum[0] + seg_wsum[1];
+        __syncthreads();
+        if (blockIdx.x == 0 && threadIdx.x == 0) *seg.total_out = M_;  // counters[0]: fzb_last_counters' filter_survivors
+    } else {
+        M_ = *n_items_ptr;
+    }
+    const u32 M = __builtin_amdgcn_readfirstlane(M_);  // wave-uniform: keeps the loop control on the scalar unit
     // wmode 3 (typos): survivors that the decide pass rejected (rare) are skipped and the records behind them move up
     const u32 nrej = wmode == 3 ? __builtin_amdgcn_readfirstlane(*rej.count) : 0u;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -180,7 +227,14 @@ __global__ __launch_bounds__(128, 4) void k2b_dp_short(const u8* __restrict__ by
     auto load_item = [&](u64 j, u32& li, u32& ws, u32& we) {
         li = 0; ws = 0; we = 0;
         if (j < M) {
-            li = items ? items[j] : (u32)j;
+            if constexpr (SEG) {  // the last segment whose prefix is <= j holds survivor j (empty segments share their successor's prefix)
+                // (over all FZB_SEG_MAX entries - those at and beyond nseg hold the total, which no j reaches: eleven fixed steps without a loop,
+                // so that the three searches in front of the pipeline interleave and the one inside it overlaps the scoring)
+                const u32 sg = seg_find(seg_pre, FZB_SEG_MAX, FZB_SEG_MAX / 2, (u32)j);
+                li = seg.list[(size_t)sg * seg.stride + ((u32)j - seg_pre[sg])];
+            } else {
+                li = items ? items[j] : (u32)j;
+            }
             if (wmode == 0) { const uint2 w = *(const uint2*)(win + 2 * j); ws = w.x; we = w.y; }
         }
     };
@@ -1006,20 +1060,20 @@ bool fzb_dp_short_applies(const CorpusDev& c, int sw_lanes, int mode) {
 
 void fzb_launch_dp(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* win, const u32* n_items_ptr, const NeedleDev& nd,
                    int sw_lanes, int mode, int wmode, int pad_ok, fzb_match_rec* out, u32 capacity, u32* dev_count, u32* overflow, u32 qcap, u32* counters, int num_cus, hipStream_t st,
-                   const RejectOut* rejects) {
+                   const RejectOut* rejects, const SegList* seg) {
     bool upper = false;  // an uppercase letter among the needle bytes as they are compared
     for (int r = 0; r < nd.rows; r++) upper = upper || (nd.c[r] >= 'A' && nd.c[r] <= 'Z');
     if (fzb_dp_short_applies(c, sw_lanes, mode)) {
         const RejectOut rj = rejects ? *rejects : RejectOut{};
         u32* kept_out = rejects ? &counters[1] : nullptr;
         // every haystack fits half a chunk (and the two prefetched vectors): the short-haystack kernel
-#define FZB_K2S(SWL, U, ET)                                                                                                             \
+#define FZB_K2S(SWL, U, SEG, SA)                                                                                                        \
     do {                                                                                                                                \
         static int per_cu = 0;                                                                                                          \
-        if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp_short<SWL, U>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
-        hipLaunchKernelGGL((k2b_dp_short<SWL, U>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, rj, kept_out, c.uniform_len); \
+        if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp_short<SWL, U, SEG>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
+        hipLaunchKernelGGL((k2b_dp_short<SWL, U, SEG>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, rj, kept_out, c.uniform_len, SA); \
     } while (0)
-#define FZB_K2S_ET(SWL, U) FZB_K2S(SWL, U, u32)
+#define FZB_K2S_ET(SWL, U) do { if (seg) FZB_K2S(SWL, U, true, *seg); else FZB_K2S(SWL, U, false, SegNone{}); } while (0)
 #define FZB_K2S_U(SWL) do { if (upper) FZB_K2S_ET(SWL, true); else FZB_K2S_ET(SWL, false); } while (0)
         if (sw_lanes == 64) FZB_K2S_U(64); else FZB_K2S_U(32);
         return;

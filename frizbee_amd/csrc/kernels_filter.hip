@@ -12,6 +12,7 @@
 #include "compact1.h"
 #include "dfa_lds.h"
 #include "sig_filter.h"
+#include "seg_list.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -141,9 +142,10 @@ __global__ __launch_bounds__(256) void k1_filter(const u8* __restrict__ bytes, c
 // 10.7 M VALU instructions per launch, the same 57 us, more LDS bank conflicts; round 6 closed the topic: profiles/r06_corun.txt, profiles/HISTORY.md.)
 // One tile of k1_dfa: the four haystacks thread `tid` owns (positions p * 256 + tid), decided and written to the bitmap; returns the
 // lane's share of the tile's count (non-zero in lane 0 of every wave only).  Shared by k1_dfa and by k1_dfa_sig's dense tiles.
-template <typename ET>
+// lds_bits (k1_dfa_sig listing its survivors): the tile's 32 decision words in LDS get the ballots too.
+template <typename ET, bool LDS_BITS = false>
 __device__ __forceinline__ u32 dfa_stream_tile(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 first, u32 count, u32 tile, int tid, u32 ulen, u32 min_len,
-                                               u32 acc_lo, const u8* dfa, u64* __restrict__ bitmap) {
+                                               u32 acc_lo, const u8* dfa, u64* __restrict__ bitmap, u32* lds_bits = nullptr) {
     u64 hs[4];
     u32 hl[4];
     uint4 v0[4], v1[4];
@@ -195,6 +197,10 @@ __device__ __forceinline__ u32 dfa_stream_tile(const u8* __restrict__ bytes, con
         if (lane_id() == 0) {
             bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
             cnt += __popcll(b);
+            if constexpr (LDS_BITS) {
+                lds_bits[p * 8 + 2 * (tid >> 6)] = (u32)b;
+                lds_bits[p * 8 + 2 * (tid >> 6) + 1] = (u32)(b >> 32);
+            }
         }
     }
     return cnt;
@@ -236,6 +242,14 @@ __global__ __launch_bounds__(256) void k1_dfa(const u8* __restrict__ bytes, cons
 // slower: 70.8 against 67.8 us per step, profiles/sig_filter.txt; not kept.)
 // Only for needles sig_filter.h calls eligible: a zero byte then matches no row, and rows are masked to their length before the chain.
 // No spin-waits, no ordering between workgroups.
+// SEG (contiguous ranges in front of k2b_dp_short: host.hip, pipe_filter_stage): the kernel also LISTS its survivors, so that no compaction
+// launch follows.  A workgroup then owns a contiguous run of tiles instead of a grid-strided set (seg_list.h: the partition k_compact1
+// uses), every tile's decisions - a dense tile's ballots too - end in the LDS bitmap, and after each tile all four waves rank its set bits
+// (32 word popcounts scanned in every wave, position p * 256 + tid per thread: a dense tile's stores are coalesced) and store the
+// range-relative indices in ascending order behind the run's earlier ones at seg.list[b * seg.stride + k]; seg.counts[b] = the run's
+// survivors.  Bitmap words and tile counts are written as before: every consumer outside that path still reads them.
+// Tiles are still taken one at a time (the signatures of several tiles requested in one round trip and their queues gathered together is
+// not built: profiles/sig_batched.txt).
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint4 sig_mask_vec(uint4 q, u32 nbytes) {  // bytes [nbytes, 16) -> 0
     u32 w[4] = {q.x, q.y, q.z, q.w};
@@ -258,10 +272,10 @@ __device__ __forceinline__ u32 dfa_chain16(u32 st, const uint4& q, const u8* dfa
     return st;
 }
 // (8 waves per SIMD like k1_dfa, whose grid - 8 workgroups per CU - it shares: without the bound the kernel takes 68 VGPRs and a CU holds 7)
-template <typename ET>
+template <typename ET, bool SEG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k1_dfa_sig(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u32* __restrict__ sig, u32 nsig, u64 first, u32 count,
                                                   const u8* __restrict__ dfa_g, int rows, u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts,
-                                                  u32* __restrict__ reset_counters, u32 ulen, u32 gather_max) {
+                                                  u32* __restrict__ reset_counters, u32 ulen, u32 gather_max, SegList seg) {
     if (blockIdx.x == 0 && threadIdx.x < 16) reset_counters[threadIdx.x] = 0;
     // LDS behind the table (which stays the first object, at address 0): tile count, queue length, the tile's 1024 decision bits, the queue
     extern __shared__ __attribute__((aligned(16))) u8 dfa[];
@@ -288,7 +302,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         }
         return s;
     };
-    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    // SEG: the workgroup's run of tiles and the survivors it has listed so far (workgroup-uniform)
+    u32 t_begin = blockIdx.x, t_end = ntiles, seg_n = 0;
+    if (SEG) seg_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, t_begin, t_end);
+    u32* const seg_out = SEG ? seg.list + (size_t)blockIdx.x * seg.stride : nullptr;
+    for (u32 tile = t_begin; tile < t_end; tile += SEG ? 1u : gridDim.x) {
         if (tid == 0) s_cnt = 0, s_q = 0;
         if (tid < 32) s_bits[tid] = 0;
         const uint4 s = load_sigs(tile);
@@ -315,8 +333,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         __syncthreads();
         const u32 Q = s_q;  // the same for the whole workgroup: so is the branch
         if (Q > gather_max) {
-            const u32 cnt = dfa_stream_tile<ET>(bytes, ends, first, count, tile, tid, ulen, min_len, acc_lo, dfa, bitmap);
-            if (lane == 0 && cnt) atomicAdd(&s_cnt, cnt);
+            const u32 cnt = dfa_stream_tile<ET, SEG>(bytes, ends, first, count, tile, tid, ulen, min_len, acc_lo, dfa, bitmap, s_bits);
+            if (!SEG && lane == 0 && cnt) atomicAdd(&s_cnt, cnt);
         } else {
             for (u32 e = tid; e < Q; e += 256) {
                 const u32 pos = queue[e];
@@ -333,17 +351,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 st = dfa_chain16(st, b, dfa);
                 if (L >= min_len && st >= acc_lo) atomicOr(&s_bits[pos >> 5], 1u << (pos & 31));
             }
-            __syncthreads();
-            if (tid < FZB_TILE / 64) {
-                const u64 word = (u64)s_bits[2 * tid] | ((u64)s_bits[2 * tid + 1] << 32);
-                bitmap[(size_t)tile * (FZB_TILE / 64) + tid] = word;
-                const u32 c = (u32)__popcll(word);
-                if (c) atomicAdd(&s_cnt, c);
+            if (!SEG) {
+                __syncthreads();
+                if (tid < FZB_TILE / 64) {
+                    const u64 word = (u64)s_bits[2 * tid] | ((u64)s_bits[2 * tid + 1] << 32);
+                    bitmap[(size_t)tile * (FZB_TILE / 64) + tid] = word;
+                    const u32 c = (u32)__popcll(word);
+                    if (c) atomicAdd(&s_cnt, c);
+                }
             }
         }
         __syncthreads();
-        if (tid == 0) tile_counts[tile] = s_cnt;
+        if (!SEG) {
+            if (tid == 0) tile_counts[tile] = s_cnt;
+        } else {
+            // every wave scans the 32 word popcounts itself (lanes 32..63 mirror 0..31): no prefix array in LDS, no barrier for one.
+            // (The thread index goes through an empty asm and the cross-lane reads are ds_bpermute with addresses made from it: as loop
+            // invariants the four word indices, the bit masks and the bitmap word's address are hoisted out of the tile loop - a dozen
+            // registers live across the dense tile's body, which the kernel's 64-VGPR bound turns into scratch.)
+            u32 t = (u32)tid;
+            asm volatile("" : "+v"(t));
+            const u32 l32 = t & 31u;
+            const u32 wl = s_bits[l32];
+            const u32 c = (u32)__popc(wl);
+            // (inclusive scan of the 32 counts: four row_shr steps inside each row of 16 lanes - lanes without a source add 0 -, then row 0's sum
+            // into row 1: some ten VALU instructions instead of five dependent cross-lane reads through LDS)
+            u32 incl = c;
+            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
+            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
+            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
+            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
+            incl += (l32 & 16u) ? (u32)__builtin_amdgcn_readlane((int)incl, 15) : 0u;
+            const u32 excl = incl - c, total = (u32)__builtin_amdgcn_readlane((int)incl, 31);
+            if (tid == 0) tile_counts[tile] = total;
+            if (Q <= gather_max && t < FZB_TILE / 64) bitmap[(size_t)tile * (FZB_TILE / 64) + t] = (u64)s_bits[2 * t] | ((u64)s_bits[2 * t + 1] << 32);  // (a dense tile's words are written)
+            if (total) {  // workgroup-uniform
+#pragma unroll
+                for (int p = 0; p < FZB_TILE / 256; p++) {
+                    const u32 pos = (u32)(p * 256) + t, w = pos >> 5;  // (one of two words per wave)
+                    const u32 word = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)wl), before = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)excl);
+                    if ((word >> (pos & 31)) & 1) seg_out[seg_n + seg_rank(before, word, pos & 31)] = tile * FZB_TILE + pos;
+                }
+            }
+            seg_n += total;
+            __syncthreads();  // the next tile clears the decision words
+        }
     }
+    if (SEG && tid == 0) seg.counts[blockIdx.x] = seg_n;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -890,9 +944,13 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
 // ---------------------------------------------------------------------------------------------------
 // host-side launch wrappers (called from host.hip)
 // ---------------------------------------------------------------------------------------------------
+bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int sig_ok) {
+    return mode == 1 && c.max_len != 0 && c.max_len <= 32 && sig_ok && needle_sig && c.sig && !fzb_knobs().no_signature;
+}
+
 void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* table, const u8* dfa, u32 dead, int rows, int mode, int need, u32 min_len,
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m, u32* tile_counts_m, u64* reject_bits, u32* tile_rejects, int nul_safe,
-                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G, u32 needle_sig, int sig_ok) {
+                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G, u32 needle_sig, int sig_ok, const SegList* seg) {
     // mode 1: `dfa` has rows + 1 states, start state 0, and accepts in the states >= acc (the subsequence / unicode / KMP automata: the last
     // state; the LCS automaton of a typo configuration: every state whose LCS reaches the need)
     const u32 acc = acc_lo < 0 ? (u32)rows : (u32)acc_lo;
@@ -903,10 +961,14 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
     if (mode == 1) {
         const size_t lds = (size_t)(rows + 1) * FZB_DFA_STRIDE + 16;  // table + the tile counter
         const bool shortc = c.max_len != 0 && c.max_len <= 32;  // every haystack fits the two pre-requested vectors
-        if (shortc && sig_ok && needle_sig && c.sig && !fzb_knobs().no_signature) {  // an eligible needle over a list with signatures (host.hip decides eligibility)
+        if (fzb_filter_sig_applies(c, mode, needle_sig, sig_ok)) {  // an eligible needle over a list with signatures (host.hip decides eligibility)
             const size_t lds_s = lds + 128 + 2 * FZB_TILE;  // + the tile's decision bits and the queue of passing rows
-#define FZB_K1S(ET) hipLaunchKernelGGL((k1_dfa_sig<ET>), dim3(grid), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE))
-            if (c.ends_u64) FZB_K1S(u64); else FZB_K1S(u32);
+#define FZB_K1S(ET, SEG, G, S) hipLaunchKernelGGL((k1_dfa_sig<ET, SEG>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE), S)
+            if (seg) {  // the filter lists its survivors: one workgroup per segment
+                if (c.ends_u64) FZB_K1S(u64, true, seg->nseg, *seg); else FZB_K1S(u32, true, seg->nseg, *seg);
+            } else {
+                if (c.ends_u64) FZB_K1S(u64, false, grid, SegList{}); else FZB_K1S(u32, false, grid, SegList{});
+            }
 #undef FZB_K1S
             return;
         }

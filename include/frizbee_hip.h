@@ -654,6 +654,9 @@ int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len,
 int fzb_debug_needle_signature(const fzb_matcher* m, uint32_t* out_mask, int* out_eligible);
 /* test hook: a 1024-haystack tile with more rows than this passing the signature test is streamed whole instead of gathered */
 uint32_t fzb_debug_signature_threshold(void);
+/* test hook: caps the grid of the signature filter where it lists its own survivors (0 = default), so that small lists exercise runs of
+ * several tiles per workgroup */
+void fzb_debug_set_filter_grid(int grid);
 
 /* test hook: the library's environment switches (frizbee_amd/csrc/knobs.h - comparison and debugging only, parsed once on first use) are
  * read again.  Matchers created before the call keep what was decided when they were created. */
