@@ -128,6 +128,9 @@ SYMBOLS = [
     "fzb_corpus_signature_info", "fzb_debug_needle_signature", "fzb_debug_signature_threshold", "fzb_debug_set_filter_grid",
     "fzb_corpus_set_bias", "fzb_corpus_update_bias", "fzb_corpus_clear_bias", "fzb_corpus_bias_info",
     "fzb_corpus_set_tags", "fzb_corpus_update_tags", "fzb_corpus_clear_tags", "fzb_corpus_set_scope", "fzb_corpus_scope_info",
+    "fzb_corpus_generation", "fzb_subset_create", "fzb_subset_free", "fzb_subset_set_indices", "fzb_subset_from_scope", "fzb_subset_info", "fzb_subset_read",
+    "fzb_match_list_subset", "fzb_match_list_top_subset", "fzb_match_list_top_subset_device", "fzb_match_list_top_indices_subset",
+    "fzb_debug_set_items_dfa_min",
 ]
 
 
@@ -249,6 +252,21 @@ def lib():
         l.fzb_corpus_clear_tags.argtypes = [C.c_void_p]
         l.fzb_corpus_set_scope.argtypes = [C.c_void_p, C.c_uint16, C.c_uint16]
         l.fzb_corpus_scope_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_debug_set_items_dfa_min.argtypes = [C.c_uint32]
+        l.fzb_debug_set_items_dfa_min.restype = None
+        l.fzb_corpus_generation.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_subset_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        l.fzb_subset_free.argtypes = [C.c_void_p]
+        l.fzb_subset_free.restype = None
+        l.fzb_subset_set_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        l.fzb_subset_from_scope.argtypes = [C.c_void_p, C.c_void_p, C.c_uint16, C.c_uint16]
+        l.fzb_subset_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        l.fzb_subset_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        l.fzb_match_list_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        l.fzb_match_list_top_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_subset_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_match_list_top_indices_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                        C.POINTER(C.c_uint64)]
         _lib = l
     return _lib
 
@@ -484,6 +502,12 @@ class Corpus:
             _check(lib().fzb_debug_corpus_read(self.h, code, buf.ctypes.data, buf.nbytes, C.byref(n)))
         return buf.view(dtype)
 
+    def generation(self):
+        """the list's generation: bumped by every append / truncate / remove / replace that changed it (what a `Subset` is checked against)"""
+        out = C.c_uint64()
+        _check(lib().fzb_corpus_generation(self.h, C.byref(out)))
+        return out.value
+
     def __len__(self):
         return lib().fzb_corpus_len(self.h)
 
@@ -497,6 +521,57 @@ class Corpus:
 
 
 SHARD_BY_COUNT, SHARD_BY_BYTES, SHARD_OVERSUBSCRIBE = 0, 1, 2  # include/frizbee_hip.h FZB_SHARD_*
+
+
+class Subset:
+    """A candidate set of one resident `Corpus`: strictly ascending haystack indices in HBM (fzb_subset).  The input (`subset=`) or the
+    captured match set (`capture=`) of `Matcher.match_list` / `match_list_top` / `match_list_top_device` / `match_list_top_indices`: a query
+    over a subset returns what it returns over an upload of those haystacks alone, every index mapped back to the full list's.  The
+    reference has no counterpart: its caller builds a new Vec of the survivors."""
+
+    def __init__(self, corpus):
+        self.corpus = corpus  # (keeps the corpus alive: the handle points at it)
+        self.h = C.c_void_p()
+        _check(lib().fzb_subset_create(corpus.h, C.byref(self.h)))
+
+    def set_indices(self, indices):
+        """the subset becomes `indices` (strictly ascending, each below len(corpus)); one host-to-device copy"""
+        a = np.asarray(indices)
+        if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("Subset.set_indices: the indices must be integers that fit uint32")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        _check(lib().fzb_subset_set_indices(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    def from_scope(self, require=0, exclude=0):
+        """the subset becomes the haystacks visible under (require, exclude) over the corpus' tags, computed on the device"""
+        _check(lib().fzb_subset_from_scope(self.h, self.corpus.h, require, exclude))
+
+    def info(self):
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_subset_info(self.h, out))
+        return dict(known=int(out[0]), count=int(out[1]), capacity=int(out[2]), generation=int(out[3]))
+
+    def read(self):
+        """the indices as a uint32 array (a synchronous copy)"""
+        out = np.zeros(max(len(self), 1), np.uint32)
+        n = C.c_size_t()
+        _check(lib().fzb_subset_read(self.h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def __len__(self):
+        return self.info()["count"]  # (synchronises when the last capture left the count on the device only)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) is not None and self.h:
+                lib().fzb_subset_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+def _h(subset):
+    return None if subset is None else subset.h
 
 
 def device_count():
@@ -843,34 +918,50 @@ class Matcher(_IterApi):
     def _corpus(self, haystacks):
         return haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
 
-    def match_list(self, haystacks, copy=True):
-        """`Matcher::match_list` (src/matcher/mod.rs:212-222). `haystacks` is a list of str/bytes or a resident `Corpus`."""
+    def match_list(self, haystacks, copy=True, *, subset=None, capture=None):
+        """`Matcher::match_list` (src/matcher/mod.rs:212-222). `haystacks` is a list of str/bytes or a resident `Corpus`.
+        subset / capture (`Subset`s of that corpus, here and in the top-`limit` forms): the query runs over `subset` only, and `capture`
+        receives the indices of every haystack the matcher accepted - before bias, scope, `limit` and ordering."""
         cp = self._corpus(haystacks)
         out, n = C.c_void_p(), C.c_size_t()
-        _check(lib().fzb_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
+        if subset is None and capture is None:
+            _check(lib().fzb_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
+        else:
+            _check(lib().fzb_match_list_subset(self.h, cp.h, _h(subset), _h(capture), C.byref(out), C.byref(n)))
         return _take(out, n, copy)
 
-    def match_list_top(self, haystacks, limit, copy=True):
+    def match_list_top(self, haystacks, limit, copy=True, *, subset=None, capture=None):
         """(`match_list(haystacks)[:limit]`, len(`match_list(haystacks)`)): the threshold score, the records of the head (ties at the cut
         as the stable sort breaks them) and their order are found on the device; only `limit` records are copied.  The reference has no
         such call - its caller truncates the Vec `match_list` returns (src/matcher/mod.rs:212-222)."""
-        return _top(lib().fzb_match_list_top, self.h, self._corpus(haystacks).h, limit, copy)
+        if subset is None and capture is None:
+            return _top(lib().fzb_match_list_top, self.h, self._corpus(haystacks).h, limit, copy)
+        out, n, found = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        _check(lib().fzb_match_list_top_subset(self.h, self._corpus(haystacks).h, _h(subset), _h(capture), limit, C.byref(out), C.byref(n), C.byref(found)))
+        return _take(out, n, copy), found.value
 
-    def match_list_top_device(self, corpus, limit, dev_out_ptr, capacity, dev_count_ptr, stream=0):
+    def match_list_top_device(self, corpus, limit, dev_out_ptr, capacity, dev_count_ptr, stream=0, *, subset=None, capture=None):
         """`match_list_top` with the result left in HBM: `capacity` >= min(limit, len(corpus)) records at `dev_out_ptr`, two count words
         (records written, matches found) at `dev_count_ptr`; asynchronous on `stream`."""
-        _check(lib().fzb_match_list_top_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_count_ptr, stream))
+        if subset is None and capture is None:
+            _check(lib().fzb_match_list_top_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_count_ptr, stream))
+        else:
+            _check(lib().fzb_match_list_top_subset_device(self.h, corpus.h, _h(subset), _h(capture), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
 
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
-    def match_list_top_indices(self, haystacks, limit):
+    def match_list_top_indices(self, haystacks, limit, *, subset=None, capture=None):
         """(the first min(limit, found) entries of `Matcher::match_list_indices` over the whole list, found): what a picker shows after a
         keystroke.  `index` is the corpus index, `indices` the matched byte positions in reverse order.  The reference's caller truncates
         the Vec (src/matcher/mod.rs:234-275); here the top stage, a traced pass over its head and the packing of the positions are ONE
         device call with one host wait."""
-        return _top_indices(lib().fzb_match_list_top_indices, self.h, self._corpus(haystacks), limit)
+        if subset is None and capture is None:
+            return _top_indices(lib().fzb_match_list_top_indices, self.h, self._corpus(haystacks), limit)
+        out, n, pos, found = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_uint64()
+        _check(lib().fzb_match_list_top_indices_subset(self.h, self._corpus(haystacks).h, _h(subset), _h(capture), limit, C.byref(out), C.byref(n), C.byref(pos), C.byref(found)))
+        return _take_indices(out, n, pos), found.value
 
     def match_list_top_indices_device(self, corpus, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream=0):
         """`match_list_top_indices` with the result left in HBM, asynchronous on `stream`: `capacity` >= min(limit, len(corpus)) records of
@@ -977,6 +1068,65 @@ class Matcher(_IterApi):
                 self.h = None
         except Exception:
             pass
+
+
+class NarrowingMatcher:
+    """The keystroke loop as a picker writes it: a `Matcher` over one resident `Corpus` and two `Subset`s that alternate.  Every query
+    captures its match set; the next query runs over that capture instead of the whole list when ALL of these hold: fuzzy matching,
+    max_typos == 0, the new needle is the previous one plus a non-empty suffix, `Matcher.info()` reports the same unicode path and lane
+    pair for both needles, the corpus generation is unchanged, the captured count is known, and it is at most max_fraction x len(corpus).
+    (The same unicode path: a non-ASCII suffix moves the matcher to the unicode kernels, whose case folding accepts haystacks the ASCII
+    automaton of the shorter needle rejected - the subset relation is not given.  Smart case going from insensitive to sensitive only
+    rejects more and needs no condition.  tests/test_oracle_narrowing_premise.py holds the premise against the oracle.)
+    max_fraction: None = DEFAULT_MAX_FRACTION = 0.8 x the largest candidate fraction at which tools/bench_subset.py measured the narrowed
+    call not slower than the whole-list call.  On its two (dense, synthetic) lists that was none - 5.5 to 17 % of the list as candidates,
+    of which 78 - 90 % match again: narrowed + 10 to + 19 us (profiles/subset.txt) - so the default is 0.0: never narrow.  A caller whose
+    lists thin out faster passes its own."""
+
+    DEFAULT_MAX_FRACTION = 0.0
+
+    def __init__(self, corpus, config=None, max_fraction=None):
+        self.corpus = corpus
+        self.config = config or Config()
+        self.max_fraction = self.DEFAULT_MAX_FRACTION if max_fraction is None else float(max_fraction)
+        self.matcher = Matcher("", self.config)
+        self.subsets = [Subset(corpus), Subset(corpus)]
+        self._cur = None         # index of the subset that holds the previous query's capture
+        self._prev = None        # (needle bytes, (unicode, pf_lanes, sw_lanes), corpus generation) of that query
+        self.last_narrowed = False
+
+    def _may_narrow(self, needle, path):
+        if self._cur is None or self._prev is None:
+            return False
+        prev_needle, prev_path, prev_gen = self._prev
+        cfg = self.config
+        if cfg.matching != Matching.Fuzzy or cfg.max_typos != 0:
+            return False
+        if not prev_needle or len(needle) <= len(prev_needle) or not needle.startswith(prev_needle):
+            return False
+        if path != prev_path or self.corpus.generation() != prev_gen:
+            return False
+        cap = self.subsets[self._cur]
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_subset_info(cap.h, out))
+        return self.max_fraction > 0 and bool(out[0]) and out[1] <= self.max_fraction * len(self.corpus)
+
+    def query(self, needle, limit, indices=False):
+        """what `Matcher.match_list_top` (indices=False) / `match_list_top_indices` (True) return for `needle`; `last_narrowed` tells
+        whether the previous capture was the input"""
+        n = _b(needle)
+        self.matcher.set_pattern(n)
+        i = self.matcher.info()
+        path = (i["unicode"], i["pf_lanes"], i["sw_lanes"])
+        narrow = self._may_narrow(n, path)
+        src = self.subsets[self._cur] if narrow else None
+        dst_i = 1 - self._cur if self._cur is not None else 0
+        dst = self.subsets[dst_i]
+        self._cur = self._prev = None  # (an error below leaves no capture to narrow from)
+        fn = self.matcher.match_list_top_indices if indices else self.matcher.match_list_top
+        res = fn(self.corpus, limit, subset=src, capture=dst)
+        self._cur, self._prev, self.last_narrowed = dst_i, (bytes(n), path, self.corpus.generation()), narrow
+        return res
 
 
 def radix_sort_matches(matches):

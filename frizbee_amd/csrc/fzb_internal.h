@@ -224,7 +224,9 @@ void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st);  // the 16
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,
                          u32* total_out2 = nullptr);
 void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, const u32* n_items_ptr, const u64* table, int rows, int mode, int need, u32 min_len,
-                             u64* bitmap, u32* tile_counts, int grid, hipStream_t st);
+                             u64* bitmap, u32* tile_counts, int grid, hipStream_t st, const u8* dfa = nullptr, int exact = 0, u32 needle_sig = 0, int sig_ok = 0, u64 n_hint = 0);
+// (dfa .. n_hint: the item list of a candidate set - k1_items_dfa where fzb_filter_items_dfa_applies, k1_items otherwise; n_hint = the list's length as far as the host knows)
+bool fzb_filter_items_dfa_applies(const CorpusDev& c, int mode, int exact, const u8* dfa, int rows, u64 n_hint);
 void fzb_launch_compact2(const u64* bitmap, const u32* counts, const u32* n_items_ptr, const u32* in_idx, const u32* in_win, u32* out_idx, u32* out_win, u32* total_out,
                          int grid, hipStream_t st);
 // kernels_window.hip
@@ -285,6 +287,10 @@ void fzb_launch_join_add(fzb_match_rec* hits, const u32* n_hits_ptr, const fzb_m
 void fzb_launch_remove_hits(const fzb_match_rec* cand, const u32* n_cand_ptr, const fzb_match_rec* hits, const u32* n_hits_ptr, u64* bitmap, u32* tile_counts,
                             fzb_match_rec* out, u32* total_out, int grid, hipStream_t st);
 void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, int grid, hipStream_t st);
+// kernels_subset.hip: the candidate sets' capture (index-ordered records -> ascending haystack indices + their count; mirror: a second word for the
+// count, may be null) and fzb_subset_from_scope's flag pass + k_compact1
+void fzb_launch_subset_capture(const fzb_match_rec* recs, const u32* n_ptr, u32 cap, u32 index_offset, u32* items, u32 items_cap, u32* count_out, u32* mirror, int grid_max, hipStream_t st);
+void fzb_launch_subset_from_scope(const uint16_t* tags, u32 n, u32 require, u32 exclude, u64* bitmap, u32* tile_counts, u32* out, u32* count_out, int grid_max, hipStream_t st);
 // kernels_literal.hip
 void fzb_launch_literal_filter(const CorpusDev& c, u64 first, u32 count, const u32* items, const u32* n_items_ptr, const NeedleDev& nd, int mode, u64* bitmap, u32* tile_counts,
                                int grid, hipStream_t st);

@@ -185,6 +185,7 @@ FzbKnobs parse_knobs() {
     k.no_dp_classes = set("FZB_NO_DP_CLASSES");
     k.no_fused_classify = set("FZB_NO_FUSED_CLASSIFY");
     k.no_seg_list = on("FZB_NO_SEG_LIST");
+    k.no_items_dfa = on("FZB_NO_ITEMS_DFA");
     k.no_dp_cfm = set("FZB_NO_DP_CFM");
     k.no_dp_cfu = set("FZB_NO_DP_CFU");
     k.unicode_multi = num("FZB_UNICODE_MULTI", -1);
@@ -1425,6 +1426,7 @@ struct Pipe {
     const TraceOut* trace;
     hipEvent_t* pev;         // profiling events of this call (nullptr: not profiled)
     int cus;
+    u64 items_hint = 0;      // the item list is a candidate set's: its length as far as the host knows (0: a few thousand items at most - the multi-pattern narrowing, a head's traced pass)
     // what the filter stage leaves for the scorers
     const u32* items = nullptr;
     const u32* win = nullptr;
@@ -1540,7 +1542,9 @@ static int pipe_filter_stage(Pipe& p) {
             HIPCHK(hipMemcpyAsync(&cnt_c[0], p.n_items_in, 4, hipMemcpyDeviceToDevice, p.st));
             p.items = p.items_in;
         } else {
-            fzb_launch_filter_items(p.cd, p.first, p.items_in, p.n_items_in, w.table, nd.rows, lc.filter_mode, need, (u32)nd.min_haystack_len, w.bitmap, w.tile_counts, p.cus * 4, p.st);
+            // (a candidate set's list, fuzzy ASCII 0 typos: k1_items_dfa - the contiguous path's automaton - from the measured size on)
+            fzb_launch_filter_items(p.cd, p.first, p.items_in, p.n_items_in, w.table, nd.rows, lc.filter_mode, need, (u32)nd.min_haystack_len, w.bitmap, w.tile_counts, p.cus * 4, p.st,
+                                    nd.unicode ? nullptr : w.dfa, lc.filter_exact, m->needle_sig, m->sig_eligible, p.items_hint);
             FZB_STAGE("filter(items)");
             fzb_launch_compact1(w.bitmap, w.tile_counts, 0, p.n_items_in, p.items_in, w.surv_idx, &cnt_c[0], p.cus * 2, p.st);
             FZB_STAGE("compact1(items)");
@@ -1808,7 +1812,7 @@ static int pipe_profile_begin(fzb_matcher* m, bool has_filter, hipStream_t st, h
 // composition.  `trace` != nullptr: the matched-indices form - every record also gets its matched byte positions (the traced generic scorer
 // replaces the fast scorers; literal modes write the needle run).
 static int run_pipeline(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, const u32* items_in, const u32* n_items_in,
-                        fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream, const TraceOut* trace = nullptr) {
+                        fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream, const TraceOut* trace = nullptr, u64 items_hint = 0) {
     if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     // an item list may repeat haystacks, so only the contiguous form bounds `count` by the corpus
     if (first > c->dev.n || (!items_in && count > c->dev.n - first)) return fail(FZB_ERR_INVALID, "range outside the corpus");
@@ -1836,7 +1840,7 @@ static int run_pipeline(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
         return FZB_OK;
     }
     if (m->long_needle) return run_pipeline_long(m, c, first, count, index_offset, items_in, n_items_in, dev_out, cap32, dev_count, st, trace);
-    Pipe p{m, c->dev, first, (u32)count, index_offset, items_in, n_items_in, (fzb_match_rec*)dev_out, cap32, dev_count, st, trace, nullptr, lc.num_cus};
+    Pipe p{m, c->dev, first, (u32)count, index_offset, items_in, n_items_in, (fzb_match_rec*)dev_out, cap32, dev_count, st, trace, nullptr, lc.num_cus, items_in ? items_hint : 0};
     if (m->literal_mode) return pipe_literal(p);
     if ((rc = pipe_profile_begin(m, lc.filter_mode && !items_in, st, &p.pev))) return rc;
     if (!items_in && lc.filter_mode != 0 && typo_fast_path_configured(m) && !trace && fzb_dp_short_applies(c->dev, lc.sw_lanes, 2)) {
@@ -1910,17 +1914,48 @@ static int reserve_slot_any_needle(fzb_matcher* m, const fzb_corpus* c) {
 }
 extern "C" {
 
-int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
-                          uint32_t* dev_count, void* stream) {
+}  // extern "C"
+// ---- candidate sets on the query path (fzb_subset; the handle's own calls are further down) ---------------------------------------------
+// What a *_subset entry point hands down: `in` (null: the whole corpus) becomes the pipeline's item list, `capture` (null: none) receives the
+// indices of the records the scorers wrote - BEFORE the list's terms, the selection and the ordering -, `mirror` (host forms) is a device word
+// next to the result's count words that gets the captured count too, so that the form's one wait brings it back.
+struct SubsetArgs {
+    const fzb_subset* in = nullptr;
+    fzb_subset* capture = nullptr;
+    u32* mirror = nullptr;
+};
+static const u32* subset_items(const SubsetArgs* sa) { return sa && sa->in ? sa->in->idx : nullptr; }
+static const u32* subset_count(const SubsetArgs* sa) { return sa && sa->in ? sa->in->count_dev : nullptr; }
+// what the host knows of the input's length (the filter's choice of kernel and grid): the count when known, else the room it was captured into
+static u64 subset_hint(const SubsetArgs* sa) { return sa && sa->in ? std::max<u64>(1, sa->in->known ? sa->in->count : (u64)sa->in->cap) : 0; }
+// the ONE place that launches the capture: recs = the producer's index-ordered records (numbered from index_offset 0 over the whole corpus)
+static int subset_capture(const SubsetArgs* sa, const fzb_corpus* c, const fzb_match_rec* recs, const u32* pair, size_t cap, int grid_max, hipStream_t st) {
+    if (!sa || !sa->capture) return FZB_OK;
+    fzb_subset* cp = sa->capture;
+    fzb_launch_subset_capture(recs, pair, (u32)std::min<size_t>(cap, 0xFFFFFFFFu), 0, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu), cp->count_dev, sa->mirror, grid_max, st);
+    HIPCHK(hipGetLastError());
+    cp->generation = c->generation;
+    cp->known = false;
+    return FZB_OK;
+}
+extern "C" {
+static int match_list_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
+                                  void* stream, const SubsetArgs* sa) {
     int rc;
     if (m && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the pipeline into the scratch, then the list's terms: drop, then bias
         if ((rc = fzb_scope_ensure(m->scope, count))) return rc;
-        if ((rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, (fzb_match*)m->scope.recs, count, m->scope.words, stream))) return rc;
+        if ((rc = run_pipeline(m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, count, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
+        if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, count, m->lc.num_cus * 2, (hipStream_t)stream))) return rc;
         return apply_terms(c, m->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
     }
-    rc = run_pipeline(m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
+    rc = run_pipeline(m, c, first, count, index_offset, subset_items(sa), subset_count(sa), dev_out, capacity, dev_count, stream, nullptr, subset_hint(sa));
     if (rc) return rc;
+    if ((rc = subset_capture(sa, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), m->lc.num_cus * 2, (hipStream_t)stream))) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
+}
+int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+                          uint32_t* dev_count, void* stream) {
+    return match_list_device_impl(m, c, first, count, index_offset, dev_out, capacity, dev_count, stream, nullptr);
 }
 
 int fzb_match_list_sorted_device(fzb_matcher* m, const fzb_corpus* c, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
@@ -1931,8 +1966,15 @@ int fzb_match_list_sorted_device(fzb_matcher* m, const fzb_corpus* c, fzb_match*
 }  // extern "C"
 // The ordered form over any sub-range, records numbered from index_offset: what one worker of `match_list_parallel` produces for its
 // share (per-run reverse / radix sort, src/matcher/parallel.rs:66-76) - fzb_match_list_parallel_sharded runs one per device
+static int sorted_range_impl(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
+                             void* stream, const SubsetArgs* sa);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream) {
+    return sorted_range_impl(m, c, first, count, index_offset, dev_out, capacity, dev_count, stream, nullptr);
+}
+// (sa: the candidate-set forms - the whole corpus from 0 - hand their item list and capture down to the pipeline's call)
+static int sorted_range_impl(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
+                             void* stream, const SubsetArgs* sa) {
     if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
     const size_t cap = std::min<size_t>(capacity, count);
@@ -1942,7 +1984,7 @@ int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, s
     if (!m->empty && count != 0 && ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, count, (hipStream_t)stream, true)))) return rc;
     if ((rc = fzb_order_begin(m, m->empty || count == 0 ? 0 : cap, (fzb_match_rec*)dev_out, &plan, fzb_corpus_bias_hi(c)))) return rc;
     // (the public call: the pipeline and, on a biased corpus, the bias pass over the index-ordered records - before anything orders them)
-    rc = fzb_match_list_device(m, c, first, count, index_offset, (fzb_match*)plan.in, plan.via_tmp ? cap : capacity, dev_count, stream);
+    rc = match_list_device_impl(m, c, first, count, index_offset, (fzb_match*)plan.in, plan.via_tmp ? cap : capacity, dev_count, stream, sa);
     if (rc) return rc;
     if (count == 0) return FZB_OK;
     return fzb_order_finish(m, plan, (fzb_match_rec*)dev_out, dev_count, (hipStream_t)stream);
@@ -2921,7 +2963,11 @@ int fzb_empty_pattern_top(size_t n, int sort, size_t limit, fzb_match** out, siz
 }
 extern "C" {
 
+static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
+    return top_device_impl(m, c, limit, dev_out, capacity, dev_count, stream, nullptr);
+}
+static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
@@ -2942,10 +2988,12 @@ int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit,
     Workspace& w = m->ws;
     u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
     if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
-        if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)m->scope.recs, n, m->scope.words, stream))) return rc;
+        if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, n, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
+        if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, n, m->lc.num_cus * 2, st))) return rc;
         if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st))) return rc;
     } else {
-        if ((rc = run_pipeline(m, c, 0, n, 0, nullptr, nullptr, (fzb_match*)w.sort.tmp, n, raw_count, stream))) return rc;
+        if ((rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)w.sort.tmp, n, raw_count, stream, nullptr, subset_hint(sa)))) return rc;
+        if ((rc = subset_capture(sa, c, w.sort.tmp, raw_count, n, m->lc.num_cus * 2, st))) return rc;
         if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
     }
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
@@ -3087,7 +3135,7 @@ int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb
 // previous result's size (*last_records, *last_positions) and a little more, and a result that outgrew it costs a second wait.
 // want / max_pos: the most records / positions the result can have.  `disagree`: what a raised inconsistency word means.
 int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32* dense, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions, const char* disagree,
-                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* fifth_word = nullptr) {  // fifth_word: words[4] is copied and returned too
     auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
     const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(*last_records, want);
     const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(*last_positions, max_pos);
@@ -3096,7 +3144,7 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
     const u32* const hw = (const u32*)stage;
     const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + 32);
     const u32* const hpos = (const u32*)(stage + 32 + grec * sizeof(fzb_match_indices));
-    hipError_t e = hipMemcpyAsync(stage, words, 16, hipMemcpyDeviceToHost, nullptr);
+    hipError_t e = hipMemcpyAsync(stage, words, fifth_word ? 20 : 16, hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess) e = fzb_stream_wait(nullptr);
@@ -3105,6 +3153,7 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
         return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
     }
     const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
+    if (fifth_word) *fifth_word = hw[4];
     if (hw[3]) {
         const u32 why = hw[3];
         fzb_pinned_put(stage);
@@ -3138,8 +3187,15 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
 }  // namespace
 extern "C" {
 
+static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                   uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
                                       uint32_t* dev_count, void* stream) {
+    return top_indices_device_impl(m, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
+}
+// (sa: the top stage runs over the candidate set and captures; the traced pass runs over the head's item list as before)
+static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                   uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!m || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
@@ -3160,7 +3216,7 @@ int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_
     u32* const head_count = m->top_idx_words;        // (records, matches found) of the head
     u32* const traced_count = m->top_idx_words + 2;  // the traced pass' pair
     u32* const n_items = m->trace_sel + m->trace_cap;
-    if ((rc = fzb_match_list_top_device(m, c, limit, (fzb_match*)m->top_head, want, head_count, stream))) return rc;
+    if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->top_head, want, head_count, stream, sa))) return rc;
     const int grid = m->lc.num_cus * 2;
     fzb_launch_top_items(m->top_head, head_count, (u32)want, m->trace_sel, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
     const TraceOut tr{m->trace_pos, m->trace_npos, stride};
@@ -3210,6 +3266,327 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
     if (!m->empty && (rc = ensure_workspace(m, n))) return rc;
     if ((rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
     return reserve_trace_cells(m, want, stride);
+}
+
+}  // extern "C"
+// ---- CANDIDATE SETS (include/frizbee_hip.h: fzb_subset) ----------------------------------------------------------------------------------
+// The handle: an ascending index list of ONE corpus in device memory, its count beside it.  The set-up calls follow the editing family's
+// rules (a corpus the library owns, on its device; they wait for outstanding device work on entry and are complete on return; an error
+// leaves the subset as it was).
+namespace {
+int subset_begin(const fzb_subset* s, const char* what) {
+    if (!s || !s->corpus) return fail(FZB_ERR_INVALID, "null argument");
+    int device = 0;
+    HIPCHK(hipGetDevice(&device));
+    if (device != s->corpus->device)
+        return fail(FZB_ERR_INVALID, std::string(what) + ": the subset's corpus lives on device " + std::to_string(s->corpus->device) + ", the current device is " + std::to_string(device));
+    HIPCHK(hipDeviceSynchronize());
+    return FZB_OK;
+}
+size_t subset_tiles(size_t items) { return ((items + FZB_TILE - 1) / FZB_TILE + 4) & ~(size_t)3; }
+// room for `want` indices: every array anew, the old ones released only when all three exist (an error leaves the subset as it was); the
+// indices are NOT carried over - every caller fills the whole list afterwards
+int subset_room(fzb_subset* s, size_t want) {
+    if (s->idx && s->cap >= want) return FZB_OK;
+    const size_t cap = std::max<size_t>(std::max<size_t>(want, s->cap * 2), 1);
+    u32* idx = nullptr;
+    u64* bitmap = nullptr;
+    u32* tiles = nullptr;
+    hipError_t e = dev_alloc((void**)&idx, cap * 4);
+    if (e == hipSuccess) e = dev_alloc((void**)&bitmap, subset_tiles(cap) * (FZB_TILE / 64) * 8);
+    if (e == hipSuccess) e = dev_alloc((void**)&tiles, subset_tiles(cap) * 4);
+    if (e != hipSuccess) {
+        if (idx) (void)hipFree(idx);
+        if (bitmap) (void)hipFree(bitmap);
+        if (tiles) (void)hipFree(tiles);
+        return fail(FZB_ERR_HIP, std::string("fzb_subset (room for ") + std::to_string(cap) + " indices): " + hipGetErrorString(e));
+    }
+    if (s->idx) (void)hipFree(s->idx);
+    if (s->bitmap) (void)hipFree(s->bitmap);
+    if (s->tiles) (void)hipFree(s->tiles);
+    s->idx = idx;
+    s->bitmap = bitmap;
+    s->tiles = tiles;
+    s->cap = cap;
+    return FZB_OK;
+}
+// the count on the host: read back (and the device waited for) only when the last capture left it unknown
+int subset_count_host(fzb_subset* s, u64* out) {
+    if (!s->known) {
+        u32 n = 0;
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(&n, s->count_dev, 4, hipMemcpyDeviceToHost));
+        s->count = n;
+        s->known = true;
+    }
+    *out = s->count;
+    return FZB_OK;
+}
+// what every *_subset query checks before anything is launched; grows the capture's room when the list outgrew it
+int subset_check(const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, const char* call) {
+    if (in && capture && in == capture) return fail(FZB_ERR_INVALID, std::string(call) + ": the capture subset is the input subset; use two and alternate them");
+    if ((in || capture) && !c->own_bytes)
+        return fail(FZB_ERR_INVALID, std::string(call) + ": the corpus borrows its device memory (fzb_corpus_from_device); a subset needs a corpus made by fzb_corpus_upload");
+    if (in && in->corpus != c) return fail(FZB_ERR_INVALID, std::string(call) + ": the input subset is stale: it belongs to another corpus");
+    if (in && in->generation != c->generation)
+        return fail(FZB_ERR_INVALID, std::string(call) + ": the input subset is stale: it was filled at generation " + std::to_string(in->generation) + " of the corpus, which is now at " +
+                                         std::to_string(c->generation) + " (the list changed since)");
+    if (capture && capture->corpus != c) return fail(FZB_ERR_INVALID, std::string(call) + ": the capture subset belongs to another corpus");
+    if (capture) return subset_room(capture, c->dev.n);
+    return FZB_OK;
+}
+// a capture whose query launched nothing (an empty corpus, an empty needle): the set itself, written by a set-up style copy
+int subset_capture_trivial(const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture) {
+    if (!capture) return FZB_OK;
+    HIPCHK(hipDeviceSynchronize());
+    if (in) {
+        u64 n = 0;
+        if (int rc = subset_count_host(const_cast<fzb_subset*>(in), &n)) return rc;
+        if (n) HIPCHK(hipMemcpy(capture->idx, in->idx, n * 4, hipMemcpyDeviceToDevice));
+        HIPCHK(hipMemcpy(capture->count_dev, in->count_dev, 4, hipMemcpyDeviceToDevice));
+        capture->count = n;
+    } else {
+        fzb_launch_subset_from_scope(nullptr, (u32)c->dev.n, 0, 0, capture->bitmap, capture->tiles, capture->idx, capture->count_dev, 512, nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+        capture->count = c->dev.n;
+    }
+    capture->known = true;
+    capture->generation = c->generation;
+    return FZB_OK;
+}
+// An empty needle over a candidate set - the picker's empty prompt restricted to a folder: the haystacks of `in`, score 0 or the clamped
+// bias, the hidden ones dropped, ordered as biased_empty_list orders (the reference's rule without a bias: reversed for the *Desc
+// strategies, never sorted).  Host work: one copy of the indices and of the columns the corpus carries.
+int subset_empty_list(const fzb_corpus* c, fzb_subset* in, int sort, size_t limit, std::vector<fzb_match>& recs, uint64_t* out_found) {
+    u64 n = 0;
+    if (int rc = subset_count_host(in, &n)) return rc;
+    std::vector<u32> idx(n);
+    if (n) HIPCHK(hipMemcpy(idx.data(), in->idx, n * 4, hipMemcpyDeviceToHost));
+    std::vector<int16_t> hb;
+    std::vector<uint16_t> ht;
+    const bool biased = fzb_corpus_bias(c) != nullptr, scoped = fzb_corpus_scoped(c);
+    if (biased)
+        if (int rc = fetch_column(fzb_corpus_bias(c), 0, (size_t)c->dev.n, hb)) return rc;
+    if (scoped)
+        if (int rc = fetch_column(c->tags.data, 0, (size_t)c->dev.n, ht)) return rc;
+    recs.clear();
+    recs.reserve(n);
+    for (u64 k = 0; k < n; k++) {
+        const u32 i = idx[k];
+        if (!scoped || scope_visible(ht[i], c->scope_require, c->scope_exclude)) recs.push_back(fzb_match{i, (uint16_t)(biased ? sbias_clamp_add(0, hb[i]) : 0), 0, 0});
+    }
+    if (sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC) std::reverse(recs.begin(), recs.end());
+    if (biased && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC))
+        std::stable_sort(recs.begin(), recs.end(), [](const fzb_match& a, const fzb_match& b) { return a.score > b.score; });
+    if (out_found) *out_found = recs.size();
+    if (recs.size() > limit) recs.resize(limit);
+    return FZB_OK;
+}
+int hand_over_matches(const std::vector<fzb_match>& recs, fzb_match** out, size_t* out_len) {
+    fzb_match* r = (fzb_match*)malloc(std::max<size_t>(recs.size(), 1) * sizeof(fzb_match));
+    if (!r) return fail(FZB_ERR_INVALID, "out of memory");
+    if (!recs.empty()) memcpy(r, recs.data(), recs.size() * sizeof(fzb_match));
+    *out = r;
+    *out_len = recs.size();
+    return FZB_OK;
+}
+// after a host form's wait: the captured count came back in `word`
+void subset_capture_known(fzb_subset* capture, u32 word) {
+    if (!capture) return;
+    capture->count = word;
+    capture->known = true;
+}
+}  // namespace
+extern "C" {
+
+int fzb_corpus_generation(const fzb_corpus* c, uint64_t* out) {
+    if (!c || !out) return fail(FZB_ERR_INVALID, "null argument");
+    *out = c->generation;
+    return FZB_OK;
+}
+
+int fzb_subset_create(const fzb_corpus* c, fzb_subset** out) {
+    if (!c || !out) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!c->own_bytes) return fail(FZB_ERR_INVALID, "fzb_subset_create: the corpus borrows its device memory (fzb_corpus_from_device); a subset needs a corpus made by fzb_corpus_upload");
+    fzb_subset* s = new fzb_subset;
+    s->corpus = c;
+    s->generation = c->generation;
+    int rc = subset_begin(s, "fzb_subset_create");
+    if (!rc) rc = subset_room(s, fzb_corpus_reserved_items(c));
+    if (!rc) {
+        hipError_t e = dev_alloc((void**)&s->count_dev, 16);
+        if (e == hipSuccess) e = hipMemset(s->count_dev, 0, 16);
+        if (e != hipSuccess) rc = fail(FZB_ERR_HIP, std::string("fzb_subset_create: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        fzb_subset_free(s);
+        return rc;
+    }
+    *out = s;
+    return FZB_OK;
+}
+
+void fzb_subset_free(fzb_subset* s) {
+    if (!s) return;
+    if (s->idx) (void)hipFree(s->idx);
+    if (s->bitmap) (void)hipFree(s->bitmap);
+    if (s->tiles) (void)hipFree(s->tiles);
+    if (s->count_dev) (void)hipFree(s->count_dev);
+    delete s;
+}
+
+int fzb_subset_set_indices(fzb_subset* s, const uint32_t* host_indices, size_t n) {
+    if (!s || (n && !host_indices)) return fail(FZB_ERR_INVALID, "null argument");
+    int rc = subset_begin(s, "fzb_subset_set_indices");
+    if (rc) return rc;
+    const fzb_corpus* c = s->corpus;
+    for (size_t k = 0; k < n; k++) {
+        if (host_indices[k] >= c->dev.n)
+            return fail(FZB_ERR_INVALID, "fzb_subset_set_indices: index " + std::to_string(host_indices[k]) + " at position " + std::to_string(k) + " is beyond the corpus' " + std::to_string(c->dev.n) + " haystacks");
+        if (k && host_indices[k] <= host_indices[k - 1])
+            return fail(FZB_ERR_INVALID, "fzb_subset_set_indices: index " + std::to_string(host_indices[k]) + " at position " + std::to_string(k) + " does not ascend (the one before it is " +
+                                             std::to_string(host_indices[k - 1]) + "); the indices must be strictly ascending");
+    }
+    if ((rc = subset_room(s, std::max<size_t>(n, c->dev.n)))) return rc;
+    const u32 n32 = (u32)n;
+    if (n) HIPCHK(hipMemcpy(s->idx, host_indices, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->count_dev, &n32, 4, hipMemcpyHostToDevice));
+    s->count = n;
+    s->known = true;
+    s->generation = c->generation;
+    return FZB_OK;
+}
+
+int fzb_subset_from_scope(fzb_subset* s, const fzb_corpus* c, uint16_t require, uint16_t exclude) {
+    if (!s || !c) return fail(FZB_ERR_INVALID, "null argument");
+    if (s->corpus != c) return fail(FZB_ERR_INVALID, "fzb_subset_from_scope: the subset belongs to another corpus");
+    int rc = subset_begin(s, "fzb_subset_from_scope");
+    if (rc) return rc;
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    if ((rc = subset_room(s, c->dev.n))) return rc;
+    fzb_launch_subset_from_scope(c->tags.data, (u32)c->dev.n, require, exclude, s->bitmap, s->tiles, s->idx, s->count_dev, 512, nullptr);
+    HIPCHK(hipGetLastError());
+    u32 n32 = 0;
+    HIPCHK(hipMemcpy(&n32, s->count_dev, 4, hipMemcpyDeviceToHost));
+    s->count = n32;
+    s->known = true;
+    s->generation = c->generation;
+    return FZB_OK;
+}
+
+int fzb_subset_info(fzb_subset* s, uint64_t out[4]) {
+    if (!s || !out) return fail(FZB_ERR_INVALID, "null argument");
+    out[0] = s->known ? 1 : 0;
+    u64 n = 0;
+    if (int rc = subset_count_host(s, &n)) return rc;
+    out[1] = n;
+    out[2] = s->cap;
+    out[3] = s->generation;
+    return FZB_OK;
+}
+
+int fzb_subset_read(fzb_subset* s, uint32_t* host_out, size_t cap, size_t* out_n) {
+    if (!s || !out_n || (cap && !host_out)) return fail(FZB_ERR_INVALID, "null argument");
+    int rc = subset_begin(s, "fzb_subset_read");
+    if (rc) return rc;
+    u64 n = 0;
+    if ((rc = subset_count_host(s, &n))) return rc;
+    *out_n = (size_t)n;
+    if (n > cap) return fail(FZB_ERR_CAPACITY, "fzb_subset_read: the subset holds " + std::to_string(n) + " indices, the buffer " + std::to_string(cap));
+    if (n) HIPCHK(hipMemcpy(host_out, s->idx, n * 4, hipMemcpyDeviceToHost));
+    return FZB_OK;
+}
+
+int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len) {
+    if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    int rc = subset_check(c, in, capture, "fzb_match_list_subset");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    if (m->empty || n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        if (!in) return fzb_match_list(m, c, out, out_len);
+        std::vector<fzb_match> recs;
+        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, n, recs, nullptr))) return rc;
+        return hand_over_matches(recs, out, out_len);
+    }
+    if ((rc = fzb_ensure_out_staging(m, n))) return rc;
+    SubsetArgs sa{in, capture, capture ? m->count_dev + 6 : nullptr};
+    if ((rc = sorted_range_impl(m, c, 0, n, 0, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr, &sa))) return rc;
+    if ((rc = fetch_records(m->fetch, m->out_dev, m->count_dev, m->out_cap, out, out_len))) return rc;
+    subset_capture_known(capture, m->fetch.count_host[6]);
+    return FZB_OK;
+}
+
+int fzb_match_list_top_subset_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match* dev_out, size_t capacity,
+                                     uint32_t* dev_count, void* stream) {
+    if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top_subset");
+    int rc = subset_check(c, in, capture, "fzb_match_list_top_subset_device");
+    if (rc) return rc;
+    if (c->dev.n == 0 && (rc = subset_capture_trivial(c, in, capture))) return rc;
+    SubsetArgs sa{in, capture, nullptr};
+    return top_device_impl(m, c, limit, dev_out, capacity, dev_count, stream, &sa);
+}
+
+int fzb_match_list_top_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (out_found) *out_found = 0;
+    int rc = subset_check(c, in, capture, "fzb_match_list_top_subset");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    if (m->empty || n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        if (!in) return fzb_match_list_top(m, c, limit, out, out_len, out_found);
+        std::vector<fzb_match> recs;
+        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, limit, recs, out_found))) return rc;
+        return hand_over_matches(recs, out, out_len);
+    }
+    const size_t want = std::min(limit, n);
+    if ((rc = fzb_ensure_out_staging(m, want))) return rc;
+    SubsetArgs sa{in, capture, capture ? m->count_dev + 6 : nullptr};
+    if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr, &sa))) return rc;
+    if ((rc = fzb_fetch_top(m->fetch_top, m->out_dev, m->count_dev, want, nullptr, out, out_len, out_found))) return rc;
+    subset_capture_known(capture, m->fetch_top.count_host[6]);
+    return FZB_OK;
+}
+
+int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
+                                      uint32_t** out_positions, uint64_t* out_found) {
+    if (!m || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    int rc = subset_check(c, in, capture, "fzb_match_list_top_indices_subset");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    if (m->empty || n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        if (!in) return fzb_match_list_top_indices(m, c, limit, out, out_len, out_positions, out_found);
+        std::vector<fzb_match> head;
+        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, limit, head, out_found))) return rc;
+        std::vector<fzb_match_indices> recs(head.size());
+        for (size_t i = 0; i < head.size(); i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};
+        return hand_over_indices(recs.data(), recs.size(), nullptr, 0, out, out_len, out_positions);
+    }
+    const size_t want = std::min(limit, n);
+    const size_t stride = trace_stride(m);
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
+    u32* const words = m->top_idx_words + 4;
+    SubsetArgs sa{in, capture, capture ? m->top_idx_words + 8 : nullptr};
+    if ((rc = top_indices_device_impl(m, c, limit, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense, m->top_dense_words, words, nullptr, &sa))) return rc;
+    u32 captured = 0;
+    rc = fetch_top_indices(words, m->top_packed, m->top_dense, want, want * stride, &m->top_last_records, &m->top_last_positions, "the traced pass disagrees with the top stage", out, out_len,
+                           out_positions, out_found, capture ? &captured : nullptr);
+    if (rc) return rc;
+    subset_capture_known(capture, captured);
+    return FZB_OK;
 }
 
 // The `from_patterns` form, a host composition of the existing pieces: the multi top goes to the host, then the multi matched-indices

@@ -88,6 +88,9 @@ struct fzb_corpus {
     void* stage_stats = nullptr;
     u64 stage_raw_cap = 0, stage_items_cap = 0, stage_tiles_cap = 0;
     int device = -1;         // where an uploaded corpus lives
+    // bumped by every call that changed the LIST (append, truncate, remove, remove_device, replace; not by bias / tags / scope / reserve): a
+    // candidate set (fzb_subset below) records it and is refused once it no longer matches (fzb_corpus_generation)
+    u64 generation = 0;
 };
 // the haystacks a matcher's buffers are sized for: the list's length, or what fzb_corpus_reserve made room for
 inline size_t fzb_corpus_reserved_items(const fzb_corpus* c) { return (size_t)(c->cap_items > c->dev.n ? c->cap_items : c->dev.n); }
@@ -96,6 +99,23 @@ inline const int16_t* fzb_corpus_bias(const fzb_corpus* c) { return c->bias.live
 inline u32 fzb_corpus_bias_hi(const fzb_corpus* c) { return c->bias.live ? c->bias_hi : 0; }
 // an active scope: (0, 0) is no scope, and a corpus without one takes the launches it took before tags existed
 inline bool fzb_corpus_scoped(const fzb_corpus* c) { return c->tags.data && (c->scope_require | c->scope_exclude) != 0; }
+
+// A CANDIDATE SET of one corpus (include/frizbee_hip.h, fzb_subset; host.hip): strictly ascending haystack indices in device memory with
+// their count beside them, the input (`in`) or the captured match set (`capture`) of the *_subset queries.  idx has room for cap indices
+// (created for fzb_corpus_reserved_items, grown geometrically when the list outgrew it); bitmap / tiles = the flag pass of
+// fzb_subset_from_scope, sized with idx.  known: `count` on the host is the device's count (set-up calls and the host forms of the queries
+// leave it known; a _device form's capture does not until fzb_subset_info asks, which synchronises).
+struct fzb_subset {
+    const fzb_corpus* corpus = nullptr;
+    u64 generation = 0;
+    u32* idx = nullptr;
+    size_t cap = 0;
+    u32* count_dev = nullptr;
+    u64* bitmap = nullptr;
+    u32* tiles = nullptr;
+    bool known = true;
+    u64 count = 0;
+};
 
 // A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
 // null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).

@@ -1248,6 +1248,7 @@ int fzb_corpus_append(fzb_corpus* c, const uint8_t* bytes, const uint64_t* end_o
     c->h2d_bytes += raw + (u64)n_new * 8;
     c->dev.n = n_old + n_new;
     c->dev.total_bytes = total;
+    c->generation++;
     c->min_len = std::min(c->min_len, st.min_len);
     c->max_len = std::max(c->max_len, st.max_len);
     c->max_short = std::max(c->max_short, st.max_short);
@@ -1282,6 +1283,7 @@ int fzb_corpus_truncate(fzb_corpus* c, size_t n) {
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, std::string("fzb_corpus_truncate: ") + hipGetErrorString(e));
     c->dev.n = n;
     c->dev.total_bytes = used + 96;
+    c->generation++;
     set_measured(c);
     rc = view_sync(c, n);
     if (!rc) rc = fzb_sig_sync(c, n);
@@ -1800,6 +1802,7 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     c->dev.n = n_new;
     c->dev.total_bytes = total;
     c->h2d_bytes += rq.batch_h2d;
+    c->generation++;
     set_measured(c);
     int rc = view_sync(c, i0);
     if (!rc) rc = fzb_sig_sync(c, i0);

@@ -12,6 +12,7 @@
 #include "compact1.h"
 #include "dfa_lds.h"
 #include "sig_filter.h"
+#include "items_filter.h"
 #include "seg_list.h"
 #include <algorithm>
 #include <cstdlib>
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         u32 tot = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            pb[j] = __ballot((sv[j] & nsig) == nsig);
+            pb[j] = __ballot(sig_passes(sv[j], nsig));
             tot += (u32)__popcll(pb[j]);
         }
         if (tot) {  // wave-uniform
@@ -926,8 +927,179 @@ __global__ __launch_bounds__(256) void k1_items(const u8* __restrict__ bytes, co
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// K1-ITEMS-DFA: the item-list filter for LARGE candidate sets - a narrowing keystroke over a captured match set, a query over the visible
+// haystacks of a sparse scope (fzb_subset): 10^5 .. 10^6 items, where k1_items' one-item-at-a-time chain of dependent round trips (item ->
+// end offset -> vectors, then the bit-vector automaton out of a 256-entry table) is what the kernel waits for.  Fuzzy matching, an ASCII
+// needle, 0 typos only: the automaton is k1_dfa's - `dfa` in LDS at address 0 (dfa_lds.h), same min_len test - and its decisions are k1_dfa's
+// on the same rows, bit for bit.  Outputs are k1_items': one bitmap bit per LIST POSITION and the per-1024 tile counts; k_compact1's item
+// form follows as before.  The per-item decision is items_filter.h's (fuzzed on the host).
+//   SHORT (the list's max_len is known and <= 32): a thread owns positions p * 256 + tid, p = 0..3, of a tile.  Its four items[] loads are
+//     issued first, then the four end offsets (none under a uniform-length promise) and - SIG: a list with letter signatures, an eligible
+//     needle - the four 4-byte signatures, then all (up to) eight 16-byte row loads, all before the first automaton step; rows that fail the
+//     signature or the length test are never requested.  The four chains advance interleaved through dfa_word4, one wait per round.
+//   ragged (max_len unknown or beyond 32): a thread per item, a loop over the row's vectors with the next one requested one ahead.
+// One ballot word per wave, one LDS atomic per wave, one tile-count store per tile.  No ordering between workgroups.
+// ---------------------------------------------------------------------------------------------------
+struct ItemsLdsStep {  // the automaton's step for items_filter.h: the table at LDS address 0, row pitch FZB_DFA_STRIDE
+    __device__ __forceinline__ u32 operator()(u32 st, u32 b) const { return (u32) * (const __attribute__((address_space(3))) u8*)(uintptr_t)(st * FZB_DFA_STRIDE + b); }
+};
+template <typename ET, bool SIG, bool SHORT>
+__global__ __launch_bounds__(256) void k1_items_dfa(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u32* __restrict__ sig, u32 nsig, u64 first,
+                                                    const u32* __restrict__ items, const u32* __restrict__ n_items_ptr, const u8* __restrict__ dfa_g, int rows, u32 min_len,
+                                                    u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts, u32 ulen) {
+    extern __shared__ __attribute__((aligned(16))) u8 dfa[];
+    u32& s_cnt = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows));
+    const int tid = threadIdx.x;
+    dfa_require_lds_base0(dfa);
+    dfa_load_lds(dfa, dfa_g, rows);
+    const u32 count = *n_items_ptr;
+    const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
+    const ItemsLdsStep step;
+    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        u32 cnt = 0;
+        if constexpr (SHORT) {
+            u32 it[4], sg[4], hl[4];
+            u64 hs[4];
+            bool want[4];
+            uint4 v0[4], v1[4];
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const u32 j = tile * FZB_TILE + p * 256 + tid;
+                it[p] = j < count ? items[j] : 0xFFFFFFFFu;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                hs[p] = 0;
+                hl[p] = 0;
+                sg[p] = 0;
+                if (it[p] != 0xFFFFFFFFu) {
+                    haystack_span_u(ends, ulen, first + it[p], hs[p], hl[p]);
+                    if (SIG) sg[p] = sig[first + it[p]];
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                want[p] = it[p] != 0xFFFFFFFFu && items_wants_row(SIG, sg[p], nsig, hl[p], min_len);
+                // (a row that is not wanted is never requested: its chain runs over zeros - so a thread whose rows are all full vectors keeps
+                // the interleaved form - and its outcome is not looked at)
+                v0[p] = make_uint4(0, 0, 0, 0);
+                v1[p] = make_uint4(0, 0, 0, 0);
+                const uint4* vp = (const uint4*)(bytes + hs[p]);
+                if (want[p] && hl[p] > 0) v0[p] = vp[0];
+                if (want[p] && hl[p] > 16) v1[p] = vp[1];
+            }
+            u32 st[4] = {0, 0, 0, 0};
+            if (hl[0] >= 16 && hl[1] >= 16 && hl[2] >= 16 && hl[3] >= 16) {
+                { const u32 w[4] = {v0[0].x, v0[1].x, v0[2].x, v0[3].x}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v0[0].y, v0[1].y, v0[2].y, v0[3].y}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v0[0].z, v0[1].z, v0[2].z, v0[3].z}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v0[0].w, v0[1].w, v0[2].w, v0[3].w}; dfa_word4<true>(st, w, dfa); }
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    const u32 w[4] = {v0[p].x, v0[p].y, v0[p].z, v0[p].w};
+                    st[p] = items_chain_vec(st[p], w, items_vec_bytes(hl[p], 0), step);
+                }
+            }
+            if (hl[0] >= 32 && hl[1] >= 32 && hl[2] >= 32 && hl[3] >= 32) {
+                { const u32 w[4] = {v1[0].x, v1[1].x, v1[2].x, v1[3].x}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v1[0].y, v1[1].y, v1[2].y, v1[3].y}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v1[0].z, v1[1].z, v1[2].z, v1[3].z}; dfa_word4<true>(st, w, dfa); }
+                { const u32 w[4] = {v1[0].w, v1[1].w, v1[2].w, v1[3].w}; dfa_word4<true>(st, w, dfa); }
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    const u32 w[4] = {v1[p].x, v1[p].y, v1[p].z, v1[p].w};
+                    st[p] = items_chain_vec(st[p], w, items_vec_bytes(hl[p], 1), step);
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const u64 b = __ballot(want[p] && st[p] >= acc_lo);
+                if (lane_id() == 0) {
+                    bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
+                    cnt += __popcll(b);
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int p = 0; p < FZB_TILE / 256; p++) {
+                const u32 j = tile * FZB_TILE + p * 256 + tid;
+                bool matched = false;
+                if (j < count) {
+                    const u32 it = items[j];
+                    u64 s;
+                    u32 L;
+                    haystack_span_u(ends, ulen, first + it, s, L);
+                    if (items_wants_row(false, 0u, 0u, L, min_len)) {
+                        const uint4* vp = (const uint4*)(bytes + s);
+                        const u32 nvec = items_vecs(L);
+                        u32 st = 0;
+                        uint4 cur = nvec ? vp[0] : make_uint4(0, 0, 0, 0);
+                        for (u32 v = 0; v < nvec; v++) {
+                            const uint4 nxt = v + 1 < nvec ? vp[v + 1] : make_uint4(0, 0, 0, 0);  // requested ahead of this vector's chain
+                            const u32 nb = items_vec_bytes(L, v);
+                            if (nb == 16) st = dfa_chain16(st, cur, dfa);
+                            else {
+                                const u32 w[4] = {cur.x, cur.y, cur.z, cur.w};
+                                st = items_chain_vec(st, w, nb, step);
+                            }
+                            cur = nxt;
+                        }
+                        matched = st >= acc_lo;
+                    }
+                }
+                const u64 b = __ballot(matched);
+                if (lane_id() == 0) {
+                    bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
+                    cnt += __popcll(b);
+                }
+            }
+        }
+        if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
+        __syncthreads();
+        if (tid == 0) tile_counts[tile] = s_cnt;
+        __syncthreads();
+    }
+}
+
+// Item lists of at least this many items (as far as the host knows: fzb_launch_filter_items' n_hint) take k1_items_dfa where it applies.
+// The crossover is measured (profiles/subset.txt, the narrowed match_list_top_device call with only the filter kernel differing, 10 M x
+// 32-byte list, us, k1_items -> k1_items_dfa): 1 k candidates 44.1 -> 45.8, 10 k 54.6 -> 57.1, 100 k 61.3 -> 59.9, 1 M 84.9 -> 70.4,
+// 5 M 149.8 -> 94.3 with signatures; 100 k 62.0 -> 59.9, 1 M 84.8 -> 80.5, 5 M 150.0 -> 128.4 without: the SHORT form from 100 000 items on.
+// The ragged form LOST at every size on the paths-shaped list (1 k 64.6 -> 76.0, 100 k 96.7 -> 109.2, 1 M 129.0 -> 152.4): it is not
+// selected; only the tests' hook (fzb_debug_set_items_dfa_min) reaches it.
+#define FZB_ITEMS_DFA_MIN_SHORT 100000u
+#define FZB_ITEMS_DFA_MIN_RAGGED 0xFFFFFFFFu
+static u32 g_items_dfa_min_short = FZB_ITEMS_DFA_MIN_SHORT, g_items_dfa_min_ragged = FZB_ITEMS_DFA_MIN_RAGGED;
+extern "C" void fzb_debug_set_items_dfa_min(uint32_t n) {
+    g_items_dfa_min_short = n ? n : FZB_ITEMS_DFA_MIN_SHORT;
+    g_items_dfa_min_ragged = n ? n : FZB_ITEMS_DFA_MIN_RAGGED;
+}
+bool fzb_filter_items_dfa_applies(const CorpusDev& c, int mode, int exact, const u8* dfa, int rows, u64 n_hint) {
+    const bool shortc = c.max_len != 0 && c.max_len <= 32;
+    return mode == 1 && exact && dfa && rows >= 1 && rows <= FZB_MAX_ROWS && !fzb_knobs().no_items_dfa && n_hint != 0 && n_hint >= (u64)(shortc ? g_items_dfa_min_short : g_items_dfa_min_ragged);
+}
+
 void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, const u32* n_items_ptr, const u64* table, int rows, int mode, int need, u32 min_len,
-                             u64* bitmap, u32* tile_counts, int grid, hipStream_t st) {
+                             u64* bitmap, u32* tile_counts, int grid, hipStream_t st, const u8* dfa, int exact, u32 needle_sig, int sig_ok, u64 n_hint) {
+    // dfa / exact / needle_sig / sig_ok / n_hint: a candidate set's item list (host.hip) - fuzzy, ASCII, 0 typos, `dfa` = the subsequence
+    // automaton (rows + 1 states, accept in the last), n_hint = what the host knows of the list's length (0: a few thousand at most)
+    if (fzb_filter_items_dfa_applies(c, mode, exact, dfa, rows, n_hint)) {
+        const size_t lds = (size_t)(rows + 1) * FZB_DFA_STRIDE + 16;  // table + the tile counter
+        const bool shortc = c.max_len != 0 && c.max_len <= 32;
+        const bool use_sig = shortc && fzb_filter_sig_applies(c, mode, needle_sig, sig_ok);
+        const u64 tiles = (n_hint + FZB_TILE - 1) / FZB_TILE;
+        const int g = (int)std::max<u64>(1, std::min<u64>((u64)std::max(1, grid) * 2, tiles));  // (`grid` = 4 workgroups per CU: 8 here, every wave slot, as k1_dfa)
+#define FZB_K1ID(ET, SIG, SHORT) hipLaunchKernelGGL((k1_items_dfa<ET, SIG, SHORT>), dim3(g), dim3(256), lds, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, items, n_items_ptr, dfa, rows, min_len, (u32)rows, bitmap, tile_counts, c.uniform_len)
+        if (c.ends_u64) { if (use_sig) FZB_K1ID(u64, true, true); else if (shortc) FZB_K1ID(u64, false, true); else FZB_K1ID(u64, false, false); }
+        else            { if (use_sig) FZB_K1ID(u32, true, true); else if (shortc) FZB_K1ID(u32, false, true); else FZB_K1ID(u32, false, false); }
+#undef FZB_K1ID
+        return;
+    }
     // MODE 1 with one-hot state needs rows + 1 bits, MODE 2 rows bits
     const bool w64 = (mode == 1) ? rows > 31 : rows > 32;
 #define FZB_K1I(TW, MODE, ET) hipLaunchKernelGGL((k1_items<TW, MODE, ET>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, items, n_items_ptr, table, rows, need, min_len, bitmap, tile_counts)

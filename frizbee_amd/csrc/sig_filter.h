@@ -28,6 +28,8 @@ FZB_SIG_FN uint32_t sig_of_bytes(const uint8_t* p, size_t n) {
     return s;
 }
 FZB_SIG_FN uint32_t needle_sig(const uint8_t* needle, size_t n) { return sig_of_bytes(needle, n); }
+// the test itself: may a haystack with signature `sig` be accepted by the needle with signature `nsig`?  (k1_dfa_sig, k1_items_dfa)
+FZB_SIG_FN bool sig_passes(uint32_t sig, uint32_t nsig) { return (sig & nsig) == nsig; }
 
 // The queries the signature may decide for: fuzzy matching with max_typos = 0 (the stream stage is the ordered-subsequence automaton) of
 // an ASCII needle without a NUL byte.  literal_mode: 0 = fuzzy (fzb_config::matching).

@@ -502,6 +502,64 @@ int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_
  * arrays the reserved form did not - typos after none - regrows the range workspace once: both as for fzb_matcher_reserve.) */
 int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, size_t max_needle_bytes);
 
+/* CANDIDATE SETS: a query over a device-resident SUBSET of the corpus.  Every picker narrows - when the query grows from `dead` to `deadb` only
+ * the haystacks that matched `dead` are looked at again - and restricts ("only this workspace folder").  The reference has no such call: its
+ * `match_list` takes the whole slice, and a caller that narrows builds a new Vec of the survivors on the host.  Here an fzb_subset holds a
+ * strictly ascending array of uint32 haystack indices of ONE corpus in device memory, its count beside it (and on the host when known), and
+ * becomes the item list of the pipeline.  The contract is the scope's sentence, restated for a set:
+ *     A query over subset S returns what the same query returns over a fzb_corpus_upload of the haystacks of S alone, in their order, with
+ *     every `index` mapped back to the full list's.
+ * The map is monotone, so the ordering rule (src/matcher/mod.rs:215-221, src/sort.rs:6-40) and the tie-breaks at a top-`limit` cut carry
+ * over; `found` counts the matches inside S.  The list's terms apply as to any index-ordered records: an active scope drops the hidden
+ * records and a score bias is added, after the scorers.
+ * The handle follows the editing family's rules: only for a corpus the library owns (fzb_corpus_upload; a borrowed one: FZB_ERR_INVALID), the
+ * set-up calls (create, set_indices, from_scope, read; info when the count is not known) wait for the device's outstanding work on entry and
+ * are complete on return, and an error leaves the subset as it was.  A subset created after fzb_corpus_reserve has room for the reserved
+ * items, so its later fills and captures allocate nothing; it grows geometrically when the list outgrew it.
+ * STALENESS: the corpus carries a generation counter (fzb_corpus_generation) that every call which changed the LIST bumps - fzb_corpus_append,
+ * _truncate, _remove, _remove_device, _replace; not _set_bias, _set_tags, _set_scope, _reserve, nor a call that changed nothing.  A subset
+ * records the generation when it is created, filled or captured into; a query handed an input subset of another corpus or of an older
+ * generation is refused with FZB_ERR_INVALID (the message says "subset" and "stale"), nothing launched.
+ * OUT OF SCOPE: the fzb_multi_matcher forms (a negated pattern's match set GROWS as it is typed: the composition needs its own design), the
+ * sharded and RCCL forms, fzb_match_list_indices (its `selection` already is a subset), and a density switch inside the library (streaming
+ * the whole list and intersecting when S covers most of it): the caller decides when a subset pays (frizbee_amd.NarrowingMatcher). */
+typedef struct fzb_subset fzb_subset;
+/* the list's generation: 0 after fzb_corpus_upload, + 1 for every call that changed the list (fzb_corpus_info's array stays 12 long) */
+int fzb_corpus_generation(const fzb_corpus* c, uint64_t* out);
+/* an empty subset of `c` with room for max(length, reserved items) indices */
+int fzb_subset_create(const fzb_corpus* c, fzb_subset** out);
+void fzb_subset_free(fzb_subset* s);
+/* The subset becomes host_indices[0 .. n): checked on the host - strictly ascending and below the corpus length; a violation gives
+ * FZB_ERR_INVALID naming the first offending position, nothing written.  One host-to-device copy; the count is known. */
+int fzb_subset_set_indices(fzb_subset* s, const uint32_t* host_indices, size_t n);
+/* The subset becomes the haystacks visible under (require, exclude) over the corpus' tags - the scope's predicate, whatever scope the corpus
+ * has set -, computed on the device (a flag pass and a stable compaction of the indices); only the count crosses the link.  A corpus without
+ * tags: every haystack for (0, 0), none when require != 0.  `c` must be the subset's corpus. */
+int fzb_subset_from_scope(fzb_subset* s, const fzb_corpus* c, uint16_t require, uint16_t exclude);
+/* out[0] = the count was known on the host when the call was made (0/1; 0 after a _device form captured into the subset: the call then
+ * synchronises the device and reads it), [1] = count, [2] = capacity in indices, [3] = the corpus generation the subset belongs to */
+int fzb_subset_info(fzb_subset* s, uint64_t out[4]);
+/* a synchronous copy of the indices: *out_n = count; more than `cap`: FZB_ERR_CAPACITY (and the count) */
+int fzb_subset_read(fzb_subset* s, uint32_t* host_out, size_t cap, size_t* out_n);
+/* The queries.  `in` == NULL: the whole corpus - exactly the launches of the call without _subset (how narrowing starts).  `capture` (may be
+ * NULL): afterwards it holds the indices of EVERY haystack of `in` the matcher accepted, ascending - the index-ordered records the scorers
+ * wrote, taken BEFORE the list's terms, the selection and the ordering, so the captured set does not depend on `limit`, the sort strategy,
+ * the bias or the scope (the user may toggle "hide ignored" between two keystrokes; the next query applies the scope again anyway).  One
+ * more launch; the count is written on the device.  The host forms bring it back in the wait they make anyway (the capture's count is then
+ * known); after the _device form it is unknown until fzb_subset_info is asked.  capture == in: FZB_ERR_INVALID (alternate two subsets); a
+ * capture of another corpus is refused; a capture takes the corpus' current generation.  After fzb_matcher_reserve(m, c) (and
+ * fzb_matcher_reserve_top_indices for the form with positions) no subset query allocates device memory.
+ * An EMPTY NEEDLE: the host forms list the haystacks of `in` - score 0, or the clamped bias, hidden ones dropped, ordered as the empty
+ * prompt of the calls without _subset - and the capture, if any, becomes `in` itself; the _device form refuses, as its siblings do.
+ * fzb_match_list_subset: fzb_match_list's order.  _top_subset / _top_subset_device: fzb_match_list_top / _top_device (dev_count: records
+ * written, found).  _top_indices_subset: fzb_match_list_top_indices; its traced pass runs over the head's item list as before. */
+int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len);
+int fzb_match_list_top_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found);
+int fzb_match_list_top_subset_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match* dev_out, size_t capacity,
+                                     uint32_t* dev_count, void* stream);
+int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
+                                      uint32_t** out_positions, uint64_t* out_found);
+
 /* `radix_sort_matches(&mut [Match])` (src/sort.rs:6-40): stable, descending score, host side */
 void fzb_radix_sort_matches(fzb_match* matches, size_t n);
 /* `k_merge_matches_by_*` (src/k_merge.rs:56-132): merges per-shard runs (each sorted per `sort`) - the
@@ -657,6 +715,10 @@ uint32_t fzb_debug_signature_threshold(void);
 /* test hook: caps the grid of the signature filter where it lists its own survivors (0 = default), so that small lists exercise runs of
  * several tiles per workgroup */
 void fzb_debug_set_filter_grid(int grid);
+
+/* test hook: item lists of a candidate set (fzb_subset) that hold at least n items - as far as the host knows - take the filter kernel for large
+ * candidate sets where it applies (fuzzy, ASCII, 0 typos), so that small lists exercise it; 0 = the measured default */
+void fzb_debug_set_items_dfa_min(uint32_t n);
 
 /* test hook: the library's environment switches (frizbee_amd/csrc/knobs.h - comparison and debugging only, parsed once on first use) are
  * read again.  Matchers created before the call keep what was decided when they were created. */

@@ -259,9 +259,53 @@ class Corpus {
         return ScopeInfo{o[0], o[1], o[2], o[3]};
     }
 
+    // the list's generation: + 1 for every append / truncate / remove / replace that changed it (what a Subset is checked against)
+    uint64_t generation() const {
+        uint64_t g = 0;
+        check(fzb_corpus_generation(h_.get(), &g));
+        return g;
+    }
+
   private:
     struct Del { void operator()(fzb_corpus* c) const { fzb_corpus_free(c); } };
     std::unique_ptr<fzb_corpus, Del> h_;
+};
+
+// A candidate set of one resident Corpus (fzb_subset): strictly ascending haystack indices in HBM - the input or the captured match set of
+// Matcher::match_list / match_list_top / match_list_top_device / match_list_top_indices with a Subset.  A query over a subset returns what it
+// returns over an upload of those haystacks alone, every index that of the full list.  The reference has no counterpart.  The corpus must
+// outlive the subset; single-pattern matchers only.
+class Subset {
+  public:
+    explicit Subset(const Corpus& corpus) : corpus_(corpus.raw()) {
+        fzb_subset* s = nullptr;
+        check(fzb_subset_create(corpus_, &s));
+        h_.reset(s);
+    }
+    void set_indices(const std::vector<uint32_t>& ascending) { check(fzb_subset_set_indices(h_.get(), ascending.data(), ascending.size())); }
+    void from_scope(uint16_t require = 0, uint16_t exclude = 0) { check(fzb_subset_from_scope(h_.get(), corpus_, require, exclude)); }
+    struct Info {
+        uint64_t known, count, capacity, generation;
+    };
+    Info info() const {
+        uint64_t o[4] = {};
+        check(fzb_subset_info(h_.get(), o));
+        return Info{o[0], o[1], o[2], o[3]};
+    }
+    size_t len() const { return (size_t)info().count; }  // (synchronises when the last capture left the count on the device only)
+    std::vector<uint32_t> read() const {
+        std::vector<uint32_t> v(len());
+        size_t n = 0;
+        check(fzb_subset_read(h_.get(), v.data(), v.size(), &n));
+        v.resize(n);
+        return v;
+    }
+    fzb_subset* raw() const { return h_.get(); }
+
+  private:
+    struct Del { void operator()(fzb_subset* s) const { fzb_subset_free(s); } };
+    const fzb_corpus* corpus_;
+    std::unique_ptr<fzb_subset, Del> h_;
 };
 
 // The list cut into one contiguous shard per GPU (fzb_corpus_upload_sharded): the devices of a node in the role of
@@ -425,6 +469,40 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_match_list_top_indices_device(single_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
         else check(fzb_multi_match_list_top_indices_device(multi_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
     }
+    // The same four calls over a candidate set (fzb_match_list_subset and friends; a single plain pattern only): `in` = the haystacks looked
+    // at (nullptr: the whole corpus), `capture` (nullptr: none) receives the indices of every haystack the matcher accepted - before bias,
+    // scope, limit and ordering.  in == capture is refused: alternate two subsets.
+    std::vector<Match> match_list(const Corpus& corpus, const Subset* in, Subset* capture) {
+        fzb_match* out = nullptr;
+        size_t n = 0;
+        check(fzb_match_list_subset(single_only("match_list"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, &out, &n));
+        return take(out, n);
+    }
+    std::vector<Match> match_list_top(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, size_t* found = nullptr) {
+        fzb_match* out = nullptr;
+        size_t n = 0;
+        uint64_t f = 0;
+        check(fzb_match_list_top_subset(single_only("match_list_top"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &f));
+        if (found) *found = (size_t)f;
+        return take(out, n);
+    }
+    void match_list_top_device(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream = nullptr) {
+        check(fzb_match_list_top_subset_device(single_only("match_list_top_device"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, dev_out, capacity,
+                                               dev_count, stream));
+    }
+    std::vector<MatchIndices> match_list_top_indices(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, size_t* found = nullptr) {
+        fzb_match_indices* out = nullptr;
+        uint32_t* pos = nullptr;
+        size_t n = 0;
+        uint64_t f = 0;
+        check(fzb_match_list_top_indices_subset(single_only("match_list_top_indices"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &pos, &f));
+        if (found) *found = (size_t)f;
+        std::vector<MatchIndices> v(n);
+        for (size_t i = 0; i < n; i++)
+            v[i] = MatchIndices{out[i].score, out[i].index, out[i].exact != 0, std::vector<uint32_t>(pos + out[i].positions_begin, pos + out[i].positions_begin + out[i].positions_len)};
+        fzb_match_indices_free(out, pos);
+        return v;
+    }
     // after reserve-ing the matcher for the corpus: no match_list_top_indices call with this limit or a smaller one, on a needle of up to
     // max_needle_bytes bytes, allocates device memory (`from_patterns`: while set_patterns / set_config add no pattern slot)
     void reserve_top_indices(const Corpus& corpus, size_t limit, size_t max_needle_bytes) {
@@ -587,6 +665,10 @@ class Matcher {  // src/matcher/mod.rs:77-222
         for (size_t i = 0; i < n; i++) r[i] = Match{out[i].index, out[i].score, out[i].exact != 0};
         fzb_matches_free(out);
         return r;
+    }
+    fzb_matcher* single_only(const char* call) const {  // the candidate-set forms: out of scope for `from_patterns` matchers
+        if (!single_) throw Error(FZB_ERR_INVALID, std::string(call) + " over a Subset: single-pattern matchers only");
+        return single_.get();
     }
     struct DelS { void operator()(fzb_matcher* m) const { fzb_matcher_free(m); } };
     struct DelM { void operator()(fzb_multi_matcher* m) const { fzb_multi_matcher_free(m); } };

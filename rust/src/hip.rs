@@ -124,6 +124,21 @@ extern "C" {
     fn fzb_match_list_top_indices_device(m: *mut c_void, c: *const c_void, limit: usize, dev_out: *mut FzbMatchIndices, capacity: usize, dev_positions: *mut u32,
                                          positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
     fn fzb_matcher_reserve_top_indices(m: *mut c_void, c: *const c_void, limit: usize, max_needle_bytes: usize) -> c_int;
+    // candidate sets (fzb_subset): a query over a device-resident subset of the corpus, and the capture of a query's match set
+    fn fzb_corpus_generation(c: *const c_void, out: *mut u64) -> c_int;
+    fn fzb_subset_create(c: *const c_void, out: *mut *mut c_void) -> c_int;
+    fn fzb_subset_free(s: *mut c_void);
+    fn fzb_subset_set_indices(s: *mut c_void, host_indices: *const u32, n: usize) -> c_int;
+    fn fzb_subset_from_scope(s: *mut c_void, c: *const c_void, require: u16, exclude: u16) -> c_int;
+    fn fzb_subset_info(s: *mut c_void, out: *mut u64) -> c_int;
+    fn fzb_subset_read(s: *mut c_void, host_out: *mut u32, cap: usize, out_n: *mut usize) -> c_int;
+    fn fzb_match_list_subset(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    fn fzb_match_list_top_subset(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize,
+                                 out_found: *mut u64) -> c_int;
+    fn fzb_match_list_top_subset_device(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize,
+                                        dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_match_list_top_indices_subset(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
+                                         out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
     fn fzb_match_list_top_sharded(m: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_match_list_indices(m: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
                               out_positions: *mut *mut u32) -> c_int;
@@ -293,6 +308,12 @@ impl HipCorpus {
     /// visible haystacks alone, every index that of the full list.  Host only: the "toggle ignored files" keystroke.  `(0, 0)` is no scope.
     pub fn set_scope(&mut self, require: u16, exclude: u16) {
         check(unsafe { fzb_corpus_set_scope(self.handle, require, exclude) });
+    }
+    /// The list's generation: + 1 for every append / truncate / remove / replace that changed it (what a candidate set is checked against).
+    pub fn generation(&self) -> u64 {
+        let mut g = 0u64;
+        check(unsafe { fzb_corpus_generation(self.handle, &mut g) });
+        g
     }
     /// [scope active (0/1), entries the tags array has room for, require | exclude << 16, device bytes].
     pub fn scope_info(&self) -> [u64; 4] {
