@@ -130,7 +130,7 @@ SYMBOLS = [
     "fzb_corpus_set_tags", "fzb_corpus_update_tags", "fzb_corpus_clear_tags", "fzb_corpus_set_scope", "fzb_corpus_scope_info",
     "fzb_corpus_generation", "fzb_subset_create", "fzb_subset_free", "fzb_subset_set_indices", "fzb_subset_from_scope", "fzb_subset_info", "fzb_subset_read",
     "fzb_match_list_subset", "fzb_match_list_top_subset", "fzb_match_list_top_subset_device", "fzb_match_list_top_indices_subset",
-    "fzb_debug_set_items_dfa_min",
+    "fzb_debug_set_items_dfa_min", "fzb_debug_launch_grids",
 ]
 
 
@@ -254,6 +254,7 @@ def lib():
         l.fzb_corpus_scope_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_debug_set_items_dfa_min.argtypes = [C.c_uint32]
         l.fzb_debug_set_items_dfa_min.restype = None
+        l.fzb_debug_launch_grids.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
         l.fzb_corpus_generation.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_subset_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         l.fzb_subset_free.argtypes = [C.c_void_p]
@@ -643,6 +644,16 @@ class Pattern:
     unicode: "UnicodeMatching | None" = None
     scoring: "Scoring | None" = None
     matching: "Matching | None" = None
+
+
+def launch_grids(clear=True):
+    """fzb_debug_launch_grids: {kernel: (min_grid, max_grid, launches)} of the launches recorded since the record was last cleared (test hook:
+    nothing is recorded unless FZB_DEBUG_CUS is set)"""
+    n = C.c_size_t()
+    _check(lib().fzb_debug_launch_grids(None, 0, C.byref(n), 0))
+    buf = C.create_string_buffer(n.value + 1)
+    _check(lib().fzb_debug_launch_grids(buf, n.value + 1, C.byref(n), 1 if clear else 0))
+    return {f[0]: (int(f[1]), int(f[2]), int(f[3])) for f in (line.split() for line in buf.value.decode().splitlines())}
 
 
 def device_allocs():

@@ -180,6 +180,7 @@ FzbKnobs parse_knobs() {
     k.no_filter_view = getenv("FZB_FILTER_VIEW") != nullptr && atoi(getenv("FZB_FILTER_VIEW")) == 0;
     k.no_signature = on("FZB_NO_SIGNATURE");
     k.verify_promises = num("FZB_VERIFY_PROMISES", 1) != 0;
+    k.debug_cus = std::max(0, num("FZB_DEBUG_CUS", 0));
     k.no_lcs_dfa = set("FZB_NO_LCS_DFA");
     k.no_cdfa = set("FZB_NO_CDFA");
     k.no_dp_classes = set("FZB_NO_DP_CLASSES");
@@ -203,10 +204,86 @@ FzbKnobs& knobs_storage() {
 }
 }  // namespace
 const FzbKnobs& fzb_knobs() { return knobs_storage(); }
+
+// ---- the compute-unit count every grid derives from, and the record of the grids launched under an override (knobs.h) -----------------
+namespace {
+struct GridRecord {
+    unsigned min_grid, max_grid, launches;
+};
+std::mutex g_grid_mu;
+std::map<std::string, GridRecord> g_grid_log;
+}  // namespace
+bool g_fzb_record_grids = fzb_knobs().debug_cus > 0;
+
+int fzb_effective_cus(int* out) {
+    const int forced = fzb_knobs().debug_cus;
+    if (forced > 0) {
+        *out = forced;
+        return 0;
+    }
+    static std::atomic<int> cached[64];  // per device ordinal; 0 = not asked yet
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    const bool slot = dev >= 0 && dev < 64;
+    if (slot && cached[dev].load(std::memory_order_relaxed) > 0) {
+        *out = cached[dev].load(std::memory_order_relaxed);
+        return 0;
+    }
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return (int)e;
+    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (slot) cached[dev].store(cus, std::memory_order_relaxed);
+    *out = cus;
+    return 0;
+}
+// for the launches that have nowhere to report to (a launch on a device that cannot be asked fails by itself): 256 then
+static int cus_or_default() {
+    int cus = 256;
+    if (fzb_effective_cus(&cus) != 0) {
+        (void)hipGetLastError();
+        cus = 256;
+    }
+    return cus;
+}
+unsigned fzb_grid_cap(uint64_t want, unsigned per_cu) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus_or_default() * per_cu)); }
+
+// `kernel` is FZB_LAUNCH's first argument as written: "(k2b_dp<SWL, B, U>)" is recorded as k2b_dp
+void fzb_record_grid(const char* kernel, unsigned grid) {
+    std::string name(kernel);
+    name.erase(0, name.find_first_not_of("( "));
+    name.erase(std::min(name.size(), name.find_first_of("<) ")));
+    std::lock_guard<std::mutex> lk(g_grid_mu);
+    auto it = g_grid_log.find(name);
+    if (it == g_grid_log.end()) g_grid_log[name] = GridRecord{grid, grid, 1};
+    else {
+        it->second.min_grid = std::min(it->second.min_grid, grid);
+        it->second.max_grid = std::max(it->second.max_grid, grid);
+        it->second.launches++;
+    }
+}
 extern "C" {
 // test hook: re-read the environment (tests/test_gpu_knobs.py switches paths inside one process; matchers created BEFORE the call keep
 // what was decided at their creation - the LCS automaton, the unicode scorer's form)
-void fzb_debug_reload_knobs(void) { knobs_storage() = parse_knobs(); }
+void fzb_debug_reload_knobs(void) {
+    knobs_storage() = parse_knobs();
+    g_fzb_record_grids = knobs_storage().debug_cus > 0;
+    std::lock_guard<std::mutex> lk(g_grid_mu);
+    g_grid_log.clear();
+}
+
+// test hook: the launches recorded since the record was last cleared, one line "kernel min_grid max_grid launches" each (see frizbee_hip.h)
+int fzb_debug_launch_grids(char* out, size_t cap, size_t* out_len, int clear) {
+    if (!out_len || (!out && cap)) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(g_grid_mu);
+    std::string text;
+    for (const auto& kv : g_grid_log) text += kv.first + " " + std::to_string(kv.second.min_grid) + " " + std::to_string(kv.second.max_grid) + " " + std::to_string(kv.second.launches) + "\n";
+    *out_len = text.size();
+    if (cap < text.size() + 1) return cap ? fzb_fail(FZB_ERR_CAPACITY, "fzb_debug_launch_grids: the record has " + std::to_string(text.size() + 1) + " bytes") : FZB_OK;
+    memcpy(out, text.c_str(), text.size() + 1);
+    if (clear) g_grid_log.clear();
+    return FZB_OK;
+}
 
 void fzb_config_default(fzb_config* out) {
     if (!out) return;
@@ -964,9 +1041,9 @@ static int verify_promise(const fzb_corpus* c, u32 uniform_len, u32 max_len, con
     const unsigned long long init[2] = {0ull, ~0ull};
     hipError_t e = hipMemcpy(d, init, 16, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        const int grid = (int)std::min<u64>((c->dev.n + 255) / 256, 4096);
-        if (c->dev.ends_u64) hipLaunchKernelGGL((k_verify_promise<u64>), dim3(grid), dim3(256), 0, 0, (const u64*)c->dev.ends, c->dev.n, c->dev.total_bytes, uniform_len, max_len, d);
-        else hipLaunchKernelGGL((k_verify_promise<u32>), dim3(grid), dim3(256), 0, 0, (const u32*)c->dev.ends, c->dev.n, c->dev.total_bytes, uniform_len, max_len, d);
+        const int grid = (int)fzb_grid_cap((c->dev.n + 255) / 256, 16);  // (4096 on 256 CUs)
+        if (c->dev.ends_u64) FZB_LAUNCH((k_verify_promise<u64>), dim3(grid), dim3(256), 0, 0, (const u64*)c->dev.ends, c->dev.n, c->dev.total_bytes, uniform_len, max_len, d);
+        else FZB_LAUNCH((k_verify_promise<u32>), dim3(grid), dim3(256), 0, 0, (const u32*)c->dev.ends, c->dev.n, c->dev.total_bytes, uniform_len, max_len, d);
         e = hipGetLastError();
     }
     unsigned long long got[2] = {0, 0};
@@ -1060,10 +1137,10 @@ int fzb_bind_device(fzb_matcher* m) {
             return fail(FZB_ERR_INVALID, "matcher is bound to device " + std::to_string(m->device) + " (its workspace lives there) but device " + std::to_string(dev) + " is current");
         return FZB_OK;
     }
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
+    int cus = 0;
+    HIPCHK((hipError_t)fzb_effective_cus(&cus));  // (a device that cannot be asked is reported here, at bind time, and leaves the matcher unbound)
     m->device = dev;
-    m->lc.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    m->lc.num_cus = cus;
     return FZB_OK;
 }
 extern "C" {
@@ -2734,13 +2811,7 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
         return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
     hipStream_t st = (hipStream_t)stream;
-    if (!mm->num_cus) {
-        int dev = 0;
-        HIPCHK(hipGetDevice(&dev));
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, dev));
-        mm->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mm->num_cus) HIPCHK((hipError_t)fzb_effective_cus(&mm->num_cus));
     const int cus = mm->num_cus;
     const u32 cap32 = (u32)std::min<size_t>(capacity, 0xFFFFFFFFu);
     auto& ps = mm->patterns;
@@ -3346,7 +3417,7 @@ int subset_capture_trivial(const fzb_corpus* c, const fzb_subset* in, fzb_subset
         HIPCHK(hipMemcpy(capture->count_dev, in->count_dev, 4, hipMemcpyDeviceToDevice));
         capture->count = n;
     } else {
-        fzb_launch_subset_from_scope(nullptr, (u32)c->dev.n, 0, 0, capture->bitmap, capture->tiles, capture->idx, capture->count_dev, 512, nullptr);
+        fzb_launch_subset_from_scope(nullptr, (u32)c->dev.n, 0, 0, capture->bitmap, capture->tiles, capture->idx, capture->count_dev, (int)fzb_grid_cap(~0ull, 2), nullptr);  // (512 on 256 CUs)
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());
         capture->count = c->dev.n;
@@ -3466,7 +3537,7 @@ int fzb_subset_from_scope(fzb_subset* s, const fzb_corpus* c, uint16_t require, 
     if (rc) return rc;
     if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
     if ((rc = subset_room(s, c->dev.n))) return rc;
-    fzb_launch_subset_from_scope(c->tags.data, (u32)c->dev.n, require, exclude, s->bitmap, s->tiles, s->idx, s->count_dev, 512, nullptr);
+    fzb_launch_subset_from_scope(c->tags.data, (u32)c->dev.n, require, exclude, s->bitmap, s->tiles, s->idx, s->count_dev, (int)fzb_grid_cap(~0ull, 2), nullptr);  // (512 on 256 CUs)
     HIPCHK(hipGetLastError());
     u32 n32 = 0;
     HIPCHK(hipMemcpy(&n32, s->count_dev, 4, hipMemcpyDeviceToHost));

@@ -420,8 +420,8 @@ inline u64 long_cap_of(u64 n) { return std::min<u64>(n / 256 + 64, 0x7FFFFFFFu);
 hipError_t batch_measure(const u64* d_ends64, u64 n, u64 ends_base, u64* d_tiles, UpStats* d_stats, UpStats* st) {
     hipError_t e = hipMemcpy(d_stats, &UP_STATS_INIT, sizeof(UpStats), hipMemcpyHostToDevice);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_up_tiles, dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_ends64, n, ends_base, d_tiles, d_stats);
-    hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_tiles, up_tiles(n), d_stats);
+    FZB_LAUNCH(k_up_tiles, dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_ends64, n, ends_base, d_tiles, d_stats);
+    FZB_LAUNCH(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_tiles, up_tiles(n), d_stats);
     return hipMemcpy(st, d_stats, sizeof(UpStats), hipMemcpyDeviceToHost);
 }
 // Second half: the batch's bytes from byte `out_base` of `out_bytes` on (copy = false: they are there already, `raw` is the padded layout)
@@ -429,7 +429,7 @@ hipError_t batch_measure(const u64* d_ends64, u64 n, u64 ends_base, u64* d_tiles
 void batch_lay_out(const u8* d_raw, const u64* d_ends64, u64 n, u64 ends_base, const u64* d_tiles, u8* out_bytes, u64 out_base, void* out_ends, u64 index_base, bool ends_u64,
                    bool copy) {
 #define FZB_UP_BUILD(ET, COPY) \
-    hipLaunchKernelGGL((k_up_build<ET, COPY>), dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_raw, d_ends64, n, ends_base, d_tiles, out_bytes, (ET*)out_ends, out_base, index_base)
+    FZB_LAUNCH((k_up_build<ET, COPY>), dim3((unsigned)up_tiles(n)), dim3(UP_THREADS), 0, nullptr, d_raw, d_ends64, n, ends_base, d_tiles, out_bytes, (ET*)out_ends, out_base, index_base)
     if (ends_u64) { if (copy) FZB_UP_BUILD(u64, true); else FZB_UP_BUILD(u64, false); }
     else { if (copy) FZB_UP_BUILD(u32, true); else FZB_UP_BUILD(u32, false); }
 #undef FZB_UP_BUILD
@@ -576,14 +576,14 @@ int view_sync(fzb_corpus* c, u64 n_valid) {
     e = hipMemcpy(d_stats, &init, sizeof(init), hipMemcpyHostToDevice);
     if (e != hipSuccess) return bail(e);
     if (live && c->dev.n_long && c->view_items > t0 * UP_TILE)
-        hipLaunchKernelGGL(k_up_vlong_prune, dim3(1), dim3(1024), 0, nullptr, (u32*)c->own_view[5], c->dev.n_long, (u32)(t0 * UP_TILE), d_stats);
+        FZB_LAUNCH(k_up_vlong_prune, dim3(1), dim3(1024), 0, nullptr, (u32*)c->own_view[5], c->dev.n_long, (u32)(t0 * UP_TILE), d_stats);
     const u32 long_room = (u32)long_cap_of(c->view_cap_items);
     if (tiles_r) {
         if (c->dev.ends_u64)
-            hipLaunchKernelGGL((k_up_view_sort<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
+            FZB_LAUNCH((k_up_view_sort<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
         else
-            hipLaunchKernelGGL((k_up_view_sort<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
-        hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_vt, tiles_r, d_stats);  // total_padded = the rebuilt tiles' size in 16-byte units
+            FZB_LAUNCH((k_up_view_sort<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (u16*)c->own_view[4], (u16*)c->own_view[3], (u8*)c->own_view[2], d_vt, d_stats, (u32*)c->own_view[5], long_room, (u32)t0);
+        FZB_LAUNCH(k_up_scan, dim3(1), dim3(1024), 0, nullptr, d_vt, tiles_r, d_stats);  // total_padded = the rebuilt tiles' size in 16-byte units
     }
     UpStats vst = UP_STATS_INIT;
     e = hipMemcpy(&vst, d_stats, sizeof(vst), hipMemcpyDeviceToHost);
@@ -608,9 +608,9 @@ int view_sync(fzb_corpus* c, u64 n_valid) {
     }
     if (tiles_r) {
         if (c->dev.ends_u64)
-            hipLaunchKernelGGL((k_up_view_fill<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
+            FZB_LAUNCH((k_up_view_fill<u64>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
         else
-            hipLaunchKernelGGL((k_up_view_fill<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
+            FZB_LAUNCH((k_up_view_fill<u32>), dim3((unsigned)tiles_r), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, n, (const u16*)c->own_view[4], (const u8*)c->own_view[2], (const u64*)d_vt, (u8*)c->own_view[0], (u32*)c->own_view[1], (u32)t0, base_units);
     }
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
@@ -636,9 +636,9 @@ hipError_t measure_resident(fzb_corpus* c, u64 n) {
     if (n) {
         e = hipMemcpy(c->stage_stats, &UP_STATS_INIT, sizeof(UpStats), hipMemcpyHostToDevice);
         if (e != hipSuccess) return e;
-        const unsigned grid = (unsigned)std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 2048);
-        if (c->dev.ends_u64) hipLaunchKernelGGL((k_up_measure<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (UpStats*)c->stage_stats);
-        else hipLaunchKernelGGL((k_up_measure<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (UpStats*)c->stage_stats);
+        const unsigned grid = fzb_grid_cap((n + UP_THREADS - 1) / UP_THREADS, 8);  // (2048 on 256 CUs)
+        if (c->dev.ends_u64) FZB_LAUNCH((k_up_measure<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, (UpStats*)c->stage_stats);
+        else FZB_LAUNCH((k_up_measure<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, (UpStats*)c->stage_stats);
         e = hipMemcpy(&st, c->stage_stats, sizeof(st), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return e;
     }
@@ -701,9 +701,9 @@ int fzb_sig_sync(fzb_corpus* c, u64 n_valid) {
     }
     if (n > n_valid) {
         const u64 cnt = n - n_valid;
-        const unsigned grid = (unsigned)std::min<u64>((cnt + UP_THREADS - 1) / UP_THREADS, 8192);
-        if (c->dev.ends_u64) hipLaunchKernelGGL((k_sig_build<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
-        else hipLaunchKernelGGL((k_sig_build<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
+        const unsigned grid = fzb_grid_cap((cnt + UP_THREADS - 1) / UP_THREADS, 32);  // (8192 on 256 CUs)
+        if (c->dev.ends_u64) FZB_LAUNCH((k_sig_build<u64>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u64*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
+        else FZB_LAUNCH((k_sig_build<u32>), dim3(grid), dim3(UP_THREADS), 0, nullptr, c->dev.bytes, (const u32*)c->dev.ends, c->dev.uniform_len, n_valid, cnt, (u32*)c->own_sig);
     }
     c->dev.sig = (const u32*)c->own_sig;
     return FZB_OK;
@@ -1058,8 +1058,8 @@ int col_update(fzb_corpus* c, ItemColumn<V>& col, const std::string& what, const
     hipError_t e = col_create(c, col, n);
     if (e == hipSuccess) e = hipMemcpy(c->pair_stage, pairs.data(), pairs.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, what + ": " + hipGetErrorString(e));
-    const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>((n + UP_THREADS - 1) / UP_THREADS, 1024));
-    hipLaunchKernelGGL(k_col_scatter<V>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->pair_stage, (const V*)((const u8*)c->pair_stage + n * 4), (u64)n, col.data, c->dev.n);
+    const unsigned grid = fzb_grid_cap((n + UP_THREADS - 1) / UP_THREADS, 4);  // (1024 on 256 CUs)
+    FZB_LAUNCH(k_col_scatter<V>, dim3(grid), dim3(UP_THREADS), 0, nullptr, (const u32*)c->pair_stage, (const V*)((const u8*)c->pair_stage + n * 4), (u64)n, col.data, c->dev.n);
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return fzb_fail(FZB_ERR_HIP, what + " (scatter): " + hipGetErrorString(e));
@@ -1704,7 +1704,7 @@ hipError_t col_scratch_alloc(ColScratch<V>& s, u64 bytes) {
 template <typename V>
 hipError_t col_compact(ItemColumn<V>& col, const ColScratch<V>& s, const u32* bitmap, const u64* tile_cnt, u64 tiles, u64 n, u64 i0, u64 n_new) {
     if (!s.work) return hipSuccess;
-    hipLaunchKernelGGL(k_col_compact<V>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const V*)col.data, bitmap, tile_cnt, n, i0, s.work, n - i0);
+    FZB_LAUNCH(k_col_compact<V>, dim3((unsigned)tiles), dim3(SBIAS_TILE), 0, nullptr, (const V*)col.data, bitmap, tile_cnt, n, i0, s.work, n - i0);
     hipError_t e = hipSuccess;
     if (n_new > i0) e = hipMemcpyAsync(col.data + i0, s.work, (n_new - i0) * sizeof(V), hipMemcpyDeviceToDevice, nullptr);
     if (e == hipSuccess && n > n_new) e = hipMemsetAsync(col.data + n_new, 0, (n - n_new) * sizeof(V), nullptr);
@@ -1743,8 +1743,8 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     if (e == hipSuccess && replace) e = hipMemcpy(aux + off_rk, rq.host_rk, rq.max_count * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "scratch");
     const u32* d_idx = rq.host_idx ? (const u32*)(aux + off_idx) : (const u32*)rq.dev_idx;
-    const unsigned mark_grid = (unsigned)std::max<u64>(1, std::min<u64>((rq.max_count + UP_THREADS - 1) / UP_THREADS, 2048));
-    hipLaunchKernelGGL(k_ed_mark, dim3(mark_grid), dim3(UP_THREADS), 0, nullptr, d_idx, rq.stride_words, rq.dev_count, rq.max_count, n, d_bitmap, d_st);
+    const unsigned mark_grid = fzb_grid_cap((rq.max_count + UP_THREADS - 1) / UP_THREADS, 8);  // (2048 on 256 CUs)
+    FZB_LAUNCH(k_ed_mark, dim3(mark_grid), dim3(UP_THREADS), 0, nullptr, d_idx, rq.stride_words, rq.dev_count, rq.max_count, n, d_bitmap, d_st);
     EdStats st = ED_STATS_INIT;
     e = hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost);  // first readback: is the list valid, and where does the edit begin
     if (e != hipSuccess) return hip_fail(e, "index list");
@@ -1753,10 +1753,10 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     if (!st.count) return done(FZB_OK);
     const u64 i0 = st.first, tiles = up_tiles(n - i0);
     EdSrc src{d_bitmap, replace ? d_idx : nullptr, replace ? (const u32*)(aux + off_rk) : nullptr, (const u64*)c->stage_ends, (u32)(replace ? rq.max_count : 0), replace ? 1u : 0u};
-    if (c->dev.ends_u64) hipLaunchKernelGGL((k_ed_tiles<u64>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
-    else hipLaunchKernelGGL((k_ed_tiles<u32>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
+    if (c->dev.ends_u64) FZB_LAUNCH((k_ed_tiles<u64>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u64*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
+    else FZB_LAUNCH((k_ed_tiles<u32>), dim3((unsigned)tiles), dim3(UP_THREADS), 0, nullptr, (const u32*)c->dev.ends, n, i0, src, d_tb, d_tc, d_ts, d_st);
     const u64 chunk_knob = (u64)fzb_knobs().edit_chunk_items / UP_TILE;
-    hipLaunchKernelGGL(k_ed_scan, dim3(1), dim3(1024), 0, nullptr, d_tb, d_tc, (const u64*)d_ts, tiles, d_st, chunk_knob);
+    FZB_LAUNCH(k_ed_scan, dim3(1), dim3(1024), 0, nullptr, d_tb, d_tc, (const u64*)d_ts, tiles, d_st, chunk_knob);
     e = hipMemcpy(&st, d_st, sizeof(st), hipMemcpyDeviceToHost);  // second readback: the new suffix' size
     if (e != hipSuccess) return hip_fail(e, "sizing pass");
     const u64 old_used = c->dev.total_bytes - 96, new_used = st.start0 + st.new_bytes, total = new_used + 96, n_new = i0 + st.new_items;
@@ -1783,13 +1783,13 @@ int edit_run(fzb_corpus* c, const EditRequest& rq) {
     // ---- from here on the corpus changes ----
     for (u64 ta = 0; ta < tiles; ta += chunk_tiles) {
         const u64 te = std::min(tiles, ta + chunk_tiles);
-        const unsigned place_grid = (unsigned)std::min<u64>((te - ta) * 4, 4096);
+        const unsigned place_grid = fzb_grid_cap((te - ta) * 4, 16);  // (4096 on 256 CUs)
         if (c->dev.ends_u64) {
-            hipLaunchKernelGGL((k_ed_gather<u64>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u64*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u64*)out_e, st.start0, ta);
-            hipLaunchKernelGGL((k_ed_place<u64>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u64*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u64*)c->own_ends, st.start0, i0);
+            FZB_LAUNCH((k_ed_gather<u64>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u64*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u64*)out_e, st.start0, ta);
+            FZB_LAUNCH((k_ed_place<u64>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u64*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u64*)c->own_ends, st.start0, i0);
         } else {
-            hipLaunchKernelGGL((k_ed_gather<u32>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u32*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u32*)out_e, st.start0, ta);
-            hipLaunchKernelGGL((k_ed_place<u32>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u32*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u32*)c->own_ends, st.start0, i0);
+            FZB_LAUNCH((k_ed_gather<u32>), dim3((unsigned)(te - ta)), dim3(UP_THREADS), 0, nullptr, (const u8*)c->own_bytes, (const u32*)c->own_ends, n, i0, src, (const u8*)c->stage_raw, d_tb, d_tc, d_ts, out_b, (u32*)out_e, st.start0, ta);
+            FZB_LAUNCH((k_ed_place<u32>), dim3(place_grid), dim3(UP_THREADS), 0, nullptr, (const u8*)out_b, (const u32*)out_e, d_tb, d_tc, ta, te, (u8*)c->own_bytes, (u32*)c->own_ends, st.start0, i0);
         }
     }
     e = hipSuccess;

@@ -531,7 +531,7 @@ __global__ __launch_bounds__(128, (REAL * 4 <= SWL ? 4 : REAL * 8 <= 3 * SWL ? 3
 void fzb_launch_compact1_classify(const CorpusDev& c, u64 first, const u64* bitmap, const u32* tile_counts, u32 n_items, u32* out_idx, u32* total_out, const NeedleDev& nd, int sw_lanes,
                                   int wmode, u32 capacity, u32* dev_count, u32* overflow, u32 qcap, u32* counters, u32* win_out, u32* lists, u32 list_stride, int grid, hipStream_t st,
                                   int split_multi) {
-    hipLaunchKernelGGL((k_compact1_classify<3>), dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_items, out_idx, total_out, c.bytes, EndsAny{c.ends, c.ends_u64}, first, nd, wmode,
+    FZB_LAUNCH((k_compact1_classify<3>), dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_items, out_idx, total_out, c.bytes, EndsAny{c.ends, c.ends_u64}, first, nd, wmode,
                        (u32)sw_lanes, (uint4*)win_out, lists, list_stride, overflow, qcap, counters, capacity, dev_count, (u32)split_multi);
 }
 
@@ -544,7 +544,7 @@ void fzb_launch_dp_classes(const CorpusDev& c, u64 first, u32 index_offset, cons
     for (int r = 0; r < nd.rows; r++) upper = upper || (nd.c[r] >= 'A' && nd.c[r] <= 'Z');
     if (part != 2) {
         // (two survivors per thread: 1 / 2 / 4 gave 0.458 / 0.454 / 0.464 ms for the C4 shard's step)
-#define FZB_K2W(ET) hipLaunchKernelGGL((k2w_classify<2>), dim3(num_cus * 8), dim3(256), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, items, win_in, n_items_ptr, nd, wmode, (u32)sw_lanes, (uint4*)win_out, lists, list_stride, overflow, qcap, counters, capacity, dev_count, (u32)split_multi)
+#define FZB_K2W(ET) FZB_LAUNCH((k2w_classify<2>), dim3(num_cus * 8), dim3(256), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, items, win_in, n_items_ptr, nd, wmode, (u32)sw_lanes, (uint4*)win_out, lists, list_stride, overflow, qcap, counters, capacity, dev_count, (u32)split_multi)
         FZB_K2W(u32);
 #undef FZB_K2W
     }
@@ -553,7 +553,7 @@ void fzb_launch_dp_classes(const CorpusDev& c, u64 first, u32 index_offset, cons
     do {                                                                                                                                  \
         static int per_cu = 0;                                                                                                            \
         if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp_class<SWL, U, REAL>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
-        hipLaunchKernelGGL((k2b_dp_class<SWL, U, REAL>), dim3(num_cus * per_cu), dim3(128), 0, st, index_offset, items, (const uint4*)win_out, lists + (size_t)CLS * list_stride, &counters[8 + CLS], nd, out); \
+        FZB_LAUNCH((k2b_dp_class<SWL, U, REAL>), dim3(num_cus * per_cu), dim3(128), 0, st, index_offset, items, (const uint4*)win_out, lists + (size_t)CLS * list_stride, &counters[8 + CLS], nd, out); \
     } while (0)
 #define FZB_K2C_ALL(SWL, U) do { FZB_K2C(SWL, U, SWL / 4, 0); FZB_K2C(SWL, U, 3 * SWL / 8, 1); FZB_K2C(SWL, U, SWL / 2, 2); } while (0)
 #define FZB_K2C_U(SWL) do { if (upper) FZB_K2C_ALL(SWL, true); else FZB_K2C_ALL(SWL, false); } while (0)
@@ -781,7 +781,7 @@ size_t fzb_dp_long_quad_words_per_block(const NeedleLongDev& nd, int sw_lanes) {
 }
 void fzb_launch_dp_long_quad(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* win, int wmode, const u32* n_items_ptr, const NeedleLongDev& nd, int sw_lanes,
                              int upper, fzb_match_rec* out, u32 capacity, u32* dev_count, u32* scratch, u32* queue, u32* counters, int grid, hipStream_t st) {
-#define FZB_K2Q(SWL, U) hipLaunchKernelGGL((k2d_dp_long_quad<SWL, U>), dim3(grid), dim3(256), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, wmode, n_items_ptr, nd, out, capacity, dev_count, scratch, queue, counters)
+#define FZB_K2Q(SWL, U) FZB_LAUNCH((k2d_dp_long_quad<SWL, U>), dim3(grid), dim3(256), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, wmode, n_items_ptr, nd, out, capacity, dev_count, scratch, queue, counters)
     if (sw_lanes == 64) { if (upper) FZB_K2Q(64, true); else FZB_K2Q(64, false); }
     else { if (upper) FZB_K2Q(32, true); else FZB_K2Q(32, false); }
 #undef FZB_K2Q
@@ -792,7 +792,7 @@ size_t fzb_dp_long_scratch_words_per_thread(const NeedleLongDev& nd, int sw_lane
 
 void fzb_launch_dp_long(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* win, int wmode, const u32* n_items_ptr, const NeedleLongDev& nd, int sw_lanes,
                         int bias_ok, fzb_match_rec* out, u32 capacity, u32* dev_count, u32* scratch, u32* queue, u32* counters, int grid, hipStream_t st) {
-#define FZB_K2L(SWL, B) hipLaunchKernelGGL((k2d_dp_long<SWL, B>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, wmode, n_items_ptr, nd, out, capacity, dev_count, scratch, queue, counters)
+#define FZB_K2L(SWL, B) FZB_LAUNCH((k2d_dp_long<SWL, B>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, wmode, n_items_ptr, nd, out, capacity, dev_count, scratch, queue, counters)
 #define FZB_K2L_B(SWL) do { if (bias_ok) FZB_K2L(SWL, true); else FZB_K2L(SWL, false); } while (0)
     switch (sw_lanes) {
         case 64: FZB_K2L_B(64); break;
@@ -1014,7 +1014,7 @@ void fzb_launch_classes_all(const CorpusDev& c, u64 first, u32 index_offset, con
     // 46.4 -> 38.7 / 50.0 -> 43.7 us; 8..128-byte lists: 25 k windows 57.7 -> 54.2, 50 k 66.3 -> 69.3, 112 k (1.4 M paths) 90.9 -> 92.1)
     const u32 quad_all_below = std::min<u32>(coop_below, (u32)gm * 32u);
     const size_t dyn_lds = std::max((size_t)nd.rows * park_dw * 128 * 4, coop_below ? coop_lds : (size_t)0);
-#define FZB_K2A(SWL, U) hipLaunchKernelGGL((k2_classes_all<SWL, U>), dim3(gm + 3 * gc), dim3(128), dyn_lds, st, index_offset, items, (const uint4*)win, lists, list_stride, counters, nd, out, capacity, scratch, (u32)gm, (u32)gc, park_dw, coop_below, quad_all_below)
+#define FZB_K2A(SWL, U) FZB_LAUNCH((k2_classes_all<SWL, U>), dim3(gm + 3 * gc), dim3(128), dyn_lds, st, index_offset, items, (const uint4*)win, lists, list_stride, counters, nd, out, capacity, scratch, (u32)gm, (u32)gc, park_dw, coop_below, quad_all_below)
 #define FZB_K2A_U(SWL) do { if (upper) FZB_K2A(SWL, true); else FZB_K2A(SWL, false); } while (0)
     switch (sw_lanes) {
         case 64: FZB_K2A_U(64); break;
@@ -1032,7 +1032,7 @@ void fzb_launch_dp_multi(const CorpusDev& c, u64 first, u32 index_offset, const 
         bool upper = false;
         for (int r = 0; r < nd.rows; r++) upper = upper || (nd.c[r] >= 'A' && nd.c[r] <= 'Z');
         const u32 park_dw = fzb_park_lds_dwords(nd, sw_lanes);
-#define FZB_K2T(SWL, U, ET) hipLaunchKernelGGL((k2d_dp_multi_t<SWL, U>), dim3(grid), dim3(128), (size_t)nd.rows * park_dw * 128 * 4, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch, park_dw)
+#define FZB_K2T(SWL, U, ET) FZB_LAUNCH((k2d_dp_multi_t<SWL, U>), dim3(grid), dim3(128), (size_t)nd.rows * park_dw * 128 * 4, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch, park_dw)
 #define FZB_K2T_ET(SWL, U) FZB_K2T(SWL, U, u32)
 #define FZB_K2T_U(SWL) do { if (upper) FZB_K2T_ET(SWL, true); else FZB_K2T_ET(SWL, false); } while (0)
         switch (sw_lanes) {
@@ -1043,7 +1043,7 @@ void fzb_launch_dp_multi(const CorpusDev& c, u64 first, u32 index_offset, const 
         }
         return;
     }
-#define FZB_K2D(SWL, B, ET) hipLaunchKernelGGL((k2d_dp_multi<SWL, B>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch)
+#define FZB_K2D(SWL, B, ET) FZB_LAUNCH((k2d_dp_multi<SWL, B>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch)
 #define FZB_K2D_ET(SWL, B) FZB_K2D(SWL, B, u32)
 #define FZB_K2D_B(SWL) do { if (bias_ok) FZB_K2D_ET(SWL, true); else FZB_K2D_ET(SWL, false); } while (0)
     switch (sw_lanes) {
@@ -1071,7 +1071,7 @@ void fzb_launch_dp(const CorpusDev& c, u64 first, u32 index_offset, const u32* i
     do {                                                                                                                                \
         static int per_cu = 0;                                                                                                          \
         if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp_short<SWL, U, SEG>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
-        hipLaunchKernelGGL((k2b_dp_short<SWL, U, SEG>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, rj, kept_out, c.uniform_len, SA); \
+        FZB_LAUNCH((k2b_dp_short<SWL, U, SEG>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, rj, kept_out, c.uniform_len, SA); \
     } while (0)
 #define FZB_K2S_ET(SWL, U) do { if (seg) FZB_K2S(SWL, U, true, *seg); else FZB_K2S(SWL, U, false, SegNone{}); } while (0)
 #define FZB_K2S_U(SWL) do { if (upper) FZB_K2S_ET(SWL, true); else FZB_K2S_ET(SWL, false); } while (0)
@@ -1083,7 +1083,7 @@ void fzb_launch_dp(const CorpusDev& c, u64 first, u32 index_offset, const u32* i
     do {                                                                                                                                \
         static int per_cu = 0;                                                                                                          \
         if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp<SWL, B, U>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
-        hipLaunchKernelGGL((k2b_dp<SWL, B, U>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, pad_ok, out, capacity, dev_count, overflow, qcap, counters); \
+        FZB_LAUNCH((k2b_dp<SWL, B, U>), dim3(num_cus * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, pad_ok, out, capacity, dev_count, overflow, qcap, counters); \
     } while (0)
 #define FZB_K2B_ET(SWL, B, U) FZB_K2B(SWL, B, U, u32)
 #define FZB_K2B_U(SWL, B) do { if (upper) FZB_K2B_ET(SWL, B, true); else FZB_K2B_ET(SWL, B, false); } while (0)

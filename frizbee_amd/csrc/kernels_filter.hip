@@ -1094,7 +1094,7 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
         const bool use_sig = shortc && fzb_filter_sig_applies(c, mode, needle_sig, sig_ok);
         const u64 tiles = (n_hint + FZB_TILE - 1) / FZB_TILE;
         const int g = (int)std::max<u64>(1, std::min<u64>((u64)std::max(1, grid) * 2, tiles));  // (`grid` = 4 workgroups per CU: 8 here, every wave slot, as k1_dfa)
-#define FZB_K1ID(ET, SIG, SHORT) hipLaunchKernelGGL((k1_items_dfa<ET, SIG, SHORT>), dim3(g), dim3(256), lds, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, items, n_items_ptr, dfa, rows, min_len, (u32)rows, bitmap, tile_counts, c.uniform_len)
+#define FZB_K1ID(ET, SIG, SHORT) FZB_LAUNCH((k1_items_dfa<ET, SIG, SHORT>), dim3(g), dim3(256), lds, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, items, n_items_ptr, dfa, rows, min_len, (u32)rows, bitmap, tile_counts, c.uniform_len)
         if (c.ends_u64) { if (use_sig) FZB_K1ID(u64, true, true); else if (shortc) FZB_K1ID(u64, false, true); else FZB_K1ID(u64, false, false); }
         else            { if (use_sig) FZB_K1ID(u32, true, true); else if (shortc) FZB_K1ID(u32, false, true); else FZB_K1ID(u32, false, false); }
 #undef FZB_K1ID
@@ -1102,7 +1102,7 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
     }
     // MODE 1 with one-hot state needs rows + 1 bits, MODE 2 rows bits
     const bool w64 = (mode == 1) ? rows > 31 : rows > 32;
-#define FZB_K1I(TW, MODE, ET) hipLaunchKernelGGL((k1_items<TW, MODE, ET>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, items, n_items_ptr, table, rows, need, min_len, bitmap, tile_counts)
+#define FZB_K1I(TW, MODE, ET) FZB_LAUNCH((k1_items<TW, MODE, ET>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, items, n_items_ptr, table, rows, need, min_len, bitmap, tile_counts)
     if (c.ends_u64) {
         if (mode == 1) { if (w64) FZB_K1I(u64, 1, u64); else FZB_K1I(u32, 1, u64); }
         else           { if (w64) FZB_K1I(u64, 2, u64); else FZB_K1I(u32, 2, u64); }
@@ -1135,7 +1135,7 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
         const bool shortc = c.max_len != 0 && c.max_len <= 32;  // every haystack fits the two pre-requested vectors
         if (fzb_filter_sig_applies(c, mode, needle_sig, sig_ok)) {  // an eligible needle over a list with signatures (host.hip decides eligibility)
             const size_t lds_s = lds + 128 + 2 * FZB_TILE;  // + the tile's decision bits and the queue of passing rows
-#define FZB_K1S(ET, SEG, G, S) hipLaunchKernelGGL((k1_dfa_sig<ET, SEG>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE), S)
+#define FZB_K1S(ET, SEG, G, S) FZB_LAUNCH((k1_dfa_sig<ET, SEG>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE), S)
             if (seg) {  // the filter lists its survivors: one workgroup per segment
                 if (c.ends_u64) FZB_K1S(u64, true, seg->nseg, *seg); else FZB_K1S(u32, true, seg->nseg, *seg);
             } else {
@@ -1145,7 +1145,7 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
             return;
         }
         if (shortc) {
-#define FZB_K1D(ET) hipLaunchKernelGGL((k1_dfa<ET>), dim3(grid), dim3(256), lds, st, c.bytes, (const ET*)c.ends, first, count, dfa, rows, min_len, dead, acc, bitmap, tile_counts, reset_counters, c.uniform_len)
+#define FZB_K1D(ET) FZB_LAUNCH((k1_dfa<ET>), dim3(grid), dim3(256), lds, st, c.bytes, (const ET*)c.ends, first, count, dfa, rows, min_len, dead, acc, bitmap, tile_counts, reset_counters, c.uniform_len)
             if (c.ends_u64) FZB_K1D(u64); else FZB_K1D(u32);
 #undef FZB_K1D
             return;
@@ -1168,8 +1168,8 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
             // 1.4 M items (1 374 tiles) on the 256-thread form's six workgroups per CU win (34.5 against 38.3)
             const bool wide = nul_safe && len_free && ntiles < (u32)cus * 2u;
 #define FZB_K1VA const_cast<const u8*>(c.vbytes), c.vgofs, c.vgnv, c.vlen, c.vperm, first, count, cdfa, cdfa_bytes, (u32)cdfa_K, kg, min_len, dead, acc, bitmap, tile_counts, reset_counters
-#define FZB_K1V(SAN, G, NV, LEN) hipLaunchKernelGGL((k1_cdfa_view<SAN, G, NV, LEN>), dim3(g), dim3(256), lds_v, st, FZB_K1VA)
-#define FZB_K1W(G, NV) hipLaunchKernelGGL((k1_cdfa_view<false, G, NV, false, 1024>), dim3(g), dim3(1024), lds_v, st, FZB_K1VA)
+#define FZB_K1V(SAN, G, NV, LEN) FZB_LAUNCH((k1_cdfa_view<SAN, G, NV, LEN>), dim3(g), dim3(256), lds_v, st, FZB_K1VA)
+#define FZB_K1W(G, NV) FZB_LAUNCH((k1_cdfa_view<false, G, NV, false, 1024>), dim3(g), dim3(1024), lds_v, st, FZB_K1VA)
 #define FZB_K1V_S(SAN, G, NV) do { if (!SAN && wide) FZB_K1W(G, NV); else if (!SAN && len_free) FZB_K1V(SAN, G, NV, false); else FZB_K1V(SAN, G, NV, true); } while (0)
 #define FZB_K1V_NV(SAN, G) do { if (c.view_nv <= 8) FZB_K1V_S(SAN, G, 8); else FZB_K1V_S(SAN, G, 16); } while (0)
 #define FZB_K1V_G(SAN) do { if (cdfa_G == 4) FZB_K1V_NV(SAN, 4); else FZB_K1V_NV(SAN, 2); } while (0)
@@ -1184,8 +1184,8 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
                 const u32 ns_o = (cdfa_bytes - 256u) / kg;  // the automaton's states (the table is padded to 16 bytes: at most a phantom state more)
                 const u32 wpw = ((cdfa_bytes + 15) & ~(size_t)15) + (size_t)4 * 64 * ns_o + 16 <= 60 * 1024 ? 4u : 1u;
                 const size_t lds_o = ((cdfa_bytes + 15) & ~(size_t)15) + (size_t)wpw * 64 * ns_o + 16;
-                const int go = (int)std::max<u32>(1u, std::min<u32>((c.n_long + wpw - 1) / wpw, 4096u));
-#define FZB_K1O(ET, SAN, G) hipLaunchKernelGGL((k1_cdfa_outliers<ET, SAN, G>), dim3(go), dim3(64 * wpw), lds_o, st, c.bytes, (const ET*)c.ends, first, count, c.vlong, c.n_long, cdfa, cdfa_bytes, (u32)cdfa_K, kg, ns_o, min_len, dead, acc, bitmap, tile_counts)
+                const int go = (int)std::max<u32>(1u, std::min<u32>((c.n_long + wpw - 1) / wpw, (u32)cus * 16u));  // (4096 on 256 CUs)
+#define FZB_K1O(ET, SAN, G) FZB_LAUNCH((k1_cdfa_outliers<ET, SAN, G>), dim3(go), dim3(64 * wpw), lds_o, st, c.bytes, (const ET*)c.ends, first, count, c.vlong, c.n_long, cdfa, cdfa_bytes, (u32)cdfa_K, kg, ns_o, min_len, dead, acc, bitmap, tile_counts)
 #define FZB_K1O_G(ET, SAN) do { if (cdfa_G == 4) FZB_K1O(ET, SAN, 4); else FZB_K1O(ET, SAN, 2); } while (0)
                 if (c.ends_u64) { if (nul_safe) FZB_K1O_G(u64, false); else FZB_K1O_G(u64, true); }
                 else            { if (nul_safe) FZB_K1O_G(u32, false); else FZB_K1O_G(u32, true); }
@@ -1197,7 +1197,7 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
         if (composite) {
             const size_t lds_c = ((cdfa_bytes + 15) & ~(size_t)15) + 16;
             const int g = std::max(1, std::min<int>(cus * 5, (int)ntiles));
-#define FZB_K1CD(ET, SAN, G) hipLaunchKernelGGL((k1_cdfa_ragged<ET, SAN, G>), dim3(g), dim3(256), lds_c, st, c.bytes, (const ET*)c.ends, first, count, cdfa, cdfa_bytes, (u32)cdfa_K, kg, min_len, dead, acc, bitmap, tile_counts, reset_counters)
+#define FZB_K1CD(ET, SAN, G) FZB_LAUNCH((k1_cdfa_ragged<ET, SAN, G>), dim3(g), dim3(256), lds_c, st, c.bytes, (const ET*)c.ends, first, count, cdfa, cdfa_bytes, (u32)cdfa_K, kg, min_len, dead, acc, bitmap, tile_counts, reset_counters)
 #define FZB_K1CD_G(ET, SAN) do { if (cdfa_G == 4) FZB_K1CD(ET, SAN, 4); else FZB_K1CD(ET, SAN, 2); } while (0)
             if (c.ends_u64) { if (nul_safe) FZB_K1CD_G(u64, false); else FZB_K1CD_G(u64, true); }
             else            { if (nul_safe) FZB_K1CD_G(u32, false); else FZB_K1CD_G(u32, true); }
@@ -1205,7 +1205,7 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
 #undef FZB_K1CD
             return;
         }
-#define FZB_K1B(ET, SAN) hipLaunchKernelGGL((k1_dfa_ragged_burst<ET, SAN>), dim3(grid), dim3(256), lds, st, c.bytes, (const ET*)c.ends, first, count, dfa, rows, min_len, dead, acc, bitmap, tile_counts, reset_counters)
+#define FZB_K1B(ET, SAN) FZB_LAUNCH((k1_dfa_ragged_burst<ET, SAN>), dim3(grid), dim3(256), lds, st, c.bytes, (const ET*)c.ends, first, count, dfa, rows, min_len, dead, acc, bitmap, tile_counts, reset_counters)
         if (c.ends_u64) { if (nul_safe) FZB_K1B(u64, false); else FZB_K1B(u64, true); }
         else            { if (nul_safe) FZB_K1B(u32, false); else FZB_K1B(u32, true); }
 #undef FZB_K1B
@@ -1214,13 +1214,13 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
     const bool w64 = (mode == 1) ? rows > 31 : rows > 32;
     if (mode == 2 && bitmap_m) {  // LCS filter with the "nothing to spare" bit (typo configurations on the short-haystack path)
         const MargOut mo{bitmap_m, tile_counts_m, reject_bits, tile_rejects};
-#define FZB_K1M(TW, ET) hipLaunchKernelGGL((k1_filter<TW, 2, ET, true>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, count, table, rows, need, min_len, bitmap, tile_counts, reset_counters, mo, c.uniform_len)
+#define FZB_K1M(TW, ET) FZB_LAUNCH((k1_filter<TW, 2, ET, true>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, count, table, rows, need, min_len, bitmap, tile_counts, reset_counters, mo, c.uniform_len)
         if (c.ends_u64) { if (w64) FZB_K1M(u64, u64); else FZB_K1M(u32, u64); }
         else            { if (w64) FZB_K1M(u64, u32); else FZB_K1M(u32, u32); }
 #undef FZB_K1M
         return;
     }
-#define FZB_K1(TW, MODE, ET) hipLaunchKernelGGL((k1_filter<TW, MODE, ET>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, count, table, rows, need, min_len, bitmap, tile_counts, reset_counters, MargOut{}, c.uniform_len)
+#define FZB_K1(TW, MODE, ET) FZB_LAUNCH((k1_filter<TW, MODE, ET>), dim3(grid), dim3(256), 0, st, c.bytes, (const ET*)c.ends, first, count, table, rows, need, min_len, bitmap, tile_counts, reset_counters, MargOut{}, c.uniform_len)
     if (c.ends_u64) {
         if (mode == 1) { if (w64) FZB_K1(u64, 1, u64); else FZB_K1(u32, 1, u64); }
         else           { if (w64) FZB_K1(u64, 2, u64); else FZB_K1(u32, 2, u64); }
@@ -1259,20 +1259,20 @@ __global__ __launch_bounds__(1024) void k_scan_rejects(const u32* __restrict__ t
     }
 }
 void fzb_launch_scan_rejects(const u32* tile_rejects, u32 ntiles, const u32* reject_count, u32* rej_prefix, hipStream_t st) {
-    hipLaunchKernelGGL(k_scan_rejects, dim3(1), dim3(1024), 0, st, tile_rejects, ntiles, reject_count, rej_prefix);
+    FZB_LAUNCH(k_scan_rejects, dim3(1), dim3(1024), 0, st, tile_rejects, ntiles, reject_count, rej_prefix);
 }
 
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,
                          u32* total_out2) {
-    hipLaunchKernelGGL(k_compact1, dim3(grid), dim3(256), 0, st, bitmap, counts, n_items, n_items_ptr, src, out_idx, total_out, total_out2);
+    FZB_LAUNCH(k_compact1, dim3(grid), dim3(256), 0, st, bitmap, counts, n_items, n_items_ptr, src, out_idx, total_out, total_out2);
 }
 
 __global__ void k_init_counters(u32* __restrict__ counters, u32 n0) {
     if (threadIdx.x < 16) counters[threadIdx.x] = threadIdx.x == 0 ? n0 : 0u;
 }
-void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st) { hipLaunchKernelGGL(k_init_counters, dim3(1), dim3(64), 0, st, counters, n0); }
+void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st) { FZB_LAUNCH(k_init_counters, dim3(1), dim3(64), 0, st, counters, n0); }
 
 void fzb_launch_compact2(const u64* bitmap, const u32* counts, const u32* n_items_ptr, const u32* in_idx, const u32* in_win, u32* out_idx, u32* out_win, u32* total_out,
                          int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_compact2, dim3(grid), dim3(256), 0, st, bitmap, counts, n_items_ptr, in_idx, in_win, out_idx, out_win, total_out);
+    FZB_LAUNCH(k_compact2, dim3(grid), dim3(256), 0, st, bitmap, counts, n_items_ptr, in_idx, in_win, out_idx, out_win, total_out);
 }

@@ -225,12 +225,12 @@ void fzb_launch_multi_union(const fzb_match_rec* head, const u32* head_count, u3
     a.pos_u = pos_u;
     a.U = U;
     const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, (max_records + 255) / 256));
-    if (by_value) hipLaunchKernelGGL((k_multi_union<true>), dim3(g), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_multi_union<false>), dim3(g), dim3(256), 0, st, a);
+    if (by_value) FZB_LAUNCH((k_multi_union<true>), dim3(g), dim3(256), 0, st, a);
+    else FZB_LAUNCH((k_multi_union<false>), dim3(g), dim3(256), 0, st, a);
 }
 
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_top_items, dim3(grid), dim3(256), 0, st, head, head_count, cap, items, n_items, dev_count);
+    FZB_LAUNCH(k_top_items, dim3(grid), dim3(256), 0, st, head, head_count, cap, items, n_items, dev_count);
 }
 
 // u32 words of `tiles` the pack needs for heads of up to max_records records
@@ -244,11 +244,11 @@ void fzb_launch_indices_pack(const fzb_match_rec* head, const u32* head_count, c
     const u32 ntiles_cap = (max_records + IPACK_TILE - 1) / IPACK_TILE + 1;
     const PackArgs a{head, head_count, traced, traced_count, npos, pos, stride, out, std::min<u32>(out_cap, max_records), dense, dense_cap, dev_count, tiles, ntiles_cap};
     if (max_records <= IPACK_TILE) {
-        hipLaunchKernelGGL((k_ipack_scatter<false>), dim3(1), dim3(IPACK_THREADS), 0, st, a);
+        FZB_LAUNCH((k_ipack_scatter<false>), dim3(1), dim3(IPACK_THREADS), 0, st, a);
         return;
     }
     const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, ntiles_cap));
-    hipLaunchKernelGGL(k_ipack_tile_sums, dim3(g), dim3(IPACK_THREADS), 0, st, a);
-    hipLaunchKernelGGL(k_ipack_scan_tiles, dim3(1), dim3(64), 0, st, a);
-    hipLaunchKernelGGL((k_ipack_scatter<true>), dim3(g), dim3(IPACK_THREADS), 0, st, a);
+    FZB_LAUNCH(k_ipack_tile_sums, dim3(g), dim3(IPACK_THREADS), 0, st, a);
+    FZB_LAUNCH(k_ipack_scan_tiles, dim3(1), dim3(64), 0, st, a);
+    FZB_LAUNCH((k_ipack_scatter<true>), dim3(g), dim3(IPACK_THREADS), 0, st, a);
 }

@@ -204,23 +204,23 @@ __global__ __launch_bounds__(256) void k_literal_score(const u8* __restrict__ by
 
 void fzb_launch_literal_filter(const CorpusDev& c, u64 first, u32 count, const u32* items, const u32* n_items_ptr, const NeedleDev& nd, int mode, u64* bitmap, u32* tile_counts,
                                int grid, hipStream_t st) {
-    if (c.ends_u64) hipLaunchKernelGGL((k_literal_filter<u64>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
-    else hipLaunchKernelGGL((k_literal_filter<u32>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
+    if (c.ends_u64) FZB_LAUNCH((k_literal_filter<u64>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
+    else FZB_LAUNCH((k_literal_filter<u32>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
 }
 void fzb_launch_literal_score(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* n_items_ptr, const NeedleDev& nd, int mode, fzb_match_rec* out,
                               u32 capacity, u32* dev_count, u32* tpos, u32* tnpos, u32 tstride, int grid, hipStream_t st) {
-    if (c.ends_u64) hipLaunchKernelGGL((k_literal_score<u64>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
-    else hipLaunchKernelGGL((k_literal_score<u32>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
+    if (c.ends_u64) FZB_LAUNCH((k_literal_score<u64>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
+    else FZB_LAUNCH((k_literal_score<u32>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
 }
 
 // long needles (NeedleLongDev: needle arrays in device memory): the same two kernels
 void fzb_launch_literal_filter_long(const CorpusDev& c, u64 first, u32 count, const u32* items, const u32* n_items_ptr, const NeedleLongDev& nd, int mode, u64* bitmap,
                                     u32* tile_counts, int grid, hipStream_t st) {
-    if (c.ends_u64) hipLaunchKernelGGL((k_literal_filter<u64, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
-    else hipLaunchKernelGGL((k_literal_filter<u32, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
+    if (c.ends_u64) FZB_LAUNCH((k_literal_filter<u64, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
+    else FZB_LAUNCH((k_literal_filter<u32, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, count, items, n_items_ptr, nd, mode, bitmap, tile_counts);
 }
 void fzb_launch_literal_score_long(const CorpusDev& c, u64 first, u32 index_offset, const u32* items, const u32* n_items_ptr, const NeedleLongDev& nd, int mode, fzb_match_rec* out,
                                    u32 capacity, u32* dev_count, u32* tpos, u32* tnpos, u32 tstride, int grid, hipStream_t st) {
-    if (c.ends_u64) hipLaunchKernelGGL((k_literal_score<u64, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
-    else hipLaunchKernelGGL((k_literal_score<u32, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
+    if (c.ends_u64) FZB_LAUNCH((k_literal_score<u64, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u64*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
+    else FZB_LAUNCH((k_literal_score<u32, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, (const u32*)c.ends, first, index_offset, items, n_items_ptr, nd, mode, out, capacity, dev_count, tpos, tnpos, tstride);
 }

@@ -146,19 +146,19 @@ __global__ __launch_bounds__(256) void k_copy_records(const fzb_match_rec* __res
 }
 
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_records_to_items, dim3(grid), dim3(256), 0, st, cand, n_ptr, index_offset, items);
+    FZB_LAUNCH(k_records_to_items, dim3(grid), dim3(256), 0, st, cand, n_ptr, index_offset, items);
 }
 void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u32* count_out, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_identity_records, dim3(grid), dim3(256), 0, st, out, n, index_offset, count_out);
+    FZB_LAUNCH(k_identity_records, dim3(grid), dim3(256), 0, st, out, n, index_offset, count_out);
 }
 void fzb_launch_join_add(fzb_match_rec* hits, const u32* n_hits_ptr, const fzb_match_rec* cand, const u32* n_cand_ptr, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_join_add, dim3(grid), dim3(256), 0, st, hits, n_hits_ptr, cand, n_cand_ptr);
+    FZB_LAUNCH(k_join_add, dim3(grid), dim3(256), 0, st, hits, n_hits_ptr, cand, n_cand_ptr);
 }
 void fzb_launch_remove_hits(const fzb_match_rec* cand, const u32* n_cand_ptr, const fzb_match_rec* hits, const u32* n_hits_ptr, u64* bitmap, u32* tile_counts,
                             fzb_match_rec* out, u32* total_out, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_flag_absent, dim3(grid), dim3(256), 0, st, cand, n_cand_ptr, hits, n_hits_ptr, bitmap, tile_counts);
-    hipLaunchKernelGGL(k_compact_records, dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_cand_ptr, cand, out, total_out);
+    FZB_LAUNCH(k_flag_absent, dim3(grid), dim3(256), 0, st, cand, n_cand_ptr, hits, n_hits_ptr, bitmap, tile_counts);
+    FZB_LAUNCH(k_compact_records, dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_cand_ptr, cand, out, total_out);
 }
 void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_copy_records, dim3(grid), dim3(256), 0, st, in, n_ptr, out, capacity, count_out);
+    FZB_LAUNCH(k_copy_records, dim3(grid), dim3(256), 0, st, in, n_ptr, out, capacity, count_out);
 }

@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_concat_runs(RunSet rs, const u32* __res
 }
 
 void fzb_launch_concat_runs(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, u32* cut_flag, hipStream_t st) {
-    hipLaunchKernelGGL(k_concat_runs, dim3(grid), dim3(256), 0, st, rs, base_in, total_out, out, capacity, cut_flag);
+    FZB_LAUNCH(k_concat_runs, dim3(grid), dim3(256), 0, st, rs, base_in, total_out, out, capacity, cut_flag);
 }
 
 // records: `buf` (n = *n_ptr records, capacity cap) sorted in place; tmp >= cap records; hist >= 2 * 256 * ntiles_cap words
@@ -202,29 +202,29 @@ __global__ __launch_bounds__(256) void k_sort_copy_back(const fzb_match_rec* __r
 // byte would move every record to where it already is - the sorted list is copied back instead (a 4 MB copy instead of a 45 us pass)
 void fzb_launch_sort(fzb_match_rec* buf, fzb_match_rec* tmp, const u32* n_ptr, u32* hist, u32 ntiles_cap, int reverse_first, int by_score, int grid, hipStream_t st, int passes) {
     // passes = -1: one pass, and the unsorted records are in `tmp` already (the pipeline wrote them there): tmp -> buf, no copy back
-    if (reverse_first) hipLaunchKernelGGL(k_reverse, dim3(grid), dim3(256), 0, st, passes == -1 ? tmp : buf, n_ptr);
+    if (reverse_first) FZB_LAUNCH(k_reverse, dim3(grid), dim3(256), 0, st, passes == -1 ? tmp : buf, n_ptr);
     if (!by_score) return;
     u32* offs = hist + (size_t)256 * ntiles_cap;  // the scanned histogram (second half of the buffer)
     u32* dtot = hist + (size_t)512 * ntiles_cap;  // behind both: two sets of 256 digit totals + the phase word (FZB_SORT_HIST_WORDS)
     if (passes == -1) {
-        hipLaunchKernelGGL(k_sort_hist, dim3(grid), dim3(256), 0, st, tmp, n_ptr, 0, hist, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(grid), dim3(256), 0, st, tmp, buf, n_ptr, 0, offs, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_hist, dim3(grid), dim3(256), 0, st, tmp, n_ptr, 0, hist, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scatter, dim3(grid), dim3(256), 0, st, tmp, buf, n_ptr, 0, offs, ntiles_cap, dtot);
         return;
     }
     if (passes == 1) {
-        hipLaunchKernelGGL(k_sort_hist, dim3(grid), dim3(256), 0, st, buf, n_ptr, 0, hist, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(grid), dim3(256), 0, st, buf, tmp, n_ptr, 0, offs, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_copy_back, dim3(grid), dim3(256), 0, st, tmp, buf, n_ptr);
+        FZB_LAUNCH(k_sort_hist, dim3(grid), dim3(256), 0, st, buf, n_ptr, 0, hist, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scatter, dim3(grid), dim3(256), 0, st, buf, tmp, n_ptr, 0, offs, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_copy_back, dim3(grid), dim3(256), 0, st, tmp, buf, n_ptr);
         return;
     }
     for (int pass = 0; pass < 2; pass++) {
         const fzb_match_rec* src = pass == 0 ? buf : tmp;
         fzb_match_rec* dst = pass == 0 ? tmp : buf;
         const int shift = pass * 8;
-        hipLaunchKernelGGL(k_sort_hist, dim3(grid), dim3(256), 0, st, src, n_ptr, shift, hist, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(grid), dim3(256), 0, st, src, dst, n_ptr, shift, offs, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_hist, dim3(grid), dim3(256), 0, st, src, n_ptr, shift, hist, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scan, dim3(16), dim3(1024), 0, st, hist, offs, n_ptr, ntiles_cap, dtot);
+        FZB_LAUNCH(k_sort_scatter, dim3(grid), dim3(256), 0, st, src, dst, n_ptr, shift, offs, ntiles_cap, dtot);
     }
 }

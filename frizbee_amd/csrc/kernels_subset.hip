@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void k_subset_capture(const fzb_match_rec* __r
 void fzb_launch_subset_capture(const fzb_match_rec* recs, const u32* n_ptr, u32 cap, u32 index_offset, u32* items, u32 items_cap, u32* count_out, u32* mirror, int grid_max, hipStream_t st) {
     const u32 blocks = (cap + 255u) / 256u, most = grid_max > 0 ? (u32)grid_max : 1u;
     const int grid = (int)(blocks < most ? (blocks ? blocks : 1u) : most);
-    hipLaunchKernelGGL(k_subset_capture, dim3(grid), dim3(256), 0, st, recs, n_ptr, cap, index_offset, items, items_cap, count_out, mirror);
+    FZB_LAUNCH(k_subset_capture, dim3(grid), dim3(256), 0, st, recs, n_ptr, cap, index_offset, items, items_cap, count_out, mirror);
 }
 
 // The flag pass of fzb_subset_from_scope, in the shape of k_scope_flag but over the HAYSTACKS 0 .. n - 1 instead of over records: one ballot
@@ -52,6 +52,6 @@ __global__ __launch_bounds__(256) void k_subset_scope_flag(const uint16_t* __res
 void fzb_launch_subset_from_scope(const uint16_t* tags, u32 n, u32 require, u32 exclude, u64* bitmap, u32* tile_counts, u32* out, u32* count_out, int grid_max, hipStream_t st) {
     const u32 tiles = (n + SCOPE_TILE - 1) / SCOPE_TILE, most = grid_max > 0 ? (u32)grid_max : 1u;
     const int grid = (int)(tiles < most ? (tiles ? tiles : 1u) : most);
-    hipLaunchKernelGGL(k_subset_scope_flag, dim3(grid), dim3(256), 0, st, tags, n, require, exclude, bitmap, tile_counts);
+    FZB_LAUNCH(k_subset_scope_flag, dim3(grid), dim3(256), 0, st, tags, n, require, exclude, bitmap, tile_counts);
     fzb_launch_compact1(bitmap, tile_counts, n, nullptr, nullptr, out, count_out, grid, st);
 }

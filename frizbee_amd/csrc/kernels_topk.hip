@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void k_topk_concat(RunSet rs, const u32* __res
 }
 
 void fzb_launch_topk_concat(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_topk_concat, dim3(grid), dim3(256), 0, st, rs, base_in, total_out, out, capacity);
+    FZB_LAUNCH(k_topk_concat, dim3(grid), dim3(256), 0, st, rs, base_in, total_out, out, capacity);
 }
 
 // in: *in_count records (at most in_cap) in record order, in_count[1] = matches found.  out: the kept records in record order,
@@ -267,17 +267,17 @@ hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, 
         const hipError_t e = hipMemsetAsync(scratch, 0, 512 * sizeof(u32), st);
         if (e != hipSuccess) return e;  // (nothing launched: the bins would hold the previous query's counts)
         if (!one_pass) {
-            hipLaunchKernelGGL(k_topk_hist, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, limit, 0, fixed_hi, scratch);
-            hipLaunchKernelGGL(k_topk_cut, dim3(1), dim3(256), 0, st, in_count, in_cap, limit, 0, by_score, desc, fixed_hi, scratch);
+            FZB_LAUNCH(k_topk_hist, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, limit, 0, fixed_hi, scratch);
+            FZB_LAUNCH(k_topk_cut, dim3(1), dim3(256), 0, st, in_count, in_cap, limit, 0, by_score, desc, fixed_hi, scratch);
         }
-        hipLaunchKernelGGL(k_topk_hist, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, limit, 1, fixed_hi, scratch);
+        FZB_LAUNCH(k_topk_hist, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, limit, 1, fixed_hi, scratch);
     }
-    hipLaunchKernelGGL(k_topk_cut, dim3(1), dim3(256), 0, st, in_count, in_cap, limit, 1, by_score, desc, fixed_hi, scratch);
+    FZB_LAUNCH(k_topk_cut, dim3(1), dim3(256), 0, st, in_count, in_cap, limit, 1, by_score, desc, fixed_hi, scratch);
     if (by_score) {
-        hipLaunchKernelGGL(k_topk_tile_counts, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, scratch, ntiles_cap);
-        hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(128), 0, st, in_count, in_cap, scratch, ntiles_cap);
+        FZB_LAUNCH(k_topk_tile_counts, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, scratch, ntiles_cap);
+        FZB_LAUNCH(k_topk_scan, dim3(1), dim3(128), 0, st, in_count, in_cap, scratch, ntiles_cap);
     }
-    hipLaunchKernelGGL(k_topk_scatter, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, by_score, out, out_cap, out_count, scratch, ntiles_cap);
+    FZB_LAUNCH(k_topk_scatter, dim3(grid), dim3(256), 0, st, in, in_count, in_cap, by_score, out, out_cap, out_count, scratch, ntiles_cap);
     return hipGetLastError();
 }
 
@@ -308,7 +308,7 @@ void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const
     if (!cap || !n_bias) return;
     const u32 blocks = (cap + 255u) / 256u, most = grid_max > 0 ? (u32)grid_max : 1u;
     const int grid = (int)(blocks < most ? blocks : most);
-    hipLaunchKernelGGL(k_bias_apply, dim3(grid), dim3(256), 0, st, recs, count, cap, bias, n_bias, first, index_offset);
+    FZB_LAUNCH(k_bias_apply, dim3(grid), dim3(256), 0, st, recs, count, cap, bias, n_bias, first, index_offset);
 }
 
 // ---- the corpus' visibility scope (scope.h): hidden haystacks' records are dropped ----------------------------------------------------
@@ -412,6 +412,6 @@ void fzb_launch_scope_drop(const fzb_match_rec* recs, const u32* count, u32 cap,
                            u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st) {
     const u32 tiles = (cap + SCOPE_TILE - 1) / SCOPE_TILE, most = grid_max > 0 ? (u32)grid_max : 1u;
     const int grid = (int)(tiles < most ? (tiles ? tiles : 1u) : most);
-    hipLaunchKernelGGL(k_scope_flag, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts);
-    hipLaunchKernelGGL(k_scope_compact, dim3(grid), dim3(256), 0, st, (const u64*)bitmap, (const u32*)tile_counts, count, cap, (const scope_rec*)recs, (scope_rec*)out, capacity, count_out);
+    FZB_LAUNCH(k_scope_flag, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts);
+    FZB_LAUNCH(k_scope_compact, dim3(grid), dim3(256), 0, st, (const u64*)bitmap, (const u32*)tile_counts, count, cap, (const scope_rec*)recs, (scope_rec*)out, capacity, count_out);
 }

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k2u_split_wide(const EndsAny ends, u64 fi
 
 void fzb_launch_unicode_split_wide(const CorpusDev& c, u64 first, const u32* items, const u32* n_items_ptr, int sw_lanes, u32 capacity, u32* overflow, u32 qcap, u32* counters,
                                    int grid, hipStream_t st) {
-    hipLaunchKernelGGL(k2u_split_wide, dim3(grid), dim3(256), 0, st, EndsAny{c.ends, c.ends_u64}, first, items, n_items_ptr, c.uniform_len, (u32)sw_lanes, capacity, overflow, qcap, counters);
+    FZB_LAUNCH(k2u_split_wide, dim3(grid), dim3(256), 0, st, EndsAny{c.ends, c.ends_u64}, first, items, n_items_ptr, c.uniform_len, (u32)sw_lanes, capacity, overflow, qcap, counters);
 }
 
 #define FZB_K2U_PARAMS const u8* __restrict__ bytes, const EndsAny ends, u64 first, u32 index_offset, const u32* __restrict__ items, const u32* __restrict__ win, \
@@ -209,7 +209,7 @@ void fzb_launch_dp_unicode(const CorpusDev& c, u64 first, u32 index_offset, cons
     do {                                                                                                                               \
         static int per_cu = 0;                                                                                                         \
         if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, 128, 0) != hipSuccess || per_cu < 1)) per_cu = DFLT; \
-        hipLaunchKernelGGL(KERNEL, dim3(one_round_wgs > 0 ? one_round_wgs : grid * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, overflow, qcap, counters, c.uniform_len, (u32)multi_front); \
+        FZB_LAUNCH(KERNEL, dim3(one_round_wgs > 0 ? one_round_wgs : grid * per_cu), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, items, win, n_items_ptr, nd, wmode, out, capacity, dev_count, overflow, qcap, counters, c.uniform_len, (u32)multi_front); \
     } while (0)
 #define FZB_K2U_SW(SWL)                                                                                                                \
     do {                                                                                                                               \
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(128) void k2u_dp_unicode_multi(const u8* __restrict
 
 void fzb_launch_dp_unicode_multi(const CorpusDev& c, u64 first, u32 index_offset, const u32* list, const u32* n_list_ptr, const NeedleDev& nd, int sw_lanes,
                                  fzb_match_rec* out, u32 capacity, u32* scratch, int grid, hipStream_t st, u32 only_from, int tform, u32* counters, u32* back_end, u32 fwd_cap) {
-#define FZB_K2UM(SWL, TF) hipLaunchKernelGGL((k2u_dp_unicode_multi<SWL, TF>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch, only_from, counters, back_end, fwd_cap)
+#define FZB_K2UM(SWL, TF) FZB_LAUNCH((k2u_dp_unicode_multi<SWL, TF>), dim3(grid), dim3(128), 0, st, c.bytes, EndsAny{c.ends, c.ends_u64}, first, index_offset, list, n_list_ptr, nd, out, capacity, scratch, only_from, counters, back_end, fwd_cap)
 #define FZB_K2UM_ET(SWL) do { if (tform) FZB_K2UM(SWL, true); else FZB_K2UM(SWL, false); } while (0)
     switch (sw_lanes) {
         case 64: FZB_K2UM_ET(64); break;

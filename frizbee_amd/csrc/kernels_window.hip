@@ -759,7 +759,7 @@ static void launch_window_pfl(const CorpusDev& c, u64 first, const u32* surv_idx
     const size_t lds = use_cache ? (size_t)nd.rows * 256 * 8 : 0;
     const ManyScratch none{nullptr, nullptr};
     if (decide) {  // ASCII typo algorithms only (the unicode path keeps the full form)
-#define FZB_K2A_D(ALG) hipLaunchKernelGGL((k2a_window<PFL, ALG, true>), dim3(grid), dim3(256), lds, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, use_cache, *decide, 0u, none)
+#define FZB_K2A_D(ALG) FZB_LAUNCH((k2a_window<PFL, ALG, true>), dim3(grid), dim3(256), lds, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, use_cache, *decide, 0u, none)
         if (alg == ALG_ASCII_1) FZB_K2A_D(ALG_ASCII_1);
         else if (alg == ALG_ASCII_2) FZB_K2A_D(ALG_ASCII_2);
         else FZB_K2A_D(ALG_ASCII_N);
@@ -772,7 +772,7 @@ static void launch_window_pfl(const CorpusDev& c, u64 first, const u32* surv_idx
         const u32 ntiles_max = (max_items + FZB_TILE - 1) / FZB_TILE;
         (void)hipMemsetAsync(tile_counts2, 0, (size_t)ntiles_max * 4, st);
         const size_t dyn = (size_t)40 * 1024;
-#define FZB_K2A_P(ALG) hipLaunchKernelGGL((k2a_window_pre<PFL, ALG>), dim3(std::max<u32>(1u, std::min<u32>(ntiles_max * 4u, (u32)grid * 8u))), dim3(256), dyn, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, (u32)(dyn / 8 / (size_t)std::max(nd.rows, 1)))
+#define FZB_K2A_P(ALG) FZB_LAUNCH((k2a_window_pre<PFL, ALG>), dim3(std::max<u32>(1u, std::min<u32>(ntiles_max * 4u, (u32)grid * 8u))), dim3(256), dyn, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, (u32)(dyn / 8 / (size_t)std::max(nd.rows, 1)))
         switch (alg) {
             case ALG_ASCII_1: FZB_K2A_P(ALG_ASCII_1); break;
             case ALG_ASCII_2: FZB_K2A_P(ALG_ASCII_2); break;
@@ -784,7 +784,7 @@ static void launch_window_pfl(const CorpusDev& c, u64 first, const u32* surv_idx
 #undef FZB_K2A_P
         return;
     }
-#define FZB_K2A(ALG) hipLaunchKernelGGL((k2a_window<PFL, ALG>), dim3(grid), dim3(256), lds, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, use_cache, RejectOut{}, 0u, none)
+#define FZB_K2A(ALG) FZB_LAUNCH((k2a_window<PFL, ALG>), dim3(grid), dim3(256), lds, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, use_cache, RejectOut{}, 0u, none)
     switch (alg) {
         case ALG_ASCII_1: FZB_K2A(ALG_ASCII_1); break;
         case ALG_ASCII_2: FZB_K2A(ALG_ASCII_2); break;
@@ -823,7 +823,7 @@ static void launch_window_long_pfl(const CorpusDev& c, u64 first, const u32* sur
         many.nmask = (u64*)scratch;  // 8-byte entries first (alignment), then the 4-byte ones
         many.idx = (u32*)((u8*)scratch + (size_t)(k + 1) * (size_t)grid * 256 * sizeof(u64));
     }
-#define FZB_K2A_L(ALG) hipLaunchKernelGGL((k2a_window<PFL, ALG, false, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, 0, RejectOut{}, (u32)nd.min_haystack_len, many)
+#define FZB_K2A_L(ALG) FZB_LAUNCH((k2a_window<PFL, ALG, false, NeedleLongDev>), dim3(grid), dim3(256), 0, st, c.bytes, c.ends, c.ends_u64, first, surv_idx, n_surv_ptr, nd, win, bitmap2, tile_counts2, 0, RejectOut{}, (u32)nd.min_haystack_len, many)
     switch (alg) {
         case ALG_ASCII_0: FZB_K2A_L(ALG_ASCII_0); break;
         case ALG_ASCII_1: FZB_K2A_L(ALG_ASCII_1); break;

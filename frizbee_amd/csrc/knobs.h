@@ -11,6 +11,7 @@ struct FzbKnobs {
     bool typo_exact_window = false;  // FZB_TYPO_EXACT_WINDOW=1 no typo fast path: every survivor of a typo query re-decided at the exact lane width (nothing rests on DESIGN.md "Typo configurations")
     bool no_filter_view = false;     // FZB_FILTER_VIEW=0       no interleaved filter view (not built at upload - saves a second copy of the bytes in HBM -, not used by the filter)
     bool no_signature = false;       // FZB_NO_SIGNATURE=1      no letter signatures (not built with the corpus - saves 4 bytes per haystack in HBM -, not used by the filter: k1_dfa reads every row instead of k1_dfa_sig)
+    int debug_cus = 0;               // FZB_DEBUG_CUS=n         behave as on a device of n compute units (0: the device's own): every grid, the scratch sized by a grid and the thresholds written in CUs follow fzb_effective_cus(); while set, each launch's grid is recorded (fzb_debug_launch_grids)
     bool verify_promises = true;     // FZB_VERIFY_PROMISES=0   fzb_corpus_set_uniform_len / _set_max_len on BORROWED memory accepted without the device pass over the end offsets
     // --- force the form that serves inputs outside the fast form's preconditions ---
     bool no_lcs_dfa = false;         // FZB_NO_LCS_DFA=1        typo filter: the bit-vector kernel k1_filter (needles whose LCS automaton has more than 226 states) instead of the automaton in k1_dfa
@@ -32,3 +33,21 @@ struct FzbKnobs {
 };
 
 const FzbKnobs& fzb_knobs();
+
+// The ONE place the library learns how many compute units it runs on: the current device's own count unless FZB_DEBUG_CUS overrides it.
+// Every grid (and what is sized by one) derives from this number; nothing else reads the device's count.
+int fzb_effective_cus(int* out);  // 0, or the hipError_t of the device query
+// min(want, effective CUs * per_cu), at least 1: the grid of a grid-stride pass over `want` units of work
+unsigned fzb_grid_cap(uint64_t want, unsigned per_cu);
+
+// Every kernel launch of the library goes through FZB_LAUNCH: hipLaunchKernelGGL, and - only while FZB_DEBUG_CUS is set - a record of the
+// kernel's name and grid, so that tests can prove how many trips a grid-stride loop took (fzb_debug_launch_grids).
+// (a plain bool: written by fzb_debug_reload_knobs() alone, which the tests call between queries, never while a launch is in flight)
+extern bool g_fzb_record_grids;
+void fzb_record_grid(const char* kernel, unsigned grid);
+#define FZB_LAUNCH(kernel, grid, ...)                                  \
+    do {                                                               \
+        const dim3 fzb_grid_ = (grid);                                 \
+        if (g_fzb_record_grids) fzb_record_grid(#kernel, fzb_grid_.x); \
+        hipLaunchKernelGGL(kernel, fzb_grid_, __VA_ARGS__);            \
+    } while (0)

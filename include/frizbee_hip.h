@@ -724,6 +724,14 @@ void fzb_debug_set_items_dfa_min(uint32_t n);
  * read again.  Matchers created before the call keep what was decided when they were created. */
 void fzb_debug_reload_knobs(void);
 
+/* test hook: the launches recorded while the environment switch FZB_DEBUG_CUS=n is set ("behave as on a device of n compute units": every grid,
+ * the scratch sized by a grid and the thresholds written in compute units follow n; matchers and corpora created after
+ * fzb_debug_reload_knobs() see it).  One text line per kernel launched since the record was last cleared, "name min_grid max_grid launches\n",
+ * NUL-terminated, sorted by name; *out_len = the text's length without the NUL (cap == 0: only the length).  FZB_ERR_CAPACITY when cap is
+ * less than *out_len + 1.  clear != 0 empties the record after a successful copy; fzb_debug_reload_knobs() empties it too.  Nothing is
+ * recorded while the switch is unset. */
+int fzb_debug_launch_grids(char* out, size_t cap, size_t* out_len, int clear);
+
 /* test hook: device allocations (hipMalloc) this process's library has made so far - how a test sees that a re-query allocates nothing.
  * Page-locked host result lists are not counted. */
 int fzb_debug_device_allocs(uint64_t* out);
