@@ -95,6 +95,10 @@ struct CorpusDev {
     // LETTER SIGNATURES (sig_filter.h) of a list whose haystacks all fit 32 bytes (the lists k1_dfa serves): sig[i] = which letters / byte
     // classes occur in haystack i; nullptr = none.  A 0-typo ASCII query reads these 4 bytes per haystack and the bytes of the rows that can match only.
     const u32* sig;
+    // The signatures a second time, as BIT-PLANES (sig_filter.h: [tile][bit][16 x u64], zero at and beyond n; another 4 bytes per haystack):
+    // what k1_dfa_sig reads when it lists its survivors over a tile-aligned range - the planes of the needle's letters only.  nullptr = none
+    // (no signatures, or no room for the planes: the filter reads `sig`).
+    const u64* sig_planes;
 };
 
 struct fzb_match_rec {  // == fzb_match; `_pad` carries the valid flag between kernels (0 in final output)
@@ -219,6 +223,7 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
                        int cdfa_K = 0, int cdfa_G = 0, u32 needle_sig = 0, int sig_ok = 0,  // sig_ok: the needle is eligible for the signature form (sig_filter.h)
                        const SegList* seg = nullptr);  // seg (only where fzb_filter_sig_applies): grid = seg->nseg, the kernel also lists its survivors
 bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int sig_ok);  // fzb_launch_filter takes k1_dfa_sig
+void fzb_launch_sig_planes(const u32* sig, u64 n, u64 t0, u64* planes, int grid, hipStream_t st);  // the bit-planes of the tiles from t0 on, out of sig[0, n)
 void fzb_launch_scan_rejects(const u32* tile_rejects, u32 ntiles, const u32* reject_count, u32* rej_prefix, hipStream_t st);
 void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st);  // the 16-word counter block: [0] = n0, the rest 0
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,

@@ -186,6 +186,7 @@ FzbKnobs parse_knobs() {
     k.no_dp_classes = set("FZB_NO_DP_CLASSES");
     k.no_fused_classify = set("FZB_NO_FUSED_CLASSIFY");
     k.no_seg_list = on("FZB_NO_SEG_LIST");
+    k.no_sig_planes = on("FZB_NO_SIG_PLANES");
     k.no_items_dfa = on("FZB_NO_ITEMS_DFA");
     k.no_dp_cfm = set("FZB_NO_DP_CFM");
     k.no_dp_cfu = set("FZB_NO_DP_CFU");
@@ -1075,6 +1076,7 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_bytes) (void)hipFree(c->own_bytes);
     if (c->own_ends) (void)hipFree(c->own_ends);
     if (c->own_sig) (void)hipFree(c->own_sig);
+    if (c->own_planes) (void)hipFree(c->own_planes);
     fzb_column_release(c->bias);
     fzb_column_release(c->tags);
     if (c->pair_stage) (void)hipFree(c->pair_stage);

@@ -66,6 +66,8 @@ struct fzb_corpus {
     u64 view_cap_units = 0;
     void* own_sig = nullptr; // the letter signatures (CorpusDev::sig; also of a borrowed corpus: the library's own array), room for sig_cap_items haystacks
     u64 sig_cap_items = 0;
+    void* own_planes = nullptr;  // the signatures' bit-planes (CorpusDev::sig_planes), room for planes_cap_tiles tiles of 4 KB; follows own_sig
+    u64 planes_cap_tiles = 0;
     int sig_device = -1;     // a borrowed corpus: the device the signatures were built on (where its bytes live)
     // the two columns (ItemColumn above) and what is specific to each:
     // the score bias (fzb_corpus_set_bias / _update_bias, score_bias.h) is live while the queries add it - from set / update to clear,

@@ -272,14 +272,195 @@ __device__ __forceinline__ u32 dfa_chain16(u32 st, const uint4& q, const u8* dfa
     }
     return st;
 }
+// Listing one tile from its 32 decision words in LDS (SEG): tile count, the bitmap words (write_words: a gathered tile's - a dense tile's
+// were written by dfa_stream_tile) and the survivors' range-relative indices, ascending, at seg_out[seg_n ..].  Returns the tile's count.
+// Every wave scans the 32 word popcounts itself (lanes 32..63 mirror 0..31): no prefix array in LDS, no barrier for one.
+__device__ __forceinline__ u32 seg_list_tile(const u32* s_bits, u32 t, u32 tile, bool write_words, u64* __restrict__ bitmap, u32* __restrict__ tile_counts, u32* __restrict__ seg_out, u32 seg_n) {
+    const u32 l32 = t & 31u;
+    const u32 wl = s_bits[l32];
+    const u32 c = (u32)__popc(wl);
+    // (inclusive scan of the 32 counts: four row_shr steps inside each row of 16 lanes - lanes without a source add 0 -, then row 0's sum
+    // into row 1: some ten VALU instructions instead of five dependent cross-lane reads through LDS)
+    u32 incl = c;
+    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
+    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
+    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
+    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
+    incl += (l32 & 16u) ? (u32)__builtin_amdgcn_readlane((int)incl, 15) : 0u;
+    const u32 excl = incl - c, total = (u32)__builtin_amdgcn_readlane((int)incl, 31);
+    if (t == 0) tile_counts[tile] = total;
+    if (write_words && t < FZB_TILE / 64) bitmap[(size_t)tile * (FZB_TILE / 64) + t] = (u64)s_bits[2 * t] | ((u64)s_bits[2 * t + 1] << 32);
+    if (total) {  // workgroup-uniform
+#pragma unroll
+        for (int p = 0; p < FZB_TILE / 256; p++) {
+            const u32 pos = (u32)(p * 256) + t, w = pos >> 5;  // (one of two words per wave)
+            const u32 word = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)wl), before = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)excl);
+            if ((word >> (pos & 31)) & 1) seg_out[seg_n + seg_rank(before, word, pos & 31)] = tile * FZB_TILE + pos;
+        }
+    }
+    return total;
+}
+
+// The PLANE form of k1_dfa_sig<.., SEG> (sig_filter.h, "bit-planes"; `first` a multiple of the tile): the workgroup's run in batches of at
+// most FZB_SIG_BATCH_TILES tiles, and per batch TWO dependent round trips instead of two per tile -
+//   1. thread (tile, word) ANDs the plane words of the needle's letters (nsig's set bits: uniform) - the batch's candidates, 128 B per
+//      tile, in LDS; nothing of a signature stays in registers;
+//   2. one popcount scan (a tile = a row of 16 lanes) gives every tile its count and every candidate of a tile within gather_max its slot
+//      in ONE queue of batch-relative positions; tiles beyond it stream as in the u32 form;
+//   3. the queue is gathered two rows per thread and round of 512: all row loads first, then the two chains interleaved; decisions by LDS
+//      atomic-or into the batch's decision words;
+//   4. the tiles are listed one by one from LDS, exactly as in the u32 form (seg_list_tile).
+// LDS behind the table: candidate words [B][16] u64, decision words [B][32], tile counts [B], queue [B * gather_max] u16 - 8 224 B for B = 8.
+template <typename ET>
+__device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u64* __restrict__ planes, u32 nsig, u64 first, u32 count, u32 rows,
+                                               u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts, u32 ulen, u32 gather_max, const SegList& seg, u8* dfa, const u8* __restrict__ dfa_g) {
+    constexpr u32 B = FZB_SIG_BATCH_TILES;
+    static_assert(B * 16 <= 256 && B * 32 <= 256 && B * FZB_TILE <= 65536, "a batch's words are one per thread, its positions fit the queue's u16");
+    u8* const behind = dfa + FZB_DFA_LDS_BYTES(rows);
+    u64* const s_cand = (u64*)behind;                          // (the table's rows are multiples of 32 bytes)
+    u32* const s_dec = (u32*)(behind + 128 * B);
+    u32* const s_tq = (u32*)(behind + 256 * B);                // candidates per tile of the batch
+    u16* const queue = (u16*)(behind + 256 * B + 4 * B);
+    const u32 tid = threadIdx.x;
+    const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
+    const u64 tile0 = first / FZB_TILE;
+    u32 t_begin, t_end, seg_n = 0;
+    seg_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, t_begin, t_end);
+    u32* const seg_out = seg.list + (size_t)blockIdx.x * seg.stride;
+    const u32 j = tid >> 4, w = tid & 15u;  // my (tile of the batch, word)
+    // 1. a batch's candidate words.  The plane words are requested four at a time and only then AND-ed (nsig is uniform: scalar branches),
+    // so that a needle of up to four letters is ONE round trip - as a plain loop every load waited for the one before it.
+    auto load_cand = [&](u32 tb, u32 nb) -> u64 {
+        if (tid >= nb * 16) return 0;
+        u64 cand = sig_plane_valid(tb + j, w, count);
+        const u64* pl = planes + sig_plane_index(tile0 + tb + j, 0, w);
+        u32 m = nsig;
+        while (m) {
+            u64 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                v[q] = ~0ull;
+                if (m) {
+                    v[q] = pl[(u32)__builtin_ctz(m) * FZB_SIG_PLANE_WORDS];
+                    m &= m - 1u;
+                }
+            }
+            cand &= (v[0] & v[1]) & (v[2] & v[3]);
+        }
+        return cand;
+    };
+    // (the first batch's words are requested BEFORE the table is copied into LDS: both arrive in one round trip)
+    u64 cand = t_begin < t_end ? load_cand(t_begin, min(B, t_end - t_begin)) : 0;
+    dfa_load_lds(dfa, dfa_g, (int)rows);
+    for (u32 tb = t_begin; tb < t_end; tb += B) {
+        const u32 nb = min(B, t_end - tb);
+        if (tb != t_begin) cand = load_cand(tb, nb);
+        if (tid < B * 32) s_dec[tid] = 0;
+        // 2. counts and slots: inclusive scan inside each row of 16 lanes = one tile
+        const u32 c = (u32)__popcll(cand);
+        u32 incl = c;
+        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
+        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
+        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
+        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
+        if (tid < B * 16) {
+            s_cand[tid] = cand;
+            if (w == 15) s_tq[j] = incl;
+        }
+        __syncthreads();
+        u32 qbase = 0, QT = 0, dense = 0;  // my tile's first slot; the queue's length and the tiles that stream (workgroup-uniform)
+#pragma unroll
+        for (u32 k = 0; k < B; k++) {
+            const u32 q = s_tq[k];
+            if (q > gather_max) dense |= 1u << k;
+            else {
+                if (k < j) qbase += q;
+                QT += q;
+            }
+        }
+        if (tid < nb * 16 && !((dense >> j) & 1)) {
+            u32 slot = qbase + incl - c;
+            for (u64 m = cand; m; m &= m - 1) queue[slot++] = (u16)(j * FZB_TILE + w * 64 + (u32)__builtin_ctzll(m));
+        }
+        // 3a. dense tiles: k1_dfa's streaming body, ballots into the tile's decision words too
+        for (u32 d = dense; d; d &= d - 1) {
+            const u32 k = (u32)__builtin_ctz(d);
+            (void)dfa_stream_tile<ET, true>(bytes, ends, first, count, tb + k, (int)tid, ulen, min_len, acc_lo, dfa, bitmap, s_dec + 32 * k);
+        }
+        __syncthreads();
+        // 3b. the queue, two rows per thread and round
+        for (u32 e0 = 0; e0 < QT; e0 += 512) {
+            const bool two = e0 + 256 < QT;  // workgroup-uniform
+            u32 pos[2] = {0, 0};
+            bool has[2];
+            uint4 a[2], b[2];
+            u32 L[2];
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const u32 e = e0 + (u32)r * 256 + tid;
+                has[r] = e < QT && (r == 0 || two);
+                a[r] = make_uint4(0, 0, 0, 0);
+                b[r] = make_uint4(0, 0, 0, 0);
+                L[r] = 0;
+                if (has[r]) {
+                    pos[r] = queue[e];
+                    u64 hs;
+                    haystack_span_u(ends, ulen, first + (u64)tb * FZB_TILE + pos[r], hs, L[r]);
+                    const uint4* vp = (const uint4*)(bytes + hs);
+                    if (L[r] > 0) a[r] = vp[0];
+                    if (L[r] > 16) b[r] = vp[1];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 2; r++) {  // (a zero byte matches no row of an eligible needle: an absent row stays in state 0)
+                if (L[r] < 16) a[r] = sig_mask_vec(a[r], L[r]);
+                if (L[r] < 32) b[r] = sig_mask_vec(b[r], L[r] > 16 ? L[r] - 16 : 0u);
+            }
+            u32 st[2] = {0, 0};
+            if (two) {
+                const u32 w0[8] = {a[0].x, a[0].y, a[0].z, a[0].w, b[0].x, b[0].y, b[0].z, b[0].w}, w1[8] = {a[1].x, a[1].y, a[1].z, a[1].w, b[1].x, b[1].y, b[1].z, b[1].w};
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    st[0] = dfa_step<0>(st[0], w0[k], dfa); st[1] = dfa_step<0>(st[1], w1[k], dfa);
+                    st[0] = dfa_step<1>(st[0], w0[k], dfa); st[1] = dfa_step<1>(st[1], w1[k], dfa);
+                    st[0] = dfa_step<2>(st[0], w0[k], dfa); st[1] = dfa_step<2>(st[1], w1[k], dfa);
+                    st[0] = dfa_step<3>(st[0], w0[k], dfa); st[1] = dfa_step<3>(st[1], w1[k], dfa);
+                }
+            } else {
+                st[0] = dfa_chain16(0u, a[0], dfa);
+                st[0] = dfa_chain16(st[0], b[0], dfa);
+            }
+#pragma unroll
+            for (int r = 0; r < 2; r++)
+                if (has[r] && L[r] >= min_len && st[r] >= acc_lo) atomicOr(&s_dec[pos[r] >> 5], 1u << (pos[r] & 31));
+        }
+        __syncthreads();
+        // 4. the tiles leave one by one, from LDS
+        for (u32 k = 0; k < nb; k++) {
+            u32 t = tid;
+            asm volatile("" : "+v"(t));  // (nothing of the listing is hoisted out of the loops: see the u32 form)
+            seg_n += seg_list_tile(s_dec + 32 * k, t, tb + k, !((dense >> k) & 1), bitmap, tile_counts, seg_out, seg_n);
+        }
+        __syncthreads();  // the next batch clears the decision words
+    }
+    if (tid == 0) seg.counts[blockIdx.x] = seg_n;
+}
+
 // (8 waves per SIMD like k1_dfa, whose grid - 8 workgroups per CU - it shares: without the bound the kernel takes 68 VGPRs and a CU holds 7)
-template <typename ET, bool SEG>
+// PLANES (only with SEG): `sig` points at the corpus' bit-planes (u64 words) and sig_planes_run above is the kernel's body.
+template <typename ET, bool SEG, bool PLANES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k1_dfa_sig(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u32* __restrict__ sig, u32 nsig, u64 first, u32 count,
                                                   const u8* __restrict__ dfa_g, int rows, u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts,
                                                   u32* __restrict__ reset_counters, u32 ulen, u32 gather_max, SegList seg) {
     if (blockIdx.x == 0 && threadIdx.x < 16) reset_counters[threadIdx.x] = 0;
     // LDS behind the table (which stays the first object, at address 0): tile count, queue length, the tile's 1024 decision bits, the queue
     extern __shared__ __attribute__((aligned(16))) u8 dfa[];
+    if constexpr (PLANES) {
+        static_assert(SEG, "the plane form lists its survivors");
+        dfa_require_lds_base0(dfa);
+        sig_planes_run<ET>(bytes, ends, (const u64*)sig, nsig, first, count, (u32)rows, min_len, acc_lo, bitmap, tile_counts, ulen, gather_max, seg, dfa, dfa_g);
+        return;
+    }
     u32& s_cnt = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows));
     u32& s_q = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows) + 4);
     u32* const s_bits = (u32*)(dfa + FZB_DFA_LDS_BYTES(rows) + 16);
@@ -366,35 +547,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (!SEG) {
             if (tid == 0) tile_counts[tile] = s_cnt;
         } else {
-            // every wave scans the 32 word popcounts itself (lanes 32..63 mirror 0..31): no prefix array in LDS, no barrier for one.
             // (The thread index goes through an empty asm and the cross-lane reads are ds_bpermute with addresses made from it: as loop
             // invariants the four word indices, the bit masks and the bitmap word's address are hoisted out of the tile loop - a dozen
             // registers live across the dense tile's body, which the kernel's 64-VGPR bound turns into scratch.)
             u32 t = (u32)tid;
             asm volatile("" : "+v"(t));
-            const u32 l32 = t & 31u;
-            const u32 wl = s_bits[l32];
-            const u32 c = (u32)__popc(wl);
-            // (inclusive scan of the 32 counts: four row_shr steps inside each row of 16 lanes - lanes without a source add 0 -, then row 0's sum
-            // into row 1: some ten VALU instructions instead of five dependent cross-lane reads through LDS)
-            u32 incl = c;
-            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
-            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
-            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
-            incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
-            incl += (l32 & 16u) ? (u32)__builtin_amdgcn_readlane((int)incl, 15) : 0u;
-            const u32 excl = incl - c, total = (u32)__builtin_amdgcn_readlane((int)incl, 31);
-            if (tid == 0) tile_counts[tile] = total;
-            if (Q <= gather_max && t < FZB_TILE / 64) bitmap[(size_t)tile * (FZB_TILE / 64) + t] = (u64)s_bits[2 * t] | ((u64)s_bits[2 * t + 1] << 32);  // (a dense tile's words are written)
-            if (total) {  // workgroup-uniform
-#pragma unroll
-                for (int p = 0; p < FZB_TILE / 256; p++) {
-                    const u32 pos = (u32)(p * 256) + t, w = pos >> 5;  // (one of two words per wave)
-                    const u32 word = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)wl), before = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)excl);
-                    if ((word >> (pos & 31)) & 1) seg_out[seg_n + seg_rank(before, word, pos & 31)] = tile * FZB_TILE + pos;
-                }
-            }
-            seg_n += total;
+            seg_n += seg_list_tile(s_bits, t, tile, Q <= gather_max, bitmap, tile_counts, seg_out, seg_n);
             __syncthreads();  // the next tile clears the decision words
         }
     }
@@ -1114,6 +1272,38 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The signatures' BIT-PLANES (sig_filter.h) of the tiles [t0, tiles of n), built from the u32 signatures fzb_sig_sync has just written:
+// a workgroup per tile and trip reads the tile's 4 KB coalesced (zero at and beyond n), every wave turns 64 rows into 32 ballots - lane b
+// keeps plane b's word -, the tile's 512 words meet in LDS and leave as one coalesced 4 KB store.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sig_planes_build(const u32* __restrict__ sig, u64 n, u64 t0, u64* __restrict__ planes) {
+    __shared__ u64 s_pl[32 * FZB_SIG_PLANE_WORDS];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 tiles = sig_plane_tiles(n);
+    for (u64 tile = t0 + blockIdx.x; tile < tiles; tile += gridDim.x) {
+#pragma unroll
+        for (u32 p = 0; p < FZB_TILE / 256; p++) {
+            const u64 i = tile * FZB_TILE + p * 256 + tid;
+            const u32 s = i < n ? sig[i] : 0u;
+            u64 mine = 0;
+            for (u32 b = 0; b < 32; b++) {
+                const u64 bal = __ballot((s >> b) & 1u);
+                if (lane == b) mine = bal;
+            }
+            if (lane < 32) s_pl[lane * FZB_SIG_PLANE_WORDS + p * 4 + wave] = mine;  // (rows p * 256 + wave * 64 ..: word p * 4 + wave)
+        }
+        __syncthreads();
+        u64* out = planes + sig_plane_index(tile, 0, 0);
+        out[tid] = s_pl[tid];
+        out[tid + 256] = s_pl[tid + 256];
+        __syncthreads();
+    }
+}
+void fzb_launch_sig_planes(const u32* sig, u64 n, u64 t0, u64* planes, int grid, hipStream_t st) {
+    FZB_LAUNCH(k_sig_planes_build, dim3(std::max(1, grid)), dim3(256), 0, st, sig, n, t0, planes);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // host-side launch wrappers (called from host.hip)
 // ---------------------------------------------------------------------------------------------------
 bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int sig_ok) {
@@ -1134,12 +1324,18 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
         const size_t lds = (size_t)(rows + 1) * FZB_DFA_STRIDE + 16;  // table + the tile counter
         const bool shortc = c.max_len != 0 && c.max_len <= 32;  // every haystack fits the two pre-requested vectors
         if (fzb_filter_sig_applies(c, mode, needle_sig, sig_ok)) {  // an eligible needle over a list with signatures (host.hip decides eligibility)
-            const size_t lds_s = lds + 128 + 2 * FZB_TILE;  // + the tile's decision bits and the queue of passing rows
-#define FZB_K1S(ET, SEG, G, S) FZB_LAUNCH((k1_dfa_sig<ET, SEG>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE), S)
-            if (seg) {  // the filter lists its survivors: one workgroup per segment
-                if (c.ends_u64) FZB_K1S(u64, true, seg->nseg, *seg); else FZB_K1S(u32, true, seg->nseg, *seg);
+            const u32 gmax = std::min<u32>(FZB_SIG_GATHER_MAX, FZB_TILE);
+            // u32 form: + the tile's decision bits and the queue of passing rows; plane form: + a batch's tile counts, candidate words, decision bits and queue
+            const bool planes = seg && c.sig_planes && first % FZB_TILE == 0 && !fzb_knobs().no_sig_planes;
+            const size_t lds_s = planes ? FZB_DFA_LDS_BYTES(rows) + FZB_SIG_BATCH_TILES * (4 + 256 + 2 * (size_t)gmax) : lds + 128 + 2 * FZB_TILE;
+#define FZB_K1S(ET, SEG, PL, G, S) FZB_LAUNCH((k1_dfa_sig<ET, SEG, PL>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, PL ? (const u32*)c.sig_planes : c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, gmax, S)
+            if (planes) {  // ... from the corpus' bit-planes, a run's tiles in batches (an aligned range; FZB_NO_SIG_PLANES unset)
+                if (g_fzb_record_grids) fzb_record_grid("k1_dfa_sig_planes", seg->nseg);  // (the kernel's name does not say which form ran: a second record for the tests)
+                if (c.ends_u64) FZB_K1S(u64, true, true, seg->nseg, *seg); else FZB_K1S(u32, true, true, seg->nseg, *seg);
+            } else if (seg) {  // the filter lists its survivors: one workgroup per segment
+                if (c.ends_u64) FZB_K1S(u64, true, false, seg->nseg, *seg); else FZB_K1S(u32, true, false, seg->nseg, *seg);
             } else {
-                if (c.ends_u64) FZB_K1S(u64, false, grid, SegList{}); else FZB_K1S(u32, false, grid, SegList{});
+                if (c.ends_u64) FZB_K1S(u64, false, false, grid, SegList{}); else FZB_K1S(u32, false, false, grid, SegList{});
             }
 #undef FZB_K1S
             return;

@@ -19,7 +19,8 @@ struct FzbKnobs {
     bool no_dp_classes = false;      // FZB_NO_DP_CLASSES=1     ASCII scorer: per-wave choice of computed lanes (k2b_dp: scorings outside dp_cf.h) instead of classified scoring
     bool no_fused_classify = false;  // FZB_NO_FUSED_CLASSIFY=1 ragged ASCII lists: k_compact1 + k2w_classify as two launches (the form typo queries and item lists take) instead of k_compact1_classify
     bool no_seg_list = false;        // FZB_NO_SEG_LIST=1       short lists with signatures: filter -> k_compact1 -> scorer as three launches (the form sub-32-lane scorings, typo / unicode queries and item lists take) instead of the filter listing its survivors
-    bool no_items_dfa = false;       // FZB_NO_ITEMS_DFA=1      item lists of a candidate set (fzb_subset): the bit-vector thread-per-item filter k1_items (what the multi-pattern narrowing and every other filter mode take) instead of k1_items_dfa
+    bool no_sig_planes = false;      // FZB_NO_SIG_PLANES=1     the signature filter that lists its survivors reads the u32 signatures tile by tile (the form unaligned sub-ranges and corpora without room for the planes take) instead of the bit-planes in batches; the planes are still built
+    bool no_items_dfa = false;      // FZB_NO_ITEMS_DFA=1      item lists of a candidate set (fzb_subset): the bit-vector thread-per-item filter k1_items (what the multi-pattern narrowing and every other filter mode take) instead of k1_items_dfa
     bool no_dp_cfm = false;          // FZB_NO_DP_CFM=1         multi-chunk scorer in its first form (dp_body.h: scorings outside dp_cfm.h)
     bool no_dp_cfu = false;          // FZB_NO_DP_CFU=1         unicode scorer in its first form (scorings outside dp_unicode.h's biased form)
     int unicode_multi = -1;          // FZB_UNICODE_MULTI=0|1   unicode windows of 65..1024 bytes: never / always thread per haystack (k2u_dp_unicode_multi); default: by the queue's length, on the device

@@ -40,6 +40,40 @@ FZB_SIG_FN bool needle_sig_eligible(const uint8_t* needle, size_t n, int max_typ
     return true;
 }
 
+// The signatures a SECOND time, transposed into BIT-PLANES: one 64-bit word per (tile of 1024 haystacks, signature bit, 64 haystacks).
+// Bit i of word w of plane b of tile t = bit b of the signature of item 1024 t + 64 w + i, zero at and beyond the corpus' item count.
+// Tile-major: a (tile, bit) is one 128-byte line, a tile is 4 KB (the same 4 bytes per haystack as the u32 array).  A query ANDs the
+// planes of its needle's letters: 16 words per tile and letter are the tile's candidates, ready-made (k1_dfa_sig's plane form).
+#define FZB_SIG_PLANE_TILE 1024u
+#define FZB_SIG_PLANE_WORDS 16u  // 64-bit words per (tile, bit)
+FZB_SIG_FN uint64_t sig_plane_tiles(uint64_t n_items) { return (n_items + FZB_SIG_PLANE_TILE - 1) / FZB_SIG_PLANE_TILE; }
+FZB_SIG_FN uint64_t sig_plane_words(uint64_t n_items) { return sig_plane_tiles(n_items) * 32u * FZB_SIG_PLANE_WORDS; }
+FZB_SIG_FN uint64_t sig_plane_index(uint64_t tile, uint32_t bit, uint32_t word) { return (tile * 32u + bit) * FZB_SIG_PLANE_WORDS + word; }
+// valid bits of word w of tile t in a list (or range) of `count` items: the mask the filter applies, and what the build leaves set
+FZB_SIG_FN uint64_t sig_plane_valid(uint64_t tile, uint32_t word, uint64_t count) {
+    const uint64_t base = tile * FZB_SIG_PLANE_TILE + 64u * word;
+    return base >= count ? 0ull : count - base >= 64u ? ~0ull : (1ull << (count - base)) - 1ull;
+}
+// reference transposition (host tests; the device build is k_sig_planes_build): planes holds sig_plane_words(n) words
+FZB_SIG_FN void sig_planes_transpose_ref(const uint32_t* sig, uint64_t n, uint64_t* planes) {
+    const uint64_t words = sig_plane_words(n);
+    for (uint64_t k = 0; k < words; k++) planes[k] = 0;
+    for (uint64_t i = 0; i < n; i++)
+        for (uint32_t b = 0; b < 32; b++)
+            if ((sig[i] >> b) & 1u) planes[sig_plane_index(i / FZB_SIG_PLANE_TILE, b, (uint32_t)(i % FZB_SIG_PLANE_TILE) / 64u)] |= 1ull << (i % 64u);
+}
+// the candidates of word w of tile t for a needle: the AND of its letters' planes (nsig != 0); bit i set <=> sig_passes(sig[item], nsig)
+FZB_SIG_FN uint64_t sig_plane_candidates(const uint64_t* planes, uint64_t tile, uint32_t word, uint32_t nsig) {
+    uint64_t c = ~0ull;
+    for (uint32_t m = nsig; m; m &= m - 1u) c &= planes[sig_plane_index(tile, (uint32_t)__builtin_ctz(m), word)];
+    return c;
+}
+// Tiles of one batch of the plane form (a workgroup's run is taken in batches of at most this many tiles; one batch covers the run of 5
+// that 10 M haystacks give on 256 compute units)
+#ifndef FZB_SIG_BATCH_TILES
+#define FZB_SIG_BATCH_TILES 8u
+#endif
+
 // Tiles of k1_dfa_sig with more passing rows than this stream the whole tile (coalesced loads, four chains per thread) instead of
 // gathering the passing rows one chain per thread.
 #ifndef FZB_SIG_GATHER_MAX

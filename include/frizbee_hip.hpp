@@ -191,6 +191,13 @@ class Corpus {
         check(fzb_corpus_info(h_.get(), o));
         return Info{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11]};
     }
+    // the signatures' bit-planes of a list of short haystacks (fzb_corpus_signature_planes_info): device bytes, 0 without them
+    uint64_t signature_planes_bytes() const {
+        int built = 0;
+        uint64_t bytes = 0;
+        check(fzb_corpus_signature_planes_info(h_.get(), &built, &bytes));
+        return built ? bytes : 0;
+    }
     // A corpus that is edited (fzb_corpus_remove and friends): the other haystacks keep their order and are renumbered, as Vec::retain
     // would; only the indices - and a replace's new bytes - cross the link, nothing in front of the first touched haystack moves.
     void remove(const std::vector<uint32_t>& indices) { check(fzb_corpus_remove(h_.get(), indices.data(), indices.size())); }
