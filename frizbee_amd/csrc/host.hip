@@ -319,7 +319,7 @@ void fzb_sort_release(SortBuffers& s) {
 int fzb_scope_ensure(ScopeScratch& s, size_t count) {
     const size_t tiles = (count + SCOPE_TILE - 1) / SCOPE_TILE;
     int rc;
-    if ((rc = fzb_grow_dev(&s.recs, &s.recs_cap, count, 16)) || (rc = fzb_grow_dev(&s.bitmap, &s.bitmap_words, tiles * SCOPE_WORDS, 1)) || (rc = fzb_grow_dev(&s.tiles, &s.tiles_cap, tiles, 1)))
+    if ((rc = fzb_grow_dev(&s.recs, &s.recs_cap, count, 16)) || (rc = fzb_grow_dev(&s.bitmap, &s.bitmap_words, tiles * SCOPE_WORDS, 1)) || (rc = fzb_grow_dev(&s.tiles, &s.tiles_cap, tiles, 4)))
         return rc;
     return fzb_grow_dev(&s.words, &s.words_cap, 16);
 }
@@ -1172,7 +1172,7 @@ static int ensure_workspace(fzb_matcher* m, size_t count, hipStream_t st = nullp
     }
     free_workspace(w);
     const size_t cap = count + count / 8 + 4096;
-    const size_t ntiles = (cap + FZB_TILE - 1) / FZB_TILE + 2;
+    const size_t ntiles = ((cap + FZB_TILE - 1) / FZB_TILE + 5) & ~(size_t)3;  // (two spare, then a multiple of four entries: the compactions sum the counts as 16-byte vectors)
     HIPCHK(dev_alloc((void**)&w.bitmap, (cap / 64 + 17) * 8));
     HIPCHK(dev_alloc((void**)&w.tile_counts, ntiles * 4));
     HIPCHK(dev_alloc((void**)&w.surv_idx, cap * 4));
@@ -1649,7 +1649,7 @@ static int pipe_filter_stage(Pipe& p) {
         u32 grid = std::min<u32>(std::min<u32>((u32)p.cus * 8u, FZB_SEG_MAX), ntiles);
         if (g_debug_filter_grid > 0) grid = std::min<u32>(grid, (u32)g_debug_filter_grid);
         grid = std::max<u32>(grid, 1u);
-        const u32 stride = seg_tiles_per_run(ntiles, grid) * FZB_TILE;
+        const u32 stride = tc_tiles_per_run(ntiles, grid) * FZB_TILE;
         if ((size_t)ntiles * FZB_TILE > w.cap_items) return fail(FZB_ERR_INVALID, "internal: the survivor list does not hold the range rounded up to a tile");
         p.seg = SegList{w.surv_idx, w.seg_counts, grid, stride, &cnt_c[0]};
         p.segmented = true;
@@ -2559,7 +2559,7 @@ static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
     HIPCHK(dev_alloc((void**)&mm->counts, 64));
     HIPCHK(dev_alloc((void**)&mm->items, cap * 4));
     HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
-    HIPCHK(dev_alloc((void**)&mm->tile_counts, ((cap + FZB_TILE - 1) / FZB_TILE + 2) * 4));
+    HIPCHK(dev_alloc((void**)&mm->tile_counts, (((cap + FZB_TILE - 1) / FZB_TILE + 5) & ~(size_t)3) * 4));  // (as the workspace's: a multiple of four entries)
     mm->cap = cap;
     return FZB_OK;
 }

@@ -4,6 +4,7 @@
 
 #include "fzb_internal.h"
 #include "knobs.h"
+#include "tile_compact.h"
 
 #define FZB_WAVE 64
 

@@ -279,13 +279,9 @@ __device__ __forceinline__ u32 seg_list_tile(const u32* s_bits, u32 t, u32 tile,
     const u32 l32 = t & 31u;
     const u32 wl = s_bits[l32];
     const u32 c = (u32)__popc(wl);
-    // (inclusive scan of the 32 counts: four row_shr steps inside each row of 16 lanes - lanes without a source add 0 -, then row 0's sum
-    // into row 1: some ten VALU instructions instead of five dependent cross-lane reads through LDS)
-    u32 incl = c;
-    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
-    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
-    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
-    incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
+    // (inclusive scan of the 32 counts: inside each row of 16 lanes (tc_scan16), then row 0's sum into row 1: some ten VALU instructions
+    // instead of five dependent cross-lane reads through LDS)
+    u32 incl = tc_scan16(c);
     incl += (l32 & 16u) ? (u32)__builtin_amdgcn_readlane((int)incl, 15) : 0u;
     const u32 excl = incl - c, total = (u32)__builtin_amdgcn_readlane((int)incl, 31);
     if (t == 0) tile_counts[tile] = total;
@@ -295,7 +291,7 @@ __device__ __forceinline__ u32 seg_list_tile(const u32* s_bits, u32 t, u32 tile,
         for (int p = 0; p < FZB_TILE / 256; p++) {
             const u32 pos = (u32)(p * 256) + t, w = pos >> 5;  // (one of two words per wave)
             const u32 word = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)wl), before = (u32)__builtin_amdgcn_ds_bpermute((int)(w << 2), (int)excl);
-            if ((word >> (pos & 31)) & 1) seg_out[seg_n + seg_rank(before, word, pos & 31)] = tile * FZB_TILE + pos;
+            if ((word >> (pos & 31)) & 1) seg_out[tc_rank32(seg_n + before, word, pos & 31)] = tile * FZB_TILE + pos;
         }
     }
     return total;
@@ -325,7 +321,7 @@ __device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, con
     const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
     const u64 tile0 = first / FZB_TILE;
     u32 t_begin, t_end, seg_n = 0;
-    seg_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, t_begin, t_end);
+    tc_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, &t_begin, &t_end);
     u32* const seg_out = seg.list + (size_t)blockIdx.x * seg.stride;
     const u32 j = tid >> 4, w = tid & 15u;  // my (tile of the batch, word)
     // 1. a batch's candidate words.  The plane words are requested four at a time and only then AND-ed (nsig is uniform: scalar branches),
@@ -358,11 +354,7 @@ __device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, con
         if (tid < B * 32) s_dec[tid] = 0;
         // 2. counts and slots: inclusive scan inside each row of 16 lanes = one tile
         const u32 c = (u32)__popcll(cand);
-        u32 incl = c;
-        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);
-        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);
-        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);
-        incl += (u32)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);
+        const u32 incl = tc_scan16(c);
         if (tid < B * 16) {
             s_cand[tid] = cand;
             if (w == 15) s_tq[j] = incl;
@@ -486,7 +478,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     };
     // SEG: the workgroup's run of tiles and the survivors it has listed so far (workgroup-uniform)
     u32 t_begin = blockIdx.x, t_end = ntiles, seg_n = 0;
-    if (SEG) seg_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, t_begin, t_end);
+    if (SEG) tc_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, &t_begin, &t_end);
     u32* const seg_out = SEG ? seg.list + (size_t)blockIdx.x * seg.stride : nullptr;
     for (u32 tile = t_begin; tile < t_end; tile += SEG ? 1u : gridDim.x) {
         if (tid == 0) s_cnt = 0, s_q = 0;
@@ -953,71 +945,36 @@ __global__ __launch_bounds__(256) void k_compact2(const u64* __restrict__ bitmap
     __shared__ u32 red[4];
     __shared__ u32 pre[FZB_C2_BATCH];
     __shared__ u32 woff[FZB_C2_BATCH * (FZB_TILE / 64)];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 tid = threadIdx.x;
     const u32 n_items = *n_items_ptr;
     const u32 ntiles = (n_items + FZB_TILE - 1) / FZB_TILE;
-    const u32 T = (ntiles + gridDim.x - 1) / gridDim.x;
-    const u32 t0 = min(blockIdx.x * T, ntiles), t1 = min(t0 + T, ntiles);
-    // (16-byte loads, four in flight per thread: this sum is the kernel's critical path - up to ntiles counts per workgroup)
-    u32 part = 0;
-    {
-        const uint4* c4 = (const uint4*)counts;
-        const u32 n4 = t0 / 4;
-        u32 i = tid;
-        for (; i + 768 < n4; i += 1024) {
-            const uint4 a = c4[i], b = c4[i + 256], c = c4[i + 512], d = c4[i + 768];
-            part += (a.x + a.y + a.z + a.w) + (b.x + b.y + b.z + b.w) + (c.x + c.y + c.z + c.w) + (d.x + d.y + d.z + d.w);
-        }
-        for (; i < n4; i += 256) {
-            const uint4 a = c4[i];
-            part += a.x + a.y + a.z + a.w;
-        }
-        for (u32 k = 4 * n4 + tid; k < t0; k += 256) part += counts[k];
-    }
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    u32 base = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
+    u32 t0, t1;
+    tc_run(ntiles, tc_tiles_per_run(ntiles, gridDim.x), blockIdx.x, &t0, &t1);
+    u32 base = tc_prefix(counts, t0, red);
     const u32 nwords = (n_items + 63) / 64;
     for (u32 tb = t0; tb < t1; tb += FZB_C2_BATCH) {
         const u32 nt = min((u32)FZB_C2_BATCH, t1 - tb);
-        // exclusive scan of the batch's tile counts (nt <= 64: one wave)
-        if (wave == 0) {
-            const u32 c = (u32)lane < nt ? counts[tb + lane] : 0u;
-            u32 incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const u32 v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
-            }
-            if ((u32)lane < nt) pre[lane] = base + incl - c;
-            if (lane == 63) red[0] = incl;
-        }
+        const u32 c_tile = tid < nt ? counts[tb + tid] : 0u;
         // offset of every bitmap word inside its tile: 16-lane segmented scan of the popcounts
         const u32 w0 = tb * (FZB_TILE / 64), w1 = (tb + nt) * (FZB_TILE / 64);
         for (u32 wb0 = w0; wb0 < w1; wb0 += 256) {
             const u32 w = wb0 + tid;
             const u32 c = (w < w1 && w < nwords) ? (u32)__popcll(bitmap[w]) : 0u;
-            u32 incl = c;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const u32 v = __shfl_up(incl, off, 16);
-                if ((lane & 15) >= off) incl += v;
-            }
-            if (w < w1) woff[w - w0] = incl - c;
+            if (w < w1) woff[w - w0] = tc_scan16(c) - c;
         }
-        __syncthreads();
+        // exclusive scan of the batch's tile counts (its second barrier publishes woff too)
+        const u32 batch_total = tc_batch_scan<FZB_C2_BATCH>(c_tile, base, pre, red);
         const u32 j0 = tb * FZB_TILE, j1 = min((tb + nt) * FZB_TILE, n_items);
         for (u32 j = j0 + tid; j < j1; j += 256) {
             const u32 w = j >> 6;
             const u64 bits = bitmap[w];
             if (!((bits >> (j & 63)) & 1)) continue;
-            const u32 pos = pre[j / FZB_TILE - tb] + woff[w - w0] + (u32)__popcll(bits & (((u64)1 << (j & 63)) - 1));
+            const u32 pos = tc_rank64(pre[j / FZB_TILE - tb] + woff[w - w0], bits, j & 63);
             out_idx[pos] = in_idx ? in_idx[j] : j;
             *(uint2*)(out_win + 2 * (size_t)pos) = *(const uint2*)(in_win + 2 * (size_t)j);
         }
-        base += red[0];
-        __syncthreads();
+        base += batch_total;
+        __syncthreads();  // the next batch overwrites woff
     }
     if (blockIdx.x == gridDim.x - 1 && tid == 0) *total_out = base;
 }
@@ -1033,56 +990,39 @@ __global__ __launch_bounds__(256) void k1_items(const u8* __restrict__ bytes, co
                                                 const u32* __restrict__ n_items_ptr, const u64* __restrict__ Tg, int rows, int need, u32 min_len,
                                                 u64* __restrict__ bitmap, u32* __restrict__ tile_counts) {
     __shared__ TW T[256];
-    __shared__ u32 s_cnt;
-    const int tid = threadIdx.x;
-    T[tid] = (TW)Tg[tid];
+    T[threadIdx.x] = (TW)Tg[threadIdx.x];  // (published by the flag pass' first barrier)
     const u32 count = *n_items_ptr;
-    const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
-    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        u32 cnt = 0;
-#pragma unroll 1
-        for (int p = 0; p < FZB_TILE / 256; p++) {
-            const u32 j = tile * FZB_TILE + p * 256 + tid;
-            bool matched = false;
-            if (j < count) {
-                u64 s;
-                u32 L;
-                haystack_span(ends, first + items[j], s, L);
-                if (L >= min_len) {
-                    const uint4* vp = (const uint4*)(bytes + s);
-                    TW st = (MODE == 1) ? (TW)1 : (TW)~(TW)0;
-                    const u32 nvec = (L + 15) >> 4;
-                    for (u32 v = 0; v < nvec; v++) {
-                        const uint4 q = vp[v];
-                        const u32 rem = L - 16 * v;
-                        filter_word<TW, MODE>(st, q.x, rem, T);
-                        if (rem > 4) filter_word<TW, MODE>(st, q.y, rem - 4, T);
-                        if (rem > 8) filter_word<TW, MODE>(st, q.z, rem - 8, T);
-                        if (rem > 12) filter_word<TW, MODE>(st, q.w, rem - 12, T);
-                    }
-                    if (MODE == 1) {
-                        matched = (st >> rows) & 1;
-                    } else {
-                        const TW low = rows >= (int)(8 * sizeof(TW)) ? (TW)~(TW)0 : (((TW)1 << rows) - 1);
-                        const TW z = ~st & low;
-                        const int lcs = sizeof(TW) == 8 ? __popcll((u64)z) : __popc((u32)z);
-                        matched = lcs >= need;
-                    }
+    tc_flag_pass<true>(count, bitmap, tile_counts, [&](u32 tile, u32 slot) {
+        const u32 j = tile * FZB_TILE + slot;
+        bool matched = false;
+        if (j < count) {
+            u64 s;
+            u32 L;
+            haystack_span(ends, first + items[j], s, L);
+            if (L >= min_len) {
+                const uint4* vp = (const uint4*)(bytes + s);
+                TW st = (MODE == 1) ? (TW)1 : (TW)~(TW)0;
+                const u32 nvec = (L + 15) >> 4;
+                for (u32 v = 0; v < nvec; v++) {
+                    const uint4 q = vp[v];
+                    const u32 rem = L - 16 * v;
+                    filter_word<TW, MODE>(st, q.x, rem, T);
+                    if (rem > 4) filter_word<TW, MODE>(st, q.y, rem - 4, T);
+                    if (rem > 8) filter_word<TW, MODE>(st, q.z, rem - 8, T);
+                    if (rem > 12) filter_word<TW, MODE>(st, q.w, rem - 12, T);
+                }
+                if (MODE == 1) {
+                    matched = (st >> rows) & 1;
+                } else {
+                    const TW low = rows >= (int)(8 * sizeof(TW)) ? (TW)~(TW)0 : (((TW)1 << rows) - 1);
+                    const TW z = ~st & low;
+                    const int lcs = sizeof(TW) == 8 ? __popcll((u64)z) : __popc((u32)z);
+                    matched = lcs >= need;
                 }
             }
-            const u64 b = __ballot(matched);
-            if (lane_id() == 0) {
-                bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
-                cnt += __popcll(b);
-            }
         }
-        if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
-        __syncthreads();
-        if (tid == 0) tile_counts[tile] = s_cnt;
-        __syncthreads();
-    }
+        return matched;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -142,35 +142,18 @@ template <typename ET, typename ND = NeedleDev>
 __global__ __launch_bounds__(256) void k_literal_filter(const u8* __restrict__ bytes, const ET* __restrict__ ends, u64 first, u32 count_host, const u32* __restrict__ items,
                                                         const u32* __restrict__ n_items_ptr, const ND nd, int mode, u64* __restrict__ bitmap,
                                                         u32* __restrict__ tile_counts) {
-    __shared__ u32 s_cnt;
     const u32 count = items ? *n_items_ptr : count_host;
-    const u32 ntiles = (count + FZB_TILE - 1) / FZB_TILE;
-    const int tid = threadIdx.x;
-    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        u32 cnt = 0;
-#pragma unroll 1
-        for (int p = 0; p < FZB_TILE / 256; p++) {
-            const u32 j = tile * FZB_TILE + p * 256 + tid;
-            bool keep = false;
-            if (j < count) {
-                u64 s;
-                u32 L;
-                haystack_span(ends, first + (items ? items[j] : j), s, L);
-                keep = lit_accepts(nd, mode, bytes + s, L);
-            }
-            const u64 b = __ballot(keep);
-            if (lane_id() == 0) {
-                bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
-                cnt += __popcll(b);
-            }
+    tc_flag_pass<true>(count, bitmap, tile_counts, [&](u32 tile, u32 slot) {
+        const u32 j = tile * FZB_TILE + slot;
+        bool keep = false;
+        if (j < count) {
+            u64 s;
+            u32 L;
+            haystack_span(ends, first + (items ? items[j] : j), s, L);
+            keep = lit_accepts(nd, mode, bytes + s, L);
         }
-        if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
-        __syncthreads();
-        if (tid == 0) tile_counts[tile] = s_cnt;
-        __syncthreads();
-    }
+        return keep;
+    });
 }
 
 // pass 2: one thread per survivor (items = local haystack indices), record j at out[j].  With tpos != nullptr also the matched

@@ -56,85 +56,21 @@ __global__ __launch_bounds__(256) void k_join_add(fzb_match_rec* __restrict__ hi
     }
 }
 
-// negated pattern: bit j = candidate j is NOT among the hits (multi.rs:121-131); bitmap + per-1024 counts as everywhere
+// negated pattern: bit j = candidate j is NOT among the hits (multi.rs:121-131); the flag pass of tile_compact.h
 __global__ __launch_bounds__(256) void k_flag_absent(const fzb_match_rec* __restrict__ cand, const u32* __restrict__ n_cand_ptr, const fzb_match_rec* __restrict__ hits,
                                                      const u32* __restrict__ n_hits_ptr, u64* __restrict__ bitmap, u32* __restrict__ tile_counts) {
-    __shared__ u32 s_cnt;
     const u32 nc = *n_cand_ptr, nh = *n_hits_ptr;
-    const u32 ntiles = (nc + FZB_TILE - 1) / FZB_TILE;
-    const int tid = threadIdx.x;
-    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        u32 cnt = 0;
-        for (int p = 0; p < FZB_TILE / 256; p++) {
-            const u32 j = tile * FZB_TILE + p * 256 + tid;
-            const bool keep = j < nc && find_index(hits, nh, cand[j].index) == nh;
-            const u64 b = __ballot(keep);
-            if (lane_id() == 0) {
-                bitmap[(tile * FZB_TILE + p * 256) / 64 + (tid >> 6)] = b;
-                cnt += __popcll(b);
-            }
-        }
-        if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
-        __syncthreads();
-        if (tid == 0) tile_counts[tile] = s_cnt;
-        __syncthreads();
-    }
+    tc_flag_pass(nc, bitmap, tile_counts, [&](u32 tile, u32 slot) {
+        const u32 j = tile * FZB_TILE + slot;
+        return j < nc && find_index(hits, nh, cand[j].index) == nh;
+    });
 }
 
-// order-preserving compaction of records by the bitmap (same scheme as k_compact1: every workgroup derives the number of
-// kept records before its run of tiles from the per-tile counts)
+// order-preserving compaction of records by the bitmap: tile_compact.h's record compaction, unbounded, with a single total
 __global__ __launch_bounds__(256) void k_compact_records(const u64* __restrict__ bitmap, const u32* __restrict__ counts, const u32* __restrict__ n_ptr,
                                                          const fzb_match_rec* __restrict__ in, fzb_match_rec* __restrict__ out, u32* __restrict__ total_out) {
-    __shared__ u32 red[4];
-    __shared__ u32 pre[256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 n = *n_ptr;
-    const u32 ntiles = (n + FZB_TILE - 1) / FZB_TILE;
-    const u32 T = (ntiles + gridDim.x - 1) / gridDim.x;
-    const u32 t0 = min(blockIdx.x * T, ntiles), t1 = min(t0 + T, ntiles);
-    u32 part = 0;
-    for (u32 i = tid; i < t0; i += 256) part += counts[i];
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    u32 base = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    for (u32 tb = t0; tb < t1; tb += 256) {
-        const u32 nt = min(256u, t1 - tb);
-        const u32 c = (u32)tid < nt ? counts[tb + tid] : 0u;
-        u32 incl = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) red[wave] = incl;
-        __syncthreads();
-        u32 wb = 0;
-        for (int w = 0; w < wave; w++) wb += red[w];
-        pre[tid] = base + wb + incl - c;
-        const u32 batch_total = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-        const u32 w0 = tb * (FZB_TILE / 64), w1 = (tb + nt) * (FZB_TILE / 64);
-        const u32 nwords = (n + 63) / 64;
-        for (u32 w = w0 + tid; w < w1 && w < nwords; w += 256) {
-            u64 bits = bitmap[w];
-            if (!bits) continue;
-            const u32 tile = w / (FZB_TILE / 64);
-            u32 pos = pre[tile - tb];
-            for (u32 k = tile * (FZB_TILE / 64); k < w; k++) pos += __popcll(bitmap[k]);
-            while (bits) {
-                const int b = __builtin_ctzll(bits);
-                bits &= bits - 1;
-                out[pos++] = in[w * 64 + b];
-            }
-        }
-        base += batch_total;
-        __syncthreads();
-    }
-    // (n == 0: no workgroup has tiles; the last one still publishes base = 0)
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *total_out = base;
+    const u32 kept = tc_compact_items(bitmap, counts, *n_ptr, [&](u32 place, u64 j) { out[place] = in[j]; });
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = kept;
 }
 
 __global__ __launch_bounds__(256) void k_copy_records(const fzb_match_rec* __restrict__ in, const u32* __restrict__ n_ptr, fzb_match_rec* __restrict__ out, u32 capacity,

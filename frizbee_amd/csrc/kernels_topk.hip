@@ -306,8 +306,7 @@ __global__ __launch_bounds__(256) void k_bias_apply(fzb_match_rec* __restrict__ 
 // the capacity here and trimmed by the device-side count in the kernel.
 void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st) {
     if (!cap || !n_bias) return;
-    const u32 blocks = (cap + 255u) / 256u, most = grid_max > 0 ? (u32)grid_max : 1u;
-    const int grid = (int)(blocks < most ? blocks : most);
+    const int grid = tc_grid((cap + 255u) / 256u, grid_max);
     FZB_LAUNCH(k_bias_apply, dim3(grid), dim3(256), 0, st, recs, count, cap, bias, n_bias, first, index_offset);
 }
 
@@ -318,100 +317,25 @@ void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const
 // sized on the host from the capacity and trimmed by the device-side count; the kept records go to a DIFFERENT buffer.
 static_assert(SCOPE_TILE == FZB_TILE && sizeof(scope_rec) == sizeof(fzb_match_rec) && alignof(scope_rec) == alignof(fzb_match_rec), "the drop pass moves fzb_match_rec by the tile");
 
-// the flag pass, in the shape of k_flag_absent: per 1024-record tile one ballot word per wave and pass, and the tile's kept count
+// the flag pass (tile_compact.h): 2-byte tag gathered per record
 __global__ __launch_bounds__(256) void k_scope_flag(const scope_rec* __restrict__ recs, const u32* __restrict__ count, u32 cap, const uint16_t* __restrict__ tags, u64 n_tags, u64 first,
                                                     u32 index_offset, u32 require, u32 exclude, u64* __restrict__ bitmap, u32* __restrict__ tile_counts) {
-    __shared__ u32 s_cnt;
     const u32 n = min(count[0], cap);
-    const u32 ntiles = (n + SCOPE_TILE - 1) / SCOPE_TILE;
-    const int tid = threadIdx.x;
-    for (u32 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        if (tid == 0) s_cnt = 0;
-        __syncthreads();
-        u32 cnt = 0;
-        for (int p = 0; p < SCOPE_TILE / 256; p++) {
-            const bool keep = scope_tile_keeps(recs, n, tile, (u32)(p * 256 + tid), tags, n_tags, first, index_offset, require, exclude);
-            const u64 b = __ballot(keep);
-            if (lane_id() == 0) {
-                bitmap[(u64)tile * SCOPE_WORDS + p * 4 + (tid >> 6)] = b;
-                cnt += __popcll(b);
-            }
-        }
-        if (lane_id() == 0 && cnt) atomicAdd(&s_cnt, cnt);
-        __syncthreads();
-        if (tid == 0) tile_counts[tile] = s_cnt;
-        __syncthreads();
-    }
+    tc_flag_pass(n, bitmap, tile_counts, [&](u32 tile, u32 slot) { return scope_tile_keeps(recs, n, tile, slot, tags, n_tags, first, index_offset, require, exclude); });
 }
 
-// The compaction, k_compact_records' scheme with a bounded destination and the (written, found) pair: a workgroup owns a run of tiles
-// (scope_block_tiles), sums the counts in front of it, scans its own in batches of 256 and places every kept record itself - a thread per
-// record, so the loads are coalesced and the stores nearly so.  A tile's 16 words sit in lanes 0..15 of every wave; a word's base inside
-// the tile is a 16-lane scan of the popcounts.
+// The compaction: tile_compact.h's record compaction with a bounded destination (scope_store) and the (written, found) pair (scope_counts).
 __global__ __launch_bounds__(256) void k_scope_compact(const u64* __restrict__ bitmap, const u32* __restrict__ counts, const u32* __restrict__ n_ptr, u32 in_cap,
                                                        const scope_rec* __restrict__ in, scope_rec* __restrict__ out, u32 capacity, u32* __restrict__ count_out) {
-    __shared__ u32 red[4];
-    __shared__ u32 pre[256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 n = min(*n_ptr, in_cap);
-    const u32 ntiles = (n + SCOPE_TILE - 1) / SCOPE_TILE;
-    u32 t0, t1;
-    scope_block_tiles(ntiles, gridDim.x, blockIdx.x, &t0, &t1);
-    u32 part = 0;
-    for (u32 i = tid; i < t0; i += 256) part += counts[i];
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    u32 base = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    for (u32 tb = t0; tb < t1; tb += 256) {
-        const u32 nt = min(256u, t1 - tb);
-        const u32 c = (u32)tid < nt ? counts[tb + tid] : 0u;
-        u32 incl = c;
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) red[wave] = incl;
-        __syncthreads();
-        u32 wb = 0;
-        for (int w = 0; w < wave; w++) wb += red[w];
-        pre[tid] = base + wb + incl - c;
-        const u32 batch_total = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-        for (u32 t = 0; t < nt; t++) {  // (workgroup-uniform trip counts: the shuffles below need every lane)
-            const u64 w0 = (u64)(tb + t) * SCOPE_WORDS;
-            const u64 mine = lane < SCOPE_WORDS ? bitmap[w0 + lane] : 0ull;  // (every word of a tile below ntiles was written by the flag pass)
-            const u32 pc = (u32)__popcll(mine);
-            u32 scan = pc;
-#pragma unroll
-            for (int off = 1; off < SCOPE_WORDS; off <<= 1) {
-                const u32 v = __shfl_up(scan, off);
-                if (lane >= off) scan += v;
-            }
-            const u32 excl = scan - pc;
-            const u32 tile_base = pre[t];
-#pragma unroll
-            for (int p = 0; p < SCOPE_TILE / 256; p++) {
-                const int k = p * 4 + wave;
-                const u64 bits = ((u64)(u32)__shfl((int)(mine >> 32), k) << 32) | (u32)__shfl((int)(u32)mine, k);
-                const u32 word_base = (u32)__shfl((int)excl, k);
-                if ((bits >> lane) & 1) scope_store(out, capacity, scope_place(tile_base, word_base, bits, (u32)lane), in, (w0 + k) * 64 + lane);
-            }
-        }
-        base += batch_total;
-        __syncthreads();
-    }
-    // (n == 0: no workgroup has tiles; the last one still publishes the pair of an empty list)
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) scope_counts(base, capacity, count_out);
+    const u32 kept = tc_compact_items(bitmap, counts, min(*n_ptr, in_cap), [&](u32 place, u64 j) { scope_store(out, capacity, place, in, j); });
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) scope_counts(kept, capacity, count_out);
 }
 
 // recs: count[0] index-ordered records (at most `cap`); out: room for `capacity`; count_out: (written, found).  bitmap: 16 words per tile of
 // cap records, tile_counts: one word per tile.
 void fzb_launch_scope_drop(const fzb_match_rec* recs, const u32* count, u32 cap, const uint16_t* tags, u64 n_tags, u64 first, u32 index_offset, u32 require, u32 exclude, u64* bitmap,
                            u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st) {
-    const u32 tiles = (cap + SCOPE_TILE - 1) / SCOPE_TILE, most = grid_max > 0 ? (u32)grid_max : 1u;
-    const int grid = (int)(tiles < most ? (tiles ? tiles : 1u) : most);
+    const int grid = tc_grid((cap + SCOPE_TILE - 1) / SCOPE_TILE, grid_max);
     FZB_LAUNCH(k_scope_flag, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts);
     FZB_LAUNCH(k_scope_compact, dim3(grid), dim3(256), 0, st, (const u64*)bitmap, (const u32*)tile_counts, count, cap, (const scope_rec*)recs, (scope_rec*)out, capacity, count_out);
 }

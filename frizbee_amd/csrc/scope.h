@@ -9,12 +9,14 @@
 // The drop runs between the scorers and the bias / selection / ordering stage, over index-ordered records, in two launches:
 //   * the flag pass (k_scope_flag): scope_tile_keeps per record - the wave's kept mask is a ballot on the device, a loop over the lanes
 //     on the host -, one 64-bit word per 64 records and one kept count per 1024-record tile;
-//   * the compaction (k_scope_compact): a workgroup owns the run of tiles scope_block_tiles gives it, the kept records in front of the
-//     run are the sum of the earlier tiles' counts, inside a tile a record's place is scope_place - no atomics, nothing ordered between
-//     workgroups, never in place.  scope_counts is the (written, found) pair the last workgroup publishes.
+//   * the compaction (k_scope_compact): the tile scheme of tile_compact.h - a workgroup owns the run of tiles tc_run gives it, the kept
+//     records in front of the run are the sum of the earlier tiles' counts, inside a tile a record's place is scope_place (tc_rank64) - with
+//     a bounded destination (scope_store).  scope_counts is the (written, found) pair the last workgroup publishes.
 // The kernels and the host walk call the SAME functions; only the ballot, the shuffles and the barriers between them differ.
 #pragma once
 #include <stdint.h>
+
+#include "tile_compact.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define FZB_SCOPE_FN __host__ __device__ __forceinline__
@@ -22,8 +24,8 @@
 #define FZB_SCOPE_FN inline
 #endif
 
-#define SCOPE_TILE 1024  // records per tile of the drop pass: the tile of every bitmap + per-tile count pair here (FZB_TILE)
-#define SCOPE_WORDS (SCOPE_TILE / 64)
+#define SCOPE_TILE TC_TILE  // records per tile of the drop pass: the tile of every bitmap + per-tile count pair here (FZB_TILE)
+#define SCOPE_WORDS TC_WORDS
 
 // a record as the drop pass sees it: the haystack's index, then score / exact / valid - moved as a whole, never looked into
 struct scope_rec {
@@ -47,19 +49,10 @@ FZB_SCOPE_FN bool scope_tile_keeps(const scope_rec* recs, uint64_t n, uint64_t t
     return j < n && scope_visible(scope_tag_of(tags, n_tags, first, index_offset, recs[j].index), require, exclude);
 }
 
-// ---- the compaction ----
-// workgroup `block` of `grid` owns the tiles [*t0, *t1) of ntiles: a contiguous run, so that what lies in front of it is a prefix
-FZB_SCOPE_FN void scope_block_tiles(uint32_t ntiles, uint32_t grid, uint32_t block, uint32_t* t0, uint32_t* t1) {
-    const uint32_t per = (ntiles + grid - 1) / grid;
-    const uint64_t a = (uint64_t)block * per;
-    *t0 = a < ntiles ? (uint32_t)a : ntiles;
-    *t1 = (uint64_t)*t0 + per < ntiles ? *t0 + per : ntiles;
-}
+// ---- the compaction (a workgroup's run of tiles: tc_run) ----
 // the place of the record at bit `lane` of a kept word: kept records in front of the tile + in front of the word inside the tile + in
 // front of the lane inside the word
-FZB_SCOPE_FN uint32_t scope_place(uint32_t tile_base, uint32_t word_base, uint64_t bits, uint32_t lane) {
-    return tile_base + word_base + (uint32_t)__builtin_popcountll(bits & (((uint64_t)1 << lane) - 1));
-}
+FZB_SCOPE_FN uint32_t scope_place(uint32_t tile_base, uint32_t word_base, uint64_t bits, uint32_t lane) { return tc_rank64(tile_base + word_base, bits, lane); }
 // a kept record goes to its place unless the destination has no room for it (the first `capacity` kept records are written)
 FZB_SCOPE_FN void scope_store(scope_rec* out, uint32_t capacity, uint32_t place, const scope_rec* in, uint64_t j) {
     if (place < capacity) out[place] = in[j];

@@ -16,6 +16,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "tile_compact.h"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define FZB_SBIAS_FN __host__ __device__ __forceinline__
 #else
@@ -37,9 +39,6 @@ FZB_SBIAS_FN bool sbias_one_pass(uint64_t score_bound, uint32_t bias_hi) { retur
 // haystack i survives the removal: bit i of the pass' bitmap (32-bit words, bit i & 31 of word i >> 5) marks a removed haystack
 FZB_SBIAS_FN bool sbias_kept(const uint32_t* bitmap, uint64_t i) { return !((bitmap[i >> 5] >> (i & 31)) & 1u); }
 
-// kept haystacks of the wave in front of `lane` (kept_mask: bit l = lane l's haystack is kept)
-FZB_SBIAS_FN uint32_t sbias_lane_rank(uint64_t kept_mask, uint32_t lane) { return (uint32_t)__builtin_popcountll(kept_mask & (((uint64_t)1 << lane) - 1)); }
-
 // kept haystacks of the tile in front of wave `wave` (wave_totals[w] = popcount of wave w's kept mask)
 FZB_SBIAS_FN uint32_t sbias_wave_base(const uint32_t* wave_totals, uint32_t wave) {
     uint32_t run = 0;
@@ -59,6 +58,6 @@ FZB_SBIAS_FN bool sbias_tile_keeps(const uint32_t* bitmap, uint64_t n, uint64_t 
 template <typename V>
 FZB_SBIAS_FN void sbias_tile_place(const V* values, uint64_t t0, uint32_t wave, uint32_t lane, uint64_t kept_mask, const uint32_t* wave_totals, uint64_t tile_base, V* out,
                                    uint64_t out_cap) {
-    const uint64_t dst = tile_base + sbias_wave_base(wave_totals, wave) + sbias_lane_rank(kept_mask, lane);
+    const uint64_t dst = tile_base + tc_rank64(sbias_wave_base(wave_totals, wave), kept_mask, lane);  // (kept_mask: bit l = lane l's haystack is kept)
     if (dst < out_cap) out[dst] = values[t0 + (uint64_t)wave * 64 + lane];
 }

@@ -1,5 +1,5 @@
 // The SEGMENTED survivor list of the signature filter (k1_dfa_sig<.., SEG>, kernels_filter.hip -> k2b_dp_short<.., SEG>, kernels_dp.hip).
-// Workgroup b of the filter owns the contiguous run of tiles [b T, min((b + 1) T, ntiles)), T = ceil(ntiles / grid), and lists the
+// Workgroup b of the filter owns the contiguous run of tiles tile_compact.h gives it (tc_run, T = tc_tiles_per_run(ntiles, grid)), and lists the
 // survivors of its run itself, in ascending order, at seg_list[b * T * FZB_TILE + k]; seg_counts[b] says how many.  Segment b starts at its
 // first tile's first item, so segments cannot overlap and the list needs no more room than the range rounded up to a tile.  The scorer turns
 // the <= FZB_SEG_MAX counts into an exclusive prefix in LDS and maps survivor j to (segment, slot) - no compaction launch in between.
@@ -8,22 +8,13 @@
 #pragma once
 #include <stdint.h>
 
+#include "tile_compact.h"
+
 #ifndef FZB_SEG_FN
 #define FZB_SEG_FN __host__ __device__ inline
 #endif
 
 #define FZB_SEG_MAX 2048u  // segments (= workgroups of the filter) at most: the scorer's prefix array in LDS
-
-// tiles per run, and the run of workgroup b (empty for the trailing workgroups when grid does not divide ntiles)
-FZB_SEG_FN uint32_t seg_tiles_per_run(uint32_t ntiles, uint32_t grid) { return grid ? (ntiles + grid - 1) / grid : 0u; }
-FZB_SEG_FN void seg_run(uint32_t ntiles, uint32_t T, uint32_t b, uint32_t& t0, uint32_t& t1) {
-    const uint64_t lo = (uint64_t)b * T;
-    t0 = lo < ntiles ? (uint32_t)lo : ntiles;
-    t1 = lo + T < ntiles ? (uint32_t)(lo + T) : ntiles;
-}
-
-// In-tile ranking: the slot of set bit `bit` of a 32-bit decision word, `before` = set bits of the tile's (round's) earlier words.
-FZB_SEG_FN uint32_t seg_rank(uint32_t before, uint32_t word, uint32_t bit) { return before + (uint32_t)__builtin_popcount(word & ((1u << bit) - 1u)); }
 
 // The largest power of two below nseg (1 for nseg <= 2): the first step of seg_find.
 FZB_SEG_FN uint32_t seg_top(uint32_t nseg) {

@@ -17,7 +17,7 @@ def available():
 
 def build():
     so = os.path.join(HERE, "libbias_host.so")
-    srcs = [os.path.join(HERE, "bias_host.cpp"), os.path.join(HERE, "shim", "hip", "hip_runtime.h"), os.path.join(CSRC, "score_bias.h")]
+    srcs = [os.path.join(HERE, "bias_host.cpp"), os.path.join(HERE, "shim", "hip", "hip_runtime.h"), os.path.join(CSRC, "score_bias.h"), os.path.join(CSRC, "tile_compact.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-I" + os.path.join(HERE, "shim"), "-I" + CSRC, "-Wall", "-Werror",
                                "-o", so, os.path.join(HERE, "bias_host.cpp")])

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE: frizbee_amd/csrc/scope.h - the visibility predicate of a corpus' tags and the arithmetic of the drop pass - compiled
 // for the host.  sh_drop walks a record list the way k_scope_flag and k_scope_compact (kernels_topk.hip) do, through the SAME functions:
 // scope_tile_keeps per record of a tile (a loop over the lanes stands in for the wave's ballot), then, for every workgroup of a grid that is
-// a PARAMETER here, scope_block_tiles, the sum of the counts in front of the run, the scan of the run's counts in batches of `batch` tiles
+// a PARAMETER here, tc_run (tile_compact.h), the sum of the counts in front of the run, the scan of the run's counts in batches of `batch` tiles
 // (256 on the device; a parameter here, so that several tiles per workgroup and more than one batch are reached at small sizes), scope_place
 // / scope_store per kept record and scope_counts by the last workgroup.  tests/test_scope_host.py fuzzes it against numpy.
 #include <hip/hip_runtime.h>
@@ -41,7 +41,7 @@ void sh_drop(const uint32_t* rec_words, uint32_t n, const uint16_t* tags, uint64
     for (uint32_t g = 0; g < grid; g++) {
         const uint32_t block = order[g];
         uint32_t t0, t1;
-        scope_block_tiles(ntiles, grid, block, &t0, &t1);
+        tc_run(ntiles, tc_tiles_per_run(ntiles, grid), block, &t0, &t1);
         uint32_t base = 0;
         for (uint32_t i = 0; i < t0; i++) base += counts[i];
         for (uint32_t tb = t0; tb < t1; tb += batch) {

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: frizbee_amd/csrc/seg_list.h - the arithmetic of the segmented survivor list (a workgroup's run of tiles, the slot of a
-// set bit in its tile, the segment that holds survivor j) - compiled for the host.  tests/test_seg_list_host.py checks it against plain Python.
+// set bit in its tile - both tile_compact.h's -, the segment that holds survivor j) - compiled for the host.  tests/test_seg_list_host.py checks it against plain Python.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -9,8 +9,8 @@
 extern "C" {
 
 uint32_t sg_max(void) { return FZB_SEG_MAX; }
-uint32_t sg_tiles_per_run(uint32_t ntiles, uint32_t grid) { return seg_tiles_per_run(ntiles, grid); }
-void sg_run(uint32_t ntiles, uint32_t T, uint32_t b, uint32_t* out) { seg_run(ntiles, T, b, out[0], out[1]); }
+uint32_t sg_tiles_per_run(uint32_t ntiles, uint32_t grid) { return tc_tiles_per_run(ntiles, grid); }
+void sg_run(uint32_t ntiles, uint32_t T, uint32_t b, uint32_t* out) { tc_run(ntiles, T, b, &out[0], &out[1]); }
 uint32_t sg_top(uint32_t nseg) { return seg_top(nseg); }
 
 // the scorer's side: exclusive prefix of the counts (as the kernel builds it), then every j in [0, total]: out_seg[j], out_slot[j];
@@ -30,7 +30,7 @@ uint32_t sg_map_all(const uint32_t* counts, uint32_t nseg, uint32_t* pre, uint32
     return run;
 }
 
-// the filter's side: the slots of one tile's set bits from its 32 decision words (word popcounts scanned, seg_rank per bit), in the order
+// the filter's side: the slots of one tile's set bits from its 32 decision words (word popcounts scanned, tc_rank32 per bit), in the order
 // the kernel's threads take the positions (p * 256 + tid); out_pos[slot] = position; returns the tile's count
 uint32_t sg_rank_tile(const uint32_t* words, uint32_t* out_pos) {
     uint32_t excl[32], run = 0;
@@ -41,7 +41,7 @@ uint32_t sg_rank_tile(const uint32_t* words, uint32_t* out_pos) {
     for (uint32_t p = 0; p < 4; p++)
         for (uint32_t tid = 0; tid < 256; tid++) {
             const uint32_t pos = p * 256 + tid, w = pos >> 5;
-            if ((words[w] >> (pos & 31)) & 1) out_pos[seg_rank(excl[w], words[w], pos & 31)] = pos;
+            if ((words[w] >> (pos & 31)) & 1) out_pos[tc_rank32(excl[w], words[w], pos & 31)] = pos;
         }
     return run;
 }

@@ -667,3 +667,110 @@ def test_the_compactions_later_batches_at_one_compute_unit():
                 grids = F.launch_grids()
                 print("coverage 1 big subset", needle, cfg, env, grids)
                 assert -(-ntiles // grids["k_compact1"][0]) > 512, grids  # three batches
+
+
+# ---- the record passes' later batches: tile_compact.h's compaction behind k_flag_absent, k_scope_flag and the lane-exact window stage -------
+REC_N = 513 * 1024 + 5  # 514 tiles: at one compute unit the record passes' grid is 2, a run of 257 tiles - a second 256-tile batch
+REC_ODD = 500           # haystacks that hold nothing of the needles
+
+
+def record_list():
+    """packed 8-byte haystacks over letters that spell neither "zqj" nor "de": all but REC_ODD start with "deadbe" (a tenth of those with
+    one substitution, which only the typo query forgives), so that "de" leaves 513 tiles of records and "!zqj" keeps every haystack"""
+    rng = np.random.default_rng(91)
+    rows = rng.choice(np.frombuffer(b"ghiklmnoprstuv", np.uint8), (REC_N, 8))
+    rows[:, :6] = np.frombuffer(b"deadbe", np.uint8)
+    rows[rng.random(REC_N) < 0.1, 3] = ord("X")
+    odd = rng.choice(REC_N, REC_ODD, replace=False)
+    rows[odd] = rng.choice(np.frombuffer(b"ghiklmnoprstuv", np.uint8), (REC_ODD, 8))
+    return rows
+
+
+def packed(rows):
+    return rows.reshape(-1).copy(), np.arange(1, len(rows) + 1, dtype=np.uint64) * np.uint64(8)
+
+
+def tiles_per_workgroup(records, grid):
+    return -(-(-(-records // 1024)) // grid)
+
+
+def test_the_record_compactions_later_batches_at_one_compute_unit():
+    import torch
+
+    rows = record_list()
+    data, ends = packed(rows)
+    odata = opad(data)
+    with device_of(1):
+        cp = F.Corpus(packed=(data, ends))
+        # every pattern negated, every haystack kept: identity records -> k_flag_absent -> k_compact_records over 514 tiles
+        want = O.MultiMatcher(O.parse_query("!zqj"), lanes=LANES[64]).match_packed(odata, ends)
+        assert len(want) == REC_N
+        mm = F.MultiMatcher(F.parse_query("!zqj"), F.Config(pf_lanes=64, sw_lanes=0))
+        F.launch_grids()
+        same_records(mm.match_list(cp), want, "!zqj")
+        grids = F.launch_grids()
+        print("coverage 1 records !zqj", grids)
+        assert "k_flag_absent" in grids and tiles_per_workgroup(REC_N, grids["k_compact_records"][1]) > 256, grids
+        # a negated pattern that removes a part, behind a pattern nearly every haystack matches
+        want = O.MultiMatcher(O.parse_query("de !X"), lanes=LANES[64]).match_packed(odata, ends)
+        assert 400_000 < len(want) < REC_N - REC_ODD - 40_000
+        mm = F.MultiMatcher(F.parse_query("de !X"), F.Config(pf_lanes=64, sw_lanes=0))
+        F.launch_grids()
+        same_records(mm.match_list(cp), want, "de !X")
+        grids = F.launch_grids()
+        print("coverage 1 records de !X", grids)
+        assert tiles_per_workgroup(REC_N - REC_ODD, grids["k_compact_records"][1]) > 256, grids
+        # the 1-typo query over a candidate set that is the whole list: k_compact2's 64-tile batches, five to a run
+        sub = F.Subset(cp)
+        sub.set_indices(np.arange(REC_N))
+        fm, om = single("deadbe", max_typos=1)
+        want = om.match_packed(odata, ends)
+        assert len(want) == REC_N - REC_ODD
+        F.launch_grids()
+        same_records(fm.match_list(cp, subset=sub), want, "1 typo")
+        grids = F.launch_grids()
+        print("coverage 1 records 1 typo", grids, fm.last_counters())
+        assert tiles_per_workgroup(fm.last_counters()["filter_survivors"], grids["k_compact2"][1]) > 64, grids
+        # tags and a scope that hides every third haystack: k_scope_flag -> k_scope_compact over 513 tiles of records
+        vis = np.arange(REC_N) % 3 != 0
+        cp.set_tags((~vis).astype(np.uint16))
+        cp.set_scope(exclude=1)
+        fm, om = single("de", sort="IndexAsc")
+        matches = len(om.match_packed(odata, ends))
+        assert matches == REC_N - REC_ODD
+        vdata, vends = packed(rows[vis])
+        want = mapped(om.match_packed(opad(vdata), vends), vis)
+        kept = len(want)
+        assert kept > 256 * 1024
+        F.launch_grids()
+        same_records(fm.match_list(cp), want, "scope")
+        grids = F.launch_grids()
+        print("coverage 1 records scope", grids)
+        assert "k_scope_flag" in grids and tiles_per_workgroup(matches, grids["k_scope_compact"][1]) > 256, grids
+        # a bounded destination: the first `capacity` kept records and the (written, found) pair
+        for capacity in (kept // 2, 1):
+            out = torch.full(((capacity + 64) * 8,), 0xEE, dtype=torch.uint8, device="cuda")
+            cnt = torch.zeros(4, dtype=torch.int32, device="cuda")
+            fm.match_list_device(cp, out.data_ptr(), capacity, cnt.data_ptr())
+            torch.cuda.synchronize()
+            assert cnt[:2].tolist() == [capacity, kept], (capacity, cnt.tolist())
+            host = out.cpu().numpy()
+            same_records(host[: capacity * 8].view(F.MATCH_DTYPE), want[:capacity], ("scope", capacity))
+            assert (host[capacity * 8:] == 0xEE).all(), "wrote beyond the capacity"
+
+
+@pytest.mark.parametrize("n", (0, 1, 1023, 1024, 1025))
+def test_degenerate_record_counts_into_the_record_compaction(n):
+    """no tile, one record, a tile less one, a full tile, a tile and one: a NOT pattern over lists of those lengths"""
+    rng = np.random.default_rng(95 + n)
+    hs = [bytes(r) for r in rng.choice(np.frombuffer(b"ghiklmnoprstuv", np.uint8), (n, 8))]
+    with device_of(1):
+        cp = F.Corpus(hs)
+        for query in ("!g", "!zqj", "!i !k"):
+            want = O.MultiMatcher(O.parse_query(query), lanes=LANES[64]).match_list(hs) if n else np.zeros(0, F.MATCH_DTYPE)
+            assert query != "!zqj" or len(want) == n
+            mm = F.MultiMatcher(F.parse_query(query), F.Config(pf_lanes=64, sw_lanes=0))
+            F.launch_grids()
+            same(mm.match_list(cp), want, (n, query))
+            grids = F.launch_grids()
+            assert not n or ("k_flag_absent" in grids and "k_compact_records" in grids), (n, query, grids)
