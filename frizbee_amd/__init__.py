@@ -10,7 +10,8 @@ import ctypes as C
 import weakref
 import enum
 import os
-from dataclasses import dataclass, field
+from copy import deepcopy
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -130,7 +131,8 @@ SYMBOLS = [
     "fzb_corpus_set_tags", "fzb_corpus_update_tags", "fzb_corpus_clear_tags", "fzb_corpus_set_scope", "fzb_corpus_scope_info",
     "fzb_corpus_generation", "fzb_subset_create", "fzb_subset_free", "fzb_subset_set_indices", "fzb_subset_from_scope", "fzb_subset_info", "fzb_subset_read",
     "fzb_match_list_subset", "fzb_match_list_top_subset", "fzb_match_list_top_subset_device", "fzb_match_list_top_indices_subset",
-    "fzb_debug_set_items_dfa_min", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
+    "fzb_multi_match_list_subset", "fzb_multi_match_list_top_subset", "fzb_multi_match_list_top_subset_device", "fzb_multi_match_list_top_indices_subset",
+    "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
 ]
 
 
@@ -255,6 +257,8 @@ def lib():
         l.fzb_corpus_scope_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_debug_set_items_dfa_min.argtypes = [C.c_uint32]
         l.fzb_debug_set_items_dfa_min.restype = None
+        l.fzb_debug_set_fused_capture.argtypes = [C.c_int]
+        l.fzb_debug_set_fused_capture.restype = None
         l.fzb_debug_launch_grids.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
         l.fzb_corpus_generation.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_subset_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -267,8 +271,12 @@ def lib():
         l.fzb_match_list_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         l.fzb_match_list_top_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
         l.fzb_match_list_top_subset_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_multi_match_list_subset.argtypes = l.fzb_match_list_subset.argtypes
+        l.fzb_multi_match_list_top_subset.argtypes = l.fzb_match_list_top_subset.argtypes
+        l.fzb_multi_match_list_top_subset_device.argtypes = l.fzb_match_list_top_subset_device.argtypes
         l.fzb_match_list_top_indices_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                         C.POINTER(C.c_uint64)]
+        l.fzb_multi_match_list_top_indices_subset.argtypes = l.fzb_match_list_top_indices_subset.argtypes
         _lib = l
     return _lib
 
@@ -796,27 +804,46 @@ class MultiMatcher(_IterApi):
         """How the runs of the last `match_list_parallel_sharded` reached the root (see `Matcher.shard_report`)."""
         return lib().fzb_multi_matcher_shard_report(self.h).decode()
 
-    def match_list(self, haystacks, copy=True):
+    def match_list(self, haystacks, copy=True, *, subset=None, capture=None):
+        """subset / capture (`Subset`s of the corpus, here and in the top-`limit` forms): the composition runs over `subset` only, and
+        `capture` receives the indices of every haystack the COMPOSITION accepted - every non-negated pattern hit, no negated one did -
+        before bias, scope, `limit` and ordering (see `Matcher.match_list`)."""
         cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
         out, n = C.c_void_p(), C.c_size_t()
-        _check(lib().fzb_multi_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
+        if subset is None and capture is None:
+            _check(lib().fzb_multi_match_list(self.h, cp.h, C.byref(out), C.byref(n)))
+        else:
+            _check(lib().fzb_multi_match_list_subset(self.h, cp.h, _h(subset), _h(capture), C.byref(out), C.byref(n)))
         return _take(out, n, copy)
 
-    def match_list_top(self, haystacks, limit, copy=True):
+    def match_list_top(self, haystacks, limit, copy=True, *, subset=None, capture=None):
         """(`match_list(haystacks)[:limit]`, len(`match_list(haystacks)`)), selected and ordered on the device (see `Matcher.match_list_top`)."""
         cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
-        return _top(lib().fzb_multi_match_list_top, self.h, cp.h, limit, copy)
+        if subset is None and capture is None:
+            return _top(lib().fzb_multi_match_list_top, self.h, cp.h, limit, copy)
+        out, n, found = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        _check(lib().fzb_multi_match_list_top_subset(self.h, cp.h, _h(subset), _h(capture), limit, C.byref(out), C.byref(n), C.byref(found)))
+        return _take(out, n, copy), found.value
+
+    def match_list_top_device(self, corpus, limit, dev_out_ptr, capacity, dev_count_ptr, stream=0, *, subset=None, capture=None):
+        """`match_list_top` with the result left in HBM: `capacity` >= min(limit, len(corpus)) records at `dev_out_ptr`, two count words
+        (records written, matches found) at `dev_count_ptr`; asynchronous on `stream`.  A matcher without a compiled pattern is refused."""
+        _check(lib().fzb_multi_match_list_top_subset_device(self.h, corpus.h, _h(subset), _h(capture), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
 
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
-    def match_list_top_indices(self, haystacks, limit):
+    def match_list_top_indices(self, haystacks, limit, *, subset=None, capture=None):
         """(`match_list_indices(haystacks)[:limit]` with `index` = the corpus index, len of the full list) for the compiled patterns, in one
         fused device call with one host wait: the multi top stage, one traced pass per non-negated pattern over the head, the union of their
         positions and the pack, all on the device (see `Matcher.match_list_top_indices`)."""
         cp = haystacks if isinstance(haystacks, Corpus) else Corpus(haystacks)
-        return _top_indices(lib().fzb_multi_match_list_top_indices_fused, self.h, cp, limit)
+        if subset is None and capture is None:
+            return _top_indices(lib().fzb_multi_match_list_top_indices_fused, self.h, cp, limit)
+        out, n, pos, found = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_uint64()
+        _check(lib().fzb_multi_match_list_top_indices_subset(self.h, cp.h, _h(subset), _h(capture), limit, C.byref(out), C.byref(n), C.byref(pos), C.byref(found)))
+        return _take_indices(out, n, pos), found.value
 
     def match_list_top_indices_device(self, corpus, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream=0):
         """`match_list_top_indices` with the result left in HBM, asynchronous on `stream` (see `Matcher.match_list_top_indices_device`):
@@ -1089,6 +1116,17 @@ class Matcher(_IterApi):
             pass
 
 
+def _needle_extends(matching, max_typos, prev_needle, needle, prev_path, path):
+    """The narrowing premise for ONE non-negated needle (tests/test_oracle_narrowing_premise.py): fuzzy matching, max_typos == 0, `needle` is
+    `prev_needle` plus a non-empty suffix, and both report the same (unicode, pf_lanes, sw_lanes).  `NarrowingMatcher` asks it for its one
+    needle, `NarrowingQuery` for every pattern that changed."""
+    if matching != Matching.Fuzzy or max_typos != 0:
+        return False
+    if not prev_needle or len(needle) <= len(prev_needle) or not needle.startswith(prev_needle):
+        return False
+    return path == prev_path
+
+
 class NarrowingMatcher:
     """The keystroke loop as a picker writes it: a `Matcher` over one resident `Corpus` and two `Subset`s that alternate.  Every query
     captures its match set; the next query runs over that capture instead of the whole list when ALL of these hold: fuzzy matching,
@@ -1119,11 +1157,9 @@ class NarrowingMatcher:
             return False
         prev_needle, prev_path, prev_gen = self._prev
         cfg = self.config
-        if cfg.matching != Matching.Fuzzy or cfg.max_typos != 0:
+        if not _needle_extends(cfg.matching, cfg.max_typos, prev_needle, needle, prev_path, path):
             return False
-        if not prev_needle or len(needle) <= len(prev_needle) or not needle.startswith(prev_needle):
-            return False
-        if path != prev_path or self.corpus.generation() != prev_gen:
+        if self.corpus.generation() != prev_gen:
             return False
         cap = self.subsets[self._cur]
         out = (C.c_uint64 * 4)()
@@ -1145,6 +1181,126 @@ class NarrowingMatcher:
         fn = self.matcher.match_list_top_indices if indices else self.matcher.match_list_top
         res = fn(self.corpus, limit, subset=src, capture=dst)
         self._cur, self._prev, self.last_narrowed = dst_i, (bytes(n), path, self.corpus.generation()), narrow
+        return res
+
+
+class NarrowingQuery:
+    """`NarrowingMatcher` for query syntax: a `MultiMatcher` over one resident `Corpus`, `parse_query` per keystroke, two `Subset`s that
+    alternate.  Every query captures the COMPOSITION's match set; the next one runs over that capture when the rule below holds, else over
+    `within` (a `Subset`, e.g. the workspace folder; None: the whole list) - a restricted picker never falls back to the full corpus.
+    The rule.  P = the compiled patterns of the previous query, Q = those of the new one (empty needles dropped, as the library's compile
+    does).  The capture may be the input iff len(Q) >= len(P), Q[i] refines P[i] for every i < len(P), Q != P, the config, the corpus
+    generation and `within` (identity and generation) are unchanged, and the capture's count is known and at most max_fraction x len(corpus).
+    Q[i] refines P[i] when (a) the two are equal field for field, negated or not - an unchanged negated pattern removes the same haystacks -
+    or (b) both are non-negated, equal in every field but the needle, and the needles satisfy `NarrowingMatcher`'s condition under the
+    pattern's resolved config (fuzzy, resolved max_typos == 0, the new needle = the old one + a non-empty suffix, the same unicode path and
+    lane pair).  The patterns Q[len(P):] are free: a further non-negated pattern intersects, a further negated one subtracts.
+    A negated pattern that changes in any way does NOT refine: `!t` -> `!te` removes fewer haystacks, the match set grows
+    (tests/test_oracle_query_narrowing_premise.py finds such a step with the oracle).  The extension of a literal-mode atom (`^foo` ->
+    `^foob`) is monotone too but is left out on purpose: nobody has held it to the oracle yet.
+    max_fraction: None = DEFAULT_MAX_FRACTION, under `NarrowingMatcher`'s policy: 0.8 x the largest candidate fraction at which
+    tools/bench_multi_subset.py measured the narrowed call not slower than the un-narrowed one.  Measured (profiles/multi_subset.txt, host
+    time per keystroke): on the paths-shaped 1.4 M list every narrowed step at 6.1 % of the list and below won 86 - 93 us of ~ 417, and lost
+    14 - 39 us at 45 - 90 %; on the 10 M x 32 B list the step at 4.99 % won 6 us of 453 and the steps at 5.6 - 17 % lost 6 - 22 us.  The
+    largest fraction with no loss at or below it on either list is 0.0499, so the default is 0.8 x that.  (A composition pays for every
+    pattern over the whole list when it does not narrow, which is why this default is not `NarrowingMatcher`'s 0.0.)  A caller who refills
+    `within` in place at the same corpus generation calls `reset()`."""
+
+    DEFAULT_MAX_FRACTION = 0.039
+
+    def __init__(self, corpus, config=None, max_fraction=None, within=None):
+        self.corpus = corpus
+        self.config = config or Config()
+        self.max_fraction = self.DEFAULT_MAX_FRACTION if max_fraction is None else float(max_fraction)
+        self.within = within
+        self.matcher = MultiMatcher([], self.config)
+        self.subsets = [Subset(corpus), Subset(corpus)]
+        self._cur = None    # index of the subset that holds the previous query's capture
+        self._prev = None   # (compiled patterns, config, corpus generation, within key) of that query
+        self._paths = {}
+        self.last_narrowed = False
+
+    def reset(self):
+        """forget the previous capture: the next query runs over `within` / the whole list"""
+        self._cur = self._prev = None
+
+    @staticmethod
+    def _resolved(p, cfg):
+        """the config a pattern's sub-matcher gets (src/pattern.rs:230-262: `None` fields inherit the matcher's)"""
+        return Config(max_typos=cfg.max_typos if p.max_typos is None else p.max_typos, casing=cfg.casing if p.casing is None else p.casing,
+                      unicode=cfg.unicode if p.unicode is None else p.unicode, sort=SortStrategy.IndexAsc, scoring=p.scoring or cfg.scoring,
+                      pf_lanes=cfg.pf_lanes, sw_lanes=cfg.sw_lanes, matching=cfg.matching if p.matching is None else p.matching)
+
+    def compile(self, patterns, cfg=None):
+        """list[Pattern] -> [(Pattern with a bytes needle, resolved Config, (unicode, pf_lanes, sw_lanes))], empty needles dropped; host work"""
+        cfg = cfg or self.config
+        out = []
+        for p in patterns:
+            p = p if isinstance(p, Pattern) else Pattern(p)
+            n = _b(p.needle)
+            if not n:
+                continue
+            p = replace(p, needle=bytes(n))
+            r = self._resolved(p, cfg)
+            key = (p.needle, r.max_typos, int(r.casing), int(r.unicode), r.pf_lanes, r.sw_lanes, int(r.matching))
+            if key not in self._paths:
+                i = Matcher(p.needle, r).info()
+                self._paths[key] = (i["unicode"], i["pf_lanes"], i["sw_lanes"])
+            out.append((p, r, self._paths[key]))
+        return out
+
+    @staticmethod
+    def refines(old, new):
+        """Q[i] refines P[i] (entries of `compile`)"""
+        (po, ro, patho), (pn, rn, pathn) = old, new
+        if po == pn and patho == pathn:
+            return True
+        if po.negated or pn.negated or replace(po, needle=pn.needle) != pn:
+            return False
+        return _needle_extends(rn.matching, rn.max_typos, po.needle, pn.needle, patho, pathn)
+
+    @classmethod
+    def rule(cls, P, Q):
+        """the pattern part of the rule over two `compile`d lists"""
+        if len(Q) < len(P) or not all(cls.refines(o, n) for o, n in zip(P, Q)):
+            return False
+        return [e[0] for e in Q] != [e[0] for e in P]
+
+    def _within_key(self):
+        w = self.within
+        return None if w is None else (id(w), w.info()["generation"])
+
+    def _may_narrow(self, Q):
+        if self._cur is None or self._prev is None:
+            return False
+        P, prev_cfg, prev_gen, prev_within = self._prev
+        if prev_cfg != self.config or not self.rule(P, Q):
+            return False
+        if self.corpus.generation() != prev_gen or self._within_key() != prev_within:
+            return False
+        cap = self.subsets[self._cur]
+        out = (C.c_uint64 * 4)()
+        _check(lib().fzb_subset_info(cap.h, out))
+        return self.max_fraction > 0 and bool(out[0]) and out[1] <= self.max_fraction * len(self.corpus)
+
+    def set_config(self, config):
+        self.matcher.set_config(config)
+        self.config = config
+
+    def query(self, text, limit, indices=False):
+        """what `MultiMatcher.match_list_top` (indices=False) / `match_list_top_indices` (True) return for the query string `text` (or a list
+        of `Pattern`s) over `within`; `last_narrowed` tells whether the previous capture was the input"""
+        pats = parse_query(text) if isinstance(text, (str, bytes)) else list(text)
+        Q = self.compile(pats)
+        narrow = self._may_narrow(Q)
+        src = self.subsets[self._cur] if narrow else self.within
+        dst_i = 1 - self._cur if self._cur is not None else 0
+        dst = self.subsets[dst_i]
+        self._cur = self._prev = None  # (an error below leaves no capture to narrow from)
+        self.matcher.set_patterns(pats)
+        fn = self.matcher.match_list_top_indices if indices else self.matcher.match_list_top
+        res = fn(self.corpus, limit, subset=src, capture=dst)
+        self._cur, self._prev, self.last_narrowed = dst_i, (Q, deepcopy(self.config), self.corpus.generation(), self._within_key()), narrow
         return res
 
 

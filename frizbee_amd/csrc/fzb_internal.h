@@ -291,6 +291,9 @@ void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u3
 void fzb_launch_join_add(fzb_match_rec* hits, const u32* n_hits_ptr, const fzb_match_rec* cand, const u32* n_cand_ptr, int grid, hipStream_t st);
 void fzb_launch_remove_hits(const fzb_match_rec* cand, const u32* n_cand_ptr, const fzb_match_rec* hits, const u32* n_hits_ptr, u64* bitmap, u32* tile_counts,
                             fzb_match_rec* out, u32* total_out, int grid, hipStream_t st);
+void fzb_launch_items_records(fzb_match_rec* out, const u32* items, const u32* n_ptr, u32 capacity, u32 hint, u32 index_offset, u32* count_out, int grid_max, hipStream_t st);
+void fzb_launch_copy_capture_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, u32 index_offset, u32* items, u32 items_cap,
+                                     u32* items_count, u32* mirror, int grid, hipStream_t st);
 void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, int grid, hipStream_t st);
 // kernels_subset.hip: the candidate sets' capture (index-ordered records -> ascending haystack indices + their count; mirror: a second word for the
 // count, may be null) and fzb_subset_from_scope's flag pass + k_compact1

@@ -2007,14 +2007,21 @@ static const u32* subset_items(const SubsetArgs* sa) { return sa && sa->in ? sa-
 static const u32* subset_count(const SubsetArgs* sa) { return sa && sa->in ? sa->in->count_dev : nullptr; }
 // what the host knows of the input's length (the filter's choice of kernel and grid): the count when known, else the room it was captured into
 static u64 subset_hint(const SubsetArgs* sa) { return sa && sa->in ? std::max<u64>(1, sa->in->known ? sa->in->count : (u64)sa->in->cap) : 0; }
-// the ONE place that launches the capture: recs = the producer's index-ordered records (numbered from index_offset 0 over the whole corpus)
+// what every capture leaves on the handle: the count lives on the device until a host form's wait, or fzb_subset_info, brings it back
+static void subset_captured(fzb_subset* cp, const fzb_corpus* c) {
+    cp->generation = c->generation;
+    cp->known = false;
+}
+// test and benchmark hook: 0 = the composition's final copy and the capture as two launches (k_copy_records, k_subset_capture), else fused
+static int g_debug_fused_capture = 1;
+// the ONE place that launches the capture of a producer's records (the composition's final copy does its own, fused: multi_compose_device):
+// recs = the producer's index-ordered records (numbered from index_offset 0 over the whole corpus)
 static int subset_capture(const SubsetArgs* sa, const fzb_corpus* c, const fzb_match_rec* recs, const u32* pair, size_t cap, int grid_max, hipStream_t st) {
     if (!sa || !sa->capture) return FZB_OK;
     fzb_subset* cp = sa->capture;
     fzb_launch_subset_capture(recs, pair, (u32)std::min<size_t>(cap, 0xFFFFFFFFu), 0, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu), cp->count_dev, sa->mirror, grid_max, st);
     HIPCHK(hipGetLastError());
-    cp->generation = c->generation;
-    cp->known = false;
+    subset_captured(cp, c);
     return FZB_OK;
 }
 extern "C" {
@@ -2772,6 +2779,8 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     return FZB_OK;
 }
 
+void fzb_debug_set_fused_capture(int on) { g_debug_fused_capture = on ? 1 : 0; }
+
 int fzb_debug_device_allocs(uint64_t* out) {
     if (!out) return fail(FZB_ERR_INVALID, "null argument");
     *out = g_fzb_dev_allocs.load(std::memory_order_relaxed);
@@ -2806,8 +2815,11 @@ int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, si
 
 }  // extern "C"
 // the composition alone: the patterns' scores summed, no score bias
+// (sa->in: the candidate set the FIRST step runs over - the base pattern's pipeline, the Single shortcut's, or the identity records of the
+// no-pattern and all-negated cases -; every later pattern runs over the candidates' items either way.  sa->capture: the Multi case's final copy
+// writes the capture too (k_copy_capture_records) and says so in *captured; the Empty and Single cases leave it to the caller's subset_capture.)
 static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
-                                uint32_t* dev_count, void* stream) {
+                                uint32_t* dev_count, void* stream, const SubsetArgs* sa = nullptr, bool* captured = nullptr) {
     if (!mm || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
     if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
@@ -2823,12 +2835,16 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     }
     // CompiledPatterns::{Empty, Single, Multi} (src/matcher/mod.rs:178-190; a single NEGATED pattern is Multi)
     if (ps.empty()) {
-        if (count > capacity) return fail(FZB_ERR_CAPACITY, "output buffer smaller than the haystack list (no pattern: every haystack matches)");
-        fzb_launch_identity_records((fzb_match_rec*)dev_out, (u32)count, index_offset, dev_count, cus * 2, st);
+        // (over a candidate set: its count when the host knows it, else the room it was captured into - never more than the list)
+        const size_t need = subset_items(sa) ? (size_t)std::min<u64>(subset_hint(sa), count) : count;
+        if (need > capacity) return fail(FZB_ERR_CAPACITY, "output buffer smaller than the haystack list (no pattern: every haystack matches)");
+        if (subset_items(sa)) fzb_launch_items_records((fzb_match_rec*)dev_out, subset_items(sa), subset_count(sa), cap32, (u32)need, index_offset, dev_count, cus * 2, st);
+        else fzb_launch_identity_records((fzb_match_rec*)dev_out, (u32)count, index_offset, dev_count, cus * 2, st);
         HIPCHK(hipGetLastError());
         return FZB_OK;
     }
-    if (ps.size() == 1 && !ps[0].negated) return run_pipeline(ps[0].m, c, first, count, index_offset, nullptr, nullptr, dev_out, capacity, dev_count, stream);
+    if (ps.size() == 1 && !ps[0].negated)
+        return run_pipeline(ps[0].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), dev_out, capacity, dev_count, stream, nullptr, subset_hint(sa));
     if (int rc_ = multi_ensure_buffers(mm, count)) return rc_;
     // match_list_multi_into (src/matcher/multi.rs:84-152)
     size_t base = ps.size();
@@ -2837,8 +2853,11 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     int cur = 0;  // cand[cur] / counts[cur] = the candidates
     int rc;
     if (base != ps.size()) {
-        rc = run_pipeline(ps[base].m, c, first, count, index_offset, nullptr, nullptr, (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], stream);
+        rc = run_pipeline(ps[base].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], stream, nullptr, subset_hint(sa));
         if (rc) return rc;
+    } else if (subset_items(sa)) {  // all patterns negated over a candidate set: every haystack of the set is a candidate
+        fzb_launch_items_records(mm->cand[0], subset_items(sa), subset_count(sa), (u32)std::min<size_t>(mm->cap, count), (u32)std::min<u64>(subset_hint(sa), count), index_offset, &mm->counts[4 * 0],
+                                 cus * 2, st);
     } else {
         fzb_launch_identity_records(mm->cand[0], (u32)count, index_offset, &mm->counts[4 * 0], cus * 2, st);  // all patterns negated: every haystack is a candidate
     }
@@ -2862,6 +2881,15 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
             cur = oth;
         }
     }
+    if (sa && sa->capture && captured && g_debug_fused_capture) {
+        fzb_subset* cp = sa->capture;
+        fzb_launch_copy_capture_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
+                                        cp->count_dev, sa->mirror, cus * 2, st);
+        HIPCHK(hipGetLastError());
+        subset_captured(cp, c);
+        *captured = true;
+        return FZB_OK;
+    }
     fzb_launch_copy_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
     HIPCHK(hipGetLastError());
     return FZB_OK;
@@ -2869,26 +2897,39 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
 extern "C" {
 
 // (on a biased corpus the bias is added ONCE per record, after the composition's sum; with no pattern every haystack's score is its bias)
-int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
-                                uint32_t* dev_count, void* stream) {
+// (sa: the candidate-set forms - the composition runs over `in`, and the COMPOSED records are captured where the single forms capture theirs:
+// ahead of the list's terms.  A composition of several patterns captures in its final copy; the no-pattern and Single cases have no such copy
+// and take subset_capture's launch.)
+static int multi_match_list_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+                                        uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     int rc;
     if (mm && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the composition into the scratch (with no pattern: identity records), then drop, then bias
         if ((rc = fzb_scope_ensure(mm->scope, count))) return rc;
-        if ((rc = multi_compose_device(mm, c, first, count, index_offset, (fzb_match*)mm->scope.recs, count, mm->scope.words, stream))) return rc;
+        bool captured = false;
+        if ((rc = multi_compose_device(mm, c, first, count, index_offset, (fzb_match*)mm->scope.recs, count, mm->scope.words, stream, sa, &captured))) return rc;
+        if (!captured && (rc = subset_capture(sa, c, mm->scope.recs, mm->scope.words, count, mm->num_cus * 2, (hipStream_t)stream))) return rc;
         return apply_terms(c, mm->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
     }
-    rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream);
+    bool captured = false;
+    rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream, sa, &captured);
     if (rc) return rc;
+    if (count && !captured && (rc = subset_capture(sa, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), mm->num_cus * 2, (hipStream_t)stream))) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
 }
+int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+                                uint32_t* dev_count, void* stream) {
+    return multi_match_list_device_impl(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream, nullptr);
+}
 
-int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len) {
+static int multi_match_list_impl(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len, const SubsetArgs* sa);
+int fzb_multi_match_list(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len) { return multi_match_list_impl(mm, c, out, out_len, nullptr); }
+static int multi_match_list_impl(fzb_multi_matcher* mm, const fzb_corpus* c, fzb_match** out, size_t* out_len, const SubsetArgs* sa) {
     if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     const size_t count = c->dev.n;
     *out = nullptr;
     *out_len = 0;
     if (int rc_ = fzb_out_ensure(*mm, count)) return rc_;
-    int rc = fzb_multi_match_list_device(mm, c, 0, count, 0, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr);
+    int rc = multi_match_list_device_impl(mm, c, 0, count, 0, (fzb_match*)mm->out_dev, mm->out_cap, mm->count_dev, nullptr, sa);
     if (rc) return rc;
     // Matcher::match_list (src/matcher/mod.rs:212-222): reverse, then the stable radix sort unless there is no pattern at all
     const int sort = mm->config.sort;
@@ -3097,10 +3138,12 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
 // The top stage of a `from_patterns` matcher on `st`: the composition over the n haystacks into the sort's second buffer (its pair in
 // raw_count), the selection of the best `want` and their ordering into `head` (room for `want` records; its pair - records, matches found -
 // in head_count).  Nothing is read back.
-static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n, size_t want, fzb_match_rec* head, u32* head_count, u32* raw_count, hipStream_t st) {
+// (sa: the composition runs over the candidate set and its records are captured; the selection and the ordering see no difference)
+static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n, size_t want, fzb_match_rec* head, u32* head_count, u32* raw_count, hipStream_t st,
+                           const SubsetArgs* sa = nullptr) {
     int rc;
     if ((rc = fzb_sort_ensure(mm->sort, n))) return rc;
-    if ((rc = fzb_multi_match_list_device(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st))) return rc;
+    if ((rc = multi_match_list_device_impl(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st, sa))) return rc;
     const int sort = mm->config.sort;
     const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
     const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
@@ -3114,7 +3157,11 @@ static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n,
 }
 extern "C" {
 
+static int multi_match_list_top_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found, const SubsetArgs* sa);
 int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    return multi_match_list_top_impl(mm, c, limit, out, out_len, out_found, nullptr);
+}
+static int multi_match_list_top_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found, const SubsetArgs* sa) {
     if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
@@ -3123,7 +3170,7 @@ int fzb_multi_match_list_top(fzb_multi_matcher* mm, const fzb_corpus* c, size_t 
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
     int rc;
-    if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + 4, nullptr))) return rc;
+    if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + 4, nullptr, sa))) return rc;
     return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
 }
 
@@ -3746,8 +3793,15 @@ bool same_union_src(const IUnionSrc& a, const IUnionSrc& b) { return a.rec == b.
 }  // namespace
 extern "C" {
 
+static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                         size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
                                             size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
+}
+// (sa: only the top stage sees the candidate set and captures; the traced passes run over the head's item list as before)
+static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                         size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!mm || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
@@ -3786,7 +3840,8 @@ int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_cor
     u32* const head_count = mm->top_words;      // (records, matches found) of the head
     u32* const comb_count = mm->top_words + 2;  // the combined traced pair
     u32* const n_items = mm->top_words + 10;
-    if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 8, st))) return rc;
+    // (the composition's pair in words 12-13: word 8 follows the host form's four result words, where its wait picks up a captured count)
+    if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 12, st, sa))) return rc;
     const int grid = mm->num_cus * 2;
     fzb_launch_top_items(mm->top_head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
     for (auto& p : mm->patterns) {
@@ -3803,7 +3858,14 @@ int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_cor
     return FZB_OK;
 }
 
+static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
+                                        const SubsetArgs* sa);
 int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr);
+}
+// (sa: `in` and `capture` as the caller gave them; the mirror word is set here.  A no-pattern matcher never gets here with a subset.)
+static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
+                                        const SubsetArgs* sa) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
@@ -3819,9 +3881,102 @@ int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corp
     int rc;
     if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, true))) return rc;
     u32* const words = mm->top_words + 4;
-    if ((rc = fzb_multi_match_list_top_indices_device(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr))) return rc;
-    return fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out,
-                             out_len, out_positions, out_found);
+    fzb_subset* const capture = sa ? sa->capture : nullptr;
+    const SubsetArgs with_mirror{sa ? sa->in : nullptr, capture, capture ? mm->top_words + 8 : nullptr};
+    if ((rc = multi_top_indices_device_impl(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr, sa ? &with_mirror : nullptr)))
+        return rc;
+    u32 captured = 0;
+    rc = fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out, out_len,
+                           out_positions, out_found, capture ? &captured : nullptr);
+    if (rc) return rc;
+    subset_capture_known(capture, captured);
+    return FZB_OK;
+}
+
+// ---- candidate sets on the `from_patterns` forms -----------------------------------------------------------------------------------------
+// The single-matcher forms' contract for the composition: the query over `in` returns what it returns over a corpus of those haystacks alone,
+// `capture` receives the haystacks the COMPOSITION accepted (every non-negated pattern hit, no negated one did), taken ahead of bias, scope,
+// selection and ordering.  A matcher with no compiled pattern accepts every haystack of `in`: the capture is `in` itself (subset_capture_trivial)
+// and the query runs with the input alone.
+int fzb_multi_match_list_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len) {
+    if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_subset");
+    if (rc) return rc;
+    if (mm->patterns.empty() || c->dev.n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        capture = nullptr;
+    }
+    if (!in && !capture) return fzb_multi_match_list(mm, c, out, out_len);
+    if ((rc = fzb_out_ensure(*mm, c->dev.n))) return rc;
+    SubsetArgs sa{in, capture, capture ? mm->count_dev + 6 : nullptr};
+    if ((rc = multi_match_list_impl(mm, c, out, out_len, &sa))) return rc;
+    subset_capture_known(capture, mm->fetch.count_host[6]);
+    return FZB_OK;
+}
+
+int fzb_multi_match_list_top_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match** out, size_t* out_len,
+                                    uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    if (out_found) *out_found = 0;
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_subset");
+    if (rc) return rc;
+    if (mm->patterns.empty() || c->dev.n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        capture = nullptr;
+    }
+    if (!in && !capture) return fzb_multi_match_list_top(mm, c, limit, out, out_len, out_found);
+    if ((rc = fzb_out_ensure(*mm, std::min(limit, (size_t)c->dev.n)))) return rc;
+    SubsetArgs sa{in, capture, capture ? mm->count_dev + 6 : nullptr};
+    if ((rc = multi_match_list_top_impl(mm, c, limit, out, out_len, out_found, &sa))) return rc;
+    subset_capture_known(capture, mm->fetch_top.count_host[6]);
+    return FZB_OK;
+}
+
+int fzb_multi_match_list_top_subset_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match* dev_out, size_t capacity,
+                                           uint32_t* dev_count, void* stream) {
+    if (!mm || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_subset");
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_subset_device");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        HIPCHK(hipMemsetAsync(dev_count, 0, 8, (hipStream_t)stream));
+        return FZB_OK;
+    }
+    if ((rc = fzb_out_ensure(*mm, 0))) return rc;  // (the composition's pair lives next to the staging's count words)
+    SubsetArgs sa{in, capture, nullptr};
+    return multi_top_stage(mm, c, n, want, (fzb_match_rec*)dev_out, dev_count, mm->count_dev + 4, (hipStream_t)stream, &sa);
+}
+
+int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
+                                            uint32_t** out_positions, uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_indices_subset");
+    if (rc) return rc;
+    if (mm->patterns.empty() || c->dev.n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        if (!in) return fzb_multi_match_list_top_indices_fused(mm, c, limit, out, out_len, out_positions, out_found);
+        std::vector<fzb_match> head;  // no pattern over a candidate set: the single form's host list, no positions
+        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), mm->config.sort, limit, head, out_found))) return rc;
+        std::vector<fzb_match_indices> recs(head.size());
+        for (size_t i = 0; i < head.size(); i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};
+        return hand_over_indices(recs.data(), recs.size(), nullptr, 0, out, out_len, out_positions);
+    }
+    if (!in && !capture) return fzb_multi_match_list_top_indices_fused(mm, c, limit, out, out_len, out_positions, out_found);
+    SubsetArgs sa{in, capture, nullptr};
+    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, &sa);
 }
 
 // fzb_matcher_reserve_top_indices for the composition: every sub-matcher slot (the spares too) gets the trace buffers and the traced scorer's

@@ -28,6 +28,23 @@ __global__ __launch_bounds__(256) void k_identity_records(fzb_match_rec* __restr
     if (blockIdx.x == 0 && threadIdx.x == 0) { count_out[0] = n; count_out[1] = n; }
 }
 
+// the same over a candidate set: every haystack of the item list (ascending indices, *n_ptr of them - the count lives on the device: after a
+// capture the host does not know it) is a candidate with score 0; capacity bounds the records written, the pair's second word is the set's size
+__global__ __launch_bounds__(256) void k_items_records(fzb_match_rec* __restrict__ out, const u32* __restrict__ items, const u32* __restrict__ n_ptr, u32 capacity, u32 index_offset,
+                                                       u32* __restrict__ count_out) {
+    const u32 total = *n_ptr;
+    const u32 n = min(total, capacity);
+    for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        fzb_match_rec r;
+        r.index = index_offset + items[j];
+        r.score = 0;
+        r.exact = 0;
+        r.valid = 0;
+        out[j] = r;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { count_out[0] = n; count_out[1] = total; }
+}
+
 // position of the record with `index` in the index-ascending list, or n if absent
 __device__ __forceinline__ u32 find_index(const fzb_match_rec* __restrict__ list, u32 n, u32 index) {
     u32 lo = 0, hi = n;
@@ -81,11 +98,38 @@ __global__ __launch_bounds__(256) void k_copy_records(const fzb_match_rec* __res
     if (blockIdx.x == 0 && threadIdx.x == 0) { count_out[0] = n; count_out[1] = total; }  // [1] = the untruncated total
 }
 
+// k_copy_records and k_subset_capture (kernels_subset.hip) in one pass, for a composition whose match set is captured: the final records -> the
+// caller's array AND their haystack indices -> the capture's item list, the two counts beside them.  No compaction: the records are in index
+// order already, so record j's index is item j (mirror: the host forms' word, may be null).
+__global__ __launch_bounds__(256) void k_copy_capture_records(const fzb_match_rec* __restrict__ in, const u32* __restrict__ n_ptr, fzb_match_rec* __restrict__ out, u32 capacity,
+                                                              u32* __restrict__ count_out, u32 index_offset, u32* __restrict__ items, u32 items_cap, u32* __restrict__ items_count,
+                                                              u32* __restrict__ mirror) {
+    const u32 total = *n_ptr;
+    const u32 n = min(total, capacity);
+    const u32 kept = min(n, items_cap);
+    for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        const fzb_match_rec r = in[j];
+        out[j] = r;
+        if (j < kept) items[j] = r.index - index_offset;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        count_out[0] = n;
+        count_out[1] = total;  // [1] = the untruncated total
+        *items_count = kept;
+        if (mirror) *mirror = kept;
+    }
+}
+
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st) {
     FZB_LAUNCH(k_records_to_items, dim3(grid), dim3(256), 0, st, cand, n_ptr, index_offset, items);
 }
 void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u32* count_out, int grid, hipStream_t st) {
     FZB_LAUNCH(k_identity_records, dim3(grid), dim3(256), 0, st, out, n, index_offset, count_out);
+}
+// hint: what the host knows of the item list's length (its count, or the room it was captured into) - the grid's bound, not the loop's
+void fzb_launch_items_records(fzb_match_rec* out, const u32* items, const u32* n_ptr, u32 capacity, u32 hint, u32 index_offset, u32* count_out, int grid_max, hipStream_t st) {
+    const int grid = tc_grid(((u64)(hint < capacity ? hint : capacity) + 255u) / 256u, grid_max);
+    FZB_LAUNCH(k_items_records, dim3(grid), dim3(256), 0, st, out, items, n_ptr, capacity, index_offset, count_out);
 }
 void fzb_launch_join_add(fzb_match_rec* hits, const u32* n_hits_ptr, const fzb_match_rec* cand, const u32* n_cand_ptr, int grid, hipStream_t st) {
     FZB_LAUNCH(k_join_add, dim3(grid), dim3(256), 0, st, hits, n_hits_ptr, cand, n_cand_ptr);
@@ -94,6 +138,10 @@ void fzb_launch_remove_hits(const fzb_match_rec* cand, const u32* n_cand_ptr, co
                             fzb_match_rec* out, u32* total_out, int grid, hipStream_t st) {
     FZB_LAUNCH(k_flag_absent, dim3(grid), dim3(256), 0, st, cand, n_cand_ptr, hits, n_hits_ptr, bitmap, tile_counts);
     FZB_LAUNCH(k_compact_records, dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_cand_ptr, cand, out, total_out);
+}
+void fzb_launch_copy_capture_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, u32 index_offset, u32* items, u32 items_cap,
+                                     u32* items_count, u32* mirror, int grid, hipStream_t st) {
+    FZB_LAUNCH(k_copy_capture_records, dim3(grid), dim3(256), 0, st, in, n_ptr, out, capacity, count_out, index_offset, items, items_cap, items_count, mirror);
 }
 void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, int grid, hipStream_t st) {
     FZB_LAUNCH(k_copy_records, dim3(grid), dim3(256), 0, st, in, n_ptr, out, capacity, count_out);

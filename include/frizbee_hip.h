@@ -525,9 +525,14 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
  * _truncate, _remove, _remove_device, _replace; not _set_bias, _set_tags, _set_scope, _reserve, nor a call that changed nothing.  A subset
  * records the generation when it is created, filled or captured into; a query handed an input subset of another corpus or of an older
  * generation is refused with FZB_ERR_INVALID (the message says "subset" and "stale"), nothing launched.
- * OUT OF SCOPE: the fzb_multi_matcher forms (a negated pattern's match set GROWS as it is typed: the composition needs its own design), the
- * sharded and RCCL forms, fzb_match_list_indices (its `selection` already is a subset), and a density switch inside the library (streaming
- * the whole list and intersecting when S covers most of it): the caller decides when a subset pays (frizbee_amd.NarrowingMatcher). */
+ * The fzb_multi_matcher forms take a candidate set too (fzb_multi_match_list_subset and its siblings, below the composition's own calls):
+ * the device path is the same - only the composition's first step ever saw the whole range - and the capture is the COMPOSITION's match set.
+ * When the previous capture may be the next query's input is the caller's rule, never the library's: a negated pattern's match set GROWS as
+ * it is typed (`!t` -> `!te` removes fewer haystacks), so only an unchanged negated pattern keeps a capture usable
+ * (frizbee_amd.NarrowingQuery holds the whole rule).
+ * OUT OF SCOPE: the sharded and RCCL forms, the range forms (_into, _device with first / count), the list-order _indices forms
+ * (fzb_match_list_indices: its `selection` already is a subset), and a density switch inside the library (streaming the whole list and
+ * intersecting when S covers most of it): the caller decides when a subset pays (frizbee_amd.NarrowingMatcher, NarrowingQuery). */
 typedef struct fzb_subset fzb_subset;
 /* the list's generation: 0 after fzb_corpus_upload, + 1 for every call that changed the list (fzb_corpus_info's array stays 12 long) */
 int fzb_corpus_generation(const fzb_corpus* c, uint64_t* out);
@@ -640,6 +645,28 @@ int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corp
  * buffers and traced scorer's matrices (spare slots included), the unions for U = slots x max_needle_bytes and the host form's staging.
  * The exceptions of fzb_matcher_reserve_top_indices apply (a needle beyond 64 bytes / 63 rows, another scoring or lane pair). */
 int fzb_multi_matcher_reserve_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, size_t max_needle_bytes);
+/* CANDIDATE SETS for the composition (see fzb_match_list_subset: the same argument order, contract, staleness rules and refusals).  `in` ==
+ * NULL: exactly the launches of the call without _subset.  With `in`, the composition's FIRST step - the first non-negated pattern's
+ * pipeline, or the identity records when every pattern is negated - runs over the set's item list; every later pattern runs over the
+ * candidates as before.  `capture` receives the ascending indices of every haystack of `in` the COMPOSITION accepted (every non-negated
+ * pattern hit, no negated one did), taken between the composition and the list's terms: it does not depend on `limit`, the sort strategy, the
+ * bias or the scope.  A composition of several patterns captures in the launch that writes its final records (k_copy_capture_records: no
+ * launch more than without a capture); a lone non-negated pattern and no pattern at all take the single forms' capture launch.  The host forms
+ * bring the count back in the wait they make anyway, after the _device form it is unknown until fzb_subset_info is asked.  After fzb_multi_matcher_reserve(mm, c)
+ * (and fzb_multi_matcher_reserve_top_indices for the form with positions) no subset query allocates device memory.
+ * A matcher with NO COMPILED PATTERN lists the haystacks of `in` - score 0 or the clamped bias, hidden ones dropped, ordered as the empty
+ * prompt of the calls without _subset - and the capture becomes `in` itself; the _device form refuses it, as
+ * fzb_multi_match_list_top_indices_device does.
+ * _subset: fzb_multi_match_list's order.  _top_subset: fzb_multi_match_list_top.  _top_subset_device: the same head into dev_out (room for
+ * min(limit, haystacks)), dev_count = (records written, found), on `stream`, nothing read back.  _top_indices_subset:
+ * fzb_multi_match_list_top_indices_fused - only its top stage sees the set, the traced passes run over the head as before. */
+int fzb_multi_match_list_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len);
+int fzb_multi_match_list_top_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match** out, size_t* out_len,
+                                    uint64_t* out_found);
+int fzb_multi_match_list_top_subset_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match* dev_out, size_t capacity,
+                                           uint32_t* dev_count, void* stream);
+int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out,
+                                            size_t* out_len, uint32_t** out_positions, uint64_t* out_found);
 /* list-order forms (see fzb_match_list_into / fzb_match_list_indices_into): `Matcher::match_list_into` over CompiledPatterns
  * (src/matcher/mod.rs:373-392) with the result on the host, and what `match_iter` / `match_one` / `match_iter_indices` yield
  * (`match_one_multi`, `match_one_indices_multi`, src/matcher/multi.rs:29-82) */
@@ -724,6 +751,11 @@ void fzb_debug_set_filter_grid(int grid);
 /* test hook: item lists of a candidate set (fzb_subset) that hold at least n items - as far as the host knows - take the filter kernel for large
  * candidate sets where it applies (fuzzy, ASCII, 0 typos), so that small lists exercise it; 0 = the measured default */
 void fzb_debug_set_items_dfa_min(uint32_t n);
+
+/* test and benchmark hook: on == 0 makes a composition of several patterns whose match set is captured (fzb_multi_match_list_subset and its
+ * siblings) write its final records and the capture in two launches (k_copy_records, k_subset_capture) instead of one
+ * (k_copy_capture_records, the default); the results are the same */
+void fzb_debug_set_fused_capture(int on);
 
 /* test hook: the library's environment switches (frizbee_amd/csrc/knobs.h - comparison and debugging only, parsed once on first use) are
  * read again.  Matchers created before the call keep what was decided when they were created. */

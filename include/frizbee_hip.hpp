@@ -281,7 +281,7 @@ class Corpus {
 // A candidate set of one resident Corpus (fzb_subset): strictly ascending haystack indices in HBM - the input or the captured match set of
 // Matcher::match_list / match_list_top / match_list_top_device / match_list_top_indices with a Subset.  A query over a subset returns what it
 // returns over an upload of those haystacks alone, every index that of the full list.  The reference has no counterpart.  The corpus must
-// outlive the subset; single-pattern matchers only.
+// outlive the subset.
 class Subset {
   public:
     explicit Subset(const Corpus& corpus) : corpus_(corpus.raw()) {
@@ -476,33 +476,40 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_match_list_top_indices_device(single_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
         else check(fzb_multi_match_list_top_indices_device(multi_.get(), corpus.raw(), limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream));
     }
-    // The same four calls over a candidate set (fzb_match_list_subset and friends; a single plain pattern only): `in` = the haystacks looked
-    // at (nullptr: the whole corpus), `capture` (nullptr: none) receives the indices of every haystack the matcher accepted - before bias,
-    // scope, limit and ordering.  in == capture is refused: alternate two subsets.
+    // The same four calls over a candidate set (fzb_match_list_subset / fzb_multi_match_list_subset and friends): `in` = the haystacks looked
+    // at (nullptr: the whole corpus), `capture` (nullptr: none) receives the indices of every haystack the matcher - `from_patterns`: the
+    // composition - accepted, before bias, scope, limit and ordering.  in == capture is refused: alternate two subsets.
     std::vector<Match> match_list(const Corpus& corpus, const Subset* in, Subset* capture) {
         fzb_match* out = nullptr;
         size_t n = 0;
-        check(fzb_match_list_subset(single_only("match_list"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, &out, &n));
+        if (single_) check(fzb_match_list_subset(single_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, &out, &n));
+        else check(fzb_multi_match_list_subset(multi_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, &out, &n));
         return take(out, n);
     }
     std::vector<Match> match_list_top(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, size_t* found = nullptr) {
         fzb_match* out = nullptr;
         size_t n = 0;
         uint64_t f = 0;
-        check(fzb_match_list_top_subset(single_only("match_list_top"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &f));
+        if (single_) check(fzb_match_list_top_subset(single_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &f));
+        else check(fzb_multi_match_list_top_subset(multi_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &f));
         if (found) *found = (size_t)f;
         return take(out, n);
     }
     void match_list_top_device(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream = nullptr) {
-        check(fzb_match_list_top_subset_device(single_only("match_list_top_device"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, dev_out, capacity,
-                                               dev_count, stream));
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_) check(fzb_match_list_top_subset_device(single_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
+        else check(fzb_multi_match_list_top_subset_device(multi_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
     }
     std::vector<MatchIndices> match_list_top_indices(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, size_t* found = nullptr) {
         fzb_match_indices* out = nullptr;
         uint32_t* pos = nullptr;
         size_t n = 0;
         uint64_t f = 0;
-        check(fzb_match_list_top_indices_subset(single_only("match_list_top_indices"), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &pos, &f));
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_) check(fzb_match_list_top_indices_subset(single_.get(), corpus.raw(), i, cp, limit, &out, &n, &pos, &f));
+        else check(fzb_multi_match_list_top_indices_subset(multi_.get(), corpus.raw(), i, cp, limit, &out, &n, &pos, &f));
         if (found) *found = (size_t)f;
         std::vector<MatchIndices> v(n);
         for (size_t i = 0; i < n; i++)
@@ -672,10 +679,6 @@ class Matcher {  // src/matcher/mod.rs:77-222
         for (size_t i = 0; i < n; i++) r[i] = Match{out[i].index, out[i].score, out[i].exact != 0};
         fzb_matches_free(out);
         return r;
-    }
-    fzb_matcher* single_only(const char* call) const {  // the candidate-set forms: out of scope for `from_patterns` matchers
-        if (!single_) throw Error(FZB_ERR_INVALID, std::string(call) + " over a Subset: single-pattern matchers only");
-        return single_.get();
     }
     struct DelS { void operator()(fzb_matcher* m) const { fzb_matcher_free(m); } };
     struct DelM { void operator()(fzb_multi_matcher* m) const { fzb_multi_matcher_free(m); } };

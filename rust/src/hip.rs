@@ -142,6 +142,18 @@ extern "C" {
                                         dev_count: *mut u32, stream: *mut c_void) -> c_int;
     fn fzb_match_list_top_indices_subset(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
                                          out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    // the same four over a `from_patterns` matcher: the composition runs over `input`, `capture` receives the composition's match set
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize,
+                                       out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_subset_device(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize,
+                                              dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_indices_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
+                                               out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
     fn fzb_match_list_top_sharded(m: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_match_list_indices(m: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
                               out_positions: *mut *mut u32) -> c_int;
