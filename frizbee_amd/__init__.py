@@ -133,6 +133,7 @@ SYMBOLS = [
     "fzb_match_list_subset", "fzb_match_list_top_subset", "fzb_match_list_top_subset_device", "fzb_match_list_top_indices_subset",
     "fzb_multi_match_list_subset", "fzb_multi_match_list_top_subset", "fzb_multi_match_list_top_subset_device", "fzb_multi_match_list_top_indices_subset",
     "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
+    "fzb_prompt_list_device", "fzb_prompt_top_device",
 ]
 
 
@@ -274,6 +275,8 @@ def lib():
         l.fzb_multi_match_list_subset.argtypes = l.fzb_match_list_subset.argtypes
         l.fzb_multi_match_list_top_subset.argtypes = l.fzb_match_list_top_subset.argtypes
         l.fzb_multi_match_list_top_subset_device.argtypes = l.fzb_match_list_top_subset_device.argtypes
+        l.fzb_prompt_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_prompt_top_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.fzb_match_list_top_indices_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                         C.POINTER(C.c_uint64)]
         l.fzb_multi_match_list_top_indices_subset.argtypes = l.fzb_match_list_top_indices_subset.argtypes
@@ -993,6 +996,19 @@ class Matcher(_IterApi):
             _check(lib().fzb_match_list_top_device(self.h, corpus.h, limit, dev_out_ptr, capacity, dev_count_ptr, stream))
         else:
             _check(lib().fzb_match_list_top_subset_device(self.h, corpus.h, _h(subset), _h(capture), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
+
+    def prompt_list_device(self, corpus, dev_out_ptr, capacity, dev_count_ptr, stream=0, *, subset=None, first=0, count=None, index_offset=0):
+        """The empty prompt's index-ordered list left in HBM - `match_list_device` for a matcher whose needle is empty (the `_device` forms
+        refuse one): the haystacks of the range, or of `subset`, visible under the corpus' scope, score = the clamped bias (0 without one).
+        At most `capacity` records at `dev_out_ptr`, two count words (records written, found) at `dev_count_ptr`; asynchronous on `stream`."""
+        count = len(corpus) - first if count is None else count
+        _check(lib().fzb_prompt_list_device(self.h, corpus.h, _h(subset), first, count, index_offset, dev_out_ptr, capacity, dev_count_ptr, stream))
+
+    def prompt_top_device(self, corpus, limit, dev_out_ptr, capacity, dev_count_ptr, stream=0, *, subset=None):
+        """The empty prompt's ordered head left in HBM - `match_list_top_device` for a matcher whose needle is empty: `capacity` >=
+        min(limit, len(corpus)) records at `dev_out_ptr`, two count words (records written, found) at `dev_count_ptr`; asynchronous on
+        `stream`."""
+        _check(lib().fzb_prompt_top_device(self.h, corpus.h, _h(subset), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
 
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""

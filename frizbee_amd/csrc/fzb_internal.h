@@ -299,6 +299,12 @@ void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_matc
 // count, may be null) and fzb_subset_from_scope's flag pass + k_compact1
 void fzb_launch_subset_capture(const fzb_match_rec* recs, const u32* n_ptr, u32 cap, u32 index_offset, u32* items, u32 items_cap, u32* count_out, u32* mirror, int grid_max, hipStream_t st);
 void fzb_launch_subset_from_scope(const uint16_t* tags, u32 n, u32 require, u32 exclude, u64* bitmap, u32* tile_counts, u32* out, u32* count_out, int grid_max, hipStream_t st);
+// kernels_prompt.hip: the empty prompt's index-ordered records (prompt_records.h) and their (written, found) pair.  _records: the n haystacks
+// from `first`, no scope - one launch; _compact: an active scope (tags != nullptr) and / or a candidate set (items != nullptr, its count read
+// on the device, hint = what the host knows of it) - flag pass + stable compaction that writes the finished records.  bias may be null.
+void fzb_launch_prompt_records(fzb_match_rec* out, u32 n, u32 capacity, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, u32* count_out, int grid_max, hipStream_t st);
+void fzb_launch_prompt_compact(const u32* items, const u32* n_ptr, u32 n, u32 hint, const uint16_t* tags, u64 n_tags, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset,
+                               u32 require, u32 exclude, u64* bitmap, u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st);
 // kernels_literal.hip
 void fzb_launch_literal_filter(const CorpusDev& c, u64 first, u32 count, const u32* items, const u32* n_items_ptr, const NeedleDev& nd, int mode, u64* bitmap, u32* tile_counts,
                                int grid, hipStream_t st);

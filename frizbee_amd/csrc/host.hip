@@ -316,12 +316,15 @@ void fzb_sort_release(SortBuffers& s) {
     if (s.hist) (void)hipFree(s.hist);
     s = SortBuffers{};
 }
-int fzb_scope_ensure(ScopeScratch& s, size_t count) {
+int fzb_scope_ensure_flags(ScopeScratch& s, size_t count) {
     const size_t tiles = (count + SCOPE_TILE - 1) / SCOPE_TILE;
     int rc;
-    if ((rc = fzb_grow_dev(&s.recs, &s.recs_cap, count, 16)) || (rc = fzb_grow_dev(&s.bitmap, &s.bitmap_words, tiles * SCOPE_WORDS, 1)) || (rc = fzb_grow_dev(&s.tiles, &s.tiles_cap, tiles, 4)))
-        return rc;
+    if ((rc = fzb_grow_dev(&s.bitmap, &s.bitmap_words, tiles * SCOPE_WORDS, 1)) || (rc = fzb_grow_dev(&s.tiles, &s.tiles_cap, tiles, 4))) return rc;
     return fzb_grow_dev(&s.words, &s.words_cap, 16);
+}
+int fzb_scope_ensure(ScopeScratch& s, size_t count) {
+    if (int rc = fzb_grow_dev(&s.recs, &s.recs_cap, count, 16)) return rc;
+    return fzb_scope_ensure_flags(s, count);
 }
 void fzb_scope_release(ScopeScratch& s) {
     for (void* p : {(void*)s.recs, (void*)s.bitmap, (void*)s.tiles, (void*)s.words})
@@ -1312,7 +1315,99 @@ static int fetch_column(const V* col, size_t first, size_t count, std::vector<V>
     if (count) HIPCHK(hipMemcpy(out.data(), col + first, count * sizeof(V), hipMemcpyDeviceToHost));
     return FZB_OK;
 }
-// CompiledPatterns::Empty (an empty needle, no pattern) over a BIASED corpus - the picker's empty prompt, "most frecent first": every haystack
+// ---- THE EMPTY PROMPT: CompiledPatterns::Empty (an empty needle) over a corpus with a score bias, an active scope or a candidate set -------
+// The picker's first frame - "most frecent first", "the visible files", "this folder".  The rule (prompt_records.h): the haystacks of the
+// range, or of `in`, that are visible under the scope, in index order, each with score clamp(bias, 0, 65535) (0 without a bias) and exact 0;
+// reversed for the *Desc strategies; sorted stably by descending score for the Score* strategies ONLY over a biased corpus (a departure from
+// the reference, whose empty result is never sorted; without a bias every score is 0 and the reference's rule holds); found = the number
+// visible.  Everything runs on the device: the producer below writes the index-ordered records, the matcher's ordering and selection code
+// takes them from there, and the host forms copy back what they copy for any query - the head and the count pair, in their one wait.  No
+// column and no subset crosses the link.
+// The prompt's records on `st`: up to `capacity` records of [first, first + count) - or of `in`, whose count is read on the device - into
+// `out`, pair = (written, found).  One launch for a whole range without an active scope; flag pass + compaction otherwise (kernels_prompt.hip).
+// The matcher is bound (fzb_bind_device) by the caller.
+static int prompt_records(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, uint32_t index_offset, fzb_match_rec* out, size_t capacity, u32* pair,
+                          hipStream_t st) {
+    const u32 cap32 = (u32)std::min<size_t>(capacity, 0xFFFFFFFFu);
+    const int16_t* bias = fzb_corpus_bias(c);
+    const bool scoped = fzb_corpus_scoped(c);
+    const int cus = m->lc.num_cus;
+    if (!in && !scoped) {
+        fzb_launch_prompt_records(out, (u32)count, cap32, bias, c->dev.n, first, index_offset, pair, cus * 4, st);
+    } else {
+        if (int rc = fzb_scope_ensure_flags(m->scope, count)) return rc;
+        // (over a candidate set: its count when the host knows it, else the room it was captured into - never more than the list)
+        const u64 hint = in ? std::min<u64>(std::max<u64>(1, in->known ? in->count : (u64)in->cap), count) : count;
+        fzb_launch_prompt_compact(in ? in->idx : nullptr, in ? in->count_dev : nullptr, (u32)count, (u32)hint, scoped ? c->tags.data : nullptr, c->dev.n, bias, c->dev.n, first, index_offset,
+                                  c->scope_require, c->scope_exclude, m->scope.bitmap, m->scope.tiles, out, cap32, pair, cus * 2, st);
+    }
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+// What orders the prompt's list: the score is the clamped bias alone - no matrix score, no exact-match bonus - so a single radix pass / one
+// histogram level is decided by bias_hi alone (a `one_pass` that is wrongly true would make the selection read the low byte only), and
+// there is a score to sort by only over a biased corpus.
+static void prompt_order_flags(const fzb_matcher* m, const fzb_corpus* c, bool* reversed, bool* by_score, bool* one_pass) {
+    const int sort = m->config.sort;
+    *reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    *by_score = fzb_corpus_bias(c) != nullptr && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    *one_pass = sbias_one_pass(0, fzb_corpus_bias_hi(c));
+}
+// the list on `st`: index order (ordered = false: fzb_match_list_into, fzb_prompt_list_device) or what `match_list`'s post-step makes of it
+static int prompt_list_stage(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, uint32_t index_offset, bool ordered, fzb_match_rec* dev_out,
+                             size_t capacity, u32* dev_count, hipStream_t st) {
+    const size_t cap = std::min(capacity, count);
+    OrderPlan p;
+    prompt_order_flags(m, c, &p.reversed, &p.by_score, &p.one_pass);
+    if (!ordered) p.reversed = p.by_score = false;
+    p.via_tmp = p.by_score && p.one_pass && cap != 0;
+    p.in = dev_out;
+    int rc;
+    if (p.by_score) {
+        if ((rc = fzb_ensure_sort_buffers(m, cap))) return rc;
+        if (p.via_tmp) p.in = m->ws.sort.tmp;
+    }
+    if ((rc = prompt_records(m, c, in, first, count, index_offset, p.in, p.via_tmp ? cap : capacity, dev_count, st))) return rc;
+    return fzb_order_finish(m, p, dev_out, dev_count, st);
+}
+// the ordered head on `st`: the records into the sort's second buffer, the selection of the best `want` = min(limit, n) and their ordering
+// into dev_out (room for `want`), dev_count = (records, found)
+static int prompt_top_stage(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t want, fzb_match_rec* dev_out, u32* dev_count, hipStream_t st) {
+    const size_t n = c->dev.n;
+    int rc;
+    if ((rc = fzb_ensure_sort_buffers(m, n))) return rc;
+    if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
+    bool reversed, by_score, one_pass;
+    prompt_order_flags(m, c, &reversed, &by_score, &one_pass);
+    Workspace& w = m->ws;
+    u32* const raw_count = m->count_dev + 4;  // the producer's pair (records written, visible haystacks)
+    if ((rc = prompt_records(m, c, in, 0, n, 0, w.sort.tmp, n, raw_count, st))) return rc;
+    const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
+    const int grid = m->lc.num_cus * 2;
+    HIPCHK(fzb_launch_topk_select(w.sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, dev_out, (u32)want, dev_count, w.sort.hist, ntiles_cap, grid, st));
+    fzb_launch_sort(dev_out, w.sort.tmp, dev_count, w.sort.hist, ntiles_cap, reversed, by_score, grid, st, one_pass ? 1 : 2);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+// the host forms: the stage on the null stream into the matcher's staging, then the copy any query makes
+static int prompt_list_host(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, uint32_t index_offset, bool ordered, fzb_match** out, size_t* out_len) {
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = fzb_ensure_out_staging(m, count))) return rc;
+    if ((rc = prompt_list_stage(m, c, in, first, count, index_offset, ordered, m->out_dev, count, m->count_dev, nullptr))) return rc;
+    return fzb_fetch_records(m->fetch, m->out_dev, m->count_dev, 0, count, nullptr, out, out_len);
+}
+static int prompt_top_host(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    const size_t want = std::min<size_t>(limit, c->dev.n);
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = fzb_ensure_out_staging(m, want))) return rc;
+    if ((rc = prompt_top_stage(m, c, in, want, m->out_dev, m->count_dev, nullptr))) return rc;
+    return fzb_fetch_top(m->fetch_top, m->out_dev, m->count_dev, want, nullptr, out, out_len, out_found);
+}
+// does the device answer this matcher's query over [.., count) haystacks of c?  An empty needle over a non-empty range with a term or a
+// candidate set; everything else of an empty needle is the closed-form host answer (fzb_empty_pattern_top and its siblings)
+static bool prompt_on_device(const fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t count) { return m->empty && count != 0 && (in || corpus_terms(c)); }
+// The same list on the HOST, for the one caller without an fzb_matcher (the `from_patterns` matcher's top + positions form with no pattern,
+// empty_top_indices): CompiledPatterns::Empty (an empty needle, no pattern) over a BIASED corpus - the picker's empty prompt, "most frecent first": every haystack
 // of [first, first + count) matches with score clamp(bias, 0, 65535), and - unlike the reference's unsorted empty result - the list is ordered
 // per `sort` (reverse for the *Desc strategies, then the stable descending sort by score for the Score* ones), cut to `limit` records.
 // Host work: one copy of the bias and the host's stable sort.  *out: malloc'ed (fzb_matches_free); *out_found (optional) = count.
@@ -1951,9 +2046,15 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
     // (a corpus with room reserved: sized for that room, and for haystacks of any width - an append may bring them)
     const size_t n = fzb_corpus_reserved_items(c);
-    if (m->empty || n == 0) return FZB_OK;
+    if (n == 0) return FZB_OK;
     int rc = fzb_bind_device(m);
     if (rc) return rc;
+    if (m->empty) {  // the empty prompt (prompt_records): flag words, the sort's buffers (the selection's input) and the staging - with or without a scope or a bias
+        if ((rc = fzb_scope_ensure_flags(m->scope, n)) || (rc = fzb_ensure_out_staging(m, n)) || (rc = ensure_sort_buffers(m, n))) return rc;
+        if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, 32, hipHostMallocDefault));
+        if (!m->fetch.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch.count_host, 32, hipHostMallocDefault));
+        return FZB_OK;
+    }
     rc = ensure_workspace(m, n);
     if (rc) return rc;
     if (c->tags.data && (rc = fzb_scope_ensure(m->scope, n))) return rc;  // a corpus that carries tags: toggling its scope between queries allocates nothing
@@ -2229,7 +2330,7 @@ int fzb_match_list_into(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
         return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
     *out = nullptr;
     *out_len = 0;
-    if (m->empty && corpus_terms(c)) return biased_empty_list(c, first, count, index_offset, FZB_SORT_INDEX_ASC, count, out, out_len, nullptr);
+    if (prompt_on_device(m, c, nullptr, count)) return prompt_list_host(m, c, nullptr, first, count, index_offset, false, out, out_len);  // the empty prompt, index order
     if (m->empty) {  // src/matcher/mod.rs:381-384
         fzb_match* r = (fzb_match*)malloc(std::max<size_t>(count, 1) * sizeof(fzb_match));
         if (!r) return fail(FZB_ERR_INVALID, "out of memory");
@@ -2264,7 +2365,11 @@ void fzb_radix_sort_matches(fzb_match* matches, size_t n) {  // src/sort.rs:6-40
 int fzb_match_list(fzb_matcher* m, const fzb_corpus* c, fzb_match** out, size_t* out_len) {
     if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     const int sort = m->config.sort;
-    if (m->empty && corpus_terms(c)) return biased_empty_list(c, 0, c->dev.n, 0, sort, c->dev.n, out, out_len, nullptr);  // the empty prompt: the visible haystacks, ordered by the bias
+    if (prompt_on_device(m, c, nullptr, c->dev.n)) {  // the empty prompt: the visible haystacks, ordered by the bias
+        *out = nullptr;
+        *out_len = 0;
+        return prompt_list_host(m, c, nullptr, 0, c->dev.n, 0, true, out, out_len);
+    }
     if (m->empty) {  // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
         int rc = fzb_match_list_into(m, c, 0, c->dev.n, 0, out, out_len);
         if (rc) return rc;
@@ -3124,7 +3229,7 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
     *out_len = 0;
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
-    if (m->empty && corpus_terms(c)) return biased_empty_list(c, 0, n, 0, m->config.sort, limit, out, out_len, out_found);
+    if (prompt_on_device(m, c, nullptr, n)) return prompt_top_host(m, c, nullptr, limit, out, out_len, out_found);
     if (m->empty) return fzb_empty_pattern_top(n, m->config.sort, limit, out, out_len, out_found);
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
@@ -3229,6 +3334,17 @@ int hand_over_indices(const fzb_match_indices* recs, size_t nrec, const u32* pos
     return FZB_OK;
 }
 
+// the empty prompt's head with (empty) position lists: the device's head, then records without positions
+int prompt_top_indices_host(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions,
+                            uint64_t* out_found) {
+    fzb_match* head = nullptr;
+    size_t nhead = 0;
+    if (int rc_ = prompt_top_host(m, c, in, limit, &head, &nhead, out_found)) return rc_;
+    std::vector<fzb_match_indices> recs(nhead);
+    for (size_t i = 0; i < nhead; i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};
+    fzb_matches_free(head);
+    return hand_over_indices(recs.data(), nhead, nullptr, 0, out, out_len, out_positions);
+}
 // CompiledPatterns::Empty (an empty needle, no pattern): fzb_empty_pattern_top's rule - the first / last min(limit, n) indices, score 0 - and no
 // positions
 int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
@@ -3358,6 +3474,7 @@ int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
+    if (prompt_on_device(m, c, nullptr, n)) return prompt_top_indices_host(m, c, nullptr, limit, out, out_len, out_positions, out_found);
     if (m->empty) return empty_top_indices(c, n, m->config.sort, limit, out, out_len, out_positions, out_found);
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     const size_t stride = trace_stride(m);
@@ -3475,9 +3592,10 @@ int subset_capture_trivial(const fzb_corpus* c, const fzb_subset* in, fzb_subset
     capture->generation = c->generation;
     return FZB_OK;
 }
-// An empty needle over a candidate set - the picker's empty prompt restricted to a folder: the haystacks of `in`, score 0 or the clamped
-// bias, the hidden ones dropped, ordered as biased_empty_list orders (the reference's rule without a bias: reversed for the *Desc
-// strategies, never sorted).  Host work: one copy of the indices and of the columns the corpus carries.
+// No pattern over a candidate set, on the HOST, for the one caller without an fzb_matcher (fzb_multi_match_list_top_indices_subset; the single
+// matcher's empty prompt runs on the device: prompt_records) - the picker's empty prompt restricted to a folder: the haystacks of `in`, score
+// 0 or the clamped bias, the hidden ones dropped, ordered as biased_empty_list orders (the reference's rule without a bias: reversed for the
+// *Desc strategies, never sorted).  Host work: one copy of the indices and of the columns the corpus carries.
 int subset_empty_list(const fzb_corpus* c, fzb_subset* in, int sort, size_t limit, std::vector<fzb_match>& recs, uint64_t* out_found) {
     u64 n = 0;
     if (int rc = subset_count_host(in, &n)) return rc;
@@ -3629,9 +3747,8 @@ int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
     if (m->empty || n == 0) {
         if ((rc = subset_capture_trivial(c, in, capture))) return rc;
         if (!in) return fzb_match_list(m, c, out, out_len);
-        std::vector<fzb_match> recs;
-        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, n, recs, nullptr))) return rc;
-        return hand_over_matches(recs, out, out_len);
+        if (n == 0) return hand_over_matches(std::vector<fzb_match>(), out, out_len);
+        return prompt_list_host(m, c, in, 0, n, 0, true, out, out_len);
     }
     if ((rc = fzb_ensure_out_staging(m, n))) return rc;
     SubsetArgs sa{in, capture, capture ? m->count_dev + 6 : nullptr};
@@ -3663,9 +3780,8 @@ int fzb_match_list_top_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_sub
     if (m->empty || n == 0) {
         if ((rc = subset_capture_trivial(c, in, capture))) return rc;
         if (!in) return fzb_match_list_top(m, c, limit, out, out_len, out_found);
-        std::vector<fzb_match> recs;
-        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, limit, recs, out_found))) return rc;
-        return hand_over_matches(recs, out, out_len);
+        if (n == 0) return hand_over_matches(std::vector<fzb_match>(), out, out_len);
+        return prompt_top_host(m, c, in, limit, out, out_len, out_found);
     }
     const size_t want = std::min(limit, n);
     if ((rc = fzb_ensure_out_staging(m, want))) return rc;
@@ -3689,11 +3805,8 @@ int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const
     if (m->empty || n == 0) {
         if ((rc = subset_capture_trivial(c, in, capture))) return rc;
         if (!in) return fzb_match_list_top_indices(m, c, limit, out, out_len, out_positions, out_found);
-        std::vector<fzb_match> head;
-        if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), m->config.sort, limit, head, out_found))) return rc;
-        std::vector<fzb_match_indices> recs(head.size());
-        for (size_t i = 0; i < head.size(); i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};
-        return hand_over_indices(recs.data(), recs.size(), nullptr, 0, out, out_len, out_positions);
+        if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
+        return prompt_top_indices_host(m, c, in, limit, out, out_len, out_positions, out_found);
     }
     const size_t want = std::min(limit, n);
     const size_t stride = trace_stride(m);
@@ -3707,6 +3820,47 @@ int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const
     if (rc) return rc;
     subset_capture_known(capture, captured);
     return FZB_OK;
+}
+
+// ---- the empty prompt's _device forms: NEW entry points - the existing _device forms keep refusing an empty needle ---------------------
+// what both check before anything is launched (call: the entry point's name)
+static int prompt_device_check(const fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, const void* dev_out, size_t capacity, const uint32_t* dev_count, const char* call) {
+    if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    if (!m->empty) return fail(FZB_ERR_INVALID, std::string(call) + ": the matcher's needle is not empty; this call is the empty needle's form of the _device queries");
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    return subset_check(c, in, nullptr, call);
+}
+
+int fzb_prompt_list_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
+                           uint32_t* dev_count, void* stream) {
+    int rc = prompt_device_check(m, c, in, dev_out, capacity, dev_count, "fzb_prompt_list_device");
+    if (rc) return rc;
+    if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
+    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
+        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+    if (in && (first != 0 || count != c->dev.n)) return fail(FZB_ERR_INVALID, "fzb_prompt_list_device: a candidate set is queried over the whole corpus (first = 0, count = its length)");
+    hipStream_t st = (hipStream_t)stream;
+    if (count == 0) {
+        HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
+        return FZB_OK;
+    }
+    if ((rc = fzb_bind_device(m))) return rc;
+    return prompt_list_stage(m, c, in, first, count, index_offset, false, (fzb_match_rec*)dev_out, capacity, dev_count, st);
+}
+
+int fzb_prompt_top_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
+    int rc = prompt_device_check(m, c, in, dev_out, capacity, dev_count, "fzb_prompt_top_device");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
+        return FZB_OK;
+    }
+    if ((rc = fzb_bind_device(m))) return rc;
+    return prompt_top_stage(m, c, in, want, (fzb_match_rec*)dev_out, dev_count, st);
 }
 
 // The `from_patterns` form, a host composition of the existing pieces: the multi top goes to the host, then the multi matched-indices

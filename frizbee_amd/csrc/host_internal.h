@@ -171,6 +171,7 @@ struct ScopeScratch {
     size_t words_cap = 0;
 };
 int fzb_scope_ensure(ScopeScratch& s, size_t count);  // host.hip
+int fzb_scope_ensure_flags(ScopeScratch& s, size_t count);  // bitmap / tiles / words alone: the empty prompt's producer writes no records ahead of its compaction
 void fzb_scope_release(ScopeScratch& s);
 
 // A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle

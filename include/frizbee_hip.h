@@ -238,8 +238,11 @@ int fzb_corpus_edit_info(const fzb_corpus* c, uint64_t out[4]);
  * rests on); frizbee_amd.distributed.ShardExchange raises for a biased shard it is shown (check_corpus, ordered_query(corpus=...)).
  * AN EMPTY NEEDLE / NO PATTERN over a biased corpus is the picker's empty prompt, "most frecent first": every haystack matches with score
  * clamp(bias, 0, 65535) and - a DEPARTURE from the reference, whose empty result is never sorted - the list IS ordered by `config.sort`
- * (fzb_match_list, _parallel, _into (index order), _top, _top_indices with no positions, and the multi forms; host work for the single
- * matcher: one copy of the bias and the host's stable sort).  The _device forms keep refusing an empty needle.
+ * (fzb_match_list, _parallel, _into (index order), _top, _top_indices with no positions, and the multi forms).  The single matcher's
+ * prompt runs on the device: one kernel writes the index-ordered records from the bias column, the matcher's selection and ordering stage
+ * takes them from there, and the host forms copy back the head and the count pair in their one wait - no column crosses the link; after
+ * fzb_matcher_reserve(m, c) such a query allocates no device memory.  The _device forms keep refusing an empty needle; the prompt's own
+ * _device forms are fzb_prompt_list_device / fzb_prompt_top_device.
  * These are SET-UP calls under the editing family's rules: only for a corpus made by fzb_corpus_upload (a borrowed one gets FZB_ERR_INVALID),
  * they wait for the device's outstanding work on entry and are complete on return, must not run concurrently with queries over the same
  * corpus, and an error leaves the corpus as it was. */
@@ -285,7 +288,8 @@ int fzb_corpus_bias_info(const fzb_corpus* c, uint64_t out[4]);
  * names the call to use instead); none ignores the scope.  Honoured: fzb_match_list / _into / _device / _sorted_device / _parallel,
  * fzb_match_list_top / _top_device, fzb_match_list_top_indices / _device, fzb_multi_match_list / _into / _device / _top / _parallel,
  * fzb_multi_match_list_top_indices_fused / _device - an empty needle and an empty pattern list included (the picker's empty prompt with
- * "hide ignored" switched on: the visible haystacks, score 0 or the clamped bias; host work for the single matcher: one copy of the tags).
+ * "hide ignored" switched on: the visible haystacks, score 0 or the clamped bias; for the single matcher a flag pass over the tags and a
+ * stable compaction that writes the finished records, on the device - fzb_prompt_list_device / fzb_prompt_top_device are its _device forms).
  * Refused: the list-order matched-indices forms fzb_match_list_indices / _indices_into and fzb_multi_match_list_indices / _indices_into (use
  * the top-`limit` forms with positions), the composed fzb_multi_match_list_top_indices (use the fused form), fzb_match_list_parallel_rccl /
  * fzb_multi_match_list_parallel_rccl (a scoped shard is a rank-local failure that travels in the gathered status word like any other);
@@ -560,7 +564,8 @@ int fzb_subset_read(fzb_subset* s, uint32_t* host_out, size_t cap, size_t* out_n
  * capture of another corpus is refused; a capture takes the corpus' current generation.  After fzb_matcher_reserve(m, c) (and
  * fzb_matcher_reserve_top_indices for the form with positions) no subset query allocates device memory.
  * An EMPTY NEEDLE: the host forms list the haystacks of `in` - score 0, or the clamped bias, hidden ones dropped, ordered as the empty
- * prompt of the calls without _subset - and the capture, if any, becomes `in` itself; the _device form refuses, as its siblings do.
+ * prompt of the calls without _subset - and the capture, if any, becomes `in` itself; the list is made on the device (the set's count is
+ * read there, the set never crosses the link); the _device form refuses, as its siblings do - fzb_prompt_top_device takes a subset.
  * fzb_match_list_subset: fzb_match_list's order.  _top_subset / _top_subset_device: fzb_match_list_top / _top_device (dev_count: records
  * written, found).  _top_indices_subset: fzb_match_list_top_indices; its traced pass runs over the head's item list as before. */
 int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len);
@@ -569,6 +574,24 @@ int fzb_match_list_top_subset_device(fzb_matcher* m, const fzb_corpus* c, const 
                                      uint32_t* dev_count, void* stream);
 int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
                                       uint32_t** out_positions, uint64_t* out_found);
+
+/* ---- THE EMPTY PROMPT on the device ---------------------------------------------------------------------------------------------------
+ * The _device forms of an EMPTY needle, which fzb_match_list_device / _top_device / _top_subset_device / _top_indices_device refuse: a picker
+ * opens on an empty prompt and a stream-ordered host wants that list without a wait.  The rule is the host forms': the haystacks of the
+ * range, or of `in`, that are visible under the corpus' scope, in index order, each with score clamp(bias[i], 0, 65535) (0 without a bias),
+ * exact 0; the top form reverses for the *Desc strategies and sorts stably by descending score for the Score* strategies only over a
+ * biased corpus; found = the number visible.  They also serve a corpus without bias, scope or subset ("every index, score 0").
+ * m must have an empty needle (FZB_ERR_INVALID otherwise; the message names the needle).  `in` may be NULL; with `in` only first == 0 and
+ * count == the corpus length are accepted, and a stale or foreign subset is refused as in the _subset queries.  Everything is enqueued on
+ * `stream`; nothing synchronises.  An empty corpus (or count == 0) zeroes the pair.  After fzb_matcher_reserve(m, c) neither allocates. */
+/* the empty needle's index-ordered list: fzb_match_list_device for a matcher whose needle is empty.  At most `capacity` records are written;
+ * dev_count[0] = records written, dev_count[1] = found. */
+int fzb_prompt_list_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, uint32_t index_offset,
+                           fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream);
+/* ... and its ordered head: fzb_match_list_top_device / _top_subset_device.  capacity < min(limit, corpus length): FZB_ERR_CAPACITY, nothing
+ * launched; dev_count[0] = records written = min(limit, found), dev_count[1] = found. */
+int fzb_prompt_top_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, size_t limit,
+                          fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream);
 
 /* `radix_sort_matches(&mut [Match])` (src/sort.rs:6-40): stable, descending score, host side */
 void fzb_radix_sort_matches(fzb_match* matches, size_t n);

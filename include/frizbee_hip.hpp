@@ -501,6 +501,18 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_match_list_top_subset_device(single_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
         else check(fzb_multi_match_list_top_subset_device(multi_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
     }
+    // The empty prompt's _device forms (a matcher made from an empty needle; the _device forms above refuse one): the index-ordered list of the
+    // haystacks of the range, or of `in`, visible under the corpus' scope - score = the clamped bias -, and its ordered head.  dev_count =
+    // (records written, found); asynchronous on `stream`.
+    void prompt_list_device(const Corpus& corpus, const Subset* in, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
+                            void* stream = nullptr) {
+        if (!single_) throw Error(FZB_ERR_INVALID, "prompt_list_device: a from_patterns matcher has no empty needle");
+        check(fzb_prompt_list_device(single_.get(), corpus.raw(), in ? in->raw() : nullptr, first, count, index_offset, dev_out, capacity, dev_count, stream));
+    }
+    void prompt_top_device(const Corpus& corpus, const Subset* in, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream = nullptr) {
+        if (!single_) throw Error(FZB_ERR_INVALID, "prompt_top_device: a from_patterns matcher has no empty needle");
+        check(fzb_prompt_top_device(single_.get(), corpus.raw(), in ? in->raw() : nullptr, limit, dev_out, capacity, dev_count, stream));
+    }
     std::vector<MatchIndices> match_list_top_indices(const Corpus& corpus, const Subset* in, Subset* capture, size_t limit, size_t* found = nullptr) {
         fzb_match_indices* out = nullptr;
         uint32_t* pos = nullptr;

@@ -142,6 +142,11 @@ extern "C" {
                                         dev_count: *mut u32, stream: *mut c_void) -> c_int;
     fn fzb_match_list_top_indices_subset(m: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
                                          out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    // the empty prompt's _device forms (a matcher whose needle is empty; `input` may be null): the index-ordered list, and its ordered head
+    fn fzb_prompt_list_device(m: *mut c_void, c: *const c_void, input: *const c_void, first: usize, count: usize, index_offset: u32, dev_out: *mut FzbMatch, capacity: usize,
+                              dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_prompt_top_device(m: *mut c_void, c: *const c_void, input: *const c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize, dev_count: *mut u32,
+                             stream: *mut c_void) -> c_int;
     // the same four over a `from_patterns` matcher: the composition runs over `input`, `capture` receives the composition's match set
     #[allow(dead_code)]
     fn fzb_multi_match_list_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
@@ -507,6 +512,25 @@ impl MatcherHip {
     /// allocates device memory - also across `set_pattern` / `set_config`.
     pub fn reserve_top_indices(&mut self, corpus: &HipCorpus, limit: usize, max_needle_bytes: usize) {
         check(unsafe { fzb_matcher_reserve_top_indices(self.handle, corpus.handle, limit, max_needle_bytes) });
+    }
+
+    /// The empty prompt's index-ordered list left in HBM (a matcher whose needle is empty; the `_device` forms refuse one): the haystacks
+    /// of `[first, first + count)` visible under the corpus' scope, score = the clamped bias.  At most `capacity` records at `dev_out`,
+    /// `(written, found)` at `dev_count`.  Asynchronous on `stream`.
+    ///
+    /// # Safety
+    /// The two device pointers must be valid for the capacities given, on the device the corpus lives on.
+    pub unsafe fn prompt_list_device(&mut self, corpus: &HipCorpus, first: usize, count: usize, index_offset: u32, dev_out: *mut c_void, capacity: usize, dev_count: *mut u32,
+                                     stream: *mut c_void) {
+        check(fzb_prompt_list_device(self.handle, corpus.handle, std::ptr::null(), first, count, index_offset, dev_out as *mut FzbMatch, capacity, dev_count, stream));
+    }
+
+    /// The empty prompt's ordered head left in HBM: `capacity >= min(limit, len)` records at `dev_out`, `(written, found)` at `dev_count`.
+    ///
+    /// # Safety
+    /// The two device pointers must be valid for the capacities given, on the device the corpus lives on.
+    pub unsafe fn prompt_top_device(&mut self, corpus: &HipCorpus, limit: usize, dev_out: *mut c_void, capacity: usize, dev_count: *mut u32, stream: *mut c_void) {
+        check(fzb_prompt_top_device(self.handle, corpus.handle, std::ptr::null(), limit, dev_out as *mut FzbMatch, capacity, dev_count, stream));
     }
 
     /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.

@@ -10,7 +10,7 @@ result on the host, of the best `limit` records by score + bias on the first 200
 a shared host hits all alike): three corpora of the same list are resident side by side (no bias, small bias, large bias), every path keeps
 its own reserved matcher, and the needle changes outside the timed window.  `--repeats` repeats of `--queries` queries per path and list:
 the median of the repeats' medians and their spread (lowest and highest repeat median), microseconds, one JSON line per list and path.  Also
-reported: the empty prompt over the biased corpus (`Matcher("").match_list_top`, host work).  Before anything is timed (b) and (c) are
+reported: the empty prompt over the biased corpus (`Matcher("").match_list_top`; on the device since tools/bench_prompt.py measures it).  Before anything is timed (b) and (c) are
 each checked against the host-side ranking (d's code) with their own bias.
 
     python tools/bench_bias.py [--queries 300] [--repeats 5] [--only a|b|c|d] [--lists 200k,1.4M]
@@ -102,14 +102,14 @@ def main():
             print(json.dumps(dict(list="paths " + name, items=n, limit=LIMIT, path=NAMES[p], queries=a.queries * a.repeats, median_us=round(float(np.median(r)), 1),
                                   spread_us=[round(min(r), 1), round(max(r), 1)], repeat_medians_us=[round(x, 1) for x in r],
                                   bias_hi=corpora[p].bias_info()["bias_hi"])), flush=True)
-        if a.only is None:  # the empty prompt, "most frecent first": one copy of the bias and the host's stable sort
+        if a.only is None:  # the empty prompt, "most frecent first" (its own tool: tools/bench_prompt.py)
             e = F.Matcher("", F.Config(pf_lanes=64))
             ts = []
             for _ in range(max(3, a.repeats * 4)):
                 t0 = time.perf_counter()
                 e.match_list_top(corpora["c"], LIMIT)
                 ts.append((time.perf_counter() - t0) * 1e6)
-            print(json.dumps(dict(list="paths " + name, items=n, limit=LIMIT, path="empty prompt over the biased corpus (host work)", queries=len(ts),
+            print(json.dumps(dict(list="paths " + name, items=n, limit=LIMIT, path="empty prompt over the biased corpus", queries=len(ts),
                                   median_us=round(float(np.median(ts)), 1), spread_us=[round(min(ts), 1), round(max(ts), 1)])), flush=True)
         del run, corpora
 
