@@ -134,6 +134,7 @@ SYMBOLS = [
     "fzb_multi_match_list_subset", "fzb_multi_match_list_top_subset", "fzb_multi_match_list_top_subset_device", "fzb_multi_match_list_top_indices_subset",
     "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
     "fzb_prompt_list_device", "fzb_prompt_top_device",
+    "fzb_facets_create", "fzb_facets_free", "fzb_facets_read", "fzb_facets_device", "fzb_matcher_set_facets", "fzb_multi_matcher_set_facets",
 ]
 
 
@@ -280,6 +281,14 @@ def lib():
         l.fzb_match_list_top_indices_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                         C.POINTER(C.c_uint64)]
         l.fzb_multi_match_list_top_indices_subset.argtypes = l.fzb_match_list_top_indices_subset.argtypes
+        l.fzb_facets_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        l.fzb_facets_free.argtypes = [C.c_void_p]
+        l.fzb_facets_free.restype = None
+        l.fzb_facets_read.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        l.fzb_facets_device.argtypes = [C.c_void_p]
+        l.fzb_facets_device.restype = C.c_void_p
+        l.fzb_matcher_set_facets.argtypes = [C.c_void_p, C.c_void_p]
+        l.fzb_multi_matcher_set_facets.argtypes = [C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 
@@ -594,6 +603,45 @@ def _h(subset):
     return None if subset is None else subset.h
 
 
+FACET_WORDS, FACET_BITS = 34, 16  # include/frizbee_hip.h FZB_FACET_WORDS; facets.h
+
+
+class Facets:
+    """A facet sink of one resident `Corpus` (fzb_facets): the per-tag match counts of a query, counted on the device.  Attach it with
+    `Matcher.set_facets` / `MultiMatcher.set_facets`; every query that honours it then fills it, and `read()` returns, for the match set A
+    of the last such query (what `capture=` would hold: before scope, bias, `limit` and ordering): `matched` = |A|, `visible` = the members
+    of A the corpus' scope shows (the call's `found`), `all_by_bit[b]` = the members of A whose tag has bit b (hidden ones included: a chip
+    for an excluded bit shows what it hides), `visible_by_bit[b]` = the same over the visible members.  The reference has no counterpart:
+    its caller counts over the Vec `match_list` returned."""
+
+    def __init__(self, corpus):
+        self.corpus = corpus  # (keeps the corpus alive: the handle points at it)
+        self.h = C.c_void_p()
+        _check(lib().fzb_facets_create(corpus.h, C.byref(self.h)))
+
+    def read_words(self):
+        """the block as FACET_WORDS uint32 (after a `_device` form: waits for that form's stream)"""
+        out = (C.c_uint32 * FACET_WORDS)()
+        _check(lib().fzb_facets_read(self.h, out))
+        return np.frombuffer(out, dtype=np.uint32).copy()
+
+    def read(self):
+        w = self.read_words()
+        return dict(matched=int(w[0]), visible=int(w[1]), all_by_bit=w[2:2 + FACET_BITS].copy(), visible_by_bit=w[2 + FACET_BITS:2 + 2 * FACET_BITS].copy())
+
+    def device_ptr(self):
+        """the block's address in HBM, for stream-ordered consumers"""
+        return lib().fzb_facets_device(self.h)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) is not None and self.h:
+                lib().fzb_facets_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 def device_count():
     n = C.c_int()
     _check(lib().fzb_device_count(C.byref(n)))
@@ -775,6 +823,12 @@ class MultiMatcher(_IterApi):
         c = _c_config(config)
         _check(lib().fzb_multi_matcher_set_config(self.h, C.byref(c)))
         self.config = config
+
+    def set_facets(self, facets):
+        """Attach a `Facets` sink (None: detach): the counts are those of the COMPOSITION's match set.  It stays attached across
+        `set_patterns` / `set_config`; entry points that cannot fill it refuse the matcher until it is detached."""
+        _check(lib().fzb_multi_matcher_set_facets(self.h, None if facets is None else facets.h))
+        self.facets = facets  # (keeps the sink alive while the matcher points at it)
 
     def reserve(self, corpus):
         """Allocate every device buffer queries over `corpus` can need now: the composition, ordering and staging, and every sub-matcher
@@ -1100,6 +1154,12 @@ class Matcher(_IterApi):
         """`match_list` with the result left in HBM, already in `config.sort` order (device-side reverse + radix sort)."""
         _check(lib().fzb_match_list_sorted_device(self.h, corpus.h, dev_out_ptr, capacity, dev_count_ptr, stream))
 
+    def set_facets(self, facets):
+        """Attach a `Facets` sink (None: detach).  It stays attached across `set_pattern` / `set_config`; entry points that cannot fill it
+        refuse the matcher until it is detached."""
+        _check(lib().fzb_matcher_set_facets(self.h, None if facets is None else facets.h))
+        self.facets = facets  # (keeps the sink alive while the matcher points at it)
+
     def reserve(self, corpus):
         """Allocate every device buffer queries over `corpus` can need now, so that no later query (also after set_pattern) allocates."""
         _check(lib().fzb_matcher_reserve(self.h, corpus.h))
@@ -1168,6 +1228,11 @@ class NarrowingMatcher:
         self._prev = None        # (needle bytes, (unicode, pf_lanes, sw_lanes), corpus generation) of that query
         self.last_narrowed = False
 
+    def set_facets(self, facets):
+        """pass a `Facets` sink of the corpus on to the matcher (None: detach): every query fills it - over the previous capture when it
+        narrowed, whose members are the only haystacks that can still match"""
+        self.matcher.set_facets(facets)
+
     def _may_narrow(self, needle, path):
         if self._cur is None or self._prev is None:
             return False
@@ -1224,17 +1289,23 @@ class NarrowingQuery:
 
     DEFAULT_MAX_FRACTION = 0.039
 
-    def __init__(self, corpus, config=None, max_fraction=None, within=None):
+    def __init__(self, corpus, config=None, max_fraction=None, within=None, facets=None):
         self.corpus = corpus
         self.config = config or Config()
         self.max_fraction = self.DEFAULT_MAX_FRACTION if max_fraction is None else float(max_fraction)
         self.within = within
         self.matcher = MultiMatcher([], self.config)
+        if facets is not None:  # a `Facets` sink of the corpus: every query fills it with the composition's counts
+            self.matcher.set_facets(facets)
         self.subsets = [Subset(corpus), Subset(corpus)]
         self._cur = None    # index of the subset that holds the previous query's capture
         self._prev = None   # (compiled patterns, config, corpus generation, within key) of that query
         self._paths = {}
         self.last_narrowed = False
+
+    def set_facets(self, facets):
+        """pass a `Facets` sink of the corpus on to the matcher (None: detach), as `facets=` does at construction"""
+        self.matcher.set_facets(facets)
 
     def reset(self):
         """forget the previous capture: the next query runs over `within` / the whole list"""

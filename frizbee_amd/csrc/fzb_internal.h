@@ -275,7 +275,15 @@ void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const
 // the corpus' visibility scope (scope.h): the records of hidden haystacks dropped from count[0] index-ordered records (at most cap) into a DIFFERENT
 // buffer of `capacity` records - flag pass + stable compaction; count_out = (written, found); bitmap: 16 words per 1024 records of cap, tile_counts: one
 void fzb_launch_scope_drop(const fzb_match_rec* recs, const u32* count, u32 cap, const uint16_t* tags, u64 n_tags, u64 first, u32 index_offset, u32 require, u32 exclude, u64* bitmap,
-                           u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st);
+                           u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st, u32* facets = nullptr);
+// (facets: the tag facets of the records, counted in the flag pass - facets.h; the block is cleared in stream order by the caller)
+// kernels_facets.hip: the tag facets (facets.h) of a producer's index-ordered records over a corpus with no active scope, and of the empty
+// prompt's lists (items == nullptr: the n haystacks from `first`; else a candidate set, its count read on the device); `block` =
+// FZB_FACET_WORDS words cleared in stream order by the caller; tags may be null
+void fzb_launch_facets_records(const fzb_match_rec* recs, const u32* count, u32 cap, const uint16_t* tags, u64 n_tags, u64 first, u32 index_offset, u32 require, u32 exclude, u32* block,
+                               int grid_max, hipStream_t st);
+void fzb_launch_facets_column(const u32* items, const u32* n_ptr, u32 n, u32 hint, const uint16_t* tags, u64 n_tags, u64 first, u32 require, u32 exclude, u32* block, int grid_max,
+                              hipStream_t st);
 // kernels_indices.hip: the glue of the fused top + matched-positions query (item list from the sorted head; packing of the traced positions)
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st);
 size_t fzb_indices_pack_tile_words(size_t max_records);

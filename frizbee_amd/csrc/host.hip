@@ -1288,13 +1288,98 @@ static int apply_bias(const fzb_corpus* c, fzb_match_rec* recs, const u32* count
 // terms to them: drop the records of hidden haystacks (flag pass + stable compaction into the caller's array of `capacity` records,
 // dev_count = (written, visible matches)), then add the bias.  The ONE helper that launches the drop; a corpus without an active scope never
 // gets here and takes the launches it took before.
+// (f: the matcher's facet sink, or null.  With one the flag pass counts the records' tag facets as well - the fused form, facets.h - and
+// the caller may come here WITHOUT an active scope: a _device form whose `capacity` would cut the producer ahead of the count writes into
+// the scratch too, and the drop under the scope (0, 0) keeps every record.)
+static int facets_open(fzb_facets* f, hipStream_t st);
+static int facets_close(fzb_facets* f, hipStream_t st);
 static int apply_terms(const fzb_corpus* c, ScopeScratch& sc, size_t count, fzb_match_rec* dev_out, size_t capacity, u32* dev_count, size_t first, uint32_t index_offset, int grid_max,
-                       hipStream_t st) {
+                       hipStream_t st, fzb_facets* f = nullptr) {
     const u32 cap32 = (u32)std::min<size_t>(capacity, 0xFFFFFFFFu);
-    fzb_launch_scope_drop(sc.recs, sc.words, (u32)count, c->tags.data, c->dev.n, first, index_offset, c->scope_require, c->scope_exclude, sc.bitmap, sc.tiles, dev_out, cap32, dev_count,
-                          grid_max, st);
+    const bool scoped = fzb_corpus_scoped(c);
+    if (int rc = facets_open(f, st)) return rc;
+    fzb_launch_scope_drop(sc.recs, sc.words, (u32)count, c->tags.data, c->dev.n, first, index_offset, scoped ? c->scope_require : 0u, scoped ? c->scope_exclude : 0u, sc.bitmap, sc.tiles, dev_out,
+                          cap32, dev_count, grid_max, st, f ? f->block : nullptr);
     HIPCHK(hipGetLastError());
+    if (int rc = facets_close(f, st)) return rc;
     return apply_bias(c, dev_out, dev_count, std::min(capacity, count), first, index_offset, grid_max, st);
+}
+// ---- the tag facets on the query path (facets.h; fzb_facets: host_internal.h) -----------------------------------------------------------
+// A matcher with a facet sink attached: every query that honours the sink counts the tag facets of its match set A - the records the
+// producer wrote, where a capture= of the same call reads them: ahead of scope, bias, selection, limit and ordering.  Three forms:
+//   * under an active scope the count rides in the drop's flag pass (apply_terms above): no second pass over the records;
+//   * without one, facets_records - the ONE helper that launches k_facets_records, beside subset_capture and at the same sites;
+//   * the empty prompt's producers make no records for hidden haystacks: facets_column reads the tag column over the range or the set.
+// Each clears the block in stream order (facets_open), counts, and queues the block's copy to the page-locked mirror (facets_close) - in
+// front of a host form's one wait, behind nothing else.  Without a sink nothing here launches or allocates.
+int fzb_refuse_facets(const fzb_facets* f, const char* call) {
+    if (!f) return FZB_OK;
+    return fail(FZB_ERR_INVALID, std::string(call) + ": the matcher has a facet sink attached, which this call does not fill; detach it first: set_facets(NULL)");
+}
+// a sink counts over the corpus it was created on
+static int facets_check(const fzb_facets* f, const fzb_corpus* c, const char* call) {
+    if (!f || !c || f->corpus == c) return FZB_OK;
+    return fail(FZB_ERR_INVALID, std::string(call) + ": the attached facet sink belongs to another corpus; detach it first: set_facets(NULL)");
+}
+static int facets_open(fzb_facets* f, hipStream_t st) {
+    if (!f) return FZB_OK;
+    HIPCHK(hipMemsetAsync(f->block, 0, FZB_FACET_WORDS * sizeof(u32), st));
+    return FZB_OK;
+}
+static int facets_close(fzb_facets* f, hipStream_t st) {
+    if (!f) return FZB_OK;
+    HIPCHK(hipMemcpyAsync(f->mirror, f->block, FZB_FACET_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st));
+    f->on_event = st != nullptr;
+    if (f->on_event) HIPCHK(hipEventRecord(f->done, st));
+    f->pending = true;
+    return FZB_OK;
+}
+// the wait for the last query's copy into the mirror: nothing is asked of the device when it has completed
+static int facets_settle(fzb_facets* f) {
+    if (!f->pending) return FZB_OK;
+    if (f->on_event) {
+        if (hipEventQuery(f->done) != hipSuccess) HIPCHK(hipEventSynchronize(f->done));
+    } else if (hipStreamQuery(nullptr) != hipSuccess) {
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    f->pending = false;
+    return FZB_OK;
+}
+// a query that launched nothing (an empty range): every count is zero
+static int facets_none(fzb_facets* f, hipStream_t st) {
+    if (int rc = facets_open(f, st)) return rc;
+    return facets_close(f, st);
+}
+// recs = the producer's index-ordered records (pair[0] of them, at most cap) over the range that starts at haystack `first`, numbered from
+// index_offset; a corpus with no active scope (every record is visible)
+static int facets_records(fzb_facets* f, const fzb_corpus* c, const fzb_match_rec* recs, const u32* pair, size_t cap, size_t first, uint32_t index_offset, int grid_max, hipStream_t st) {
+    if (!f) return FZB_OK;
+    if (int rc = facets_open(f, st)) return rc;
+    if (cap) fzb_launch_facets_records(recs, pair, (u32)std::min<size_t>(cap, 0xFFFFFFFFu), c->tags.data, c->dev.n, first, index_offset, 0u, 0u, f->block, grid_max, st);
+    HIPCHK(hipGetLastError());
+    return facets_close(f, st);
+}
+// the haystacks [first, first + count) - or those of `in`, whose count is read on the device - under the corpus' scope: the empty prompt's A
+static int facets_column(fzb_facets* f, const fzb_corpus* c, const fzb_subset* in, size_t first, size_t count, int grid_max, hipStream_t st) {
+    if (!f) return FZB_OK;
+    if (int rc = facets_open(f, st)) return rc;
+    const bool scoped = fzb_corpus_scoped(c);
+    const u64 hint = in ? std::min<u64>(std::max<u64>(1, in->known ? in->count : (u64)in->cap), count) : count;
+    if (count)
+        fzb_launch_facets_column(in ? in->idx : nullptr, in ? in->count_dev : nullptr, (u32)count, (u32)hint, c->tags.data, c->dev.n, first, scoped ? c->scope_require : 0u,
+                                 scoped ? c->scope_exclude : 0u, f->block, grid_max, st);
+    HIPCHK(hipGetLastError());
+    return facets_close(f, st);
+}
+// the closed-form answers of an empty needle / an empty pattern list (no term, no candidate set: host work alone, nothing else is launched):
+// A is every haystack of the range, counted from the column on the null stream of the current device (the corpus': these answers bind no
+// matcher, so the grid's cap is the device's, fzb_grid_cap).  Such a form has no wait of its own to ride on, so the count's wait is made
+// HERE: like every other host form it returns with the mirror current, and fzb_facets_read does no device work behind it.
+static int facets_every(fzb_facets* f, const fzb_corpus* c, size_t first, size_t count, const char* call) {
+    if (!f) return FZB_OK;
+    if (int rc = facets_check(f, c, call)) return rc;
+    if (int rc = facets_column(f, c, nullptr, first, count, (int)fzb_grid_cap(~0ull, 2), nullptr)) return rc;
+    return facets_settle(f);
 }
 // "honours the scope or refuses": the entry points that cannot drop the hidden haystacks say so instead of ignoring the scope
 int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead) {
@@ -1332,6 +1417,7 @@ static int prompt_records(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
     const int16_t* bias = fzb_corpus_bias(c);
     const bool scoped = fzb_corpus_scoped(c);
     const int cus = m->lc.num_cus;
+    if (int rc = facets_check(m->facets, c, "the empty prompt")) return rc;
     if (!in && !scoped) {
         fzb_launch_prompt_records(out, (u32)count, cap32, bias, c->dev.n, first, index_offset, pair, cus * 4, st);
     } else {
@@ -1342,7 +1428,8 @@ static int prompt_records(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
                                   c->scope_require, c->scope_exclude, m->scope.bitmap, m->scope.tiles, out, cap32, pair, cus * 2, st);
     }
     HIPCHK(hipGetLastError());
-    return FZB_OK;
+    // (the producers above make no records for hidden haystacks: the facets of the prompt's A come from the tag column)
+    return facets_column(m->facets, c, in, first, count, cus * 2, st);
 }
 // What orders the prompt's list: the score is the clamped bias alone - no matrix score, no exact-match bonus - so a single radix pass / one
 // histogram level is decided by bias_hi alone (a `one_pass` that is wrongly true would make the selection read the low byte only), and
@@ -2057,7 +2144,9 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     }
     rc = ensure_workspace(m, n);
     if (rc) return rc;
-    if (c->tags.data && (rc = fzb_scope_ensure(m->scope, n))) return rc;  // a corpus that carries tags: toggling its scope between queries allocates nothing
+    // a corpus that carries tags: toggling its scope between queries allocates nothing; a facet sink: a _device form whose output is smaller than
+    // the match set writes into the same scratch, so that the count stays exact
+    if ((c->tags.data || m->facets) && (rc = fzb_scope_ensure(m->scope, n))) return rc;
     const bool no_wide = n == c->dev.n && c->dev.max_len != 0 && c->dev.max_len <= (u32)m->lc.sw_lanes;
     if (!m->long_needle && !m->literal_mode && !m->nd.unicode && !no_wide && ((rc = ensure_dp_scratch(m, m->lc.num_cus * 4)) || (rc = ensure_aux_stream(m)))) return rc;
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && fzb_knobs().unicode_multi != 0 && (rc = ensure_dp_scratch(m, m->lc.num_cus * 2))) return rc;
@@ -2129,15 +2218,21 @@ extern "C" {
 static int match_list_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                                   void* stream, const SubsetArgs* sa) {
     int rc;
-    if (m && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the pipeline into the scratch, then the list's terms: drop, then bias
+    fzb_facets* const fc = m ? m->facets : nullptr;
+    if ((rc = facets_check(fc, c, "fzb_match_list_device"))) return rc;
+    // (a facet sink counts every match: an output that may be too small for them must not cut the producer ahead of the count - the scratch
+    // has room for one record per haystack of the range)
+    const bool uncut = fc && capacity < count;
+    if (m && c && count && (fzb_corpus_scoped(c) || uncut) && dev_count && (dev_out || !capacity)) {  // the pipeline into the scratch, then the list's terms: drop, then bias
         if ((rc = fzb_scope_ensure(m->scope, count))) return rc;
         if ((rc = run_pipeline(m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, count, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
         if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, count, m->lc.num_cus * 2, (hipStream_t)stream))) return rc;
-        return apply_terms(c, m->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
+        return apply_terms(c, m->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream, fc);
     }
     rc = run_pipeline(m, c, first, count, index_offset, subset_items(sa), subset_count(sa), dev_out, capacity, dev_count, stream, nullptr, subset_hint(sa));
     if (rc) return rc;
     if ((rc = subset_capture(sa, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), m->lc.num_cus * 2, (hipStream_t)stream))) return rc;
+    if ((rc = facets_records(fc, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream))) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, m->lc.num_cus * 2, (hipStream_t)stream);
 }
 int fzb_match_list_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
@@ -2332,6 +2427,7 @@ int fzb_match_list_into(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
     *out_len = 0;
     if (prompt_on_device(m, c, nullptr, count)) return prompt_list_host(m, c, nullptr, first, count, index_offset, false, out, out_len);  // the empty prompt, index order
     if (m->empty) {  // src/matcher/mod.rs:381-384
+        if (int rc_ = facets_every(m->facets, c, first, count, "fzb_match_list_into")) return rc_;
         fzb_match* r = (fzb_match*)malloc(std::max<size_t>(count, 1) * sizeof(fzb_match));
         if (!r) return fail(FZB_ERR_INVALID, "out of memory");
         for (size_t i = 0; i < count; i++) r[i] = fzb_match{(uint32_t)(index_offset + i), 0, 0, 0};
@@ -2389,6 +2485,7 @@ int fzb_match_list(fzb_matcher* m, const fzb_corpus* c, fzb_match** out, size_t*
 int fzb_match_list_parallel(fzb_matcher* m, const fzb_corpus* c, size_t threads, fzb_match** out, size_t* out_len) {
     if (!m || !c) return fail(FZB_ERR_INVALID, "null argument");
     if (threads == 0) return fail(FZB_ERR_PANIC, "threads must be positive");  // parallel.rs:24
+    if (int rc_ = fzb_refuse_facets(m->facets, "fzb_match_list_parallel")) return rc_;
     return fzb_match_list(m, c, out, out_len);
 }
 
@@ -2529,12 +2626,14 @@ static int match_list_indices_impl(fzb_matcher* m, const fzb_corpus* c, const ui
 int fzb_match_list_indices(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
                            uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_scoped(c, "fzb_match_list_indices", "fzb_match_list_top_indices")) return rc_;
+    if (int rc_ = fzb_refuse_facets(m ? m->facets : nullptr, "fzb_match_list_indices")) return rc_;
     return match_list_indices_impl(m, c, selection, n_selection, m ? m->config.sort : 0, 0, out, out_len, out_positions);
 }
 
 int fzb_match_list_indices_into(fzb_matcher* m, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, uint32_t index_offset, fzb_match_indices** out,
                                 size_t* out_len, uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_scoped(c, "fzb_match_list_indices_into", "fzb_match_list_top_indices")) return rc_;
+    if (int rc_ = fzb_refuse_facets(m ? m->facets : nullptr, "fzb_match_list_indices_into")) return rc_;
     return match_list_indices_impl(m, c, selection, n_selection, FZB_SORT_INDEX_ASC, index_offset, out, out_len, out_positions);
 }
 
@@ -2878,7 +2977,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     for (fzb_matcher* m : mm->spare)
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
-    if (c->tags.data && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags: the composition's records ahead of the drop)
+    if ((c->tags.data || mm->facets) && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags, or a facet sink: the composition's records ahead of the drop / the count)
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
     if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
     return FZB_OK;
@@ -2915,6 +3014,7 @@ size_t fzb_multi_matcher_len(const fzb_multi_matcher* mm) { return mm ? mm->patt
 int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, size_t threads, fzb_match** out, size_t* out_len) {
     if (!mm || !c) return fail(FZB_ERR_INVALID, "null argument");
     if (threads == 0) return fail(FZB_ERR_PANIC, "threads must be positive");  // parallel.rs:24
+    if (int rc_ = fzb_refuse_facets(mm->facets, "fzb_multi_match_list_parallel")) return rc_;
     return fzb_multi_match_list(mm, c, out, out_len);
 }
 
@@ -3008,17 +3108,21 @@ extern "C" {
 static int multi_match_list_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
                                         uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     int rc;
-    if (mm && c && count && fzb_corpus_scoped(c) && dev_count && (dev_out || !capacity)) {  // the composition into the scratch (with no pattern: identity records), then drop, then bias
+    fzb_facets* const fc = mm ? mm->facets : nullptr;
+    if ((rc = facets_check(fc, c, "fzb_multi_match_list_device"))) return rc;
+    const bool uncut = fc && capacity < count;  // (a facet sink counts every match: the composition goes into the scratch, which has room for them)
+    if (mm && c && count && (fzb_corpus_scoped(c) || uncut) && dev_count && (dev_out || !capacity)) {  // the composition into the scratch (with no pattern: identity records), then drop, then bias
         if ((rc = fzb_scope_ensure(mm->scope, count))) return rc;
         bool captured = false;
         if ((rc = multi_compose_device(mm, c, first, count, index_offset, (fzb_match*)mm->scope.recs, count, mm->scope.words, stream, sa, &captured))) return rc;
         if (!captured && (rc = subset_capture(sa, c, mm->scope.recs, mm->scope.words, count, mm->num_cus * 2, (hipStream_t)stream))) return rc;
-        return apply_terms(c, mm->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
+        return apply_terms(c, mm->scope, count, (fzb_match_rec*)dev_out, capacity, dev_count, first, index_offset, mm->num_cus * 2, (hipStream_t)stream, fc);
     }
     bool captured = false;
     rc = multi_compose_device(mm, c, first, count, index_offset, dev_out, capacity, dev_count, stream, sa, &captured);
     if (rc) return rc;
     if (count && !captured && (rc = subset_capture(sa, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), mm->num_cus * 2, (hipStream_t)stream))) return rc;
+    if ((rc = facets_records(fc, c, (const fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, mm->num_cus * 2, (hipStream_t)stream))) return rc;
     return apply_bias(c, (fzb_match_rec*)dev_out, dev_count, std::min(capacity, count), first, index_offset, mm->num_cus * 2, (hipStream_t)stream);
 }
 int fzb_multi_match_list_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity,
@@ -3126,6 +3230,7 @@ int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, con
                                  uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_indices")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, mm ? mm->config.sort : 0, 0, out, out_len, out_positions);
 }
 
@@ -3133,6 +3238,7 @@ int fzb_multi_match_list_indices_into(fzb_multi_matcher* mm, const fzb_corpus* c
                                       fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_indices_into")) return rc_;
     return multi_match_list_indices_impl(mm, c, selection, n_selection, FZB_SORT_INDEX_ASC, index_offset, out, out_len, out_positions);
 }
 
@@ -3193,10 +3299,11 @@ static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fz
     if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
     if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
     if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top");
+    if (int rc_ = facets_check(m->facets, c, "fzb_match_list_top_device")) return rc_;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
-        return FZB_OK;
+        return facets_none(m->facets, st);
     }
     int rc;
     // (the range workspace first: growing it releases every workspace buffer, the sort's included)
@@ -3209,10 +3316,11 @@ static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fz
     if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
         if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, n, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
         if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, n, m->lc.num_cus * 2, st))) return rc;
-        if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st))) return rc;
+        if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st, m->facets))) return rc;
     } else {
         if ((rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)w.sort.tmp, n, raw_count, stream, nullptr, subset_hint(sa)))) return rc;
         if ((rc = subset_capture(sa, c, w.sort.tmp, raw_count, n, m->lc.num_cus * 2, st))) return rc;
+        if ((rc = facets_records(m->facets, c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // (room for every haystack: never cut ahead of the count)
         if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
     }
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
@@ -3230,6 +3338,9 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     if (prompt_on_device(m, c, nullptr, n)) return prompt_top_host(m, c, nullptr, limit, out, out_len, out_found);
+    if (m->empty || n == 0) {
+        if (int rc_ = facets_every(m->facets, c, 0, n, "fzb_match_list_top")) return rc_;
+    }
     if (m->empty) return fzb_empty_pattern_top(n, m->config.sort, limit, out, out_len, out_found);
     if (n == 0) return FZB_OK;
     const size_t want = std::min(limit, n);
@@ -3272,7 +3383,7 @@ static int multi_match_list_top_impl(fzb_multi_matcher* mm, const fzb_corpus* c,
     *out_len = 0;
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
-    if (n == 0) return FZB_OK;
+    if (n == 0) return facets_none(mm->facets, nullptr);
     const size_t want = std::min(limit, n);
     int rc;
     if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + 4, nullptr, sa))) return rc;
@@ -3445,7 +3556,7 @@ static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t l
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
-        return FZB_OK;
+        return facets_none(m->facets, st);
     }
     int rc;
     if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false))) return rc;
@@ -3475,6 +3586,9 @@ int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
     if (prompt_on_device(m, c, nullptr, n)) return prompt_top_indices_host(m, c, nullptr, limit, out, out_len, out_positions, out_found);
+    if (m->empty || n == 0) {
+        if (int rc_ = facets_every(m->facets, c, 0, n, "fzb_match_list_top_indices")) return rc_;
+    }
     if (m->empty) return empty_top_indices(c, n, m->config.sort, limit, out, out_len, out_positions, out_found);
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     const size_t stride = trace_stride(m);
@@ -3737,6 +3851,61 @@ int fzb_subset_read(fzb_subset* s, uint32_t* host_out, size_t cap, size_t* out_n
     return FZB_OK;
 }
 
+// ---- FACET SINKS (include/frizbee_hip.h: fzb_facets; facets.h) -----------------------------------------------------------------------------
+// The handle: FZB_FACET_WORDS counts in device memory and a page-locked mirror, of ONE corpus.  A matcher it is attached to fills it with
+// every query that honours it (facets_records / facets_column / apply_terms above).
+int fzb_facets_create(const fzb_corpus* c, fzb_facets** out) {
+    if (!c || !out) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    fzb_facets* f = new fzb_facets;
+    f->corpus = c;
+    hipError_t e = hipGetDevice(&f->device);
+    if (e == hipSuccess) e = dev_alloc((void**)&f->block, FZB_FACET_WORDS * sizeof(u32));
+    if (e == hipSuccess) e = hipMemset(f->block, 0, FZB_FACET_WORDS * sizeof(u32));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->mirror, FZB_FACET_WORDS * sizeof(u32), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        fzb_facets_free(f);
+        return fail(FZB_ERR_HIP, std::string("fzb_facets_create: ") + hipGetErrorString(e));
+    }
+    memset(f->mirror, 0, FZB_FACET_WORDS * sizeof(u32));
+    *out = f;
+    return FZB_OK;
+}
+
+void fzb_facets_free(fzb_facets* f) {
+    if (!f) return;
+    (void)facets_settle(f);  // (a copy into the mirror may still be in flight)
+    if (f->done) (void)hipEventDestroy(f->done);
+    if (f->block) (void)hipFree(f->block);
+    if (f->mirror) (void)hipHostFree(f->mirror);
+    delete f;
+}
+
+// After a host form (the null stream) the query's own wait has drained it: facets_settle finds it idle and nothing is asked of the device.
+// After a _device form the copy may still be in flight: wait for it, as fzb_subset_info does for a captured count - for the sink's own event
+// when the form ran on a stream of the caller's (that stream may have been destroyed since and is never touched), else for the null stream.
+int fzb_facets_read(fzb_facets* f, uint32_t out[FZB_FACET_WORDS]) {
+    if (!f || !out) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc = facets_settle(f)) return rc;
+    memcpy(out, f->mirror, FZB_FACET_WORDS * sizeof(u32));
+    return FZB_OK;
+}
+
+const uint32_t* fzb_facets_device(const fzb_facets* f) { return f ? f->block : nullptr; }
+
+int fzb_matcher_set_facets(fzb_matcher* m, fzb_facets* f) {
+    if (!m) return fail(FZB_ERR_INVALID, "null argument");
+    m->facets = f;
+    return FZB_OK;
+}
+
+int fzb_multi_matcher_set_facets(fzb_multi_matcher* mm, fzb_facets* f) {
+    if (!mm) return fail(FZB_ERR_INVALID, "null argument");
+    mm->facets = f;
+    return FZB_OK;
+}
+
 int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_match** out, size_t* out_len) {
     if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -3842,7 +4011,7 @@ int fzb_prompt_list_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset
     hipStream_t st = (hipStream_t)stream;
     if (count == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
-        return FZB_OK;
+        return facets_none(m->facets, st);
     }
     if ((rc = fzb_bind_device(m))) return rc;
     return prompt_list_stage(m, c, in, first, count, index_offset, false, (fzb_match_rec*)dev_out, capacity, dev_count, st);
@@ -3857,7 +4026,7 @@ int fzb_prompt_top_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
-        return FZB_OK;
+        return facets_none(m->facets, st);
     }
     if ((rc = fzb_bind_device(m))) return rc;
     return prompt_top_stage(m, c, in, want, (fzb_match_rec*)dev_out, dev_count, st);
@@ -3870,6 +4039,7 @@ int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c,
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
+    if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_top_indices")) return rc_;
     *out = nullptr;
     *out_len = 0;
     *out_positions = nullptr;
@@ -3970,7 +4140,7 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
-        return FZB_OK;
+        return facets_none(mm->facets, st);
     }
     // every buffer first: the sources of the union are final before anything is launched
     int rc;
@@ -4027,6 +4197,9 @@ static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus*
     if (out_found) *out_found = 0;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
+    if (mm->patterns.empty() || n == 0) {
+        if (int rc_ = facets_every(mm->facets, c, 0, n, "fzb_multi_match_list_top_indices_fused")) return rc_;
+    }
     if (mm->patterns.empty()) return empty_top_indices(c, n, mm->config.sort, limit, out, out_len, out_positions, out_found);  // CompiledPatterns::Empty
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
     size_t P = 0;
@@ -4123,6 +4296,7 @@ int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_cor
         if ((rc = subset_capture_trivial(c, in, capture))) return rc;
         if (!in) return fzb_multi_match_list_top_indices_fused(mm, c, limit, out, out_len, out_positions, out_found);
         std::vector<fzb_match> head;  // no pattern over a candidate set: the single form's host list, no positions
+        if ((rc = facets_check(mm->facets, c, "fzb_multi_match_list_top_indices_subset")) || (rc = facets_column(mm->facets, c, in, 0, c->dev.n, (int)fzb_grid_cap(~0ull, 2), nullptr))) return rc;
         if ((rc = subset_empty_list(c, const_cast<fzb_subset*>(in), mm->config.sort, limit, head, out_found))) return rc;
         std::vector<fzb_match_indices> recs(head.size());
         for (size_t i = 0; i < head.size(); i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, 0, 0, 0, 0};

@@ -119,6 +119,22 @@ struct fzb_subset {
     u64 count = 0;
 };
 
+// A FACET SINK of one corpus (include/frizbee_hip.h, fzb_facets; facets.h; host.hip): the block of FZB_FACET_WORDS counts in device memory
+// and its page-locked host mirror.  Attached to a matcher (MatcherState::facets, fzb_multi_matcher::facets), it is filled by every query
+// that honours it: the block is cleared, counted into and copied to the mirror in stream order on the query's stream, and `done` is recorded
+// behind the copy - an event of the sink's own, so nothing here outlives a stream the caller destroys.  A host form's one wait brings the
+// counts back; a _device form leaves them behind `done` (fzb_facets_read waits for it only when it has not completed yet).
+struct fzb_facets {
+    const fzb_corpus* corpus = nullptr;
+    u32* block = nullptr;   // device: FZB_FACET_WORDS words
+    u32* mirror = nullptr;  // page-locked host copy
+    hipEvent_t done = nullptr;  // recorded behind the last query's copy into the mirror when that query ran on a stream of the caller's
+    bool on_event = false;  // the last query recorded `done`; else it ran on the null stream, which cannot be destroyed and is waited for itself
+                            // (an event record costs a query 4 - 5 us, profiles/facets.txt: the host forms and stream 0 do not pay it)
+    bool pending = false;   // a query was enqueued since the last read or the last wait known to cover it: `done` may not have completed
+    int device = -1;
+};
+
 // A device buffer that only grows, for every helper that sizes one: fzb_dev_renew frees what *p holds and allocates `elems` anew (*p stays
 // null when that fails); fzb_grow_dev does so when *p is missing or holds fewer than `want` elements (*have, the slack excluded).
 template <typename T>
@@ -267,6 +283,7 @@ struct MatcherState : OutStaging {
     u32* top_words = nullptr;
     size_t top_words_cap = 0;  // in words
     ScopeScratch scope;        // queries over a corpus with an active scope: the pipeline's records ahead of the drop
+    fzb_facets* facets = nullptr;  // the attached facet sink (fzb_matcher_set_facets; not owned): part of the session, so it survives set_pattern / set_config
 };
 
 struct fzb_matcher : CompiledNeedle, MatcherState {};
@@ -321,6 +338,7 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
     ScopeScratch scope;  // queries over a corpus with an active scope: the composition's records ahead of the drop
+    fzb_facets* facets = nullptr;  // the attached facet sink (fzb_multi_matcher_set_facets; not owned): survives set_patterns / set_config
     fzb_matcher* order = nullptr;
     std::vector<fzb_multi_matcher*> shard_clones;
     std::vector<int> shard_devices;
@@ -379,5 +397,7 @@ int fzb_sig_sync_borrowed(fzb_corpus* c);
 int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead);
 // the same rule for the visibility scope: an entry point honours an active scope or refuses it (FZB_OK without one)
 int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead);
+// the same rule for an attached facet sink (facets.h): an entry point fills it or refuses the matcher that carries one (FZB_OK without one)
+int fzb_refuse_facets(const fzb_facets* f, const char* call);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

@@ -196,7 +196,7 @@ using ProduceFn = std::function<int(fzb_match* run, size_t capacity, u32* words,
 // A shard that carries a score bias is a rank-local failure like any other (the root's merge orders by what the matchers produce): no rank returns
 // before the all-gather.
 static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort, size_t n, uint32_t index_offset, fzb_shard_comm* c, int flags, const fzb_corpus* shard,
-                         const char* call, const ProduceFn& produce, fzb_match** out, size_t* out_len) {
+                         const fzb_facets* sink, const char* call, const ProduceFn& produce, fzb_match** out, size_t* out_len) {
     const bool all = (flags & FZB_GATHER_ALL) != 0;
     const bool receiver = all || c->rank == 0;
     // 1. the rank-local steps: this rank's run (or, for Empty, nothing to score) and its words
@@ -213,6 +213,7 @@ static int rccl_exchange(RcclApi* api, fzb_matcher* order, bool empty, int sort,
                                                 std::to_string(index_offset) + ")");
         else if ((local = fzb_refuse_biased(shard, call, "a single-device call (fzb_match_list, fzb_match_list_top) on the rank that holds the list"))) {
         } else if ((local = fzb_refuse_scoped(shard, call, "a single-device call (fzb_match_list, fzb_match_list_top) on the rank that holds the list"))) {
+        } else if ((local = fzb_refuse_facets(sink, call))) {  // (an attached facet sink: refused like a term this exchange cannot apply)
         } else if (!empty && !(local = grow(&c->run, &c->run_cap, n)))
             local = produce((fzb_match*)c->run, n ? n : 1, c->words, c->stream);
         if (local) local_msg = fzb_last_error();
@@ -317,7 +318,7 @@ int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32
     int rc = rccl_begin(m, shard, c, flags, out, out_len, &api);
     if (rc) return rc;
     const size_t n = shard->dev.n;
-    return rccl_exchange(api, m, m->empty, m->config.sort, n, index_offset, c, flags, shard, "fzb_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+    return rccl_exchange(api, m, m->empty, m->config.sort, n, index_offset, c, flags, shard, m->facets, "fzb_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
         return fzb_match_list_device(m, shard, 0, n, index_offset, run, cap, words, st);
     }, out, out_len);
 }
@@ -330,7 +331,7 @@ int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* 
     fzb_matcher* order = nullptr;
     if ((rc = fzb_multi_order_host(mm, &order))) return rc;  // host memory only: cannot fail per rank
     const size_t n = shard->dev.n;
-    return rccl_exchange(api, order, mm->patterns.empty(), mm->config.sort, n, index_offset, c, flags, shard, "fzb_multi_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
+    return rccl_exchange(api, order, mm->patterns.empty(), mm->config.sort, n, index_offset, c, flags, shard, mm->facets, "fzb_multi_match_list_parallel_rccl", [&](fzb_match* run, size_t cap, u32* words, hipStream_t st) {
         return fzb_multi_match_list_device(mm, shard, 0, n, index_offset, run, cap, words, st);
     }, out, out_len);
 }

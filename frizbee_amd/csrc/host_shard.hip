@@ -640,6 +640,7 @@ int fzb_match_list_parallel_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc
     if (!m || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
+    if (int rc_ = fzb_refuse_facets(m->facets, "fzb_match_list_parallel_sharded")) return rc_;
     // CompiledPatterns::Empty: every index, score 0, reversed if the strategy says so, never sorted (mod.rs:215-220, 381-384)
     if (m->empty) return fzb_empty_pattern_list(sc->n, 0, m->config.sort, out, out_len);
     // the shard clones of the matcher score their shards themselves
@@ -690,6 +691,7 @@ int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_shard
     if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
+    if (int rc_ = fzb_refuse_facets(mm->facets, "fzb_multi_match_list_parallel_sharded")) return rc_;
     if (mm->patterns.empty()) return fzb_empty_pattern_list(sc->n, 0, mm->config.sort, out, out_len);
     fzb_matcher* root = nullptr;
     int rc = fzb_multi_order_host(mm, &root);
@@ -706,6 +708,7 @@ int fzb_match_list_top_sharded(fzb_matcher* m, const fzb_sharded_corpus* sc, siz
     if (!m || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
+    if (int rc_ = fzb_refuse_facets(m->facets, "fzb_match_list_top_sharded")) return rc_;
     if (m->empty) return fzb_empty_pattern_top(sc->n, m->config.sort, limit, out, out_len, out_found);
     return fzb_sharded_top_query(m, sc, [](size_t, fzb_matcher* cm, const fzb_corpus* c, uint32_t index_offset, hipStream_t st) {
         return fzb_match_list_device(cm, c, 0, c->dev.n, index_offset, (fzb_match*)cm->out_dev, cm->out_cap, cm->count_dev, st);
@@ -716,6 +719,7 @@ int fzb_multi_match_list_top_sharded(fzb_multi_matcher* mm, const fzb_sharded_co
     if (!mm || !sc || !out || !out_len) return fzb_fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     *out_len = 0;
+    if (int rc_ = fzb_refuse_facets(mm->facets, "fzb_multi_match_list_top_sharded")) return rc_;
     if (mm->patterns.empty()) return fzb_empty_pattern_top(sc->n, mm->config.sort, limit, out, out_len, out_found);
     fzb_matcher* root = nullptr;
     int rc = fzb_multi_order_host(mm, &root);

@@ -15,6 +15,7 @@
 #include "topk_select.h"
 #include "score_bias.h"
 #include "scope.h"
+#include "facets.h"
 
 #define TOPK_TILE 2048
 // scratch layout (u32 words; the caller hands in the radix sort's histogram buffer, idle until the ordering step):
@@ -317,11 +318,36 @@ void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const
 // sized on the host from the capacity and trimmed by the device-side count; the kept records go to a DIFFERENT buffer.
 static_assert(SCOPE_TILE == FZB_TILE && sizeof(scope_rec) == sizeof(fzb_match_rec) && alignof(scope_rec) == alignof(fzb_match_rec), "the drop pass moves fzb_match_rec by the tile");
 
-// the flag pass (tile_compact.h): 2-byte tag gathered per record
+// the flag pass (tile_compact.h): 2-byte tag gathered per record.  FACETS: the tag facets of the records (facets.h) ride in the same pass -
+// the tag is in a register here, so a sink attached to the matcher costs no second pass over the records under an active scope; the
+// instantiation without a sink is the pass as it was.
+template <bool FACETS>
+__device__ __forceinline__ void scope_flag_pass(const scope_rec* __restrict__ recs, const u32* __restrict__ count, u32 cap, const uint16_t* __restrict__ tags, u64 n_tags, u64 first,
+                                                u32 index_offset, u32 require, u32 exclude, u64* __restrict__ bitmap, u32* __restrict__ tile_counts, u32* __restrict__ facets) {
+    const u32 n = min(count[0], cap);
+    if constexpr (!FACETS) {
+        tc_flag_pass(n, bitmap, tile_counts, [&](u32 tile, u32 slot) { return scope_tile_keeps(recs, n, tile, slot, tags, n_tags, first, index_offset, require, exclude); });
+    } else {
+        facet_acc acc;
+        facets_clear(acc);
+        tc_flag_pass(n, bitmap, tile_counts, [&](u32 tile, u32 slot) {
+            const u64 j = (u64)tile * SCOPE_TILE + slot;
+            const bool valid = j < n;
+            const u32 tag = valid ? scope_tag_of(tags, n_tags, first, index_offset, recs[j].index) : 0u;
+            facets_wave_step(acc, valid, tag, require, exclude);
+            return facet_visible(valid, tag, require, exclude);
+        });
+        facets_publish(acc, facets);
+    }
+}
 __global__ __launch_bounds__(256) void k_scope_flag(const scope_rec* __restrict__ recs, const u32* __restrict__ count, u32 cap, const uint16_t* __restrict__ tags, u64 n_tags, u64 first,
                                                     u32 index_offset, u32 require, u32 exclude, u64* __restrict__ bitmap, u32* __restrict__ tile_counts) {
-    const u32 n = min(count[0], cap);
-    tc_flag_pass(n, bitmap, tile_counts, [&](u32 tile, u32 slot) { return scope_tile_keeps(recs, n, tile, slot, tags, n_tags, first, index_offset, require, exclude); });
+    scope_flag_pass<false>(recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts, nullptr);
+}
+__global__ __launch_bounds__(256) void k_scope_flag_facets(const scope_rec* __restrict__ recs, const u32* __restrict__ count, u32 cap, const uint16_t* __restrict__ tags, u64 n_tags,
+                                                           u64 first, u32 index_offset, u32 require, u32 exclude, u64* __restrict__ bitmap, u32* __restrict__ tile_counts,
+                                                           u32* __restrict__ facets) {
+    scope_flag_pass<true>(recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts, facets);
 }
 
 // The compaction: tile_compact.h's record compaction with a bounded destination (scope_store) and the (written, found) pair (scope_counts).
@@ -332,10 +358,14 @@ __global__ __launch_bounds__(256) void k_scope_compact(const u64* __restrict__ b
 }
 
 // recs: count[0] index-ordered records (at most `cap`); out: room for `capacity`; count_out: (written, found).  bitmap: 16 words per tile of
-// cap records, tile_counts: one word per tile.
+// cap records, tile_counts: one word per tile.  facets != nullptr: the flag pass also counts the records' tag facets into that block
+// (cleared in stream order by the caller); tags may then be null (n_tags 0: every tag 0).
 void fzb_launch_scope_drop(const fzb_match_rec* recs, const u32* count, u32 cap, const uint16_t* tags, u64 n_tags, u64 first, u32 index_offset, u32 require, u32 exclude, u64* bitmap,
-                           u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st) {
+                           u32* tile_counts, fzb_match_rec* out, u32 capacity, u32* count_out, int grid_max, hipStream_t st, u32* facets) {
     const int grid = tc_grid((cap + SCOPE_TILE - 1) / SCOPE_TILE, grid_max);
-    FZB_LAUNCH(k_scope_flag, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts);
+    if (facets)
+        FZB_LAUNCH(k_scope_flag_facets, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, tags ? n_tags : 0, first, index_offset, require, exclude, bitmap, tile_counts,
+                   facets);
+    else FZB_LAUNCH(k_scope_flag, dim3(grid), dim3(256), 0, st, (const scope_rec*)recs, count, cap, tags, n_tags, first, index_offset, require, exclude, bitmap, tile_counts);
     FZB_LAUNCH(k_scope_compact, dim3(grid), dim3(256), 0, st, (const u64*)bitmap, (const u32*)tile_counts, count, cap, (const scope_rec*)recs, (scope_rec*)out, capacity, count_out);
 }

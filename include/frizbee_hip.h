@@ -736,6 +736,58 @@ int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* 
 /* fzb_matcher_shard_report for the last fzb_multi_match_list_parallel_sharded on `mm` ("" before the first) */
 const char* fzb_multi_matcher_shard_report(const fzb_multi_matcher* mm);
 
+/* ---- TAG FACETS: per-tag match counts of a query, counted on the device ------------------------------------------------------------------
+ * A picker with filter chips ("tests 1 204 - docs 87 - ignored 312", "N matches, 312 hidden by filters") needs, per keystroke, the number of
+ * matches under every tag bit and the number the active scope hides.  The reference has no such notion: its caller counts over the Vec
+ * `match_list` returned.  Here an fzb_facets holds FZB_FACET_WORDS counts in device memory and a page-locked host mirror; attached to a
+ * matcher it is filled by every query that honours it, where the records and the tag column already are.
+ * For a query, let A be the haystacks of the input (the range, or the subset `in`) that the matcher accepts - the set a `capture` of the same
+ * call would hold: taken BEFORE scope, bias, selection, `limit` and ordering; for a `from_patterns` matcher what the composition accepted;
+ * for an empty needle or an empty pattern list every haystack of the input.  With tag(i) the haystack's 16-bit tag (0 where the corpus has
+ * no tags) and (require, exclude) the corpus' scope at the time of the call:
+ *     [0]      matched            |A|
+ *     [1]      visible            the members of A with (tag & require) == require && (tag & exclude) == 0: the call's `found`
+ *     [2 + b]  all_by_bit[b]      the members of A whose tag has bit b, b = 0 .. 15 - over ALL of A: a chip for an excluded bit shows what it hides
+ *     [18 + b] visible_by_bit[b]  the same over the visible members of A
+ * The counts are exact: they depend neither on `limit` nor on the `capacity` of a _device form's output (a _device call with room for 10
+ * records over 10 000 matches counts 10 000: with a sink attached the producer writes into the matcher's scratch, which has room for one
+ * record per haystack of the range).  Bias, `exact`, positions and which haystacks match are untouched.  With no sink attached every call
+ * launches and allocates exactly what it did before sinks existed.
+ * FILLED BY: fzb_match_list, fzb_match_list_into, fzb_match_list_device, fzb_match_list_sorted_device, fzb_match_list_top, fzb_match_list_top_device,
+ * fzb_match_list_top_indices, fzb_match_list_top_indices_device, the _subset forms of each, fzb_prompt_list_device, fzb_prompt_top_device; and of a
+ * `from_patterns` matcher fzb_multi_match_list, fzb_multi_match_list_into, fzb_multi_match_list_device, fzb_multi_match_list_top, their _subset forms,
+ * fzb_multi_match_list_top_indices_device and fzb_multi_match_list_top_indices_fused (in the forms with positions the count sits at the top
+ * stage only, as the capture does).  Everything is enqueued on the query's stream: the block is cleared, counted into and copied to the
+ * mirror in stream order - in front of a host form's one wait, which makes no
+ * second one.  A _device form on a stream of the caller's also records an event of the sink's own behind the copy (the null stream needs
+ * none and does not pay for one).  (The closed-form host answers of an empty needle / an empty pattern list over a corpus without bias, scope or subset launch
+ * nothing else and have no wait of their own: with a sink attached they launch the count on the null stream of the current device and wait
+ * for it before they return.)
+ * ONE QUERY AT A TIME: a sink holds the counts of the last query that filled it.  Queries that fill the same sink - by one matcher or by
+ * several that share it - must be ordered by the caller (the same stream, or an event between the streams): the next query's clear is not
+ * ordered against the previous query's copy otherwise.  The sink keeps no handle of a caller's stream: one destroyed after its query is never touched.
+ * REFUSED: every other entry point that takes a corpus either fills an attached sink or REFUSES the matcher with FZB_ERR_INVALID - none ignores
+ * the sink; the message names set_facets(NULL).  Refused: fzb_match_list_parallel, fzb_match_list_parallel_sharded, fzb_match_list_top_sharded,
+ * fzb_match_list_parallel_rccl, fzb_match_list_indices, fzb_match_list_indices_into and their fzb_multi_* counterparts, and the composed
+ * fzb_multi_match_list_top_indices.  A sink created on one corpus is refused on another.  A sink over a corpus that never had tags counts
+ * matched and visible and leaves both by_bit rows zero.  fzb_matcher_clone / fzb_multi_matcher_clone do not carry the sink over.
+ * After fzb_matcher_reserve / fzb_multi_matcher_reserve with a sink attached no later query, and no later toggling of the scope, allocates.
+ * The sink is not owned by the matcher: detach it (or free the matcher) before fzb_facets_free. */
+#define FZB_FACET_WORDS 34
+typedef struct fzb_facets fzb_facets;
+/* a sink of `c`, all counts zero (on the current device: the corpus') */
+int fzb_facets_create(const fzb_corpus* c, fzb_facets** out);
+void fzb_facets_free(fzb_facets* f);
+/* The counts of the last query that filled the sink.  After a host form no device work: its wait brought them back (one query of the null
+ * stream, which is idle).  After a _device form the call waits for that form's copy - for the sink's event when the form ran on a stream of
+ * the caller's, else for the null stream - as fzb_subset_info waits for a captured count. */
+int fzb_facets_read(fzb_facets* f, uint32_t out[FZB_FACET_WORDS]);
+/* the block's address in device memory (FZB_FACET_WORDS uint32), for stream-ordered consumers; NULL for NULL */
+const uint32_t* fzb_facets_device(const fzb_facets* f);
+/* attach (or, with NULL, detach) a sink: part of the matcher's session, it survives fzb_matcher_set_pattern / _set_config (set_patterns) */
+int fzb_matcher_set_facets(fzb_matcher* m, fzb_facets* f);
+int fzb_multi_matcher_set_facets(fzb_multi_matcher* mm, fzb_facets* f);
+
 /* Measurement hooks (bench.py): device time of the fzb_match_list_device calls made on this matcher since
  * fzb_set_profiling(m, 1), measured with HIP events recorded on the launch stream (event records only, no
  * synchronisation until read).  fzb_last_timings averages over those calls (at most the last 32):

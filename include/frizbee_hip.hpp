@@ -315,6 +315,39 @@ class Subset {
     std::unique_ptr<fzb_subset, Del> h_;
 };
 
+// A facet sink of one resident Corpus (fzb_facets): the per-tag match counts of a query, counted on the device.  Attached with
+// Matcher::set_facets / MultiMatcher::set_facets, it is filled by every query that honours it; read() returns the counts of the last such
+// query's match set (what a capture would hold: before scope, bias, limit and ordering).  The reference has no counterpart.  The corpus
+// must outlive the sink, and the sink every matcher it is attached to.
+class Facets {
+  public:
+    struct Counts {
+        uint32_t matched, visible;
+        std::array<uint32_t, 16> all_by_bit, visible_by_bit;  // all_by_bit counts hidden matches too: a chip for an excluded bit shows what it hides
+    };
+    explicit Facets(const Corpus& corpus) {
+        fzb_facets* f = nullptr;
+        check(fzb_facets_create(corpus.raw(), &f));
+        h_.reset(f);
+    }
+    Counts read() const {  // (after a _device form: waits for that form's stream)
+        uint32_t w[FZB_FACET_WORDS] = {};
+        check(fzb_facets_read(h_.get(), w));
+        Counts c{w[0], w[1], {}, {}};
+        for (int b = 0; b < 16; b++) {
+            c.all_by_bit[b] = w[2 + b];
+            c.visible_by_bit[b] = w[18 + b];
+        }
+        return c;
+    }
+    const uint32_t* device() const { return fzb_facets_device(h_.get()); }  // FZB_FACET_WORDS uint32 in device memory
+    fzb_facets* raw() const { return h_.get(); }
+
+  private:
+    struct Del { void operator()(fzb_facets* f) const { fzb_facets_free(f); } };
+    std::unique_ptr<fzb_facets, Del> h_;
+};
+
 // The list cut into one contiguous shard per GPU (fzb_corpus_upload_sharded): the devices of a node in the role of
 // `match_list_parallel`'s worker threads (src/matcher/parallel.rs:18-89).  `gpus == 0`: every visible device.
 class ShardedCorpus {
@@ -411,6 +444,13 @@ class Matcher {  // src/matcher/mod.rs:77-222
             const fzb_config r = config_.raw();
             check(fzb_multi_matcher_set_config(multi_.get(), &r));
         }
+    }
+
+    // Attach a facet sink (nullptr: detach): every query that honours it fills it, the others refuse the matcher until it is detached.  It
+    // stays attached across set_pattern / set_patterns / set_config, also when they build the other form of the matcher.
+    void set_facets(const Facets* facets) {
+        facets_ = facets ? facets->raw() : nullptr;
+        attach_facets();
     }
 
     // `match_list(&haystacks)`: ordered per config.sort
@@ -678,6 +718,7 @@ class Matcher {  // src/matcher/mod.rs:77-222
             check(fzb_matcher_create(&r, (const uint8_t*)patterns_[last].needle.data(), patterns_[last].needle.size(), &m));
             single_.reset(m);
             if (patterns_.size() != 1) patterns_ = {patterns_[last]};
+            attach_facets();
             return;
         }
         const std::vector<fzb_pattern> raw = raw_patterns(patterns_);
@@ -685,6 +726,11 @@ class Matcher {  // src/matcher/mod.rs:77-222
         fzb_multi_matcher* mm = nullptr;
         check(fzb_multi_matcher_create(&c, raw.data(), raw.size(), &mm));
         multi_.reset(mm);
+        attach_facets();
+    }
+    void attach_facets() {
+        if (single_) check(fzb_matcher_set_facets(single_.get(), facets_));
+        if (multi_) check(fzb_multi_matcher_set_facets(multi_.get(), facets_));
     }
     static std::vector<Match> take(fzb_match* out, size_t n) {
         std::vector<Match> r(n);
@@ -696,6 +742,7 @@ class Matcher {  // src/matcher/mod.rs:77-222
     struct DelM { void operator()(fzb_multi_matcher* m) const { fzb_multi_matcher_free(m); } };
     Config config_;
     std::vector<Pattern> patterns_;
+    fzb_facets* facets_ = nullptr;  // the attached sink (not owned)
     std::unique_ptr<fzb_matcher, DelS> single_;
     std::unique_ptr<fzb_multi_matcher, DelM> multi_;
 };

@@ -147,6 +147,20 @@ extern "C" {
                               dev_count: *mut u32, stream: *mut c_void) -> c_int;
     fn fzb_prompt_top_device(m: *mut c_void, c: *const c_void, input: *const c_void, limit: usize, dev_out: *mut FzbMatch, capacity: usize, dev_count: *mut u32,
                              stream: *mut c_void) -> c_int;
+    // tag facets (fzb_facets): the per-tag match counts of a query, counted on the device into a sink attached to the matcher; `out` holds
+    // FZB_FACET_WORDS = 34 words: matched, visible, all_by_bit[16], visible_by_bit[16]
+    #[allow(dead_code)]
+    fn fzb_facets_create(c: *const c_void, out: *mut *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_facets_free(f: *mut c_void);
+    #[allow(dead_code)]
+    fn fzb_facets_read(f: *mut c_void, out: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_facets_device(f: *const c_void) -> *const u32;
+    #[allow(dead_code)]
+    fn fzb_matcher_set_facets(m: *mut c_void, f: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_matcher_set_facets(mm: *mut c_void, f: *mut c_void) -> c_int;
     // the same four over a `from_patterns` matcher: the composition runs over `input`, `capture` receives the composition's match set
     #[allow(dead_code)]
     fn fzb_multi_match_list_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
