@@ -135,6 +135,7 @@ SYMBOLS = [
     "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
     "fzb_prompt_list_device", "fzb_prompt_top_device",
     "fzb_facets_create", "fzb_facets_free", "fzb_facets_read", "fzb_facets_device", "fzb_matcher_set_facets", "fzb_multi_matcher_set_facets",
+    "fzb_match_list_top_sections", "fzb_match_list_top_sections_device", "fzb_multi_match_list_top_sections", "fzb_multi_match_list_top_sections_device",
 ]
 
 
@@ -289,6 +290,11 @@ def lib():
         l.fzb_facets_device.restype = C.c_void_p
         l.fzb_matcher_set_facets.argtypes = [C.c_void_p, C.c_void_p]
         l.fzb_multi_matcher_set_facets.argtypes = [C.c_void_p, C.c_void_p]
+        l.fzb_match_list_top_sections.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_sections_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_multi_match_list_top_sections.argtypes = l.fzb_match_list_top_sections.argtypes
+        l.fzb_multi_match_list_top_sections_device.argtypes = l.fzb_match_list_top_sections_device.argtypes
         _lib = l
     return _lib
 
@@ -316,6 +322,43 @@ def _top(fn, handle, target, limit, copy):
     out, n, found = C.c_void_p(), C.c_size_t(), C.c_uint64()
     _check(fn(handle, target, limit, C.byref(out), C.byref(n), C.byref(found)))
     return _take(out, n, copy), found.value
+
+
+SECTIONS_MAX, SECTION_LIMIT_MAX = 8, 1024  # include/frizbee_hip.h FZB_SECTIONS_MAX, FZB_SECTION_LIMIT_MAX
+
+
+def _section_array(sections):
+    """a sequence of (require, exclude) pairs -> the C ABI's fzb_section array (uint16 pairs)"""
+    arr = np.zeros((len(sections), 2), np.uint16)
+    for s, (require, exclude) in enumerate(sections):
+        if not (0 <= int(require) <= 0xFFFF and 0 <= int(exclude) <= 0xFFFF):
+            raise ValueError("a section is a pair of 16-bit masks (require, exclude): %r" % ((require, exclude),))
+        arr[s] = (int(require), int(exclude))
+    return arr
+
+
+def _top_sections(fn, handle, corpus, sections, limit, subset, capture):
+    """the host form of a sectioned top-`limit` call -> [(records, found)] in section order; one block comes back and is split here"""
+    arr = _section_array(sections)
+    S = len(arr)
+    out, lens, found = C.c_void_p(), (C.c_size_t * max(S, 1))(), (C.c_uint64 * max(S, 1))()
+    _check(fn(handle, corpus.h, arr.ctypes.data if S else None, S, limit, _h(subset), _h(capture), C.byref(out), lens, found))
+    total = sum(lens[s] for s in range(S))
+    block = np.zeros(total, MATCH_DTYPE)
+    if out.value:
+        if total:
+            C.memmove(block.ctypes.data, out, total * 8)
+        lib().fzb_matches_free(out)
+    heads, at = [], 0
+    for s in range(S):
+        heads.append((block[at:at + lens[s]].copy(), int(found[s])))
+        at += lens[s]
+    return heads
+
+
+def _top_sections_device(fn, handle, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream, subset, capture):
+    arr = _section_array(sections)
+    _check(fn(handle, corpus.h, arr.ctypes.data if len(arr) else None, len(arr), limit, _h(subset), _h(capture), dev_out_ptr, capacity, dev_counts_ptr, stream))
 
 
 def _take(out, n, copy=True):
@@ -887,6 +930,14 @@ class MultiMatcher(_IterApi):
         (records written, matches found) at `dev_count_ptr`; asynchronous on `stream`.  A matcher without a compiled pattern is refused."""
         _check(lib().fzb_multi_match_list_top_subset_device(self.h, corpus.h, _h(subset), _h(capture), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
 
+    def match_list_top_sections(self, corpus, sections, limit, *, subset=None, capture=None):
+        """`Matcher.match_list_top_sections` behind the composition: [(records, found)] per (require, exclude) section, one device call."""
+        return _top_sections(lib().fzb_multi_match_list_top_sections, self.h, corpus, sections, limit, subset, capture)
+
+    def match_list_top_sections_device(self, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream=0, *, subset=None, capture=None):
+        """`Matcher.match_list_top_sections_device` behind the composition."""
+        _top_sections_device(lib().fzb_multi_match_list_top_sections_device, self.h, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream, subset, capture)
+
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
@@ -1063,6 +1114,20 @@ class Matcher(_IterApi):
         min(limit, len(corpus)) records at `dev_out_ptr`, two count words (records written, found) at `dev_count_ptr`; asynchronous on
         `stream`."""
         _check(lib().fzb_prompt_top_device(self.h, corpus.h, _h(subset), limit, dev_out_ptr, capacity, dev_count_ptr, stream))
+
+    def match_list_top_sections(self, corpus, sections, limit, *, subset=None, capture=None):
+        """A picker's sections in one device call: `sections` is a sequence of (require, exclude) pairs over the corpus' 16 tag bits (the
+        scope's predicate; at most SECTIONS_MAX = 8, `limit` <= SECTION_LIMIT_MAX = 1024).  Returns [(records, found)] in section order:
+        element s is what `match_list_top(corpus, limit)` returns over a corpus whose scope is the corpus' own scope AND section s -
+        from ONE pass of the filter and the scorers and one host wait.  Sections may overlap, repeat or be empty; (0, 0) is everything.
+        The reference has no such call: its caller splits the Vec `match_list` returned."""
+        return _top_sections(lib().fzb_match_list_top_sections, self.h, corpus, sections, limit, subset, capture)
+
+    def match_list_top_sections_device(self, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream=0, *, subset=None, capture=None):
+        """`match_list_top_sections` with the result left in HBM: `capacity` >= len(sections) * limit records at `dev_out_ptr`, section s's
+        head at record s * limit; 2 * len(sections) count words at `dev_counts_ptr` ([2s] = records of head s, [2s + 1] = matches in
+        section s); asynchronous on `stream`.  What lies behind a head inside its slab is unspecified."""
+        _top_sections_device(lib().fzb_match_list_top_sections_device, self.h, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream, subset, capture)
 
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""

@@ -270,6 +270,12 @@ void fzb_launch_concat_runs(const RunSet& rs, const u32* base_in, u32* total_out
 hipError_t fzb_launch_topk_select(const fzb_match_rec* in, const u32* in_count, u32 in_cap, u32 limit, int by_score, int desc, int one_pass, fzb_match_rec* out, u32 out_cap,
                             u32* out_count, u32* scratch, u32 ntiles_cap, int grid, hipStream_t st);
 void fzb_launch_topk_concat(const RunSet& rs, const u32* base_in, u32* total_out, fzb_match_rec* out, u32 capacity, int grid, hipStream_t st);
+// kernels_sections.hip: the selection and ordering stage for up to SECTIONS_MAX tag sections at once (sections.h), where
+// fzb_launch_topk_select + fzb_launch_sort take one list; scratch: fzb_sections_scratch_words(in_cap) words of the matcher's own
+struct sections_set;
+size_t fzb_sections_scratch_words(size_t n_records);
+hipError_t fzb_launch_sections_select(const fzb_match_rec* in, const u32* in_count, u32 in_cap, const uint16_t* tags, u64 n_tags, const sections_set& ss, u32 limit, int by_score,
+                                      int desc, int one_pass, fzb_match_rec* out, u32* counts, u32* scratch, u32 ntiles_cap, int grid, hipStream_t st);
 // the corpus' score bias (score_bias.h) added to index-ordered records: haystack = first + (index - index_offset); the grid is sized from cap, trimmed by count[0]
 void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st);
 // the corpus' visibility scope (scope.h): the records of hidden haystacks dropped from count[0] index-ordered records (at most cap) into a DIFFERENT

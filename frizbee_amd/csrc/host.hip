@@ -29,6 +29,7 @@
 #include "sig_filter.h"
 #include "score_bias.h"
 #include "scope.h"
+#include "sections.h"
 #include "seg_list.h"
 
 namespace {
@@ -331,6 +332,15 @@ void fzb_scope_release(ScopeScratch& s) {
         if (p) (void)hipFree(p);
     s = ScopeScratch{};
 }
+int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_records) {
+    if (int rc = fzb_grow_dev(&s.words, &s.words_cap, fzb_sections_scratch_words(n_records), 16)) return rc;
+    return stage_records ? fzb_grow_dev(&s.stage, &s.stage_words, 32 + 2 * stage_records, 16) : FZB_OK;
+}
+void fzb_sections_release(SectionsScratch& s) {
+    if (s.words) (void)hipFree(s.words);
+    if (s.stage) (void)hipFree(s.stage);
+    s = SectionsScratch{};
+}
 void fzb_out_release(OutStaging& o) {
     if (o.out_dev) (void)hipFree(o.out_dev);
     if (o.count_dev) (void)hipFree(o.count_dev);
@@ -343,6 +353,7 @@ static void release_state(MatcherState& s) {
     free_workspace(s.ws);
     fzb_out_release(s);
     fzb_scope_release(s.scope);
+    fzb_sections_release(s.sections);
     for (void* p : {(void*)s.top_words, (void*)s.trace_sel, (void*)s.trace_pos, (void*)s.trace_npos, (void*)s.top_head, (void*)s.top_traced, (void*)s.top_idx_words, (void*)s.top_tiles,
                     (void*)s.top_packed, (void*)s.top_dense, s.long_blob_dev, (void*)s.long_scratch})
         if (p) (void)hipFree(p);
@@ -2758,6 +2769,7 @@ static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and p
     fzb_sort_release(mm->sort);
     fzb_out_release(*mm);
     fzb_scope_release(mm->scope);
+    fzb_sections_release(mm->sections);
 }
 
 // the composition's buffers for ranges of up to `count` haystacks
@@ -3292,6 +3304,31 @@ static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fz
 int fzb_match_list_top_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream) {
     return top_device_impl(m, c, limit, dev_out, capacity, dev_count, stream, nullptr);
 }
+// The producer of the top stages on `stream`, over the n > 0 haystacks of c (or the candidate set of sa): the pipeline, the capture, the
+// facets, the corpus' scope drop and the bias.  What the selection reads: the index-ordered records in the sort's second buffer, their pair
+// (written, found) in *raw_count, and the ordering flags.
+static int top_produce(fzb_matcher* m, const fzb_corpus* c, size_t n, void* stream, const SubsetArgs* sa, u32** raw_count_out, bool* reversed, bool* by_score, bool* one_pass) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    // (the range workspace first: growing it releases every workspace buffer, the sort's included)
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, n, st, true)) || (rc = ensure_sort_buffers(m, n))) return rc;
+    if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
+    fzb_order_flags(m, fzb_corpus_bias_hi(c), reversed, by_score, one_pass);
+    Workspace& w = m->ws;
+    u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
+    *raw_count_out = raw_count;
+    if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
+        if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, n, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
+        if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, n, m->lc.num_cus * 2, st))) return rc;
+        if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st, m->facets))) return rc;
+    } else {
+        if ((rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)w.sort.tmp, n, raw_count, stream, nullptr, subset_hint(sa)))) return rc;
+        if ((rc = subset_capture(sa, c, w.sort.tmp, raw_count, n, m->lc.num_cus * 2, st))) return rc;
+        if ((rc = facets_records(m->facets, c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // (room for every haystack: never cut ahead of the count)
+        if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
+    }
+    return FZB_OK;
+}
 static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
@@ -3306,23 +3343,10 @@ static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fz
         return facets_none(m->facets, st);
     }
     int rc;
-    // (the range workspace first: growing it releases every workspace buffer, the sort's included)
-    if ((rc = fzb_bind_device(m)) || (rc = ensure_workspace(m, n, st, true)) || (rc = ensure_sort_buffers(m, n))) return rc;
-    if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
     bool reversed, by_score, one_pass;
-    fzb_order_flags(m, fzb_corpus_bias_hi(c), &reversed, &by_score, &one_pass);
+    u32* raw_count = nullptr;
+    if ((rc = top_produce(m, c, n, stream, sa, &raw_count, &reversed, &by_score, &one_pass))) return rc;
     Workspace& w = m->ws;
-    u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
-    if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
-        if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, n, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
-        if ((rc = subset_capture(sa, c, m->scope.recs, m->scope.words, n, m->lc.num_cus * 2, st))) return rc;
-        if ((rc = apply_terms(c, m->scope, n, w.sort.tmp, n, raw_count, 0, 0, m->lc.num_cus * 2, st, m->facets))) return rc;
-    } else {
-        if ((rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)w.sort.tmp, n, raw_count, stream, nullptr, subset_hint(sa)))) return rc;
-        if ((rc = subset_capture(sa, c, w.sort.tmp, raw_count, n, m->lc.num_cus * 2, st))) return rc;
-        if ((rc = facets_records(m->facets, c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // (room for every haystack: never cut ahead of the count)
-        if ((rc = apply_bias(c, w.sort.tmp, raw_count, n, 0, 0, m->lc.num_cus * 2, st))) return rc;  // before the selection reads a score
-    }
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
     const int grid = m->lc.num_cus * 2;
     HIPCHK(fzb_launch_topk_select(w.sort.tmp, raw_count, (u32)n, (u32)want, by_score, reversed, one_pass, (fzb_match_rec*)dev_out, (u32)want, dev_count, w.sort.hist, ntiles_cap, grid, st));
@@ -4281,6 +4305,179 @@ int fzb_multi_match_list_top_subset_device(fzb_multi_matcher* mm, const fzb_corp
     if ((rc = fzb_out_ensure(*mm, 0))) return rc;  // (the composition's pair lives next to the staging's count words)
     SubsetArgs sa{in, capture, nullptr};
     return multi_top_stage(mm, c, n, want, (fzb_match_rec*)dev_out, dev_count, mm->count_dev + 4, (hipStream_t)stream, &sa);
+}
+
+// ---- sectioned top-`limit`: the best matches per tag section, one device call (sections.h, kernels_sections.hip) ---------------------------
+// The reference has no such call: a picker with sections splits the Vec `match_list` returned.  Element s = fzb_match_list_top over the
+// corpus' own scope AND section s's predicate.  The producers are the top stages' own (top_produce, prompt_records, the composition): their
+// index-ordered records - behind capture, facets, the corpus' scope drop and the bias - sit in the sort's second buffer, and the sectioned
+// stage replaces the selection and the radix sort.  Nothing is read back between the stages; the host forms make one copy and one wait.
+}  // extern "C"
+namespace {
+static_assert(SECTIONS_MAX == FZB_SECTIONS_MAX && SECTIONS_LIMIT_MAX == FZB_SECTION_LIMIT_MAX, "include/frizbee_hip.h states the limits of sections.h");
+// what every sectioned entry point checks before anything touches the device
+int sections_check(const void* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture, const char* call,
+                   sections_set* ss) {
+    if (!m || !c || (!sections && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
+    if (n_sections > FZB_SECTIONS_MAX) return fail(FZB_ERR_INVALID, std::string(call) + ": " + std::to_string(n_sections) + " sections; at most FZB_SECTIONS_MAX = 8 in one call");
+    if (limit > FZB_SECTION_LIMIT_MAX) return fail(FZB_ERR_INVALID, std::string(call) + ": limit " + std::to_string(limit) + " is above FZB_SECTION_LIMIT_MAX = 1024");
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    *ss = sections_set{};
+    ss->n = (u32)n_sections;
+    for (size_t s = 0; s < n_sections; s++) {
+        ss->require[s] = sections[s].require;
+        ss->exclude[s] = sections[s].exclude;
+    }
+    return subset_check(c, in, capture, call);
+}
+// an empty corpus: S empty heads
+int sections_nothing(const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_facets* f, size_t n_sections, u32* dev_counts, hipStream_t st) {
+    if (int rc = subset_capture_trivial(c, in, capture)) return rc;
+    if (n_sections) HIPCHK(hipMemsetAsync(dev_counts, 0, 2 * n_sections * sizeof(u32), st));
+    return facets_none(f, st);
+}
+// the stage on `st` behind a producer: slab s of dev_out = the ordered head of section s, dev_counts = the 2S result words
+int sections_stage(SectionsScratch& sc, const fzb_corpus* c, const fzb_match_rec* recs, const u32* raw_count, size_t n, const sections_set& ss, size_t limit, bool by_score,
+                   bool reversed, bool one_pass, fzb_match_rec* dev_out, u32* dev_counts, int grid, hipStream_t st) {
+    if (int rc = fzb_sections_ensure(sc, n, 0)) return rc;
+    HIPCHK(fzb_launch_sections_select(recs, raw_count, (u32)n, c->tags.data, c->dev.n, ss, (u32)limit, by_score, reversed, one_pass, dev_out, dev_counts, sc.words,
+                                      (u32)(n / SECTIONS_TILE + 2), grid, st));
+    return FZB_OK;
+}
+int single_sections_stage(fzb_matcher* m, const fzb_corpus* c, const sections_set& ss, size_t limit, const SubsetArgs* sa, fzb_match_rec* dev_out, u32* dev_counts, hipStream_t st) {
+    const size_t n = c->dev.n;
+    int rc;
+    if ((rc = facets_check(m->facets, c, "fzb_match_list_top_sections"))) return rc;
+    if (n == 0) return sections_nothing(c, sa->in, sa->capture, m->facets, ss.n, dev_counts, st);
+    bool reversed, by_score, one_pass;
+    u32* raw_count = nullptr;
+    if (m->empty) {  // the empty prompt: every visible haystack of the input, score = the clamped bias (prompt_records)
+        if ((rc = subset_capture_trivial(c, sa->in, sa->capture))) return rc;
+        if ((rc = fzb_bind_device(m)) || (rc = fzb_ensure_sort_buffers(m, n))) return rc;
+        if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
+        prompt_order_flags(m, c, &reversed, &by_score, &one_pass);
+        raw_count = m->count_dev + 4;
+        if ((rc = prompt_records(m, c, sa->in, 0, n, 0, m->ws.sort.tmp, n, raw_count, st))) return rc;
+    } else if ((rc = top_produce(m, c, n, st, sa, &raw_count, &reversed, &by_score, &one_pass))) {
+        return rc;
+    }
+    if (ss.n == 0) return FZB_OK;
+    return sections_stage(m->sections, c, m->ws.sort.tmp, raw_count, n, ss, limit, by_score, reversed, one_pass, dev_out, dev_counts, m->lc.num_cus * 2, st);
+}
+// (the composition's producer as multi_top_stage runs it; summed scores pass 255: never one level)
+int multi_sections_stage(fzb_multi_matcher* mm, const fzb_corpus* c, const sections_set& ss, size_t limit, const SubsetArgs* sa, fzb_match_rec* dev_out, u32* dev_counts, hipStream_t st) {
+    const size_t n = c->dev.n;
+    int rc;
+    if ((rc = facets_check(mm->facets, c, "fzb_multi_match_list_top_sections"))) return rc;
+    if (n == 0) return sections_nothing(c, sa->in, sa->capture, mm->facets, ss.n, dev_counts, st);
+    SubsetArgs args = *sa;
+    if (mm->patterns.empty()) {  // no pattern accepts every haystack of the input: the capture is the input itself
+        if ((rc = subset_capture_trivial(c, args.in, args.capture))) return rc;
+        args.capture = nullptr;
+    }
+    if ((rc = fzb_out_ensure(*mm, 0)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;  // (the composition's pair lives next to the staging's count words)
+    u32* const raw_count = mm->count_dev + 4;
+    if ((rc = multi_match_list_device_impl(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st, &args))) return rc;
+    const int sort = mm->config.sort;
+    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    if (ss.n == 0) return FZB_OK;
+    return sections_stage(mm->sections, c, mm->sort.tmp, raw_count, n, ss, limit, by_score, reversed, false, dev_out, dev_counts, mm->num_cus * 2, st);
+}
+// The host forms' result: the stage block - 32 words (the 2S counts, [16] = the captured count), then S slabs of `limit` records - in ONE
+// copy and one wait on the null stream; the heads are moved together in the pinned block that is handed over.
+int sections_fetch(const SectionsScratch& sc, size_t S, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found, u32* captured) {
+    const size_t bytes = 32 * sizeof(u32) + S * limit * sizeof(fzb_match);
+    uint8_t* r = (uint8_t*)pinned_pool().get(bytes);
+    if (!r) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
+    hipError_t e = hipMemcpyAsync(r, sc.stage, bytes, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess) e = fzb_stream_wait(nullptr);
+    if (e != hipSuccess) {
+        pinned_pool().put(r);
+        return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
+    }
+    u32 words[32];
+    memcpy(words, r, sizeof(words));
+    size_t total = 0;
+    for (size_t s = 0; s < S; s++) {  // (head s moves towards the front: its destination ends before any later slab begins)
+        const size_t kept = std::min<size_t>(words[2 * s], limit);
+        memmove(r + total * sizeof(fzb_match), r + sizeof(words) + s * limit * sizeof(fzb_match), kept * sizeof(fzb_match));
+        out_len[s] = kept;
+        if (out_found) out_found[s] = words[2 * s + 1];
+        total += kept;
+    }
+    *captured = words[16];
+    *out = (fzb_match*)r;
+    return FZB_OK;
+}
+}  // namespace
+extern "C" {
+
+int fzb_match_list_top_sections_device(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                       fzb_match* dev_out, size_t capacity, uint32_t* dev_counts, void* stream) {
+    sections_set ss;
+    if ((!dev_counts && n_sections) || (!dev_out && n_sections && limit)) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections_device", &ss)) return rc;
+    if (capacity < n_sections * limit)
+        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * limit: " + std::to_string(capacity) + " < " + std::to_string(n_sections * limit));
+    SubsetArgs sa{in, capture, nullptr};
+    return single_sections_stage(m, c, ss, limit, &sa, (fzb_match_rec*)dev_out, dev_counts, (hipStream_t)stream);
+}
+
+int fzb_match_list_top_sections(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    sections_set ss;
+    if (!out || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections", &ss)) return rc;
+    for (size_t s = 0; s < n_sections; s++) {
+        out_len[s] = 0;
+        if (out_found) out_found[s] = 0;
+    }
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = fzb_sections_ensure(m->sections, c->dev.n, n_sections * limit + 1))) return rc;
+    u32* const words = m->sections.stage;
+    SubsetArgs sa{in, capture, capture ? words + 16 : nullptr};
+    if ((rc = single_sections_stage(m, c, ss, limit, &sa, (fzb_match_rec*)(words + 32), words, nullptr))) return rc;
+    if (n_sections == 0 || c->dev.n == 0) return FZB_OK;
+    u32 captured = 0;
+    if ((rc = sections_fetch(m->sections, n_sections, limit, out, out_len, out_found, &captured))) return rc;
+    if (!m->empty) subset_capture_known(capture, captured);
+    return FZB_OK;
+}
+
+int fzb_multi_match_list_top_sections_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                             fzb_subset* capture, fzb_match* dev_out, size_t capacity, uint32_t* dev_counts, void* stream) {
+    sections_set ss;
+    if ((!dev_counts && n_sections) || (!dev_out && n_sections && limit)) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_device", &ss)) return rc;
+    if (capacity < n_sections * limit)
+        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * limit: " + std::to_string(capacity) + " < " + std::to_string(n_sections * limit));
+    SubsetArgs sa{in, capture, nullptr};
+    return multi_sections_stage(mm, c, ss, limit, &sa, (fzb_match_rec*)dev_out, dev_counts, (hipStream_t)stream);
+}
+
+int fzb_multi_match_list_top_sections(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                      fzb_subset* capture, fzb_match** out, size_t* out_len, uint64_t* out_found) {
+    sections_set ss;
+    if (!out || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections", &ss)) return rc;
+    for (size_t s = 0; s < n_sections; s++) {
+        out_len[s] = 0;
+        if (out_found) out_found[s] = 0;
+    }
+    int rc;
+    if ((rc = fzb_sections_ensure(mm->sections, c->dev.n, n_sections * limit + 1))) return rc;
+    u32* const words = mm->sections.stage;
+    const bool captures = capture && !mm->patterns.empty();
+    SubsetArgs sa{in, capture, captures ? words + 16 : nullptr};
+    if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, (fzb_match_rec*)(words + 32), words, nullptr))) return rc;
+    if (n_sections == 0 || c->dev.n == 0) return FZB_OK;
+    u32 captured = 0;
+    if ((rc = sections_fetch(mm->sections, n_sections, limit, out, out_len, out_found, &captured))) return rc;
+    if (captures) subset_capture_known(capture, captured);
+    return FZB_OK;
 }
 
 int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,

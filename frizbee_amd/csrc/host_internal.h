@@ -190,6 +190,18 @@ int fzb_scope_ensure(ScopeScratch& s, size_t count);  // host.hip
 int fzb_scope_ensure_flags(ScopeScratch& s, size_t count);  // bitmap / tiles / words alone: the empty prompt's producer writes no records ahead of its compaction
 void fzb_scope_release(ScopeScratch& s);
 
+// The buffers of the sectioned top-`limit` queries (sections.h; host.hip), of either matcher type: `words` = the stage's scratch (bins, cuts,
+// tile rows: fzb_sections_scratch_words), `stage` = the host forms' device-side result - 16 count words, then n_sections * limit records, so
+// that one copy brings both back.  Grown through fzb_grow_dev on the first sectioned query, released with the matcher.
+struct SectionsScratch {
+    u32* words = nullptr;
+    size_t words_cap = 0;
+    u32* stage = nullptr;
+    size_t stage_words = 0;
+};
+int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_records);  // host.hip
+void fzb_sections_release(SectionsScratch& s);
+
 // A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle
 // (host.hip) computes all of it and makes no HIP call.  fzb_matcher_set_pattern / _set_config replace it as a whole.
 struct CompiledNeedle {
@@ -283,6 +295,7 @@ struct MatcherState : OutStaging {
     u32* top_words = nullptr;
     size_t top_words_cap = 0;  // in words
     ScopeScratch scope;        // queries over a corpus with an active scope: the pipeline's records ahead of the drop
+    SectionsScratch sections;  // sectioned top-`limit` queries
     fzb_facets* facets = nullptr;  // the attached facet sink (fzb_matcher_set_facets; not owned): part of the session, so it survives set_pattern / set_config
 };
 
@@ -338,6 +351,7 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
     ScopeScratch scope;  // queries over a corpus with an active scope: the composition's records ahead of the drop
+    SectionsScratch sections;  // sectioned top-`limit` queries
     fzb_facets* facets = nullptr;  // the attached facet sink (fzb_multi_matcher_set_facets; not owned): survives set_patterns / set_config
     fzb_matcher* order = nullptr;
     std::vector<fzb_multi_matcher*> shard_clones;

@@ -788,6 +788,42 @@ const uint32_t* fzb_facets_device(const fzb_facets* f);
 int fzb_matcher_set_facets(fzb_matcher* m, fzb_facets* f);
 int fzb_multi_matcher_set_facets(fzb_multi_matcher* mm, fzb_facets* f);
 
+/* ---- SECTIONED TOP-`limit`: the best matches per tag section, one device call ---------------------------------------------------------------
+ * A picker that shows its results in sections ("Recent", "Open buffers", "Project files", "Ignored") needs, per keystroke, the best few matches
+ * of every section and how many matches each section holds.  The reference has no such call: its caller splits the Vec `match_list` returned.
+ * A section is a pair (require, exclude) over the haystacks' 16 tag bits, the predicate of the visibility scope: haystack i belongs to it iff
+ * (tag(i) & require) == require && (tag(i) & exclude) == 0, with tag(i) = 0 where the corpus has no tags.
+ * THE CONTRACT: element s of a sectioned call is what fzb_match_list_top(corpus, limit) returns over a corpus whose scope is the corpus' own
+ * scope AND section s's predicate - records, their order (ties at the cut included, for all four sort strategies), scores with the corpus' bias
+ * added, full-list indices, and `found` = the visible matches in section s - obtained from ONE pass of the filter and the scorers and one
+ * host wait.  Sections are independent predicates: they may overlap, repeat or be empty, a record may land in several, (0, 0) is
+ * "everything" and reproduces fzb_match_list_top exactly; a caller who wants first-match-wins says so with exclude bits.
+ * LIMITS: at most FZB_SECTIONS_MAX sections and limit <= FZB_SECTION_LIMIT_MAX (each section's head is ordered by one workgroup in LDS);
+ * more of either, or a null argument, is FZB_ERR_INVALID before anything touches the device.  n_sections == 0 returns nothing (`sections` may
+ * then be NULL); limit == 0 returns empty heads with correct `found`.
+ * Host forms: *out = ONE block (freed with fzb_matches_free), the heads concatenated in section order; out_len[s] = records of head s, out_found[s]
+ * (optional) = matches in section s.  One wait: the n_sections * limit record slots (at most 64 KB) and the 2 * n_sections count words are
+ * copied behind the query, and the sum(out_len) records that exist are handed over.
+ * _device forms: stream-ordered, nothing is read back; capacity >= n_sections * limit records is required (FZB_ERR_CAPACITY otherwise), section s's
+ * head starts at dev_out + s * limit and holds dev_counts[2s] records - what lies behind them in the slab is unspecified and must not be read -,
+ * dev_counts[2s + 1] = matches in section s; dev_counts has 2 * n_sections words.  An empty needle is answered by the same entry points (the
+ * empty prompt: every visible haystack of the input, score = the clamped bias).
+ * `in` / `capture` (either may be NULL) are the candidate sets of the _subset queries: the capture holds what fzb_match_list_top_subset
+ * captures.  An attached facet sink is filled as by fzb_match_list_top.  The fzb_multi_* forms do the same behind the composition of a
+ * `from_patterns` matcher.
+ * NOT OFFERED: sharded and RCCL forms, matched positions (_indices) for sectioned heads, limits above FZB_SECTION_LIMIT_MAX. */
+#define FZB_SECTIONS_MAX 8
+#define FZB_SECTION_LIMIT_MAX 1024
+typedef struct { uint16_t require, exclude; } fzb_section;
+int fzb_match_list_top_sections(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                fzb_match** out, size_t* out_len, uint64_t* out_found);
+int fzb_match_list_top_sections_device(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                       fzb_match* dev_out, size_t capacity, uint32_t* dev_counts, void* stream);
+int fzb_multi_match_list_top_sections(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                      fzb_subset* capture, fzb_match** out, size_t* out_len, uint64_t* out_found);
+int fzb_multi_match_list_top_sections_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                             fzb_subset* capture, fzb_match* dev_out, size_t capacity, uint32_t* dev_counts, void* stream);
+
 /* Measurement hooks (bench.py): device time of the fzb_match_list_device calls made on this matcher since
  * fzb_set_profiling(m, 1), measured with HIP events recorded on the launch stream (event records only, no
  * synchronisation until read).  fzb_last_timings averages over those calls (at most the last 32):

@@ -541,6 +541,44 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_match_list_top_subset_device(single_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
         else check(fzb_multi_match_list_top_subset_device(multi_.get(), corpus.raw(), i, cp, limit, dev_out, capacity, dev_count, stream));
     }
+    // Sectioned top-`limit` (fzb_match_list_top_sections): the best `limit` matches of every tag section - a (require, exclude) pair over the
+    // corpus' 16 tag bits, the scope's predicate - from ONE pass of the filter and the scorers and one host wait.  Element s is what
+    // match_list_top(corpus, limit) returns over a corpus whose scope is the corpus' own scope AND section s.  At most FZB_SECTIONS_MAX
+    // sections, limit <= FZB_SECTION_LIMIT_MAX.  The reference has no such call: its caller splits the Vec `match_list` returned.
+    struct SectionHead {
+        std::vector<Match> matches;
+        size_t found;  // the section's visible matches
+    };
+    std::vector<SectionHead> match_list_top_sections(const Corpus& corpus, const std::vector<fzb_section>& sections, size_t limit, const Subset* in = nullptr,
+                                                     Subset* capture = nullptr) {
+        const size_t S = sections.size();
+        fzb_match* out = nullptr;
+        std::vector<size_t> lens(S ? S : 1, 0);
+        std::vector<uint64_t> found(S ? S : 1, 0);
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_) check(fzb_match_list_top_sections(single_.get(), corpus.raw(), sections.data(), S, limit, i, cp, &out, lens.data(), found.data()));
+        else check(fzb_multi_match_list_top_sections(multi_.get(), corpus.raw(), sections.data(), S, limit, i, cp, &out, lens.data(), found.data()));
+        std::vector<SectionHead> heads(S);
+        size_t at = 0;
+        for (size_t s = 0; s < S; s++) {
+            heads[s].found = (size_t)found[s];
+            heads[s].matches.resize(lens[s]);
+            for (size_t k = 0; k < lens[s]; k++) heads[s].matches[k] = Match{out[at + k].index, out[at + k].score, out[at + k].exact != 0};
+            at += lens[s];
+        }
+        if (out) fzb_matches_free(out);
+        return heads;
+    }
+    // the same with the heads left in HBM: section s at dev_out + s * limit, dev_counts[2s] records, dev_counts[2s + 1] matches; capacity >=
+    // sections.size() * limit; asynchronous on `stream`
+    void match_list_top_sections_device(const Corpus& corpus, const std::vector<fzb_section>& sections, size_t limit, fzb_match* dev_out, size_t capacity, uint32_t* dev_counts,
+                                        void* stream = nullptr, const Subset* in = nullptr, Subset* capture = nullptr) {
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_) check(fzb_match_list_top_sections_device(single_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_counts, stream));
+        else check(fzb_multi_match_list_top_sections_device(multi_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_counts, stream));
+    }
     // The empty prompt's _device forms (a matcher made from an empty needle; the _device forms above refuse one): the index-ordered list of the
     // haystacks of the range, or of `in`, visible under the corpus' scope - score = the clamped bias -, and its ordered head.  dev_count =
     // (records written, found); asynchronous on `stream`.

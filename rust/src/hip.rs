@@ -50,6 +50,14 @@ struct FzbMatch {
     exact: u8,
     _pad: u8,
 }
+// a tag section of the sectioned top-`limit` calls (fzb_section): the visibility scope's predicate over the haystacks' 16 tag bits
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(dead_code)]
+struct FzbSection {
+    require: u16,
+    exclude: u16,
+}
 #[repr(C)]
 #[derive(Clone, Copy)]
 struct FzbMatchIndices {
@@ -161,6 +169,22 @@ extern "C" {
     fn fzb_matcher_set_facets(m: *mut c_void, f: *mut c_void) -> c_int;
     #[allow(dead_code)]
     fn fzb_multi_matcher_set_facets(mm: *mut c_void, f: *mut c_void) -> c_int;
+    // sectioned top-`limit`: the best `limit` matches per tag section (at most FZB_SECTIONS_MAX = 8 sections, limit <= FZB_SECTION_LIMIT_MAX =
+    // 1024) from one pass of the filter and the scorers; host forms: one block, the heads concatenated in section order, out_len / out_found
+    // per section; _device forms: section s at dev_out + s * limit, dev_counts = 2 words per section (records, matches).  No sharded, RCCL
+    // or matched-positions forms.
+    #[allow(dead_code)]
+    fn fzb_match_list_top_sections(m: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void, capture: *mut c_void,
+                                   out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_match_list_top_sections_device(m: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                          capture: *mut c_void, dev_out: *mut FzbMatch, capacity: usize, dev_counts: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_sections(mm: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                         capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_sections_device(mm: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                                capture: *mut c_void, dev_out: *mut FzbMatch, capacity: usize, dev_counts: *mut u32, stream: *mut c_void) -> c_int;
     // the same four over a `from_patterns` matcher: the composition runs over `input`, `capture` receives the composition's match set
     #[allow(dead_code)]
     fn fzb_multi_match_list_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
