@@ -132,7 +132,7 @@ SYMBOLS = [
     "fzb_corpus_generation", "fzb_subset_create", "fzb_subset_free", "fzb_subset_set_indices", "fzb_subset_from_scope", "fzb_subset_info", "fzb_subset_read",
     "fzb_match_list_subset", "fzb_match_list_top_subset", "fzb_match_list_top_subset_device", "fzb_match_list_top_indices_subset",
     "fzb_multi_match_list_subset", "fzb_multi_match_list_top_subset", "fzb_multi_match_list_top_subset_device", "fzb_multi_match_list_top_indices_subset",
-    "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info",
+    "fzb_debug_set_items_dfa_min", "fzb_debug_set_fused_capture", "fzb_debug_launch_grids", "fzb_corpus_signature_planes_info", "fzb_corpus_signature_repeat_planes_info",
     "fzb_prompt_list_device", "fzb_prompt_top_device",
     "fzb_facets_create", "fzb_facets_free", "fzb_facets_read", "fzb_facets_device", "fzb_matcher_set_facets", "fzb_multi_matcher_set_facets",
     "fzb_match_list_top_sections", "fzb_match_list_top_sections_device", "fzb_multi_match_list_top_sections", "fzb_multi_match_list_top_sections_device",
@@ -244,6 +244,7 @@ def lib():
         l.fzb_multi_matcher_reserve_top_indices.argtypes = l.fzb_matcher_reserve_top_indices.argtypes
         l.fzb_corpus_signature_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         l.fzb_corpus_signature_planes_info.argtypes = l.fzb_corpus_signature_info.argtypes
+        l.fzb_corpus_signature_repeat_planes_info.argtypes = l.fzb_corpus_signature_info.argtypes
         l.fzb_debug_needle_signature.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         l.fzb_debug_signature_threshold.argtypes = []
         l.fzb_debug_signature_threshold.restype = C.c_uint32
@@ -460,7 +461,7 @@ class Corpus:
                    "h2d_bytes")
     DEBUG_ARRAYS = {"bytes": (0, np.uint8), "ends": (1, None), "vbytes": (2, np.uint8), "vgofs": (3, np.uint32), "vgnv": (4, np.uint8), "vlen": (5, np.uint16),
                     "vperm": (6, np.uint16), "vlong": (7, np.uint32), "sig": (8, np.uint32), "bias": (9, np.int16), "tags": (10, np.uint16),
-                    "sig_planes": (11, np.uint64)}
+                    "sig_planes": (11, np.uint64), "sig_planes2": (12, np.uint64)}
 
     def set_bias(self, values):
         """fzb_corpus_set_bias: one int16 per haystack (len(values) == len(self)), added to every record's score on the device before
@@ -552,6 +553,12 @@ class Corpus:
         """fzb_corpus_signature_planes_info: (built, bytes) - whether the corpus has the signatures' bit-planes and their size in device memory."""
         built, nbytes = C.c_int(), C.c_uint64()
         _check(lib().fzb_corpus_signature_planes_info(self.h, C.byref(built), C.byref(nbytes)))
+        return bool(built.value), int(nbytes.value)
+
+    def signature_repeat_planes_info(self):
+        """fzb_corpus_signature_repeat_planes_info: (built, bytes) - whether the corpus has the repeat planes and their size in device memory."""
+        built, nbytes = C.c_int(), C.c_uint64()
+        _check(lib().fzb_corpus_signature_repeat_planes_info(self.h, C.byref(built), C.byref(nbytes)))
         return bool(built.value), int(nbytes.value)
 
     def info(self):

@@ -99,6 +99,10 @@ struct CorpusDev {
     // what k1_dfa_sig reads when it lists its survivors over a tile-aligned range - the planes of the needle's letters only.  nullptr = none
     // (no signatures, or no room for the planes: the filter reads `sig`).
     const u64* sig_planes;
+    // The REPEAT planes (sig_filter.h, "repeat signature"): the same layout, bit b of an item = its bytes hold signature bit b at least twice;
+    // built from the haystack bytes, an allocation of its own, another 4 bytes per haystack.  Read by the plane form of k1_dfa_sig for the bits a
+    // needle holds twice (`deadbe`: d and e), beside sig_planes.  nullptr = none (no planes, or no room: the filter then tests sig_planes alone).
+    const u64* sig_planes2;
 };
 
 struct fzb_match_rec {  // == fzb_match; `_pad` carries the valid flag between kernels (0 in final output)
@@ -221,9 +225,11 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m = nullptr, u32* tile_counts_m = nullptr,
                        u64* reject_bits = nullptr, u32* tile_rejects = nullptr, int nul_safe = 0, int acc_lo = -1, const u8* cdfa = nullptr, u32 cdfa_bytes = 0,
                        int cdfa_K = 0, int cdfa_G = 0, u32 needle_sig = 0, int sig_ok = 0,  // sig_ok: the needle is eligible for the signature form (sig_filter.h)
-                       const SegList* seg = nullptr);  // seg (only where fzb_filter_sig_applies): grid = seg->nseg, the kernel also lists its survivors
+                       const SegList* seg = nullptr,   // seg (only where fzb_filter_sig_applies): grid = seg->nseg, the kernel also lists its survivors
+                       u32 needle_sig2 = 0);           // the needle's repeat signature: used by the plane form over a corpus with repeat planes
 bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int sig_ok);  // fzb_launch_filter takes k1_dfa_sig
 void fzb_launch_sig_planes(const u32* sig, u64 n, u64 t0, u64* planes, int grid, hipStream_t st);  // the bit-planes of the tiles from t0 on, out of sig[0, n)
+void fzb_launch_sig_planes2(const CorpusDev& c, u64 n, u64 t0, u64* planes2, int grid, hipStream_t st);  // the repeat planes of the tiles from t0 on, out of the first n haystacks' bytes
 void fzb_launch_scan_rejects(const u32* tile_rejects, u32 ntiles, const u32* reject_count, u32* rej_prefix, hipStream_t st);
 void fzb_launch_init_counters(u32* counters, u32 n0, hipStream_t st);  // the 16-word counter block: [0] = n0, the rest 0
 void fzb_launch_compact1(const u64* bitmap, const u32* counts, u32 n_items, const u32* n_items_ptr, const u32* src, u32* out_idx, u32* total_out, int grid, hipStream_t st,

@@ -905,6 +905,7 @@ static int compile_needle(CompiledNeedle& cn, const fzb_config* config, const ui
     // the stream stage of these queries is the ordered-subsequence automaton over the needle's bytes and their case flips
     m->sig_eligible = !m->unicode && lc.filter_mode == 1 && lc.filter_exact && needle_sig_eligible(needle_utf8, needle_len, k, m->literal_mode);
     m->needle_sig = m->sig_eligible ? needle_sig(needle_utf8, needle_len) : 0u;
+    m->needle_sig2 = m->sig_eligible ? needle_sig2(needle_utf8, needle_len) : 0u;
     return FZB_OK;
 }
 
@@ -1091,6 +1092,7 @@ void fzb_corpus_free(fzb_corpus* c) {
     if (c->own_ends) (void)hipFree(c->own_ends);
     if (c->own_sig) (void)hipFree(c->own_sig);
     if (c->own_planes) (void)hipFree(c->own_planes);
+    if (c->own_planes2) (void)hipFree(c->own_planes2);
     fzb_column_release(c->bias);
     fzb_column_release(c->tags);
     if (c->pair_stage) (void)hipFree(c->pair_stage);
@@ -1848,7 +1850,7 @@ static int pipe_filter_stage(Pipe& p) {
         p.segmented = true;
         FZB_PEV(2);
         fzb_launch_filter(p.cd, p.first, p.cnt, w.table, w.dfa, lc.dead_byte, nd.rows, 1, need, (u32)nd.min_haystack_len, w.bitmap, w.tile_counts, w.counters, (int)grid, p.st, nullptr, nullptr,
-                          nullptr, nullptr, lc.pad_ok, -1, nullptr, 0, 0, 0, m->needle_sig, 1, &p.seg);
+                          nullptr, nullptr, lc.pad_ok, -1, nullptr, 0, 0, 0, m->needle_sig, 1, &p.seg, m->needle_sig2);
         FZB_PEV(3);
         FZB_STAGE("filter(lists its survivors)");
         p.items = w.surv_idx;

@@ -68,6 +68,8 @@ struct fzb_corpus {
     u64 sig_cap_items = 0;
     void* own_planes = nullptr;  // the signatures' bit-planes (CorpusDev::sig_planes), room for planes_cap_tiles tiles of 4 KB; follows own_sig
     u64 planes_cap_tiles = 0;
+    void* own_planes2 = nullptr;  // the REPEAT planes (CorpusDev::sig_planes2), room for planes2_cap_tiles tiles of 4 KB; follows own_planes
+    u64 planes2_cap_tiles = 0;
     int sig_device = -1;     // a borrowed corpus: the device the signatures were built on (where its bytes live)
     // the two columns (ItemColumn above) and what is specific to each:
     // the score bias (fzb_corpus_set_bias / _update_bias, score_bias.h) is live while the queries add it - from set / update to clear,
@@ -228,6 +230,7 @@ struct CompiledNeedle {
     int cdfa_src = 0, cdfa_K = 0, cdfa_G = 0;
     // the needle's letter signature and whether the signature form of the filter may decide for it (sig_filter.h: fuzzy, 0 typos, ASCII, no NUL)
     u32 needle_sig = 0;
+    u32 needle_sig2 = 0;  // its REPEAT signature (the bits the needle holds twice): 0 = the filter reads no repeat plane
     bool sig_eligible = false;
     // a needle beyond NeedleDev's arrays (> 64 bytes or > 63 rows): scalars in `ndl`, the arrays in one host blob with its section offsets
     // (MatcherState::long_blob_dev is its device copy, uploaded on first use: until then ndl's pointers are null)

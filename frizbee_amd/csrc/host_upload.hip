@@ -672,27 +672,29 @@ __global__ __launch_bounds__(UP_THREADS) void k_sig_build(const u8* __restrict__
     }
 }
 
-// Room for the bit-planes (sig_filter.h) of `items` haystacks, the first keep_tiles tiles taken over in one copy.  An accelerator of an
-// accelerator: without room the corpus goes on without planes (false) and the filter reads the u32 signatures.
-bool planes_ensure_room(fzb_corpus* c, u64 items, u64 keep_tiles) {
+// Room for one array of bit-planes (sig_filter.h) of `items` haystacks, the first keep_tiles tiles taken over in one copy: own / cap_tiles /
+// live = the corpus' allocation, its room and the pointer the kernels read (own_planes .. dev.sig_planes, or the repeat planes' three).
+// An accelerator of an accelerator: without room the corpus goes on without that array (false) - without planes the filter reads the u32
+// signatures, without repeat planes it tests the planes alone.
+bool planes_ensure_room(void*& own, u64& cap_tiles, const u64*& live, u64 items, u64 keep_tiles) {
     const u64 tiles = sig_plane_tiles(items);
-    if (c->own_planes && c->planes_cap_tiles >= tiles) return true;
+    if (own && cap_tiles >= tiles) return true;
     const size_t tile_bytes = 32 * FZB_SIG_PLANE_WORDS * sizeof(u64);
     void* p = nullptr;
     hipError_t e = fzb_dev_alloc(&p, (size_t)tiles * tile_bytes);
-    if (e == hipSuccess && keep_tiles && c->own_planes) e = hipMemcpy(p, c->own_planes, (size_t)std::min(keep_tiles, c->planes_cap_tiles) * tile_bytes, hipMemcpyDeviceToDevice);
-    if (c->own_planes) (void)hipFree(c->own_planes);
-    c->own_planes = nullptr;
-    c->planes_cap_tiles = 0;
+    if (e == hipSuccess && keep_tiles && own) e = hipMemcpy(p, own, (size_t)std::min(keep_tiles, cap_tiles) * tile_bytes, hipMemcpyDeviceToDevice);
+    if (own) (void)hipFree(own);
+    own = nullptr;
+    cap_tiles = 0;
     if (e != hipSuccess) {
         if (p) (void)hipFree(p);
         (void)hipGetLastError();
-        c->dev.sig_planes = nullptr;
+        live = nullptr;
         return false;
     }
-    c->own_planes = p;
-    c->planes_cap_tiles = tiles;
-    if (c->dev.sig_planes) c->dev.sig_planes = (const u64*)p;
+    own = p;
+    cap_tiles = tiles;
+    if (live) live = (const u64*)p;
     return true;
 }
 
@@ -703,12 +705,13 @@ int fzb_sig_sync(fzb_corpus* c, u64 n_valid) {
     const bool want = !fzb_knobs().no_signature && n && c->dev.max_len != 0 && c->dev.max_len <= 32;
     if (!want) {  // (the arrays stay for the list that calls for signatures again)
         c->dev.sig = nullptr;
-        c->dev.sig_planes = nullptr;
+        c->dev.sig_planes = c->dev.sig_planes2 = nullptr;
         return FZB_OK;
     }
-    if (!c->dev.sig) n_valid = 0, c->dev.sig_planes = nullptr;
+    if (!c->dev.sig) n_valid = 0, c->dev.sig_planes = c->dev.sig_planes2 = nullptr;
     n_valid = std::min(n_valid, n);
     const u64 planes_t0 = c->dev.sig_planes ? n_valid / FZB_SIG_PLANE_TILE : 0;  // the first tile whose planes are rebuilt
+    const u64 planes2_t0 = c->dev.sig_planes2 ? n_valid / FZB_SIG_PLANE_TILE : 0;
     if (!c->own_sig || c->sig_cap_items < n) {
         const u64 items = std::max<u64>(n, c->cap_items);
         void* p = nullptr;
@@ -718,7 +721,7 @@ int fzb_sig_sync(fzb_corpus* c, u64 n_valid) {
             if (p) (void)hipFree(p);
             (void)hipGetLastError();
             c->dev.sig = nullptr;
-            c->dev.sig_planes = nullptr;
+            c->dev.sig_planes = c->dev.sig_planes2 = nullptr;
             if (e == hipErrorOutOfMemory) return FZB_OK;
             return fzb_fail(FZB_ERR_HIP, std::string("letter signatures: ") + hipGetErrorString(e));
         }
@@ -734,10 +737,16 @@ int fzb_sig_sync(fzb_corpus* c, u64 n_valid) {
     }
     c->dev.sig = (const u32*)c->own_sig;
     // the bit-planes of every tile from n_valid's on, out of the signatures just written (k_sig_planes_build, kernels_filter.hip)
-    if (planes_ensure_room(c, std::max<u64>(n, c->cap_items), planes_t0)) {
-        const u64 tiles = sig_plane_tiles(n);
+    const u64 tiles = sig_plane_tiles(n);
+    if (planes_ensure_room(c->own_planes, c->planes_cap_tiles, c->dev.sig_planes, std::max<u64>(n, c->cap_items), planes_t0)) {
         if (planes_t0 < tiles) fzb_launch_sig_planes(c->dev.sig, n, planes_t0, (u64*)c->own_planes, (int)fzb_grid_cap(tiles - planes_t0, 8), nullptr);
         c->dev.sig_planes = (const u64*)c->own_planes;
+    }
+    // ... and the REPEAT planes of the same tiles, out of the haystacks' bytes (k_sig_planes2_build); only beside the planes, whose form of the filter reads them
+    if (!c->dev.sig_planes) c->dev.sig_planes2 = nullptr;
+    else if (planes_ensure_room(c->own_planes2, c->planes2_cap_tiles, c->dev.sig_planes2, std::max<u64>(n, c->cap_items), planes2_t0)) {
+        if (planes2_t0 < tiles) fzb_launch_sig_planes2(c->dev, n, planes2_t0, (u64*)c->own_planes2, (int)fzb_grid_cap(tiles - planes2_t0, 8), nullptr);
+        c->dev.sig_planes2 = (const u64*)c->own_planes2;
     }
     return FZB_OK;
 }
@@ -760,9 +769,11 @@ int fzb_sig_sync_borrowed(fzb_corpus* c) {
         c->own_sig = nullptr; c->sig_cap_items = 0;
         if (c->own_planes) (void)hipFree(c->own_planes);
         c->own_planes = nullptr; c->planes_cap_tiles = 0;
+        if (c->own_planes2) (void)hipFree(c->own_planes2);
+        c->own_planes2 = nullptr; c->planes2_cap_tiles = 0;
     }
     c->dev.sig = nullptr;  // the promise changed: nothing of an earlier build is taken over
-    c->dev.sig_planes = nullptr;
+    c->dev.sig_planes = c->dev.sig_planes2 = nullptr;
     // FZB_VERIFY_PROMISES=0: nobody has checked the end offsets, and this set-up pass must not read wherever they point
     if (!fzb_knobs().verify_promises) return FZB_OK;
     HIPCHK(hipDeviceSynchronize());  // the caller may have filled the buffers on any stream of that device
@@ -1250,9 +1261,12 @@ int fzb_corpus_reserve(fzb_corpus* c, size_t items, uint64_t bytes) {
             (void)hipGetLastError();  // (an accelerator: it grows - or goes - when it must)
         }
     }
-    // ... and their bit-planes, another 4 bytes per haystack, behind them
-    if (!fzb_knobs().no_signature && (!c->dev.n || (c->dev.max_len != 0 && c->dev.max_len <= 32)) && c->own_sig && c->sig_cap_items >= c->cap_items)
-        (void)planes_ensure_room(c, c->cap_items, c->dev.sig_planes ? sig_plane_tiles(c->dev.n) : 0);
+    // ... and their bit-planes and the repeat planes, another 4 bytes per haystack each, behind them
+    if (!fzb_knobs().no_signature && (!c->dev.n || (c->dev.max_len != 0 && c->dev.max_len <= 32)) && c->own_sig && c->sig_cap_items >= c->cap_items) {
+        if (planes_ensure_room(c->own_planes, c->planes_cap_tiles, c->dev.sig_planes, c->cap_items, c->dev.sig_planes ? sig_plane_tiles(c->dev.n) : 0))
+            (void)planes_ensure_room(c->own_planes2, c->planes2_cap_tiles, c->dev.sig_planes2, c->cap_items, c->dev.sig_planes2 ? sig_plane_tiles(c->dev.n) : 0);
+        if (!c->dev.sig_planes) c->dev.sig_planes2 = nullptr;
+    }
     HIPCHK(hipDeviceSynchronize());
     return FZB_OK;
 }
@@ -1365,6 +1379,13 @@ int fzb_corpus_signature_planes_info(const fzb_corpus* c, int* out_built, uint64
     return FZB_OK;
 }
 
+int fzb_corpus_signature_repeat_planes_info(const fzb_corpus* c, int* out_built, uint64_t* out_bytes) {
+    if (!c) return fzb_fail(FZB_ERR_INVALID, "null argument");
+    if (out_built) *out_built = c->dev.sig_planes2 != nullptr;
+    if (out_bytes) *out_bytes = c->dev.sig_planes2 ? sig_plane_words(c->dev.n) * 8 : 0;
+    return FZB_OK;
+}
+
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes) {
     if (!c || !out_bytes) return fzb_fail(FZB_ERR_INVALID, "null argument");
     const u64 n = c->dev.n, groups = up_tiles(n) * (UP_TILE / 64);
@@ -1384,6 +1405,7 @@ int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t 
         case 9: src = c->bias.data; bytes = c->bias.live ? (size_t)n * sizeof(int16_t) : 0; break;
         case 10: src = c->tags.data; bytes = c->tags.live ? (size_t)n * sizeof(uint16_t) : 0; break;
         case 11: src = c->dev.sig_planes; bytes = c->dev.sig_planes ? (size_t)sig_plane_words(n) * 8 : 0; break;
+        case 12: src = c->dev.sig_planes2; bytes = c->dev.sig_planes2 ? (size_t)sig_plane_words(n) * 8 : 0; break;
         default: return fzb_fail(FZB_ERR_INVALID, "fzb_debug_corpus_read: unknown array " + std::to_string(what));
     }
     *out_bytes = bytes;

@@ -307,8 +307,11 @@ __device__ __forceinline__ u32 seg_list_tile(const u32* s_bits, u32 t, u32 tile,
 //      atomic-or into the batch's decision words;
 //   4. the tiles are listed one by one from LDS, exactly as in the u32 form (seg_list_tile).
 // LDS behind the table: candidate words [B][16] u64, decision words [B][32], tile counts [B], queue [B * gather_max] u16 - 8 224 B for B = 8.
+#ifndef FZB_SIG_CAND_INFLIGHT
+#define FZB_SIG_CAND_INFLIGHT 8  // plane words of one thread requested before the first is used (sig_planes_run, step 1)
+#endif
 template <typename ET>
-__device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u64* __restrict__ planes, u32 nsig, u64 first, u32 count, u32 rows,
+__device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u64* __restrict__ planes, u32 nsig, const u64* __restrict__ planes2, u32 nsig2, u64 first, u32 count, u32 rows,
                                                u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts, u32 ulen, u32 gather_max, const SegList& seg, u8* dfa, const u8* __restrict__ dfa_g) {
     constexpr u32 B = FZB_SIG_BATCH_TILES;
     static_assert(B * 16 <= 256 && B * 32 <= 256 && B * FZB_TILE <= 65536, "a batch's words are one per thread, its positions fit the queue's u16");
@@ -324,24 +327,31 @@ __device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, con
     tc_run(ntiles, seg.stride / FZB_TILE, blockIdx.x, &t_begin, &t_end);
     u32* const seg_out = seg.list + (size_t)blockIdx.x * seg.stride;
     const u32 j = tid >> 4, w = tid & 15u;  // my (tile of the batch, word)
-    // 1. a batch's candidate words.  The plane words are requested four at a time and only then AND-ed (nsig is uniform: scalar branches),
-    // so that a needle of up to four letters is ONE round trip - as a plain loop every load waited for the one before it.
+    // 1. a batch's candidate words.  The plane words are requested eight at a time and only then AND-ed (the masks are uniform: scalar
+    // branches), so that a needle of up to eight plane words is ONE round trip - as a plain loop every load waited for the one before it.
+    // The REPEAT planes (sig_filter.h) are the upper half of one 64-bit mask: bit 32 + b = word of planes2's bit b, at the same index -
+    // a uniform distance from the thread's word of `planes`.  nsig2 == 0 (no repeat in the needle, or a corpus without repeat planes):
+    // the loop is the one over nsig alone.
+    const u64 need = (u64)nsig | ((u64)nsig2 << 32);
+    const ptrdiff_t to2 = nsig2 ? (ptrdiff_t)((uintptr_t)planes2 - (uintptr_t)planes) : 0;
     auto load_cand = [&](u32 tb, u32 nb) -> u64 {
         if (tid >= nb * 16) return 0;
         u64 cand = sig_plane_valid(tb + j, w, count);
-        const u64* pl = planes + sig_plane_index(tile0 + tb + j, 0, w);
-        u32 m = nsig;
+        const u8* pl = (const u8*)(planes + sig_plane_index(tile0 + tb + j, 0, w));
+        u64 m = need;
         while (m) {
-            u64 v[4];
+            u64 v[FZB_SIG_CAND_INFLIGHT];
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
+            for (int q = 0; q < FZB_SIG_CAND_INFLIGHT; q++) {
                 v[q] = ~0ull;
                 if (m) {
-                    v[q] = pl[(u32)__builtin_ctz(m) * FZB_SIG_PLANE_WORDS];
+                    const u32 k = (u32)__builtin_ctzll(m);
+                    v[q] = *(const u64*)(pl + (k < 32u ? (ptrdiff_t)(k * FZB_SIG_PLANE_WORDS * 8u) : to2 + (ptrdiff_t)((k - 32u) * FZB_SIG_PLANE_WORDS * 8u)));
                     m &= m - 1u;
                 }
             }
-            cand &= (v[0] & v[1]) & (v[2] & v[3]);
+#pragma unroll
+            for (int q = 0; q < FZB_SIG_CAND_INFLIGHT; q++) cand &= v[q];
         }
         return cand;
     };
@@ -439,18 +449,19 @@ __device__ __forceinline__ void sig_planes_run(const u8* __restrict__ bytes, con
 }
 
 // (8 waves per SIMD like k1_dfa, whose grid - 8 workgroups per CU - it shares: without the bound the kernel takes 68 VGPRs and a CU holds 7)
-// PLANES (only with SEG): `sig` points at the corpus' bit-planes (u64 words) and sig_planes_run above is the kernel's body.
+// PLANES (only with SEG): `sig` points at the corpus' bit-planes (u64 words) and sig_planes_run above is the kernel's body; planes2 / nsig2:
+// the corpus' repeat planes and the needle's repeat signature (nsig2 == 0: not read).  The u32 form makes no use of either.
 template <typename ET, bool SEG, bool PLANES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k1_dfa_sig(const u8* __restrict__ bytes, const ET* __restrict__ ends, const u32* __restrict__ sig, u32 nsig, u64 first, u32 count,
                                                   const u8* __restrict__ dfa_g, int rows, u32 min_len, u32 acc_lo, u64* __restrict__ bitmap, u32* __restrict__ tile_counts,
-                                                  u32* __restrict__ reset_counters, u32 ulen, u32 gather_max, SegList seg) {
+                                                  u32* __restrict__ reset_counters, u32 ulen, u32 gather_max, SegList seg, const u64* __restrict__ planes2, u32 nsig2) {
     if (blockIdx.x == 0 && threadIdx.x < 16) reset_counters[threadIdx.x] = 0;
     // LDS behind the table (which stays the first object, at address 0): tile count, queue length, the tile's 1024 decision bits, the queue
     extern __shared__ __attribute__((aligned(16))) u8 dfa[];
     if constexpr (PLANES) {
         static_assert(SEG, "the plane form lists its survivors");
         dfa_require_lds_base0(dfa);
-        sig_planes_run<ET>(bytes, ends, (const u64*)sig, nsig, first, count, (u32)rows, min_len, acc_lo, bitmap, tile_counts, ulen, gather_max, seg, dfa, dfa_g);
+        sig_planes_run<ET>(bytes, ends, (const u64*)sig, nsig, planes2, nsig2, first, count, (u32)rows, min_len, acc_lo, bitmap, tile_counts, ulen, gather_max, seg, dfa, dfa_g);
         return;
     }
     u32& s_cnt = *(u32*)(dfa + FZB_DFA_LDS_BYTES(rows));
@@ -1216,31 +1227,77 @@ void fzb_launch_filter_items(const CorpusDev& c, u64 first, const u32* items, co
 // a workgroup per tile and trip reads the tile's 4 KB coalesced (zero at and beyond n), every wave turns 64 rows into 32 ballots - lane b
 // keeps plane b's word -, the tile's 512 words meet in LDS and leave as one coalesced 4 KB store.
 // ---------------------------------------------------------------------------------------------------
+// (the two halves both builds share: the 32 bits `s` of row p * 256 + tid of a tile into the tile's words in LDS, and the tile's store)
+__device__ __forceinline__ void sig_planes_put(u32 s, u32 p, u64* s_pl) {
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u64 mine = 0;
+    for (u32 b = 0; b < 32; b++) {
+        const u64 bal = __ballot((s >> b) & 1u);
+        if (lane == b) mine = bal;
+    }
+    if (lane < 32) s_pl[lane * FZB_SIG_PLANE_WORDS + p * 4 + wave] = mine;  // (rows p * 256 + wave * 64 ..: word p * 4 + wave)
+}
+__device__ __forceinline__ void sig_planes_store(const u64* s_pl, u64* __restrict__ planes, u64 tile) {
+    const u32 tid = threadIdx.x;
+    __syncthreads();
+    u64* out = planes + sig_plane_index(tile, 0, 0);
+    out[tid] = s_pl[tid];
+    out[tid + 256] = s_pl[tid + 256];
+    __syncthreads();
+}
 __global__ __launch_bounds__(256) void k_sig_planes_build(const u32* __restrict__ sig, u64 n, u64 t0, u64* __restrict__ planes) {
     __shared__ u64 s_pl[32 * FZB_SIG_PLANE_WORDS];
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 tiles = sig_plane_tiles(n);
     for (u64 tile = t0 + blockIdx.x; tile < tiles; tile += gridDim.x) {
 #pragma unroll
         for (u32 p = 0; p < FZB_TILE / 256; p++) {
-            const u64 i = tile * FZB_TILE + p * 256 + tid;
-            const u32 s = i < n ? sig[i] : 0u;
-            u64 mine = 0;
-            for (u32 b = 0; b < 32; b++) {
-                const u64 bal = __ballot((s >> b) & 1u);
-                if (lane == b) mine = bal;
-            }
-            if (lane < 32) s_pl[lane * FZB_SIG_PLANE_WORDS + p * 4 + wave] = mine;  // (rows p * 256 + wave * 64 ..: word p * 4 + wave)
+            const u64 i = tile * FZB_TILE + p * 256 + threadIdx.x;
+            sig_planes_put(i < n ? sig[i] : 0u, p, s_pl);
         }
-        __syncthreads();
-        u64* out = planes + sig_plane_index(tile, 0, 0);
-        out[tid] = s_pl[tid];
-        out[tid + 256] = s_pl[tid + 256];
-        __syncthreads();
+        sig_planes_store(s_pl, planes, tile);
     }
 }
 void fzb_launch_sig_planes(const u32* sig, u64 n, u64 t0, u64* planes, int grid, hipStream_t st) {
     FZB_LAUNCH(k_sig_planes_build, dim3(std::max(1, grid)), dim3(256), 0, st, sig, n, t0, planes);
+}
+// The REPEAT planes (sig_filter.h) of the tiles [t0, tiles of n), built from the haystack BYTES - the u32 signatures carry no counts, and no
+// per-haystack array of repeat signatures stays behind: every thread derives its row's repeat signature as k_sig_build derives the signature
+// (both 16-byte vectors, cut to the row's length; uniform and ragged lists, u32 and u64 end offsets), then the ballots and the tile's store
+// as above.
+template <typename ET>
+__global__ __launch_bounds__(256) void k_sig_planes2_build(const u8* __restrict__ bytes, const ET* __restrict__ ends, u32 ulen, u64 n, u64 t0, u64* __restrict__ planes2) {
+    __shared__ u64 s_pl[32 * FZB_SIG_PLANE_WORDS];
+    const u64 tiles = sig_plane_tiles(n);
+    for (u64 tile = t0 + blockIdx.x; tile < tiles; tile += gridDim.x) {
+#pragma unroll
+        for (u32 p = 0; p < FZB_TILE / 256; p++) {
+            const u64 i = tile * FZB_TILE + p * 256 + threadIdx.x;
+            u32 once = 0, s = 0;
+            if (i < n) {
+                u64 hs;
+                u32 L;
+                haystack_span_u(ends, ulen, i, hs, L);
+                L = min(L, 32u);  // (the list's bound, as in k_sig_build)
+                const uint4* vp = (const uint4*)(bytes + hs);
+                uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
+                if (L > 0) a = vp[0];
+                if (L > 16) b = vp[1];
+                u32 w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    const u32 nvb = L > 4u * q ? L - 4u * q : 0u;
+                    if (nvb < 4) w[q] &= (1u << (8 * nvb)) - 1;
+                    sig2_accum_word(w[q], once, s);
+                }
+            }
+            sig_planes_put(s, p, s_pl);
+        }
+        sig_planes_store(s_pl, planes2, tile);
+    }
+}
+void fzb_launch_sig_planes2(const CorpusDev& c, u64 n, u64 t0, u64* planes2, int grid, hipStream_t st) {
+    if (c.ends_u64) FZB_LAUNCH((k_sig_planes2_build<u64>), dim3(std::max(1, grid)), dim3(256), 0, st, c.bytes, (const u64*)c.ends, c.uniform_len, n, t0, planes2);
+    else FZB_LAUNCH((k_sig_planes2_build<u32>), dim3(std::max(1, grid)), dim3(256), 0, st, c.bytes, (const u32*)c.ends, c.uniform_len, n, t0, planes2);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1252,7 +1309,7 @@ bool fzb_filter_sig_applies(const CorpusDev& c, int mode, u32 needle_sig, int si
 
 void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* table, const u8* dfa, u32 dead, int rows, int mode, int need, u32 min_len,
                        u64* bitmap, u32* tile_counts, u32* reset_counters, int grid, hipStream_t st, u64* bitmap_m, u32* tile_counts_m, u64* reject_bits, u32* tile_rejects, int nul_safe,
-                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G, u32 needle_sig, int sig_ok, const SegList* seg) {
+                       int acc_lo, const u8* cdfa, u32 cdfa_bytes, int cdfa_K, int cdfa_G, u32 needle_sig, int sig_ok, const SegList* seg, u32 needle_sig2) {
     // mode 1: `dfa` has rows + 1 states, start state 0, and accepts in the states >= acc (the subsequence / unicode / KMP automata: the last
     // state; the LCS automaton of a typo configuration: every state whose LCS reaches the need)
     const u32 acc = acc_lo < 0 ? (u32)rows : (u32)acc_lo;
@@ -1268,9 +1325,12 @@ void fzb_launch_filter(const CorpusDev& c, u64 first, u32 count, const u64* tabl
             // u32 form: + the tile's decision bits and the queue of passing rows; plane form: + a batch's tile counts, candidate words, decision bits and queue
             const bool planes = seg && c.sig_planes && first % FZB_TILE == 0 && !fzb_knobs().no_sig_planes;
             const size_t lds_s = planes ? FZB_DFA_LDS_BYTES(rows) + FZB_SIG_BATCH_TILES * (4 + 256 + 2 * (size_t)gmax) : lds + 128 + 2 * FZB_TILE;
-#define FZB_K1S(ET, SEG, PL, G, S) FZB_LAUNCH((k1_dfa_sig<ET, SEG, PL>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, PL ? (const u32*)c.sig_planes : c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, gmax, S)
+#define FZB_K1S(ET, SEG, PL, G, S) FZB_LAUNCH((k1_dfa_sig<ET, SEG, PL>), dim3(G), dim3(256), lds_s, st, c.bytes, (const ET*)c.ends, PL ? (const u32*)c.sig_planes : c.sig, needle_sig, first, count, dfa, rows, min_len, acc, bitmap, tile_counts, reset_counters, c.uniform_len, gmax, S, PL ? c.sig_planes2 : nullptr, PL ? nsig2 : 0u)
+            // the needle's repeat signature where the plane form reads a corpus with repeat planes: rows missing a doubled letter are no candidates
+            const u32 nsig2 = planes && c.sig_planes2 ? needle_sig2 : 0u;
             if (planes) {  // ... from the corpus' bit-planes, a run's tiles in batches (an aligned range; FZB_NO_SIG_PLANES unset)
                 if (g_fzb_record_grids) fzb_record_grid("k1_dfa_sig_planes", seg->nseg);  // (the kernel's name does not say which form ran: a second record for the tests)
+                if (g_fzb_record_grids && nsig2) fzb_record_grid("k1_dfa_sig_repeat", seg->nseg);
                 if (c.ends_u64) FZB_K1S(u64, true, true, seg->nseg, *seg); else FZB_K1S(u32, true, true, seg->nseg, *seg);
             } else if (seg) {  // the filter lists its survivors: one workgroup per segment
                 if (c.ends_u64) FZB_K1S(u64, true, false, seg->nseg, *seg); else FZB_K1S(u32, true, false, seg->nseg, *seg);

@@ -68,6 +68,41 @@ FZB_SIG_FN uint64_t sig_plane_candidates(const uint64_t* planes, uint64_t tile, 
     for (uint32_t m = nsig; m; m &= m - 1u) c &= planes[sig_plane_index(tile, (uint32_t)__builtin_ctz(m), word)];
     return c;
 }
+// The REPEAT SIGNATURE: which signature bits occur at least TWICE.  An accepted haystack holds the needle's bytes (or their case flips) at
+// DISTINCT positions, and a byte and its flip share a bit, so with c_n(b) / c_h(b) = the needle's / haystack's non-zero bytes of bit b
+//   accepted  =>  c_h(b) >= min(c_n(b), 2) for every b  <=>  (sig & nsig) == nsig && (sig2 & nsig2) == nsig2
+// - the same letter twice (`deadbe`), a letter and its flip (`dD`), two bytes of one other-byte class (`1` and `7`).  The u32 signature
+// does not carry counts: the repeat signature is made from the haystack's bytes (within its length) and kept as bit-planes only
+// (CorpusDev::sig_planes2, k_sig_planes2_build).  "At least three" (`deadbeef` has three `e`) is not built: counts cap at two.
+FZB_SIG_FN void sig2_accum_byte(uint32_t b, uint32_t& once, uint32_t& twice) {
+    const uint32_t s = sig_of_byte(b);
+    twice |= once & s;
+    once |= s;
+}
+FZB_SIG_FN void sig2_accum_word(uint32_t w, uint32_t& once, uint32_t& twice) {
+    sig2_accum_byte(w & 0xFF, once, twice);
+    sig2_accum_byte((w >> 8) & 0xFF, once, twice);
+    sig2_accum_byte((w >> 16) & 0xFF, once, twice);
+    sig2_accum_byte(w >> 24, once, twice);
+}
+// repeat signature of a haystack (its n bytes; zero bytes count for nothing): bit b set <=> c_h(b) >= 2
+FZB_SIG_FN uint32_t sig2_of_bytes(const uint8_t* p, size_t n) {
+    uint32_t once = 0, twice = 0;
+    for (size_t i = 0; i < n; i++) sig2_accum_byte(p[i], once, twice);
+    return twice;
+}
+// repeat signature of a needle: bit b set <=> c_n(b) >= 2.  0 for a needle without a repeat: the filter then reads no repeat plane.
+FZB_SIG_FN uint32_t needle_sig2(const uint8_t* needle, size_t n) { return sig2_of_bytes(needle, n); }
+FZB_SIG_FN bool sig2_passes(uint32_t sig, uint32_t sig2, uint32_t nsig, uint32_t nsig2) { return sig_passes(sig, nsig) && (sig2 & nsig2) == nsig2; }
+// reference transposition of the repeat planes (the layout of the planes above; the device build is k_sig_planes2_build)
+FZB_SIG_FN void sig_planes2_transpose_ref(const uint32_t* sig2, uint64_t n, uint64_t* planes2) { sig_planes_transpose_ref(sig2, n, planes2); }
+// the candidates under both tests: bit i set <=> sig2_passes(sig[item], sig2[item], nsig, nsig2)  (nsig != 0; planes2 is not read when nsig2 == 0)
+FZB_SIG_FN uint64_t sig_plane_candidates2(const uint64_t* planes, const uint64_t* planes2, uint64_t tile, uint32_t word, uint32_t nsig, uint32_t nsig2) {
+    uint64_t c = sig_plane_candidates(planes, tile, word, nsig);
+    for (uint32_t m = nsig2; m; m &= m - 1u) c &= planes2[sig_plane_index(tile, (uint32_t)__builtin_ctz(m), word)];
+    return c;
+}
+
 // Tiles of one batch of the plane form (a workgroup's run is taken in batches of at most this many tiles; one batch covers the run of 5
 // that 10 M haystacks give on 256 compute units)
 #ifndef FZB_SIG_BATCH_TILES

@@ -136,6 +136,12 @@ int fzb_corpus_signature_info(const fzb_corpus* c, int* out_built, uint64_t* out
  * reads the planes of its needle's letters only.  Without room for them the corpus keeps its signatures and every query its result.
  * *out_built (optional) = 1 when the corpus has them, *out_bytes (optional) = their size in device memory (4096 per started tile). */
 int fzb_corpus_signature_planes_info(const fzb_corpus* c, int* out_built, uint64_t* out_bytes);
+/* The REPEAT planes: the same layout once more (another 4 bytes per haystack, an allocation of its own), bit b of a haystack = its bytes hold
+ * signature bit b at least twice.  Built from the haystack bytes and kept in step wherever the bit-planes are; a query whose needle repeats
+ * a letter (`deadbe`: d and e) reads the repeat planes of those letters too and so skips the rows that hold them once.  Without room for
+ * them the corpus keeps its planes and every query its result.
+ * *out_built (optional) = 1 when the corpus has them, *out_bytes (optional) = their size in device memory (4096 per started tile). */
+int fzb_corpus_signature_repeat_planes_info(const fzb_corpus* c, int* out_built, uint64_t* out_bytes);
 void fzb_corpus_free(fzb_corpus* c);
 size_t fzb_corpus_len(const fzb_corpus* c);
 
@@ -886,7 +892,7 @@ int fzb_debug_device_allocs(uint64_t* out);
 
 /* test hook: copies one of the corpus' device arrays to the host - what: 0 = canonical bytes up to the padded size + the 96-byte tail,
  * 1 = end offsets (u32 or u64, fzb_corpus_info out[9]), 2 = vbytes, 3 = vgofs, 4 = vgnv, 5 = vlen, 6 = vperm, 7 = vlong (2..7: the
- * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them), 9 = the score bias (int16 per haystack, nothing without one), 10 = the tags (uint16 per haystack, nothing when the corpus has none), 11 = the signatures' bit-planes (uint64 [tile][bit][16], nothing without them).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
+ * filter's view, nothing without one), 8 = the letter signatures (u32 per haystack, nothing without them), 9 = the score bias (int16 per haystack, nothing without one), 10 = the tags (uint16 per haystack, nothing when the corpus has none), 11 = the signatures' bit-planes (uint64 [tile][bit][16], nothing without them), 12 = the repeat planes (the same layout, nothing without them).  *out_bytes = the array's size; FZB_ERR_CAPACITY (and the size) when cap_bytes is less. */
 int fzb_debug_corpus_read(const fzb_corpus* c, int what, void* host_out, size_t cap_bytes, size_t* out_bytes);
 
 #ifdef __cplusplus

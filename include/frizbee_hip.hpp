@@ -198,6 +198,13 @@ class Corpus {
         check(fzb_corpus_signature_planes_info(h_.get(), &built, &bytes));
         return built ? bytes : 0;
     }
+    // the repeat planes beside them (fzb_corpus_signature_repeat_planes_info): device bytes, 0 without them
+    uint64_t signature_repeat_planes_bytes() const {
+        int built = 0;
+        uint64_t bytes = 0;
+        check(fzb_corpus_signature_repeat_planes_info(h_.get(), &built, &bytes));
+        return built ? bytes : 0;
+    }
     // A corpus that is edited (fzb_corpus_remove and friends): the other haystacks keep their order and are renumbered, as Vec::retain
     // would; only the indices - and a replace's new bytes - cross the link, nothing in front of the first touched haystack moves.
     void remove(const std::vector<uint32_t>& indices) { check(fzb_corpus_remove(h_.get(), indices.data(), indices.size())); }

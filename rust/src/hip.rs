@@ -104,6 +104,9 @@ extern "C" {
     // the signatures' bit-planes of a list of short haystacks (another 4 bytes per haystack): whether the corpus has them, and their size
     #[allow(dead_code)]
     fn fzb_corpus_signature_planes_info(c: *const c_void, out_built: *mut c_int, out_bytes: *mut u64) -> c_int;
+    // the repeat planes beside them (which signature bits a haystack holds at least twice; another 4 bytes per haystack)
+    #[allow(dead_code)]
+    fn fzb_corpus_signature_repeat_planes_info(c: *const c_void, out_built: *mut c_int, out_bytes: *mut u64) -> c_int;
     // a corpus that is edited: haystacks removed or replaced anywhere; only the indices (and a replace's new bytes) cross the link
     fn fzb_corpus_remove(c: *mut c_void, indices: *const u32, n_indices: usize) -> c_int;
     #[allow(dead_code)]
