@@ -136,6 +136,8 @@ SYMBOLS = [
     "fzb_prompt_list_device", "fzb_prompt_top_device",
     "fzb_facets_create", "fzb_facets_free", "fzb_facets_read", "fzb_facets_device", "fzb_matcher_set_facets", "fzb_multi_matcher_set_facets",
     "fzb_match_list_top_sections", "fzb_match_list_top_sections_device", "fzb_multi_match_list_top_sections", "fzb_multi_match_list_top_sections_device",
+    "fzb_match_list_top_sections_indices", "fzb_match_list_top_sections_indices_device", "fzb_multi_match_list_top_sections_indices",
+    "fzb_multi_match_list_top_sections_indices_device",
 ]
 
 
@@ -296,6 +298,12 @@ def lib():
         l.fzb_match_list_top_sections_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         l.fzb_multi_match_list_top_sections.argtypes = l.fzb_match_list_top_sections.argtypes
         l.fzb_multi_match_list_top_sections_device.argtypes = l.fzb_match_list_top_sections_device.argtypes
+        l.fzb_match_list_top_sections_indices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                          C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        l.fzb_match_list_top_sections_indices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        l.fzb_multi_match_list_top_sections_indices.argtypes = l.fzb_match_list_top_sections_indices.argtypes
+        l.fzb_multi_match_list_top_sections_indices_device.argtypes = l.fzb_match_list_top_sections_indices_device.argtypes
         _lib = l
     return _lib
 
@@ -360,6 +368,27 @@ def _top_sections(fn, handle, corpus, sections, limit, subset, capture):
 def _top_sections_device(fn, handle, corpus, sections, limit, dev_out_ptr, capacity, dev_counts_ptr, stream, subset, capture):
     arr = _section_array(sections)
     _check(fn(handle, corpus.h, arr.ctypes.data if len(arr) else None, len(arr), limit, _h(subset), _h(capture), dev_out_ptr, capacity, dev_counts_ptr, stream))
+
+
+def _top_sections_indices(fn, handle, corpus, sections, limit, subset, capture):
+    """the host form of a sectioned top-`limit` call with matched positions -> [(list[MatchIndices], found)] in section order; one block of
+    records and one dense position array come back and are split here"""
+    arr = _section_array(sections)
+    S = len(arr)
+    out, pos, lens, found = C.c_void_p(), C.c_void_p(), (C.c_size_t * max(S, 1))(), (C.c_uint64 * max(S, 1))()
+    _check(fn(handle, corpus.h, arr.ctypes.data if S else None, S, limit, _h(subset), _h(capture), C.byref(out), lens, C.byref(pos), found))
+    block = _take_indices(out, C.c_size_t(sum(lens[s] for s in range(S))), pos) if out.value else []
+    heads, at = [], 0
+    for s in range(S):
+        heads.append((block[at:at + lens[s]], int(found[s])))
+        at += lens[s]
+    return heads
+
+
+def _top_sections_indices_device(fn, handle, corpus, sections, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_counts_ptr, stream, subset, capture):
+    arr = _section_array(sections)
+    _check(fn(handle, corpus.h, arr.ctypes.data if len(arr) else None, len(arr), limit, _h(subset), _h(capture), dev_out_ptr, capacity, dev_positions_ptr, positions_capacity,
+              dev_counts_ptr, stream))
 
 
 def _take(out, n, copy=True):
@@ -949,6 +978,17 @@ class MultiMatcher(_IterApi):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_multi_match_list_top_sharded, self.h, sharded.h, limit, copy)
 
+    def match_list_top_sections_indices(self, corpus, sections, limit, *, subset=None, capture=None):
+        """`Matcher.match_list_top_sections_indices` behind the composition: every record's positions are the de-duplicated union over the
+        non-negated patterns, as `match_list_indices` reports them."""
+        return _top_sections_indices(lib().fzb_multi_match_list_top_sections_indices, self.h, corpus, sections, limit, subset, capture)
+
+    def match_list_top_sections_indices_device(self, corpus, sections, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_counts_ptr, stream=0, *, subset=None,
+                                               capture=None):
+        """`Matcher.match_list_top_sections_indices_device` behind the composition; the positions' stride is the non-negated patterns' bytes, summed."""
+        _top_sections_indices_device(lib().fzb_multi_match_list_top_sections_indices_device, self.h, corpus, sections, limit, dev_out_ptr, capacity, dev_positions_ptr,
+                                     positions_capacity, dev_counts_ptr, stream, subset, capture)
+
     def match_list_top_indices(self, haystacks, limit, *, subset=None, capture=None):
         """(`match_list_indices(haystacks)[:limit]` with `index` = the corpus index, len of the full list) for the compiled patterns, in one
         fused device call with one host wait: the multi top stage, one traced pass per non-negated pattern over the head, the union of their
@@ -1139,6 +1179,23 @@ class Matcher(_IterApi):
     def match_list_top_sharded(self, sharded, limit, copy=True):
         """`match_list_top` over a `ShardedCorpus`: every shard selects its own head, only those records reach the root."""
         return _top(lib().fzb_match_list_top_sharded, self.h, sharded.h, limit, copy)
+
+    def match_list_top_sections_indices(self, corpus, sections, limit, *, subset=None, capture=None):
+        """`match_list_top_sections` with the matched byte positions of every head's records: [(list[MatchIndices], found)] in section
+        order.  Element s is what `match_list_top_indices(corpus, limit)` returns over a corpus whose scope is the corpus' own scope AND
+        section s - from ONE pass of the filter and the scorers, one traced pass over the heads and one host wait.  A haystack that sits
+        in several sections appears in each head with its positions.  An empty needle returns the prompt's records with no positions."""
+        return _top_sections_indices(lib().fzb_match_list_top_sections_indices, self.h, corpus, sections, limit, subset, capture)
+
+    def match_list_top_sections_indices_device(self, corpus, sections, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_counts_ptr, stream=0, *, subset=None,
+                                               capture=None):
+        """`match_list_top_sections_indices` with the result left in HBM, asynchronous on `stream`: the heads DENSELY concatenated in section
+        order at `dev_out_ptr` (`capacity` >= len(sections) * min(limit, len(corpus)) records of MATCH_INDICES_DTYPE), their dense positions
+        at `dev_positions_ptr` (`positions_capacity` >= that many records * len(needle) uint32), and 2 S + 4 count words at `dev_counts_ptr`,
+        S = len(sections): [2s] = records of head s, [2s + 1] = matches in section s, [2S] = records in all, [2S + 2] = positions written,
+        [2S + 3] = 0 (non-zero: the traced pass disagreed with the stage).  Not for an empty needle."""
+        _top_sections_indices_device(lib().fzb_match_list_top_sections_indices_device, self.h, corpus, sections, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity,
+                                     dev_counts_ptr, stream, subset, capture)
 
     def match_list_top_indices(self, haystacks, limit, *, subset=None, capture=None):
         """(the first min(limit, found) entries of `Matcher::match_list_indices` over the whole list, found): what a picker shows after a

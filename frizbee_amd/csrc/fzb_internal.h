@@ -282,6 +282,10 @@ struct sections_set;
 size_t fzb_sections_scratch_words(size_t n_records);
 hipError_t fzb_launch_sections_select(const fzb_match_rec* in, const u32* in_count, u32 in_cap, const uint16_t* tags, u64 n_tags, const sections_set& ss, u32 limit, int by_score,
                                       int desc, int one_pass, fzb_match_rec* out, u32* counts, u32* scratch, u32 ntiles_cap, int grid, hipStream_t st);
+// the sectioned query with matched positions: the stage's slabs and 2S count words -> one dense head (cap records), its pair, the item list of the
+// traced pass and its length, and the caller's 2S + 4 words ([2S], [2S + 1] are the pack's: fzb_launch_indices_pack with dev_counts + 2S)
+void fzb_launch_sections_items(const fzb_match_rec* slabs, const u32* counts, u32 n_sections, u32 limit, u32 cap, fzb_match_rec* head, u32* head_count, u32* items, u32* n_items,
+                               u32* dev_counts, int grid, hipStream_t st);
 // the corpus' score bias (score_bias.h) added to index-ordered records: haystack = first + (index - index_offset); the grid is sized from cap, trimmed by count[0]
 void fzb_launch_bias_apply(fzb_match_rec* recs, const u32* count, u32 cap, const int16_t* bias, u64 n_bias, u64 first, u32 index_offset, int grid_max, hipStream_t st);
 // the corpus' visibility scope (scope.h): the records of hidden haystacks dropped from count[0] index-ordered records (at most cap) into a DIFFERENT

@@ -336,9 +336,11 @@ int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_recor
     if (int rc = fzb_grow_dev(&s.words, &s.words_cap, fzb_sections_scratch_words(n_records), 16)) return rc;
     return stage_records ? fzb_grow_dev(&s.stage, &s.stage_words, 32 + 2 * stage_records, 16) : FZB_OK;
 }
+int fzb_sections_ensure_slabs(SectionsScratch& s, size_t slab_records) { return fzb_grow_dev(&s.slabs, &s.slabs_words, SECTIONS_SLAB_WORDS + 2 * slab_records, 16); }
 void fzb_sections_release(SectionsScratch& s) {
     if (s.words) (void)hipFree(s.words);
     if (s.stage) (void)hipFree(s.stage);
+    if (s.slabs) (void)hipFree(s.slabs);
     s = SectionsScratch{};
 }
 void fzb_out_release(OutStaging& o) {
@@ -3507,17 +3509,24 @@ int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb
 // rule), and so are its positions while they are no more than the records would be at that bound (256 KB); beyond, the copy takes the
 // previous result's size (*last_records, *last_positions) and a little more, and a result that outgrew it costs a second wait.
 // want / max_pos: the most records / positions the result can have.  `disagree`: what a raised inconsistency word means.
+// The sectioned form (SectionWords): `words` are sw->n words, the pack's four at sw->pack; all of them are copied and handed back in sw->host.
+struct SectionWords {
+    size_t n, pack;
+    u32 host[SECTIONS_SLAB_WORDS];
+};
 int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32* dense, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions, const char* disagree,
-                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* fifth_word = nullptr) {  // fifth_word: words[4] is copied and returned too
+                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* fifth_word = nullptr,  // fifth_word: words[4] is copied and returned too
+                      SectionWords* sw = nullptr) {
     auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
     const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(*last_records, want);
     const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(*last_positions, max_pos);
-    u8* stage = (u8*)fzb_pinned_get(32 + grec * sizeof(fzb_match_indices) + gpos * 4);
+    const size_t front = sw ? (sw->n * 4 + 31) / 32 * 32 : 32;  // the words' room in front of the records
+    u8* stage = (u8*)fzb_pinned_get(front + grec * sizeof(fzb_match_indices) + gpos * 4);
     if (!stage) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
-    const u32* const hw = (const u32*)stage;
-    const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + 32);
-    const u32* const hpos = (const u32*)(stage + 32 + grec * sizeof(fzb_match_indices));
-    hipError_t e = hipMemcpyAsync(stage, words, fifth_word ? 20 : 16, hipMemcpyDeviceToHost, nullptr);
+    const u32* const hw = (const u32*)stage + (sw ? sw->pack : 0);
+    const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + front);
+    const u32* const hpos = (const u32*)(stage + front + grec * sizeof(fzb_match_indices));
+    hipError_t e = hipMemcpyAsync(stage, words, sw ? sw->n * 4 : fifth_word ? 20 : 16, hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess) e = fzb_stream_wait(nullptr);
@@ -3527,6 +3536,7 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
     }
     const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
     if (fifth_word) *fifth_word = hw[4];
+    if (sw) memcpy(sw->host, stage, sw->n * 4);
     if (hw[3]) {
         const u32 why = hw[3];
         fzb_pinned_put(stage);
@@ -3560,6 +3570,28 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
 }  // namespace
 extern "C" {
 
+// The tail of every fused "head + matched positions" query of a single matcher: m->top_head holds a head of up to `want` records in the caller's
+// order, m->top_idx_words its pair, m->trace_sel / the word behind it the head's item list (k_top_items; k_sec_items for sectioned heads).
+// From there: the traced pass over the items, the bias on the traced records, the pack into the caller's buffers and four words at dev_count.
+static int top_indices_tail(fzb_matcher* m, const fzb_corpus* c, size_t want, u32 stride, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                            uint32_t* dev_count, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    u32* const head_count = m->top_idx_words;
+    u32* const traced_count = m->top_idx_words + 2;  // the traced pass' pair
+    u32* const n_items = m->trace_sel + m->trace_cap;
+    const int grid = m->lc.num_cus * 2;
+    int rc;
+    const TraceOut tr{m->trace_pos, m->trace_npos, stride};
+    // (grids from the head's capacity on the host, trimmed by the item count on the device; want == 0 - limit 0 - clears the pair and launches nothing)
+    if ((rc = run_pipeline(m, c, 0, want, 0, m->trace_sel, n_items, (fzb_match*)m->top_traced, want, traced_count, stream, &tr))) return rc;
+    // (the head's scores are biased: the traced records get the same pass, so the pack holds them to the head on the scores the caller sees)
+    if ((rc = apply_bias(c, m->top_traced, traced_count, want, 0, 0, grid, st))) return rc;
+    fzb_launch_indices_pack(m->top_head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top_tiles, (u32)want, grid, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
 static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
                                    uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
@@ -3587,20 +3619,11 @@ static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t l
     int rc;
     if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false))) return rc;
     u32* const head_count = m->top_idx_words;        // (records, matches found) of the head
-    u32* const traced_count = m->top_idx_words + 2;  // the traced pass' pair
     u32* const n_items = m->trace_sel + m->trace_cap;
     if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->top_head, want, head_count, stream, sa))) return rc;
     const int grid = m->lc.num_cus * 2;
     fzb_launch_top_items(m->top_head, head_count, (u32)want, m->trace_sel, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
-    const TraceOut tr{m->trace_pos, m->trace_npos, stride};
-    // (grids from min(limit, n) on the host, trimmed by the item count on the device; want == 0 - limit 0 - clears the pair and launches nothing)
-    if ((rc = run_pipeline(m, c, 0, want, 0, m->trace_sel, n_items, (fzb_match*)m->top_traced, want, traced_count, stream, &tr))) return rc;
-    // (the head's scores are biased: the traced records get the same pass, so the pack holds them to the head on the scores the caller sees)
-    if ((rc = apply_bias(c, m->top_traced, traced_count, want, 0, 0, grid, st))) return rc;
-    fzb_launch_indices_pack(m->top_head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
-                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top_tiles, (u32)want, grid, st);
-    HIPCHK(hipGetLastError());
-    return FZB_OK;
+    return top_indices_tail(m, c, want, stride, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream);
 }
 
 int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
@@ -4143,6 +4166,54 @@ bool same_union_src(const IUnionSrc& a, const IUnionSrc& b) { return a.rec == b.
 }  // namespace
 extern "C" {
 
+// The two halves every fused "head + matched positions" query of the composition shares.  Ahead of the first launch: the composition's and every
+// positive pattern's buffers for a head of up to `want` records, and the sources of the union (uploaded beyond IUNION_BY_VALUE).
+static int multi_top_indices_sources(fzb_multi_matcher* mm, size_t want, size_t U, size_t P, std::vector<IUnionSrc>* src, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, false))) return rc;
+    src->clear();
+    src->reserve(P);
+    for (auto& p : mm->patterns) {
+        if (p.negated) continue;
+        fzb_matcher* m = p.m;
+        if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
+        src->push_back(IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0});
+    }
+    if (P > IUNION_BY_VALUE) {
+        bool same = mm->union_src_host.size() == P;
+        for (size_t i = 0; same && i < P; i++) same = same_union_src(mm->union_src_host[i], (*src)[i]);
+        if (!same) {  // (a pattern or a buffer changed since the array was written: ahead of the first launch, ordered on the stream)
+            mm->union_src_host = *src;
+            HIPCHK(hipMemcpyAsync(mm->union_src, mm->union_src_host.data(), P * sizeof(IUnionSrc), hipMemcpyHostToDevice, st));
+        }
+    }
+    return FZB_OK;
+}
+// Behind the head (mm->top_head, its pair in mm->top_words) and its item list (mm->top_items, the length in mm->top_words[10]; k_top_items, or
+// k_sec_items for sectioned heads): one traced pass per positive pattern, the union, the bias, the pack and four words at dev_count.
+static int multi_top_indices_tail(fzb_multi_matcher* mm, const fzb_corpus* c, size_t want, size_t U, const std::vector<IUnionSrc>& src, fzb_match_indices* dev_out, size_t capacity,
+                                  uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    u32* const head_count = mm->top_words;
+    u32* const comb_count = mm->top_words + 2;  // the combined traced pair
+    u32* const n_items = mm->top_words + 10;
+    const int grid = mm->num_cus * 2;
+    int rc;
+    for (auto& p : mm->patterns) {
+        if (p.negated) continue;
+        fzb_matcher* m = p.m;
+        const TraceOut tr{m->trace_pos, m->trace_npos, trace_stride(m)};
+        if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
+    }
+    fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)src.size(), mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U,
+                           grid, st);
+    if ((rc = apply_bias(c, mm->top_comb, comb_count, want, 0, 0, grid, st))) return rc;  // once, after the sum: as the head's records
+    fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
 static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
                                          size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
@@ -4170,42 +4241,15 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
     }
     // every buffer first: the sources of the union are final before anything is launched
     int rc;
-    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, false))) return rc;
     std::vector<IUnionSrc> src;
-    src.reserve(P);
-    for (auto& p : mm->patterns) {
-        if (p.negated) continue;
-        fzb_matcher* m = p.m;
-        if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
-        src.push_back(IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0});
-    }
-    if (P > IUNION_BY_VALUE) {
-        bool same = mm->union_src_host.size() == P;
-        for (size_t i = 0; same && i < P; i++) same = same_union_src(mm->union_src_host[i], src[i]);
-        if (!same) {  // (a pattern or a buffer changed since the array was written: ahead of the first launch, ordered on the stream)
-            mm->union_src_host = src;
-            HIPCHK(hipMemcpyAsync(mm->union_src, mm->union_src_host.data(), P * sizeof(IUnionSrc), hipMemcpyHostToDevice, st));
-        }
-    }
+    if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st))) return rc;
     u32* const head_count = mm->top_words;      // (records, matches found) of the head
-    u32* const comb_count = mm->top_words + 2;  // the combined traced pair
     u32* const n_items = mm->top_words + 10;
     // (the composition's pair in words 12-13: word 8 follows the host form's four result words, where its wait picks up a captured count)
     if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 12, st, sa))) return rc;
     const int grid = mm->num_cus * 2;
     fzb_launch_top_items(mm->top_head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
-    for (auto& p : mm->patterns) {
-        if (p.negated) continue;
-        fzb_matcher* m = p.m;
-        const TraceOut tr{m->trace_pos, m->trace_npos, trace_stride(m)};
-        if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
-    }
-    fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)P, mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, grid, st);
-    if ((rc = apply_bias(c, mm->top_comb, comb_count, want, 0, 0, grid, st))) return rc;  // once, after the sum: as the head's records
-    fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
-                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
-    HIPCHK(hipGetLastError());
-    return FZB_OK;
+    return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream);
 }
 
 static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
@@ -4479,6 +4523,187 @@ int fzb_multi_match_list_top_sections(fzb_multi_matcher* mm, const fzb_corpus* c
     u32 captured = 0;
     if ((rc = sections_fetch(mm->sections, n_sections, limit, out, out_len, out_found, &captured))) return rc;
     if (captures) subset_capture_known(capture, captured);
+    return FZB_OK;
+}
+
+// ---- sectioned top-`limit` WITH matched positions: one fused device call ---------------------------------------------------------------------
+// Element s = fzb_match_list_top_indices over the corpus' own scope AND section s's predicate.  The sectioned stage runs as above, into slabs of
+// the matcher's own (SectionsScratch::slabs); k_sec_items makes the slabs ONE dense head of up to n_sections * min(limit, haystacks) records with
+// its item list, and from there the fused queries' tail runs unchanged (top_indices_tail / multi_top_indices_tail): the traced pass(es) over the
+// items, the union, the bias, the pack.  A haystack that sits in several sections is an item several times and is traced once per section.
+}  // extern "C"
+namespace {
+// what the _device forms check behind sections_check; *want = the records the dense head has room for
+int sections_indices_room(size_t n_sections, size_t limit, size_t n, size_t stride, size_t capacity, size_t positions_capacity, size_t* want) {
+    *want = n_sections * std::min(limit, n);
+    if (capacity < *want)
+        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(*want));
+    if (positions_capacity < *want * stride)
+        return fail(FZB_ERR_CAPACITY,
+                    "positions buffer smaller than n_sections * min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(*want * stride));
+    if ((u64)*want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "n_sections * min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
+    return FZB_OK;
+}
+// the host forms' answer where no positions exist (an empty needle, no pattern) or nothing is selected (no section, an empty corpus): the
+// sectioned call's records with empty position lists
+int sections_indices_plain(fzb_match* head, size_t n_sections, const size_t* out_len, fzb_match_indices** out, uint32_t** out_positions) {
+    size_t total = 0;
+    for (size_t s = 0; s < n_sections; s++) total += out_len[s];
+    std::vector<fzb_match_indices> recs(total);
+    for (size_t i = 0; i < total; i++) recs[i] = fzb_match_indices{head[i].index, head[i].score, head[i].exact, 0, 0, 0};
+    if (head) fzb_matches_free(head);
+    size_t len = 0;
+    return hand_over_indices(recs.data(), total, nullptr, 0, out, &len, out_positions);
+}
+// the host forms' one wait: the 2S + 4 words (and the captured count at word 24), the dense head, the dense positions
+int sections_indices_fetch(SectionsScratch& sc, const fzb_indices_rec* packed, const u32* dense, size_t S, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions,
+                           const char* disagree, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* captured) {
+    SectionWords sw{};
+    sw.n = 32;
+    sw.pack = 2 * S;
+    size_t total = 0;
+    if (int rc = fetch_top_indices(sc.slabs + 16, packed, dense, want, max_pos, last_records, last_positions, disagree, out, &total, out_positions, nullptr, nullptr, &sw)) return rc;
+    for (size_t s = 0; s < S; s++) {
+        out_len[s] = sw.host[2 * s];
+        if (out_found) out_found[s] = sw.host[2 * s + 1];
+    }
+    *captured = sw.host[24];
+    return FZB_OK;
+}
+}  // namespace
+extern "C" {
+
+// (mirror: where the host form's wait picks up the captured count, or null)
+static int sections_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                        u32* mirror, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_counts, void* stream) {
+    sections_set ss;
+    if (!dev_counts || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections_indices_device", &ss))) return rc;
+    if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top_sections_indices");
+    const size_t n = c->dev.n;
+    const u32 stride = trace_stride(m);
+    size_t want;
+    if ((rc = sections_indices_room(n_sections, limit, n, stride, capacity, positions_capacity, &want))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    SubsetArgs sa{in, capture, mirror};
+    if (n == 0 || n_sections == 0) {  // nothing to select: the sectioned call's side effects (capture, facets), 2S + 4 zero words
+        if ((rc = single_sections_stage(m, c, ss, limit, &sa, nullptr, dev_counts, st))) return rc;
+        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, 16, st));
+        return FZB_OK;
+    }
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false)) || (rc = fzb_sections_ensure_slabs(m->sections, n_sections * limit))) return rc;
+    u32* const slab_counts = m->sections.slabs;
+    fzb_match_rec* const slabs = (fzb_match_rec*)(m->sections.slabs + SECTIONS_SLAB_WORDS);
+    if ((rc = single_sections_stage(m, c, ss, limit, &sa, slabs, slab_counts, st))) return rc;
+    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, m->top_head, m->top_idx_words, m->trace_sel, m->trace_sel + m->trace_cap, dev_counts,
+                              m->lc.num_cus * 2, st);
+    return top_indices_tail(m, c, want, stride, dev_out, capacity, dev_positions, positions_capacity, dev_counts + 2 * n_sections, stream);
+}
+
+int fzb_match_list_top_sections_indices_device(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                               fzb_subset* capture, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                               uint32_t* dev_counts, void* stream) {
+    return sections_indices_device_impl(m, c, sections, n_sections, limit, in, capture, nullptr, dev_out, capacity, dev_positions, positions_capacity, dev_counts, stream);
+}
+
+int fzb_match_list_top_sections_indices(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                        fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    sections_set ss;
+    if (!out || !out_positions || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_positions = nullptr;
+    int rc;
+    if ((rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections_indices", &ss))) return rc;
+    const size_t n = c->dev.n;
+    if (m->empty || n == 0 || n_sections == 0) {
+        fzb_match* head = nullptr;
+        if ((rc = fzb_match_list_top_sections(m, c, sections, n_sections, limit, in, capture, &head, out_len, out_found))) return rc;
+        return sections_indices_plain(head, n_sections, out_len, out, out_positions);
+    }
+    for (size_t s = 0; s < n_sections; s++) {
+        out_len[s] = 0;
+        if (out_found) out_found[s] = 0;
+    }
+    const size_t stride = trace_stride(m), want = n_sections * std::min(limit, n);
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true)) || (rc = fzb_sections_ensure_slabs(m->sections, n_sections * limit))) return rc;
+    u32* const words = m->sections.slabs + 16;
+    if ((rc = sections_indices_device_impl(m, c, sections, n_sections, limit, in, capture, capture ? words + 24 : nullptr, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense,
+                                           m->top_dense_words, words, nullptr)))
+        return rc;
+    u32 captured = 0;
+    if ((rc = sections_indices_fetch(m->sections, m->top_packed, m->top_dense, n_sections, want, want * stride, &m->top_last_records, &m->top_last_positions,
+                                     "the traced pass disagrees with the sectioned stage", out, out_len, out_positions, out_found, &captured)))
+        return rc;
+    subset_capture_known(capture, captured);
+    return FZB_OK;
+}
+
+static int multi_sections_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                              fzb_subset* capture, u32* mirror, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                              uint32_t* dev_counts, void* stream) {
+    sections_set ss;
+    if (!dev_counts || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_indices_device", &ss))) return rc;
+    if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_sections_indices");
+    const size_t n = c->dev.n;
+    size_t P = 0, want;
+    const size_t U = multi_union_stride(mm, &P);
+    if ((rc = sections_indices_room(n_sections, limit, n, U, capacity, positions_capacity, &want))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    SubsetArgs sa{in, capture, mirror};
+    if (n == 0 || n_sections == 0) {
+        if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, nullptr, dev_counts, st))) return rc;
+        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, 16, st));
+        return FZB_OK;
+    }
+    // every buffer first: the sources of the union are final before anything is launched
+    std::vector<IUnionSrc> src;
+    if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st)) || (rc = fzb_sections_ensure_slabs(mm->sections, n_sections * limit))) return rc;
+    u32* const slab_counts = mm->sections.slabs;
+    fzb_match_rec* const slabs = (fzb_match_rec*)(mm->sections.slabs + SECTIONS_SLAB_WORDS);
+    if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, slabs, slab_counts, st))) return rc;
+    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, mm->top_head, mm->top_words, mm->top_items, mm->top_words + 10, dev_counts, mm->num_cus * 2, st);
+    return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_counts + 2 * n_sections, stream);
+}
+
+int fzb_multi_match_list_top_sections_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                                     fzb_subset* capture, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                                     uint32_t* dev_counts, void* stream) {
+    return multi_sections_indices_device_impl(mm, c, sections, n_sections, limit, in, capture, nullptr, dev_out, capacity, dev_positions, positions_capacity, dev_counts, stream);
+}
+
+int fzb_multi_match_list_top_sections_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                              fzb_subset* capture, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    sections_set ss;
+    if (!out || !out_positions || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out_positions = nullptr;
+    int rc;
+    if ((rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_indices", &ss))) return rc;
+    const size_t n = c->dev.n;
+    if (mm->patterns.empty() || n == 0 || n_sections == 0) {
+        fzb_match* head = nullptr;
+        if ((rc = fzb_multi_match_list_top_sections(mm, c, sections, n_sections, limit, in, capture, &head, out_len, out_found))) return rc;
+        return sections_indices_plain(head, n_sections, out_len, out, out_positions);
+    }
+    for (size_t s = 0; s < n_sections; s++) {
+        out_len[s] = 0;
+        if (out_found) out_found[s] = 0;
+    }
+    size_t P = 0;
+    const size_t U = multi_union_stride(mm, &P), want = n_sections * std::min(limit, n);
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, true)) || (rc = fzb_sections_ensure_slabs(mm->sections, n_sections * limit))) return rc;
+    u32* const words = mm->sections.slabs + 16;
+    if ((rc = multi_sections_indices_device_impl(mm, c, sections, n_sections, limit, in, capture, capture ? words + 24 : nullptr, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap,
+                                                 mm->top_dense, mm->top_dense_words, words, nullptr)))
+        return rc;
+    u32 captured = 0;
+    if ((rc = sections_indices_fetch(mm->sections, mm->top_packed, mm->top_dense, n_sections, want, want * U, &mm->top_last_records, &mm->top_last_positions,
+                                     "the traced passes disagree with the sectioned multi stage", out, out_len, out_positions, out_found, &captured)))
+        return rc;
+    subset_capture_known(capture, captured);
     return FZB_OK;
 }
 

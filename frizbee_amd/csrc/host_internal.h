@@ -194,14 +194,20 @@ void fzb_scope_release(ScopeScratch& s);
 
 // The buffers of the sectioned top-`limit` queries (sections.h; host.hip), of either matcher type: `words` = the stage's scratch (bins, cuts,
 // tile rows: fzb_sections_scratch_words), `stage` = the host forms' device-side result - 16 count words, then n_sections * limit records, so
-// that one copy brings both back.  Grown through fzb_grow_dev on the first sectioned query, released with the matcher.
+// that one copy brings both back; `slabs` = the form with matched positions: SECTIONS_SLAB_WORDS words (the stage's 2S count words at 0, the host
+// form's 2S + 4 result words at 16 and its captured count at 40), then the n_sections * limit slab records that k_sec_items makes one dense
+// head.  Grown through fzb_grow_dev on the first sectioned query, released with the matcher.
+#define SECTIONS_SLAB_WORDS 48
 struct SectionsScratch {
     u32* words = nullptr;
     size_t words_cap = 0;
     u32* stage = nullptr;
     size_t stage_words = 0;
+    u32* slabs = nullptr;
+    size_t slabs_words = 0;
 };
 int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_records);  // host.hip
+int fzb_sections_ensure_slabs(SectionsScratch& s, size_t slab_records);
 void fzb_sections_release(SectionsScratch& s);
 
 // A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle

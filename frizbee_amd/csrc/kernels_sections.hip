@@ -10,6 +10,7 @@
 //   k_sec_scan         exclusive scans of the 2S rows, a wave per row, and the rows' totals
 //   k_sec_scatter      one stable pass: topk_dest per record and section it belongs to, into the slab out[s * limit + d]; the 2S result words
 //   k_sec_order        a workgroup per section: the slab's <= 1024 kept records ranked in LDS (sections_rank) and written back in order
+//   k_sec_items        (the form with matched positions) the slabs' kept records -> one dense head + the item list of the traced pass
 // The record count lives in device memory; no count is read back between the kernels.  Every loop over records, tiles, rows or sections is
 // grid-stride with trip counts that are uniform around ballots, shuffles and barriers.
 #include "kernels_common.h"
@@ -277,6 +278,51 @@ __global__ __launch_bounds__(256) void k_sec_order(fzb_match_rec* __restrict__ o
         for (u32 i = threadIdx.x; i < kept; i += 256) dst[sections_rank(slab, kept, i, by_score, desc)] = slab[i];
         __syncthreads();
     }
+}
+
+// Sectioned top-`limit` with matched positions: the stage's slabs -> ONE dense head and the item list of the traced pass, where k_top_items
+// (kernels_indices.hip) takes a head that is dense already.  Every workgroup re-derives the exclusive prefix of the S <= 8 kept counts
+// (sections_head_base) from the stage's count words: no extra launch, no workgroup waits for another one.  Slot k of the slabs goes to
+// head[base_s + j] and items[base_s + j]; workgroup 0 writes the item count, the head's pair (records in all, twice: the pack copies the
+// second word into the word the contract leaves unspecified), the caller's 2S count words, and clears the two words the pack only raises.
+__global__ __launch_bounds__(256) void k_sec_items(const fzb_match_rec* __restrict__ slabs, const u32* __restrict__ counts, u32 n_sections, u32 limit, u32 cap,
+                                                   fzb_match_rec* __restrict__ head, u32* __restrict__ head_count, u32* __restrict__ items, u32* __restrict__ n_items,
+                                                   u32* __restrict__ dev_counts) {
+    __shared__ u32 s_counts[2 * SECTIONS_MAX], s_base[SECTIONS_MAX + 1];
+    const u32 S = min(n_sections, (u32)SECTIONS_MAX);
+    if (threadIdx.x < 2 * S) s_counts[threadIdx.x] = counts[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x <= S) s_base[threadIdx.x] = sections_head_base(s_counts, threadIdx.x, limit);
+    __syncthreads();
+    const u32 slots = S * limit;
+    for (u32 k = blockIdx.x * 256u + threadIdx.x; k < slots; k += gridDim.x * 256u) {
+        const u32 d = sections_head_dest(s_counts, s_base, limit, k);
+        if (d != SECTIONS_NO_SLOT && d < cap) {  // (the sum of the kept counts is at most S * min(limit, haystacks) = cap)
+            const fzb_match_rec r = slabs[k];
+            head[d] = r;
+            items[d] = r.index;
+        }
+    }
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < 2 * S) dev_counts[threadIdx.x] = (threadIdx.x & 1u) ? s_counts[threadIdx.x] : sections_slab_kept(s_counts, threadIdx.x >> 1, limit);
+        if (threadIdx.x == 0) {
+            const u32 total = min(s_base[S], cap);
+            n_items[0] = total;
+            head_count[0] = total;
+            head_count[1] = total;
+            dev_counts[2 * S + 2] = 0;
+            dev_counts[2 * S + 3] = 0;
+        }
+    }
+}
+
+// slabs / counts: what fzb_launch_sections_select wrote (n_sections slabs of `limit` records, 2 n_sections words).  head / items: room for cap >=
+// n_sections * min(limit, haystacks) entries; head_count: two words; n_items: one; dev_counts: 2 n_sections + 4 words, of which [2S] and
+// [2S + 1] are left to the pack (fzb_launch_indices_pack with dev_count = dev_counts + 2S).
+void fzb_launch_sections_items(const fzb_match_rec* slabs, const u32* counts, u32 n_sections, u32 limit, u32 cap, fzb_match_rec* head, u32* head_count, u32* items, u32* n_items,
+                               u32* dev_counts, int grid, hipStream_t st) {
+    const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, (n_sections * limit + 255) / 256));
+    FZB_LAUNCH(k_sec_items, dim3(g), dim3(256), 0, st, slabs, counts, n_sections, limit, cap, head, head_count, items, n_items, dev_counts);
 }
 
 // in: *in_count records (at most in_cap) in record order, numbered from 0 over the corpus whose tag column is `tags` (n_tags entries; null /

@@ -107,3 +107,21 @@ FZB_SEC_FN uint32_t sections_rank(const sections_rec* slab, uint32_t kept, uint3
     for (uint32_t j = 0; j < kept; j++) r += sections_before(sections_score(slab[j]), j, si, i, by_score, desc) ? 1u : 0u;
     return r;
 }
+
+// ---- the placement of the slabs in ONE dense head (sectioned top-`limit` with matched positions: k_sec_items) ----
+// counts = the stage's 2S result words (counts[2s] = records of slab s); slab s holds its records at [s * limit, s * limit + kept_s).
+// the records of slab s as the dense head takes them: never more than the slab has room for
+FZB_SEC_FN uint32_t sections_slab_kept(const uint32_t* counts, uint32_t s, uint32_t limit) { return counts[2 * s] < limit ? counts[2 * s] : limit; }
+// where head s begins in the dense head: the records of the sections in front of it (s == n_sections: the records in all)
+FZB_SEC_FN uint32_t sections_head_base(const uint32_t* counts, uint32_t s, uint32_t limit) {
+    uint32_t base = 0;
+    for (uint32_t t = 0; t < s && t < SECTIONS_MAX; t++) base += sections_slab_kept(counts, t, limit);
+    return base;
+}
+#define SECTIONS_NO_SLOT 0xFFFFFFFFu
+// slab slot k (0 <= k < n_sections * limit; section k / limit, record k % limit) -> its place in the dense head, SECTIONS_NO_SLOT for a
+// slot without a record.  bases[s] = sections_head_base(counts, s, limit).
+FZB_SEC_FN uint32_t sections_head_dest(const uint32_t* counts, const uint32_t* bases, uint32_t limit, uint32_t k) {
+    const uint32_t s = k / limit, j = k - s * limit;
+    return j < sections_slab_kept(counts, s, limit) ? bases[s] + j : SECTIONS_NO_SLOT;
+}

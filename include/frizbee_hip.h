@@ -817,7 +817,8 @@ int fzb_multi_matcher_set_facets(fzb_multi_matcher* mm, fzb_facets* f);
  * `in` / `capture` (either may be NULL) are the candidate sets of the _subset queries: the capture holds what fzb_match_list_top_subset
  * captures.  An attached facet sink is filled as by fzb_match_list_top.  The fzb_multi_* forms do the same behind the composition of a
  * `from_patterns` matcher.
- * NOT OFFERED: sharded and RCCL forms, matched positions (_indices) for sectioned heads, limits above FZB_SECTION_LIMIT_MAX. */
+ * NOT OFFERED: sharded and RCCL forms, matched positions (_indices) of sharded or RCCL heads, limits above FZB_SECTION_LIMIT_MAX.  (Matched
+ * positions for the sectioned heads of ONE device are offered: the _sections_indices forms below.) */
 #define FZB_SECTIONS_MAX 8
 #define FZB_SECTION_LIMIT_MAX 1024
 typedef struct { uint16_t require, exclude; } fzb_section;
@@ -829,6 +830,37 @@ int fzb_multi_match_list_top_sections(fzb_multi_matcher* mm, const fzb_corpus* c
                                       fzb_subset* capture, fzb_match** out, size_t* out_len, uint64_t* out_found);
 int fzb_multi_match_list_top_sections_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
                                              fzb_subset* capture, fzb_match* dev_out, size_t capacity, uint32_t* dev_counts, void* stream);
+
+/* SECTIONED TOP-`limit` WITH MATCHED POSITIONS, one fused call: the heads a picker shows in sections, with what it highlights.
+ * THE CONTRACT: element s is what fzb_match_list_top_indices(corpus, limit) returns over a corpus whose scope is the corpus' own scope AND
+ * section s's predicate - the records and their order (ties at the cut included, all four sort strategies), scores with the corpus' bias added,
+ * full-list indices, every record's matched byte positions as fzb_match_list_indices reports them (descending; for a `from_patterns` matcher the
+ * de-duplicated union over the non-negated patterns), and `found` = the visible matches in section s - from ONE pass of the filter and the
+ * scorers, ONE traced pass over the heads (one per non-negated pattern) and ONE host wait.  Sections, limits, refusals, `in` / `capture`, an
+ * attached facet sink, the bias and the corpus' scope behave exactly as in fzb_match_list_top_sections; (0, 0) reproduces
+ * fzb_match_list_top_indices.  A haystack that sits in several sections appears in each head with its positions (it is traced once per head).
+ * Host forms: *out = ONE block (freed with fzb_match_indices_free together with *out_positions), the heads concatenated in section order;
+ * out_len[s] = records of head s, out_found[s] (optional) = matches in section s; positions_begin indexes the one *out_positions array, which
+ * is dense over the whole block.  An empty needle / an empty pattern list is answered as by the sectioned call: the prompt's records, with empty
+ * position lists.
+ * _device forms: stream-ordered, nothing is read back.  dev_out holds the heads DENSELY concatenated in section order (head s starts behind the
+ * records of the heads in front of it); capacity >= n_sections * min(limit, haystacks) records and positions_capacity >= n_sections *
+ * min(limit, haystacks) x stride dwords, with the stride of fzb_match_list_top_indices_device (needle bytes) / fzb_multi_match_list_top_indices_device
+ * (the non-negated patterns' bytes, summed); less of either is FZB_ERR_CAPACITY before any launch.  dev_counts has 2 * n_sections + 4 words, S =
+ * n_sections: [2s] = records of head s, [2s + 1] = matches in section s, [2S] = records in all, [2S + 1] unspecified, [2S + 2] = position
+ * dwords written, [2S + 3] = 0, or non-zero when a traced pass disagreed with the stage (as dev_count[3] of fzb_match_list_top_indices_device).
+ * Not for an empty needle / an empty pattern list (FZB_ERR_INVALID: the host forms answer those).
+ * Buffers grow on first use, sized by n_sections * min(limit, haystacks); a second call of the same shape allocates nothing. */
+int fzb_match_list_top_sections_indices(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in, fzb_subset* capture,
+                                        fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found);
+int fzb_match_list_top_sections_indices_device(fzb_matcher* m, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                               fzb_subset* capture, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                               uint32_t* dev_counts, void* stream);
+int fzb_multi_match_list_top_sections_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                              fzb_subset* capture, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found);
+int fzb_multi_match_list_top_sections_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
+                                                     fzb_subset* capture, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                                     uint32_t* dev_counts, void* stream);
 
 /* Measurement hooks (bench.py): device time of the fzb_match_list_device calls made on this matcher since
  * fzb_set_profiling(m, 1), measured with HIP events recorded on the launch stream (event records only, no

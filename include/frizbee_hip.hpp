@@ -586,6 +586,54 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_match_list_top_sections_device(single_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_counts, stream));
         else check(fzb_multi_match_list_top_sections_device(multi_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_counts, stream));
     }
+    // Sectioned top-`limit` WITH matched positions (fzb_match_list_top_sections_indices / fzb_multi_match_list_top_sections_indices): element s
+    // is what match_list_top_indices(corpus, limit) returns over a corpus whose scope is the corpus' own scope AND section s - one pass of the
+    // filter and the scorers, one traced pass over the heads (one per non-negated pattern), one host wait.  A haystack that sits in several
+    // sections appears in each head with its positions.
+    struct SectionHeadIndices {
+        std::vector<MatchIndices> matches;
+        size_t found;  // the section's visible matches
+    };
+    std::vector<SectionHeadIndices> match_list_top_sections_indices(const Corpus& corpus, const std::vector<fzb_section>& sections, size_t limit, const Subset* in = nullptr,
+                                                                    Subset* capture = nullptr) {
+        const size_t S = sections.size();
+        fzb_match_indices* out = nullptr;
+        uint32_t* pos = nullptr;
+        std::vector<size_t> lens(S ? S : 1, 0);
+        std::vector<uint64_t> found(S ? S : 1, 0);
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_) check(fzb_match_list_top_sections_indices(single_.get(), corpus.raw(), sections.data(), S, limit, i, cp, &out, lens.data(), &pos, found.data()));
+        else check(fzb_multi_match_list_top_sections_indices(multi_.get(), corpus.raw(), sections.data(), S, limit, i, cp, &out, lens.data(), &pos, found.data()));
+        std::vector<SectionHeadIndices> heads(S);
+        size_t at = 0;
+        for (size_t s = 0; s < S; s++) {
+            heads[s].found = (size_t)found[s];
+            heads[s].matches.resize(lens[s]);
+            for (size_t k = 0; k < lens[s]; k++) {
+                const fzb_match_indices& r = out[at + k];
+                heads[s].matches[k] = MatchIndices{r.score, r.index, r.exact != 0, std::vector<uint32_t>(pos + r.positions_begin, pos + r.positions_begin + r.positions_len)};
+            }
+            at += lens[s];
+        }
+        if (out || pos) fzb_match_indices_free(out, pos);
+        return heads;
+    }
+    // the same left in HBM, asynchronous on `stream`: the heads densely concatenated in section order, capacity >= sections.size() * min(limit,
+    // haystacks) records, positions_capacity >= that x the stride of match_list_top_indices_device, 2 * sections.size() + 4 words at dev_counts
+    // (see fzb_match_list_top_sections_indices_device)
+    void match_list_top_sections_indices_device(const Corpus& corpus, const std::vector<fzb_section>& sections, size_t limit, fzb_match_indices* dev_out, size_t capacity,
+                                                uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_counts, void* stream = nullptr, const Subset* in = nullptr,
+                                                Subset* capture = nullptr) {
+        const fzb_subset* i = in ? in->raw() : nullptr;
+        fzb_subset* cp = capture ? capture->raw() : nullptr;
+        if (single_)
+            check(fzb_match_list_top_sections_indices_device(single_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_positions, positions_capacity,
+                                                             dev_counts, stream));
+        else
+            check(fzb_multi_match_list_top_sections_indices_device(multi_.get(), corpus.raw(), sections.data(), sections.size(), limit, i, cp, dev_out, capacity, dev_positions,
+                                                                   positions_capacity, dev_counts, stream));
+    }
     // The empty prompt's _device forms (a matcher made from an empty needle; the _device forms above refuse one): the index-ordered list of the
     // haystacks of the range, or of `in`, visible under the corpus' scope - score = the clamped bias -, and its ordered head.  dev_count =
     // (records written, found); asynchronous on `stream`.

@@ -174,8 +174,8 @@ extern "C" {
     fn fzb_multi_matcher_set_facets(mm: *mut c_void, f: *mut c_void) -> c_int;
     // sectioned top-`limit`: the best `limit` matches per tag section (at most FZB_SECTIONS_MAX = 8 sections, limit <= FZB_SECTION_LIMIT_MAX =
     // 1024) from one pass of the filter and the scorers; host forms: one block, the heads concatenated in section order, out_len / out_found
-    // per section; _device forms: section s at dev_out + s * limit, dev_counts = 2 words per section (records, matches).  No sharded, RCCL
-    // or matched-positions forms.
+    // per section; _device forms: section s at dev_out + s * limit, dev_counts = 2 words per section (records, matches).  No sharded or
+    // RCCL forms; matched positions: the _sections_indices forms below.
     #[allow(dead_code)]
     fn fzb_match_list_top_sections(m: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void, capture: *mut c_void,
                                    out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
@@ -188,6 +188,24 @@ extern "C" {
     #[allow(dead_code)]
     fn fzb_multi_match_list_top_sections_device(mm: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
                                                 capture: *mut c_void, dev_out: *mut FzbMatch, capacity: usize, dev_counts: *mut u32, stream: *mut c_void) -> c_int;
+    // sectioned top-`limit` with matched positions: element s = fzb_match_list_top_indices over the corpus' scope AND section s.  Host forms:
+    // one block of records (heads concatenated in section order) and one dense position array, freed with fzb_match_indices_free; _device
+    // forms: the heads densely concatenated, dev_counts = 2 * n_sections + 4 words ([2s] records of head s, [2s + 1] matches in section s,
+    // [2S] records in all, [2S + 2] positions written, [2S + 3] the pack's inconsistency word)
+    #[allow(dead_code)]
+    fn fzb_match_list_top_sections_indices(m: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                           capture: *mut c_void, out: *mut *mut FzbMatchIndices, out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_match_list_top_sections_indices_device(m: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                                  capture: *mut c_void, dev_out: *mut FzbMatchIndices, capacity: usize, dev_positions: *mut u32, positions_capacity: usize,
+                                                  dev_counts: *mut u32, stream: *mut c_void) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_sections_indices(mm: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                                 capture: *mut c_void, out: *mut *mut FzbMatchIndices, out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_multi_match_list_top_sections_indices_device(mm: *mut c_void, c: *const c_void, sections: *const FzbSection, n_sections: usize, limit: usize, input: *const c_void,
+                                                        capture: *mut c_void, dev_out: *mut FzbMatchIndices, capacity: usize, dev_positions: *mut u32, positions_capacity: usize,
+                                                        dev_counts: *mut u32, stream: *mut c_void) -> c_int;
     // the same four over a `from_patterns` matcher: the composition runs over `input`, `capture` receives the composition's match set
     #[allow(dead_code)]
     fn fzb_multi_match_list_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
