@@ -138,6 +138,7 @@ SYMBOLS = [
     "fzb_match_list_top_sections", "fzb_match_list_top_sections_device", "fzb_multi_match_list_top_sections", "fzb_multi_match_list_top_sections_device",
     "fzb_match_list_top_sections_indices", "fzb_match_list_top_sections_indices_device", "fzb_multi_match_list_top_sections_indices",
     "fzb_multi_match_list_top_sections_indices_device",
+    "fzb_multi_matcher_create_groups", "fzb_multi_matcher_set_pattern_groups", "fzb_parse_query_groups", "fzb_query_groups_free",
 ]
 
 
@@ -217,6 +218,11 @@ def lib():
         l.fzb_multi_matcher_set_config.argtypes = [C.c_void_p, C.POINTER(_CConfig)]
         l.fzb_multi_matcher_reserve.argtypes = [C.c_void_p, C.c_void_p]
         l.fzb_multi_matcher_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        l.fzb_multi_matcher_create_groups.argtypes = [C.POINTER(_CConfig), C.POINTER(_CPattern), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
+        l.fzb_multi_matcher_set_pattern_groups.argtypes = [C.c_void_p, C.POINTER(_CPattern), C.c_size_t, C.POINTER(C.c_uint32)]
+        l.fzb_parse_query_groups.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.POINTER(_CPattern)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t)]
+        l.fzb_query_groups_free.argtypes = [C.POINTER(_CPattern), C.POINTER(C.c_uint32), C.c_size_t]
+        l.fzb_query_groups_free.restype = None
         l.fzb_multi_match_list_parallel.argtypes = l.fzb_match_list_parallel.argtypes
         l.fzb_multi_match_list_parallel_sharded.argtypes = l.fzb_match_list_parallel_sharded.argtypes
         l.fzb_multi_match_list_parallel_rccl.argtypes = l.fzb_match_list_parallel_rccl.argtypes
@@ -838,6 +844,30 @@ def parse_query(query):
     return out
 
 
+def parse_query_groups(query):
+    """`parse_query` with the any-of operator -> (list[Pattern], group_of): an atom that is exactly `|` joins the atoms around it into one
+    group (`^src rs$ | py$ | go$ !test`); group_of[i] is the term id of pattern i, equal ids = the alternatives of one group.  Pass both to
+    `MultiMatcher(patterns, config, groups=group_of)`."""
+    q = _b(query)
+    arr, ids, n = C.POINTER(_CPattern)(), C.POINTER(C.c_uint32)(), C.c_size_t()
+    _check(lib().fzb_parse_query_groups(q, len(q), C.byref(arr), C.byref(ids), C.byref(n)))
+    out = [Pattern(C.string_at(arr[i].needle_utf8, arr[i].needle_len).decode("utf-8"), negated=bool(arr[i].negated),
+                   matching=None if arr[i].matching < 0 else Matching(arr[i].matching)) for i in range(n.value)]
+    group_of = [int(ids[i]) for i in range(n.value)]
+    lib().fzb_query_groups_free(arr, ids, n.value)
+    return out, group_of
+
+
+def _c_groups(groups, n):
+    """group_of (one term id per pattern) -> the C array, or None for no grouping"""
+    if groups is None:
+        return None
+    groups = [int(g) for g in groups]
+    if len(groups) != n:
+        raise ValueError("groups: one term id per pattern (%d ids for %d patterns)" % (len(groups), n))
+    return (C.c_uint32 * max(n, 1))(*groups)
+
+
 class _IterApi:
     """The per-item side of the reference's interface (`match_iter`, `match_one`, `match_iter_indices`, `match_one_indices`,
     src/matcher/mod.rs:277-371), served by ONE batched device pass in list order - there is no per-item CPU path."""
@@ -874,28 +904,39 @@ def fuzzy_match_indices(haystacks, needle, config=None):
 class MultiMatcher(_IterApi):
     """`Matcher::from_patterns(&patterns, &config)` (src/matcher/mod.rs:95-111; composition src/matcher/multi.rs:84-152)."""
 
-    def __init__(self, patterns, config=None):
+    def __init__(self, patterns, config=None, groups=None):
+        """groups: one term id per pattern (`parse_query_groups`' second result) - patterns with equal, adjacent ids are the alternatives of
+        one any-of group (matches when any of them does, scores their maximum); None: every pattern is a term of its own"""
         self.config = config or Config()
         pats = [p if isinstance(p, Pattern) else Pattern(p) for p in patterns]
         arr, self._keep = _c_patterns(pats)
         c = _c_config(self.config)
         self.h = C.c_void_p()
-        _check(lib().fzb_multi_matcher_create(C.byref(c), arr, len(pats), C.byref(self.h)))
+        if groups is None:
+            _check(lib().fzb_multi_matcher_create(C.byref(c), arr, len(pats), C.byref(self.h)))
+        else:
+            _check(lib().fzb_multi_matcher_create_groups(C.byref(c), arr, len(pats), _c_groups(groups, len(pats)), C.byref(self.h)))
         self.patterns = pats  # `Matcher::patterns` / `Matcher::config` (src/matcher/mod.rs:144-150) are these two attributes
+        self.groups = None if groups is None else [int(g) for g in groups]
 
     def __len__(self):
         return lib().fzb_multi_matcher_len(self.h)
 
-    def set_patterns(self, patterns):
+    def set_patterns(self, patterns, groups=None):
         """`Matcher::set_patterns` (src/matcher/mod.rs:170-176): skipped when the patterns are the same; otherwise the sub-matchers are
         rebuilt in place and their device buffers kept (a re-query per keystroke allocates nothing once `reserve` sized them).  `patterns`:
-        a list of `Pattern` / needles, or a query string, which is parsed with `parse_query` (`Matcher::from_query`'s syntax)."""
+        a list of `Pattern` / needles, or a query string, which is parsed with `parse_query` (`Matcher::from_query`'s syntax).
+        groups: as the constructor's; None makes every pattern a single term again."""
         if isinstance(patterns, (str, bytes)):
             patterns = parse_query(patterns)
         pats = [p if isinstance(p, Pattern) else Pattern(p) for p in patterns]
         arr, keep = _c_patterns(pats)
-        _check(lib().fzb_multi_matcher_set_patterns(self.h, arr, len(pats)))
+        if groups is None:
+            _check(lib().fzb_multi_matcher_set_patterns(self.h, arr, len(pats)))
+        else:
+            _check(lib().fzb_multi_matcher_set_pattern_groups(self.h, arr, len(pats), _c_groups(groups, len(pats))))
         self.patterns, self._keep = pats, keep
+        self.groups = None if groups is None else [int(g) for g in groups]
 
     def set_config(self, config):
         """`Matcher::set_config` (src/matcher/mod.rs:154-162); a change of `sort` alone rebuilds no sub-matcher"""
@@ -920,6 +961,7 @@ class MultiMatcher(_IterApi):
         out.h = C.c_void_p()
         _check(lib().fzb_multi_matcher_clone(self.h, C.byref(out.h)))
         out.config, out.patterns, out._keep = self.config, list(self.patterns), list(self._keep)
+        out.groups = None if getattr(self, "groups", None) is None else list(self.groups)
         return out
 
     def match_list_parallel(self, haystacks, threads):

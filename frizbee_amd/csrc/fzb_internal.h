@@ -319,6 +319,12 @@ void fzb_launch_items_records(fzb_match_rec* out, const u32* items, const u32* n
 void fzb_launch_copy_capture_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, u32 index_offset, u32* items, u32 items_cap,
                                      u32* items_count, u32* mirror, int grid, hipStream_t st);
 void fzb_launch_copy_records(const fzb_match_rec* in, const u32* n_ptr, fzb_match_rec* out, u32 capacity, u32* count_out, int grid, hipStream_t st);
+// any-of groups (anyof.h): the slots of a group cleared, one alternative's hits folded in, the hit positions kept as records (flag + compact)
+void fzb_launch_anyof_clear(u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, int grid_max, hipStream_t st);
+void fzb_launch_anyof_accumulate(const fzb_match_rec* hits, const u32* n_hits_ptr, u32 hits_cap, u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, u32 index_offset,
+                                 const u32* items, const fzb_match_rec* cand, int grid_max, hipStream_t st);
+void fzb_launch_anyof_keep(const u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, u32 index_offset, const u32* items, const fzb_match_rec* cand, u64* bitmap, u32* tile_counts,
+                           fzb_match_rec* out, u32* total_out, int grid_max, hipStream_t st);
 // kernels_subset.hip: the candidate sets' capture (index-ordered records -> ascending haystack indices + their count; mirror: a second word for the
 // count, may be null) and fzb_subset_from_scope's flag pass + k_compact1
 void fzb_launch_subset_capture(const fzb_match_rec* recs, const u32* n_ptr, u32 cap, u32 index_offset, u32* items, u32 items_cap, u32* count_out, u32* mirror, int grid_max, hipStream_t st);

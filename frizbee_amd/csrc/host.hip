@@ -1331,6 +1331,12 @@ int fzb_refuse_facets(const fzb_facets* f, const char* call) {
     if (!f) return FZB_OK;
     return fail(FZB_ERR_INVALID, std::string(call) + ": the matcher has a facet sink attached, which this call does not fill; detach it first: set_facets(NULL)");
 }
+// any-of groups (anyof.h): the forms that return matched positions, and the multi-device forms, do not compose them - the traced union
+// (indices_union.h) assumes every positive pattern matches every head record, and an alternative need not
+int fzb_refuse_groups(const fzb_multi_matcher* mm, const char* call) {
+    if (!mm || !mm->grouped) return FZB_OK;
+    return fail(FZB_ERR_INVALID, std::string(call) + ": the matcher has an any-of group, which this call does not compose; use the records forms (fzb_multi_match_list, _top, _top_sections)");
+}
 // a sink counts over the corpus it was created on
 static int facets_check(const fzb_facets* f, const fzb_corpus* c, const char* call) {
     if (!f || !c || f->corpus == c) return FZB_OK;
@@ -2697,16 +2703,16 @@ ParsedAtom parse_atom(const std::vector<u32>& atom) {
 }  // namespace
 extern "C" {
 
-int fzb_parse_query(const uint8_t* query_utf8, size_t query_len, fzb_pattern** out_patterns, size_t* out_n) {
-    if (!out_patterns || !out_n || (query_len && !query_utf8)) return fail(FZB_ERR_INVALID, "null argument");
+}  // extern "C"
+namespace {
+// the atoms of a query, unparsed: split at unescaped whitespace, `\x` keeps x in its atom
+bool split_atoms(const uint8_t* query_utf8, size_t query_len, std::vector<std::vector<u32>>& raw) {
     std::vector<u32> cps;
-    if (!decode_utf8(query_utf8, query_len, cps)) return fail(FZB_ERR_INVALID, "query is not valid UTF-8");
-    std::vector<ParsedAtom> atoms;
+    if (!decode_utf8(query_utf8, query_len, cps)) return false;
     std::vector<u32> cur;
     bool in_atom = false, escaped = false;
     auto flush = [&]() {
-        ParsedAtom a = parse_atom(cur);
-        if (!a.needle.empty()) atoms.push_back(a);  // atoms with an empty needle (`!`, `^$`) are dropped
+        raw.push_back(cur);
         cur.clear();
         in_atom = false;
     };
@@ -2717,6 +2723,9 @@ int fzb_parse_query(const uint8_t* query_utf8, size_t query_len, fzb_pattern** o
         else { in_atom = true; cur.push_back(c); }
     }
     if (in_atom) flush();
+    return true;
+}
+int patterns_from_atoms(const std::vector<ParsedAtom>& atoms, fzb_pattern** out_patterns) {
     fzb_pattern* arr = (fzb_pattern*)calloc(std::max<size_t>(atoms.size(), 1), sizeof(fzb_pattern));
     if (!arr) return fail(FZB_ERR_INVALID, "out of memory");
     for (size_t i = 0; i < atoms.size(); i++) {
@@ -2736,8 +2745,61 @@ int fzb_parse_query(const uint8_t* query_utf8, size_t query_len, fzb_pattern** o
         arr[i].matching = atoms[i].matching;
     }
     *out_patterns = arr;
+    return FZB_OK;
+}
+}  // namespace
+extern "C" {
+
+int fzb_parse_query(const uint8_t* query_utf8, size_t query_len, fzb_pattern** out_patterns, size_t* out_n) {
+    if (!out_patterns || !out_n || (query_len && !query_utf8)) return fail(FZB_ERR_INVALID, "null argument");
+    std::vector<std::vector<u32>> raw;
+    if (!split_atoms(query_utf8, query_len, raw)) return fail(FZB_ERR_INVALID, "query is not valid UTF-8");
+    std::vector<ParsedAtom> atoms;
+    for (const auto& r : raw) {
+        ParsedAtom a = parse_atom(r);
+        if (!a.needle.empty()) atoms.push_back(a);  // atoms with an empty needle (`!`, `^$`) are dropped
+    }
+    if (int rc_ = patterns_from_atoms(atoms, out_patterns)) return rc_;
     *out_n = atoms.size();
     return FZB_OK;
+}
+
+// fzb_parse_query with the any-of operator: an atom that is exactly `|` joins the atom before it and the atom after it into one group
+// when both exist, neither is negated and neither is itself `|`; anywhere else it is the needle `|` it always was.  `\|` is the needle `|`.
+int fzb_parse_query_groups(const uint8_t* query_utf8, size_t query_len, fzb_pattern** out_patterns, uint32_t** out_group_of, size_t* out_n) {
+    if (!out_patterns || !out_group_of || !out_n || (query_len && !query_utf8)) return fail(FZB_ERR_INVALID, "null argument");
+    std::vector<std::vector<u32>> raw;
+    if (!split_atoms(query_utf8, query_len, raw)) return fail(FZB_ERR_INVALID, "query is not valid UTF-8");
+    struct Atom { ParsedAtom a; bool bar; };
+    std::vector<Atom> all;
+    for (const auto& r : raw) {
+        Atom t{parse_atom(r), r.size() == 1 && r[0] == '|'};
+        if (r.size() == 2 && r[0] == '\\' && r[1] == '|') t.a.needle = "|";
+        if (!t.a.needle.empty()) all.push_back(t);
+    }
+    std::vector<ParsedAtom> atoms;
+    std::vector<uint32_t> group_of;
+    uint32_t next_id = 0;
+    bool join_next = false;
+    for (size_t i = 0; i < all.size(); i++) {
+        const bool joins = all[i].bar && i > 0 && i + 1 < all.size() && !all[i - 1].bar && !all[i + 1].bar && !all[i - 1].a.negated && !all[i + 1].a.negated;
+        if (joins) { join_next = true; continue; }
+        group_of.push_back(join_next ? group_of.back() : next_id++);
+        atoms.push_back(all[i].a);
+        join_next = false;
+    }
+    uint32_t* ids = (uint32_t*)malloc(std::max<size_t>(group_of.size(), 1) * sizeof(uint32_t));
+    if (!ids) return fail(FZB_ERR_INVALID, "out of memory");
+    if (int rc_ = patterns_from_atoms(atoms, out_patterns)) { free(ids); return rc_; }
+    if (!group_of.empty()) memcpy(ids, group_of.data(), group_of.size() * sizeof(uint32_t));
+    *out_group_of = ids;
+    *out_n = atoms.size();
+    return FZB_OK;
+}
+
+void fzb_query_groups_free(fzb_pattern* patterns, uint32_t* group_of, size_t n) {
+    fzb_patterns_free(patterns, n);
+    free(group_of);
 }
 
 void fzb_patterns_free(fzb_pattern* patterns, size_t n) {
@@ -2759,6 +2821,13 @@ static void multi_free_buffers(fzb_multi_matcher* mm) {
     mm->tile_counts = nullptr;
     mm->cap = 0;
 }
+static void multi_free_group_buffers(fzb_multi_matcher* mm) {
+    if (mm->group_slots) (void)hipFree(mm->group_slots);
+    if (mm->group_hits) (void)hipFree(mm->group_hits);
+    mm->group_slots = nullptr;
+    mm->group_hits = nullptr;
+    mm->group_cap = 0;
+}
 static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and pinned word the composition itself owns
     multi_free_buffers(mm);
     for (void* p : {(void*)mm->top_head, (void*)mm->top_comb, (void*)mm->top_items, (void*)mm->top_npos_u, (void*)mm->top_tiles, (void*)mm->top_words, (void*)mm->top_pos_u,
@@ -2774,6 +2843,7 @@ static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and p
     fzb_out_release(*mm);
     fzb_scope_release(mm->scope);
     fzb_sections_release(mm->sections);
+    multi_free_group_buffers(mm);
 }
 
 // the composition's buffers for ranges of up to `count` haystacks
@@ -2788,6 +2858,16 @@ static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
     HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
     HIPCHK(dev_alloc((void**)&mm->tile_counts, (((cap + FZB_TILE - 1) / FZB_TILE + 5) & ~(size_t)3) * 4));  // (as the workspace's: a multiple of four entries)
     mm->cap = cap;
+    return FZB_OK;
+}
+
+// the buffers of the any-of steps, beside the composition's own and of their size: only a matcher that has a group allocates them
+static int multi_ensure_group_buffers(fzb_multi_matcher* mm) {
+    if (mm->group_cap >= mm->cap) return FZB_OK;
+    multi_free_group_buffers(mm);
+    HIPCHK(dev_alloc((void**)&mm->group_slots, (mm->cap + 16) * sizeof(u32)));  // (k_anyof_clear stores whole 16-byte words)
+    HIPCHK(dev_alloc((void**)&mm->group_hits, (mm->cap + 16) * sizeof(fzb_match_rec)));
+    mm->group_cap = mm->cap;
     return FZB_OK;
 }
 
@@ -2871,11 +2951,43 @@ static std::vector<fzb_pattern> raw_patterns(const fzb_multi_matcher* mm) {  // 
     return v;
 }
 
+// group_of -> terms numbered 0, 1, .. in order of appearance (nullptr: every pattern its own term); equal ids must be adjacent
+static int normalise_terms(const uint32_t* group_of, size_t n, std::vector<u32>& out) {
+    out.resize(n);
+    std::vector<uint32_t> seen;
+    for (size_t i = 0; i < n; i++) {
+        if (!group_of) { out[i] = (u32)i; continue; }
+        if (i && group_of[i] == group_of[i - 1]) { out[i] = out[i - 1]; continue; }
+        if (std::find(seen.begin(), seen.end(), group_of[i]) != seen.end())
+            return fail(FZB_ERR_INVALID, "group_of: term id " + std::to_string(group_of[i]) + " appears again at pattern " + std::to_string(i) + " (equal ids must be adjacent)");
+        seen.push_back(group_of[i]);
+        out[i] = (u32)seen.size() - 1;
+    }
+    return FZB_OK;
+}
+
 // set_patterns / set_config / create: compile, and on success record what was compiled; on an error the previous patterns are compiled
 // again (they were accepted before, so that cannot fail) and the matcher answers as it did
-static int multi_compile(fzb_multi_matcher* mm, const fzb_config& config, const fzb_pattern* patterns, size_t n_patterns) {
+// (raw_terms: the term of every pattern as normalise_terms numbers them - checked here, before anything is compiled)
+static int multi_compile(fzb_multi_matcher* mm, const fzb_config& config, const fzb_pattern* patterns, size_t n_patterns, const std::vector<u32>& raw_terms) {
     for (size_t i = 0; i < n_patterns; i++)
         if (patterns[i].needle_len && !patterns[i].needle_utf8) return fail(FZB_ERR_INVALID, "null needle");
+    std::vector<u32> terms;  // per compiled pattern: alternatives with an empty needle are dropped like any empty pattern
+    for (size_t i = 0; i < n_patterns; i++)
+        if (patterns[i].needle_len) terms.push_back(raw_terms[i]);
+    bool grouped = false;
+    for (size_t i = 0, k = 0; i < n_patterns; i++) {
+        if (!patterns[i].needle_len) continue;
+        size_t b = k, e = k;
+        while (b > 0 && terms[b - 1] == terms[k]) b--;
+        while (e < terms.size() && terms[e] == terms[k]) e++;
+        if (e - b >= 2) {
+            grouped = true;
+            if (patterns[i].negated) return fail(FZB_ERR_INVALID, "any-of group: a negated alternative (pattern " + std::to_string(i) + ") is not defined");
+            if (e - b > FZB_GROUP_ALTS_MAX) return fail(FZB_ERR_INVALID, "any-of group: " + std::to_string(e - b) + " alternatives, at most FZB_GROUP_ALTS_MAX = 8");
+        }
+        k++;
+    }
     int rc = compile_into_slots(mm, config, patterns, n_patterns);
     if (rc) {
         const std::string msg = fzb_last_error();
@@ -2883,6 +2995,9 @@ static int multi_compile(fzb_multi_matcher* mm, const fzb_config& config, const 
         (void)compile_into_slots(mm, mm->config, old.data(), old.size());
         return fail(rc, msg);
     }
+    mm->raw_terms = raw_terms;
+    mm->terms.swap(terms);
+    mm->grouped = grouped;
     std::vector<fzb_multi_matcher::Raw> raw;
     for (size_t i = 0; i < n_patterns; i++) {
         fzb_multi_matcher::Raw r{patterns[i].needle_len ? std::string((const char*)patterns[i].needle_utf8, patterns[i].needle_len) : std::string(), patterns[i]};
@@ -2900,7 +3015,7 @@ static void multi_follow(fzb_multi_matcher* mm) {
     if (mm->shard_clones.empty()) return;
     const std::vector<fzb_pattern> pats = raw_patterns(mm);
     bool ok = true;
-    for (fzb_multi_matcher* cm : mm->shard_clones) ok = ok && multi_compile(cm, mm->config, pats.data(), pats.size()) == FZB_OK;
+    for (fzb_multi_matcher* cm : mm->shard_clones) ok = ok && multi_compile(cm, mm->config, pats.data(), pats.size(), mm->raw_terms) == FZB_OK;
     if (!ok) {  // cannot happen for patterns the parent accepted; drop the clones rather than keep stale ones (they are made again on the next query)
         int cur = 0;
         const bool have_cur = hipGetDevice(&cur) == hipSuccess;
@@ -2927,10 +3042,16 @@ int fzb_multi_order_host(fzb_multi_matcher* mm, fzb_matcher** out) {
 extern "C" {
 
 int fzb_multi_matcher_create(const fzb_config* config, const fzb_pattern* patterns, size_t n_patterns, fzb_multi_matcher** out) {
+    return fzb_multi_matcher_create_groups(config, patterns, n_patterns, nullptr, out);
+}
+
+int fzb_multi_matcher_create_groups(const fzb_config* config, const fzb_pattern* patterns, size_t n_patterns, const uint32_t* group_of, fzb_multi_matcher** out) {
     if (!config || !out || (n_patterns && !patterns)) return fail(FZB_ERR_INVALID, "null argument");
+    std::vector<u32> terms;
+    if (int rc_ = normalise_terms(group_of, n_patterns, terms)) return rc_;
     auto mm = new fzb_multi_matcher();
     mm->config = *config;
-    int rc = multi_compile(mm, *config, patterns, n_patterns);
+    int rc = multi_compile(mm, *config, patterns, n_patterns, terms);
     if (rc) {
         const std::string msg = fzb_last_error();
         fzb_multi_matcher_free(mm);
@@ -2941,14 +3062,20 @@ int fzb_multi_matcher_create(const fzb_config* config, const fzb_pattern* patter
 }
 
 int fzb_multi_matcher_set_patterns(fzb_multi_matcher* mm, const fzb_pattern* patterns, size_t n_patterns) {
+    return fzb_multi_matcher_set_pattern_groups(mm, patterns, n_patterns, nullptr);  // (on a grouped matcher: every pattern a single term again)
+}
+
+int fzb_multi_matcher_set_pattern_groups(fzb_multi_matcher* mm, const fzb_pattern* patterns, size_t n_patterns, const uint32_t* group_of) {
     if (!mm || (n_patterns && !patterns)) return fail(FZB_ERR_INVALID, "null argument");
     for (size_t i = 0; i < n_patterns; i++)
         if (patterns[i].needle_len && !patterns[i].needle_utf8) return fail(FZB_ERR_INVALID, "null needle");
-    bool same = n_patterns == mm->raw.size();
+    std::vector<u32> terms;
+    if (int rc_ = normalise_terms(group_of, n_patterns, terms)) return rc_;
+    bool same = n_patterns == mm->raw.size() && terms == mm->raw_terms;
     for (size_t i = 0; same && i < n_patterns; i++) same = same_pattern(mm->raw[i], patterns[i]);
-    if (same) return FZB_OK;  // "Skipped if the patterns are the same" (src/matcher/mod.rs:170-176)
+    if (same) return FZB_OK;  // "Skipped if the patterns are the same" (src/matcher/mod.rs:170-176) - and the grouping
     const fzb_config cfg = mm->config;
-    int rc = multi_compile(mm, cfg, patterns, n_patterns);
+    int rc = multi_compile(mm, cfg, patterns, n_patterns, terms);
     if (rc) return rc;
     multi_follow(mm);
     return FZB_OK;
@@ -2959,7 +3086,8 @@ int fzb_multi_matcher_set_config(fzb_multi_matcher* mm, const fzb_config* config
     if (same_config(mm->config, *config)) return FZB_OK;
     // every pattern is resolved again; a change of `sort` alone leaves every slot as it is (sub-matchers run IndexAsc)
     const std::vector<fzb_pattern> pats = raw_patterns(mm);
-    int rc = multi_compile(mm, *config, pats.data(), pats.size());
+    const std::vector<u32> terms = mm->raw_terms;
+    int rc = multi_compile(mm, *config, pats.data(), pats.size(), terms);
     if (rc) return rc;
     multi_follow(mm);
     return FZB_OK;
@@ -2970,6 +3098,9 @@ int fzb_multi_matcher_clone(const fzb_multi_matcher* src, fzb_multi_matcher** ou
     auto mm = new fzb_multi_matcher();
     mm->config = src->config;
     mm->raw = src->raw;
+    mm->raw_terms = src->raw_terms;
+    mm->terms = src->terms;
+    mm->grouped = src->grouped;
     for (const auto& c : src->patterns) {
         fzb_matcher* m = nullptr;
         int rc = fzb_matcher_clone(c.m, &m);  // keeps the resolved lane pair
@@ -2993,6 +3124,7 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     for (fzb_matcher* m : mm->spare)
         if ((rc = reserve_slot_any_needle(m, c))) return rc;
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
+    if (mm->grouped && (rc = multi_ensure_group_buffers(mm))) return rc;
     if ((c->tags.data || mm->facets) && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags, or a facet sink: the composition's records ahead of the drop / the count)
     if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
     if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
@@ -3035,6 +3167,86 @@ int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, si
 }
 
 }  // extern "C"
+// The composition of a matcher that has an any-of group (anyof.h): an AND of TERMS, where a term is a single pattern - composed exactly as
+// multi_compose_device composes it - or a group of k alternatives, which behaves as ONE non-negated pattern whose hits are the union of the
+// alternatives' hits under the max rule.  Per group: one clear of the slots, then per alternative its pipeline (into group_hits) and one
+// accumulate, then one flag and one compact that write the group's records - k pipelines + k + 3 launches, every count on the device.
+//   base group  (the first non-negated term): the alternatives run over the whole range through the streaming filter (items == nullptr), or
+//               over the candidate set; a slot per haystack of the range / per item of the set; records (index_offset + haystack, score_G, exact_G)
+//   later group: the alternatives run over the surviving candidates' items; a slot per candidate; records = candidate joined with the key
+static int multi_compose_groups(fzb_multi_matcher* mm, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, u32 cap32, uint32_t* dev_count,
+                                hipStream_t st, const SubsetArgs* sa, bool* captured) {
+    int rc;
+    if ((rc = multi_ensure_buffers(mm, count)) || (rc = multi_ensure_group_buffers(mm))) return rc;
+    const int cus = mm->num_cus;
+    auto& ps = mm->patterns;
+    struct Term { size_t b, e; };  // compiled patterns [b, e)
+    std::vector<Term> terms;
+    for (size_t i = 0; i < ps.size();) {
+        size_t e = i + 1;
+        while (e < ps.size() && mm->terms[e] == mm->terms[i]) e++;
+        terms.push_back({i, e});
+        i = e;
+    }
+    size_t base = terms.size();
+    for (size_t t = 0; t < terms.size(); t++)
+        if (!ps[terms[t].b].negated) { base = t; break; }  // (a group has no negated alternative; a grouped matcher has a non-negated term)
+    const u32 n_max = (u32)count;
+    u32* const hit_count = &mm->counts[4 * 3];
+    int cur = 0;
+    // the group `t` over the candidates cand[cur] (cand_in == nullptr: as the base term) -> cand[dst]
+    auto run_group = [&](const Term& t, const fzb_match_rec* cand_in, const u32* n_ptr, const u32* slot_items, u32 n_bound, int dst) -> int {
+        fzb_launch_anyof_clear(mm->group_slots, n_ptr, n_max, n_bound, cus * 4, st);
+        for (size_t pi = t.b; pi < t.e; pi++) {
+            int rc_ = cand_in ? run_pipeline(ps[pi].m, c, first, count, index_offset, mm->items, n_ptr, (fzb_match*)mm->group_hits, mm->group_cap, hit_count, st)
+                              : run_pipeline(ps[pi].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->group_hits, mm->group_cap, hit_count, st, nullptr,
+                                             subset_hint(sa));
+            if (rc_) return rc_;
+            fzb_launch_anyof_accumulate(mm->group_hits, hit_count, (u32)std::min<size_t>(mm->group_cap, 0xFFFFFFFFu), mm->group_slots, n_ptr, n_max, n_bound, index_offset, slot_items, cand_in,
+                                        cus * 4, st);
+        }
+        fzb_launch_anyof_keep(mm->group_slots, n_ptr, n_max, n_bound, index_offset, slot_items, cand_in, mm->bitmap, mm->tile_counts, mm->cand[dst], &mm->counts[4 * dst], cus * 2, st);
+        return FZB_OK;
+    };
+    const Term& bt = terms[base];
+    if (bt.e - bt.b >= 2) {
+        const u32 n_bound = subset_items(sa) ? (u32)std::min<u64>(subset_hint(sa), count) : n_max;
+        if ((rc = run_group(bt, nullptr, subset_count(sa), subset_items(sa), n_bound, 0))) return rc;
+    } else if ((rc = run_pipeline(ps[bt.b].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], st, nullptr,
+                                  subset_hint(sa)))) {
+        return rc;
+    }
+    for (size_t ti = 0; ti < terms.size(); ti++) {
+        if (ti == base) continue;
+        const Term& t = terms[ti];
+        fzb_launch_records_to_items(mm->cand[cur], &mm->counts[4 * cur], index_offset, mm->items, cus * 2, st);
+        const int oth = cur ^ 1;
+        if (t.e - t.b >= 2) {
+            if ((rc = run_group(t, mm->cand[cur], &mm->counts[4 * cur], nullptr, n_max, oth))) return rc;
+        } else if (!ps[t.b].negated) {
+            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)mm->cand[oth], mm->cap, &mm->counts[4 * oth], st))) return rc;
+            fzb_launch_join_add(mm->cand[oth], &mm->counts[4 * oth], mm->cand[cur], &mm->counts[4 * cur], cus * 2, st);
+        } else {
+            fzb_match_rec* hits = mm->cand[oth];  // (as multi_compose_device: read by the flag pass, then overwritten by the compaction)
+            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)hits, mm->cap, &mm->counts[4 * 2], st))) return rc;
+            fzb_launch_remove_hits(mm->cand[cur], &mm->counts[4 * cur], hits, &mm->counts[4 * 2], mm->bitmap, mm->tile_counts, mm->cand[oth], &mm->counts[4 * oth], cus * 2, st);
+        }
+        cur = oth;
+    }
+    if (sa && sa->capture && captured && g_debug_fused_capture) {
+        fzb_subset* cp = sa->capture;
+        fzb_launch_copy_capture_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
+                                        cp->count_dev, sa->mirror, cus * 2, st);
+        HIPCHK(hipGetLastError());
+        subset_captured(cp, c);
+        *captured = true;
+        return FZB_OK;
+    }
+    fzb_launch_copy_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
+    HIPCHK(hipGetLastError());
+    return FZB_OK;
+}
+
 // the composition alone: the patterns' scores summed, no score bias
 // (sa->in: the candidate set the FIRST step runs over - the base pattern's pipeline, the Single shortcut's, or the identity records of the
 // no-pattern and all-negated cases -; every later pattern runs over the candidates' items either way.  sa->capture: the Multi case's final copy
@@ -3054,6 +3266,7 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
         return FZB_OK;
     }
+    if (mm->grouped) return multi_compose_groups(mm, c, first, count, index_offset, dev_out, cap32, dev_count, st, sa, captured);
     // CompiledPatterns::{Empty, Single, Multi} (src/matcher/mod.rs:178-190; a single NEGATED pattern is Multi)
     if (ps.empty()) {
         // (over a candidate set: its count when the host knows it, else the room it was captured into - never more than the list)
@@ -3244,6 +3457,7 @@ static int multi_match_list_indices_impl(fzb_multi_matcher* mm, const fzb_corpus
 
 int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, fzb_match_indices** out, size_t* out_len,
                                  uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_indices")) return rc_;
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_indices")) return rc_;
@@ -3252,6 +3466,7 @@ int fzb_multi_match_list_indices(fzb_multi_matcher* mm, const fzb_corpus* c, con
 
 int fzb_multi_match_list_indices_into(fzb_multi_matcher* mm, const fzb_corpus* c, const uint32_t* selection, size_t n_selection, uint32_t index_offset,
                                       fzb_match_indices** out, size_t* out_len, uint32_t** out_positions) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_indices_into")) return rc_;
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_indices_into", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_indices_into")) return rc_;
@@ -4086,6 +4301,7 @@ int fzb_prompt_top_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
 // from the position in the selection to the corpus index.
 int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices")) return rc_;
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_top_indices")) return rc_;
@@ -4218,6 +4434,7 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
                                          size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa);
 int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
                                             size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_device")) return rc_;
     return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
 }
 // (sa: only the top stage sees the candidate set and captures; the traced passes run over the head's item list as before)
@@ -4255,6 +4472,7 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
 static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
                                         const SubsetArgs* sa);
 int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_fused")) return rc_;
     return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr);
 }
 // (sa: `in` and `capture` as the caller gave them; the mirror word is set here.  A no-pattern matcher never gets here with a subset.)
@@ -4646,6 +4864,7 @@ static int multi_sections_indices_device_impl(fzb_multi_matcher* mm, const fzb_c
     if (!dev_counts || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
     int rc;
     if ((rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_indices_device", &ss))) return rc;
+    if ((rc = fzb_refuse_groups(mm, "fzb_multi_match_list_top_sections_indices_device"))) return rc;
     if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_sections_indices");
     const size_t n = c->dev.n;
     size_t P = 0, want;
@@ -4682,6 +4901,7 @@ int fzb_multi_match_list_top_sections_indices(fzb_multi_matcher* mm, const fzb_c
     *out_positions = nullptr;
     int rc;
     if ((rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_indices", &ss))) return rc;
+    if ((rc = fzb_refuse_groups(mm, "fzb_multi_match_list_top_sections_indices"))) return rc;
     const size_t n = c->dev.n;
     if (mm->patterns.empty() || n == 0 || n_sections == 0) {
         fzb_match* head = nullptr;
@@ -4710,6 +4930,7 @@ int fzb_multi_match_list_top_sections_indices(fzb_multi_matcher* mm, const fzb_c
 int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
                                             uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_subset")) return rc_;
     *out = nullptr;
     *out_len = 0;
     *out_positions = nullptr;

@@ -321,12 +321,20 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     // the patterns as the caller gave them (set_patterns: "skipped if the patterns are the same"); pattern.needle_utf8 is not kept
     struct Raw { std::string needle; fzb_pattern pattern; };
     std::vector<Raw> raw;
+    // any-of groups (anyof.h): the term of every raw pattern, numbered 0, 1, .. in order (equal = alternatives of one group; without a
+    // grouping every pattern is its own term), the same per COMPILED pattern, and whether some term has two or more compiled alternatives -
+    // only then does the composition take the group steps and allocate `group_slots` / `group_hits` (for ranges of up to group_cap haystacks)
+    std::vector<u32> raw_terms, terms;
+    bool grouped = false;
+    u32* group_slots = nullptr;           // one key per candidate position
+    fzb_match_rec* group_hits = nullptr;  // an alternative's hits (the ping-pong lists hold the candidates and the group's result)
+    size_t group_cap = 0;
     int num_cus = 0;
     // device buffers, grown on demand: two candidate lists (ping-pong), their lengths, the item list handed to the next pattern,
     // and the bitmap / per-tile counts of the negation's compaction
     size_t cap = 0;
     fzb_match_rec* cand[2] = {nullptr, nullptr};
-    u32* counts = nullptr;  // [0],[4] = lengths of cand[0], cand[1]; [8] = hits of a negated pattern (each slot: count, untruncated total)
+    u32* counts = nullptr;  // [0],[4] = lengths of cand[0], cand[1]; [8] = hits of a negated pattern, [12] = hits of a group's alternative (each slot: count, untruncated total)
     u32* items = nullptr;
     u64* bitmap = nullptr;
     u32* tile_counts = nullptr;
@@ -422,5 +430,7 @@ int fzb_refuse_biased(const fzb_corpus* c, const char* call, const char* instead
 int fzb_refuse_scoped(const fzb_corpus* c, const char* call, const char* instead);
 // the same rule for an attached facet sink (facets.h): an entry point fills it or refuses the matcher that carries one (FZB_OK without one)
 int fzb_refuse_facets(const fzb_facets* f, const char* call);
+// the same rule for any-of groups: an entry point composes them or refuses a matcher that has a term of two or more alternatives
+int fzb_refuse_groups(const fzb_multi_matcher* mm, const char* call);
 int fzb_sorted_range_device(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match* dev_out, size_t capacity, uint32_t* dev_count,
                             void* stream);

@@ -326,6 +326,8 @@ int fzb_match_list_parallel_rccl(fzb_matcher* m, const fzb_corpus* shard, uint32
 // the same exchange with this rank's AND / NOT composition (fzb_multi_match_list_device) as its run
 int fzb_multi_match_list_parallel_rccl(fzb_multi_matcher* mm, const fzb_corpus* shard, uint32_t index_offset, fzb_shard_comm* c, int flags, fzb_match** out, size_t* out_len) {
     RcclApi* api;
+    if (mm && shard && c && out && out_len)  // (ahead of the library's load; rccl_begin names a null argument)
+        if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_parallel_rccl")) return rc_;
     int rc = rccl_begin(mm, shard, c, flags, out, out_len, &api);
     if (rc) return rc;
     fzb_matcher* order = nullptr;

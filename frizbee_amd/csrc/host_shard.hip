@@ -692,6 +692,7 @@ int fzb_multi_match_list_parallel_sharded(fzb_multi_matcher* mm, const fzb_shard
     *out = nullptr;
     *out_len = 0;
     if (int rc_ = fzb_refuse_facets(mm->facets, "fzb_multi_match_list_parallel_sharded")) return rc_;
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_parallel_sharded")) return rc_;
     if (mm->patterns.empty()) return fzb_empty_pattern_list(sc->n, 0, mm->config.sort, out, out_len);
     fzb_matcher* root = nullptr;
     int rc = fzb_multi_order_host(mm, &root);
@@ -720,6 +721,7 @@ int fzb_multi_match_list_top_sharded(fzb_multi_matcher* mm, const fzb_sharded_co
     *out = nullptr;
     *out_len = 0;
     if (int rc_ = fzb_refuse_facets(mm->facets, "fzb_multi_match_list_top_sharded")) return rc_;
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_sharded")) return rc_;
     if (mm->patterns.empty()) return fzb_empty_pattern_top(sc->n, mm->config.sort, limit, out, out_len, out_found);
     fzb_matcher* root = nullptr;
     int rc = fzb_multi_order_host(mm, &root);

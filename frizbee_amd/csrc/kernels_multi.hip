@@ -8,6 +8,8 @@
 // `index` instead of the reference's position bookkeeping; list lengths stay in device memory throughout.
 #include "kernels_common.h"
 
+#include "anyof.h"
+
 // candidates -> local haystack indices for the next pattern's pipeline
 __global__ __launch_bounds__(256) void k_records_to_items(const fzb_match_rec* __restrict__ cand, const u32* __restrict__ n_ptr, u32 index_offset,
                                                           u32* __restrict__ items) {
@@ -118,6 +120,83 @@ __global__ __launch_bounds__(256) void k_copy_capture_records(const fzb_match_re
         *items_count = kept;
         if (mirror) *mirror = kept;
     }
+}
+
+// ---- any-of groups (anyof.h): one u32 slot per candidate position holds the maximum key of the alternatives that hit it -----------------
+// The positions of a group: a LATER group's are those of the candidates (cand != nullptr: found by find_index on the index-ascending list);
+// the BASE group's are the local haystack positions of the range (items == nullptr) or the places in the candidate set's item list.
+// n = min(*n_ptr, n_max) where the count lives on the device (n_ptr != nullptr), else n_max: never more slots than were allocated.
+__device__ __forceinline__ u32 anyof_slots(const u32* __restrict__ n_ptr, u32 n_max) { return n_ptr ? min(*n_ptr, n_max) : n_max; }
+
+// clear: 16-byte stores over the slots of the group (the array is padded to a multiple of four words)
+__global__ __launch_bounds__(256) void k_anyof_clear(u32* __restrict__ slots, const u32* __restrict__ n_ptr, u32 n_max) {
+    const u32 n4 = (anyof_slots(n_ptr, n_max) + 3u) / 4u;
+    uint4* s4 = (uint4*)slots;
+    for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < n4; j += gridDim.x * blockDim.x) s4[j] = make_uint4(0, 0, 0, 0);
+}
+
+// accumulate: one alternative's hits folded into the slots.  A plain read-max-write: the alternatives are serialised by the stream and one
+// alternative hits a position at most once.  A hit whose position is not found (cannot happen: the hits are a subset of the positions)
+// is dropped, never written out of bounds.
+__global__ __launch_bounds__(256) void k_anyof_accumulate(const fzb_match_rec* __restrict__ hits, const u32* __restrict__ n_hits_ptr, u32 hits_cap, u32* __restrict__ slots,
+                                                          const u32* __restrict__ n_ptr, u32 n_max, u32 index_offset, const u32* __restrict__ items,
+                                                          const fzb_match_rec* __restrict__ cand) {
+    const u32 nh = min(*n_hits_ptr, hits_cap), n = anyof_slots(n_ptr, n_max);
+    for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < nh; j += gridDim.x * blockDim.x) {
+        const fzb_match_rec h = hits[j];
+        const u32 p = cand ? find_index(cand, n, h.index) : items ? anyof_find(items, n, h.index - index_offset) : h.index - index_offset;
+        if (p < n) anyof_fold(&slots[p], h.score, h.exact);
+    }
+}
+
+// flag: bit j = some alternative hit position j; the flag pass of tile_compact.h
+__global__ __launch_bounds__(256) void k_anyof_flag(const u32* __restrict__ slots, const u32* __restrict__ n_ptr, u32 n_max, u64* __restrict__ bitmap,
+                                                    u32* __restrict__ tile_counts) {
+    const u32 n = anyof_slots(n_ptr, n_max);
+    tc_flag_pass(n, bitmap, tile_counts, [&](u32 tile, u32 slot) {
+        const u32 j = tile * FZB_TILE + slot;
+        return j < n && anyof_hit(slots[j]);
+    });
+}
+
+// compact: the hit positions, in order, as the group's records - a later group's are the candidates joined with the group's key, the base
+// group's are (index_offset + haystack, score_G, exact_G)
+__global__ __launch_bounds__(256) void k_anyof_compact(const u64* __restrict__ bitmap, const u32* __restrict__ counts, const u32* __restrict__ n_ptr, u32 n_max,
+                                                       const u32* __restrict__ slots, u32 index_offset, const u32* __restrict__ items, const fzb_match_rec* __restrict__ cand,
+                                                       fzb_match_rec* __restrict__ out, u32* __restrict__ total_out) {
+    const u32 kept = tc_compact_items(bitmap, counts, anyof_slots(n_ptr, n_max), [&](u32 place, u64 j) {
+        const u32 key = slots[j];
+        fzb_match_rec r;
+        u32 score, exact;
+        if (cand) {
+            r = cand[j];
+            anyof_join(r.score, r.exact, key, &score, &exact);
+        } else {
+            r.index = index_offset + (items ? items[j] : (u32)j);
+            r.valid = 0;
+            score = anyof_score(key);
+            exact = anyof_exact(key);
+        }
+        r.score = (u16)score;
+        r.exact = (u8)exact;
+        out[place] = r;
+    });
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { total_out[0] = kept; total_out[1] = kept; }
+}
+
+// n_bound: what the host knows of the number of positions (the grids' bound, not the loops')
+void fzb_launch_anyof_clear(u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, int grid_max, hipStream_t st) {
+    FZB_LAUNCH(k_anyof_clear, dim3(tc_grid(((u64)n_bound / 4u + 256u) / 256u, grid_max)), dim3(256), 0, st, slots, n_ptr, n_max);
+}
+void fzb_launch_anyof_accumulate(const fzb_match_rec* hits, const u32* n_hits_ptr, u32 hits_cap, u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, u32 index_offset,
+                                 const u32* items, const fzb_match_rec* cand, int grid_max, hipStream_t st) {
+    FZB_LAUNCH(k_anyof_accumulate, dim3(tc_grid(((u64)n_bound + 255u) / 256u, grid_max)), dim3(256), 0, st, hits, n_hits_ptr, hits_cap, slots, n_ptr, n_max, index_offset, items, cand);
+}
+void fzb_launch_anyof_keep(const u32* slots, const u32* n_ptr, u32 n_max, u32 n_bound, u32 index_offset, const u32* items, const fzb_match_rec* cand, u64* bitmap, u32* tile_counts,
+                           fzb_match_rec* out, u32* total_out, int grid_max, hipStream_t st) {
+    const int grid = tc_grid(((u64)n_bound + FZB_TILE - 1) / FZB_TILE, grid_max);
+    FZB_LAUNCH(k_anyof_flag, dim3(grid), dim3(256), 0, st, slots, n_ptr, n_max, bitmap, tile_counts);
+    FZB_LAUNCH(k_anyof_compact, dim3(grid), dim3(256), 0, st, bitmap, tile_counts, n_ptr, n_max, slots, index_offset, items, cand, out, total_out);
 }
 
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st) {

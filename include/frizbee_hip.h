@@ -729,6 +729,44 @@ int fzb_multi_matcher_clone(const fzb_multi_matcher* mm, fzb_multi_matcher** out
 /* `Matcher::match_list_parallel(&haystacks, threads)` (src/matcher/parallel.rs:18-89) of a `from_patterns` matcher: as
  * fzb_match_list_parallel - 0 => FZB_ERR_PANIC "threads must be positive", otherwise fzb_multi_match_list's result. */
 int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, size_t threads, fzb_match** out, size_t* out_len);
+
+/* ---- ANY-OF GROUPS: `a | b` composed on the device ------------------------------------------------------------------------------
+ * The reference has no such operator.  A query is an AND of TERMS; a term is a single pattern, possibly negated, exactly as above, or an
+ * ANY-OF GROUP of 2..FZB_GROUP_ALTS_MAX non-negated patterns ("alternatives"), each resolved against the matcher's config like any pattern.
+ * SEMANTICS: a group matches a haystack iff at least one alternative matches it; the group's score is the maximum of the matching
+ * alternatives' scores and its exact flag the OR of the exact flags of the alternatives whose score equals that maximum - on the device a
+ * plain max over the key score << 1 | exact, so the result does not depend on the order of the alternatives.  In the composition a group
+ * behaves exactly like ONE non-negated pattern with those hits: it can be the base term (the first non-negated term runs over the whole
+ * range, or over the `in` candidate set), later groups run over the surviving candidates only, score = saturating sum, exact = OR; bias,
+ * scope, facets, capture, sort and `found` apply to the composed records unchanged.  Alternatives with an empty needle are dropped; a group
+ * left with one alternative IS that plain pattern (the same launches, bit-identical results), one left with none is dropped.  A negated
+ * alternative, more than FZB_GROUP_ALTS_MAX alternatives, equal term ids that are not adjacent or a null argument: FZB_ERR_INVALID before
+ * anything touches the device.
+ * LAUNCHES per group of k alternatives: k pipelines, k accumulates, one clear, one flag, one compact; every count stays on the device.  The
+ * slots and the alternatives' hit buffer are allocated only by a matcher that has a group (fzb_multi_matcher_reserve covers them); a matcher
+ * without one allocates and launches exactly what it did.
+ * SERVED for a matcher with a group: fzb_multi_match_list, _into, _device, _top, _parallel, the _subset forms of these (_subset, _top_subset,
+ * _top_subset_device), _top_sections, _top_sections_device and an attached facet sink (fzb_multi_matcher_set_facets).
+ * REFUSED for a matcher with a group (FZB_ERR_INVALID, the message names the entry point and says "any-of group"): every form with matched
+ * positions - fzb_multi_match_list_indices, _indices_into, _top_indices, _top_indices_device, _top_indices_fused, _top_indices_subset,
+ * _top_sections_indices, _top_sections_indices_device - and the multi-device forms fzb_multi_match_list_parallel_sharded, _top_sharded and
+ * _parallel_rccl.  (The traced union assumes every non-negated pattern matches every head record; an alternative need not.) */
+#define FZB_GROUP_ALTS_MAX 8
+/* fzb_multi_matcher_create with a grouping: group_of[i] = the term id of pattern i; equal ids must be adjacent and make one group, an id
+ * used once is a single term.  group_of == NULL is fzb_multi_matcher_create. */
+int fzb_multi_matcher_create_groups(const fzb_config* config, const fzb_pattern* patterns, size_t n_patterns, const uint32_t* group_of, fzb_multi_matcher** out);
+/* fzb_multi_matcher_set_patterns with a grouping: the in-place re-query (spare sub-matchers are reused), skipped when the patterns AND the
+ * grouping are unchanged.  fzb_multi_matcher_set_patterns on a grouped matcher makes every pattern a single term again;
+ * fzb_multi_matcher_clone carries the grouping; fzb_multi_matcher_set_config keeps it. */
+int fzb_multi_matcher_set_pattern_groups(fzb_multi_matcher* mm, const fzb_pattern* patterns, size_t n_patterns, const uint32_t* group_of);
+/* fzb_parse_query with the any-of operator.  Atoms are split exactly as fzb_parse_query splits them (`\ ` included).  An atom that is
+ * exactly `|` joins the atom before it and the atom after it into one group - transitively: `a | b | c` is one group of three - when both
+ * atoms exist, neither is negated and neither is itself `|`; in every other position (leading, trailing, doubled, next to a `!atom`) it
+ * stays the ordinary needle `|` that fzb_parse_query makes of it.  The atom `\|` is the literal needle `|`.  A query without a joining `|`
+ * yields fzb_parse_query's patterns with all-distinct ids.  group_of[i] = the term id of pattern i, ascending from 0.  Both arrays are
+ * released with fzb_query_groups_free. */
+int fzb_parse_query_groups(const uint8_t* query_utf8, size_t query_len, fzb_pattern** out_patterns, uint32_t** out_group_of, size_t* out_n);
+void fzb_query_groups_free(fzb_pattern* patterns, uint32_t* group_of, size_t n);
 /* The multi-device form (see fzb_match_list_parallel_sharded): the whole AND / NOT composition runs per shard on the shard's device
  * through per-shard clones the matcher keeps (they follow set_patterns / set_config), each run numbered from its shard's first index;
  * the runs are gathered and ordered once on the root (the caller's current device).  Result = fzb_multi_match_list on the unsharded

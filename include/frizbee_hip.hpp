@@ -147,6 +147,24 @@ struct Pattern {  // src/pattern.rs:9-18
         fzb_patterns_free(arr, n);
         return out;
     }
+    // parse_query with the any-of operator (fzb_parse_query_groups): an atom that is exactly `|` joins the atoms around it into one group;
+    // group_of[i] = the term id of pattern i, for Matcher::from_pattern_groups
+    static std::vector<Pattern> parse_query_groups(std::string_view query, std::vector<uint32_t>* group_of) {
+        fzb_pattern* arr = nullptr;
+        uint32_t* ids = nullptr;
+        size_t n = 0;
+        check(fzb_parse_query_groups((const uint8_t*)query.data(), query.size(), &arr, &ids, &n));
+        std::vector<Pattern> out;
+        if (group_of) group_of->assign(ids, ids + n);
+        for (size_t i = 0; i < n; i++) {
+            Pattern p(std::string((const char*)arr[i].needle_utf8, arr[i].needle_len));
+            p.negated = arr[i].negated != 0;
+            if (arr[i].matching >= 0) p.config.matching = (Matching)arr[i].matching;
+            out.push_back(std::move(p));
+        }
+        fzb_query_groups_free(arr, ids, n);
+        return out;
+    }
 };
 
 // The haystack list `match_list(&haystacks)` borrows: packed and uploaded once, it stays resident in HBM across queries.
@@ -415,6 +433,18 @@ class Matcher {  // src/matcher/mod.rs:77-222
     // `Matcher::from_patterns(&patterns, &config)`
     Matcher(const std::vector<Pattern>& patterns, const Config& config) : config_(config), patterns_(patterns) { build(); }
     static Matcher from_patterns(const std::vector<Pattern>& patterns, const Config& config = {}) { return Matcher(patterns, config); }
+    // any-of groups: group_of[i] = the term id of pattern i; patterns with equal, adjacent ids are the alternatives of one group (matches when
+    // any of them does, scores their maximum).  Always a composition; the forms with matched positions and the multi-device forms refuse it.
+    // set_pattern / set_patterns make every pattern a single term again.
+    static Matcher from_pattern_groups(const std::vector<Pattern>& patterns, const std::vector<uint32_t>& group_of, const Config& config = {}) {
+        if (group_of.size() != patterns.size()) throw Error(FZB_ERR_INVALID, "from_pattern_groups: one term id per pattern");
+        return Matcher(patterns, group_of, config);
+    }
+    static Matcher from_query_groups(std::string_view query, const Config& config = {}) {
+        std::vector<uint32_t> group_of;
+        const std::vector<Pattern> patterns = Pattern::parse_query_groups(query, &group_of);
+        return Matcher(patterns, group_of, config);
+    }
     // `Matcher::from_query(query, &config)`
     static Matcher from_query(std::string_view query, const Config& config = {}) { return Matcher(Pattern::parse_query(query), config); }
 
@@ -432,7 +462,22 @@ class Matcher {  // src/matcher/mod.rs:77-222
         }
         set_patterns({p});
     }
+    // the in-place re-query with a grouping (fzb_multi_matcher_set_pattern_groups: skipped when patterns and grouping are unchanged)
+    void set_pattern_groups(const std::vector<Pattern>& patterns, const std::vector<uint32_t>& group_of) {
+        if (group_of.size() != patterns.size()) throw Error(FZB_ERR_INVALID, "set_pattern_groups: one term id per pattern");
+        if (multi_ && !group_of.empty()) {
+            const std::vector<fzb_pattern> raw = raw_patterns(patterns);
+            check(fzb_multi_matcher_set_pattern_groups(multi_.get(), raw.data(), raw.size(), group_of.data()));
+            patterns_ = patterns;
+            groups_ = group_of;
+            return;
+        }
+        patterns_ = patterns;
+        groups_ = group_of;
+        build();
+    }
     void set_patterns(const std::vector<Pattern>& patterns) {
+        groups_.clear();
         if (multi_ && !is_single(patterns)) {
             const std::vector<fzb_pattern> raw = raw_patterns(patterns);
             check(fzb_multi_matcher_set_patterns(multi_.get(), raw.data(), raw.size()));
@@ -801,9 +846,19 @@ class Matcher {  // src/matcher/mod.rs:77-222
         }
         return raw;
     }
+    Matcher(const std::vector<Pattern>& patterns, const std::vector<uint32_t>& group_of, const Config& config) : config_(config), patterns_(patterns), groups_(group_of) { build(); }
     void build() {
         single_.reset();
         multi_.reset();
+        if (!groups_.empty()) {
+            const std::vector<fzb_pattern> raw = raw_patterns(patterns_);
+            const fzb_config c = config_.raw();
+            fzb_multi_matcher* mm = nullptr;
+            check(fzb_multi_matcher_create_groups(&c, raw.data(), raw.size(), groups_.data(), &mm));
+            multi_.reset(mm);
+            attach_facets();
+            return;
+        }
         size_t last = 0;
         if (is_single(patterns_, &last)) {
             const fzb_config r = resolve(patterns_[last]);
@@ -835,6 +890,7 @@ class Matcher {  // src/matcher/mod.rs:77-222
     struct DelM { void operator()(fzb_multi_matcher* m) const { fzb_multi_matcher_free(m); } };
     Config config_;
     std::vector<Pattern> patterns_;
+    std::vector<uint32_t> groups_;  // from_pattern_groups: the term id of every pattern (empty: every pattern a term of its own)
     fzb_facets* facets_ = nullptr;  // the attached sink (not owned)
     std::unique_ptr<fzb_matcher, DelS> single_;
     std::unique_ptr<fzb_multi_matcher, DelM> multi_;

@@ -259,6 +259,13 @@ extern "C" {
     fn fzb_multi_matcher_reserve(mm: *mut c_void, c: *const c_void) -> c_int;
     #[allow(dead_code)]
     fn fzb_multi_matcher_clone(mm: *const c_void, out: *mut *mut c_void) -> c_int;
+    // any-of groups (`a | b`): group_of[i] = the term id of pattern i, equal adjacent ids = the alternatives of one group
+    fn fzb_multi_matcher_create_groups(cfg: *const FzbConfig, patterns: *const FzbPattern, n_patterns: usize, group_of: *const u32, out: *mut *mut c_void) -> c_int;
+    fn fzb_multi_matcher_set_pattern_groups(mm: *mut c_void, patterns: *const FzbPattern, n_patterns: usize, group_of: *const u32) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_parse_query_groups(query: *const u8, len: usize, out_patterns: *mut *mut FzbPattern, out_group_of: *mut *mut u32, out_n: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn fzb_query_groups_free(patterns: *mut FzbPattern, group_of: *mut u32, n: usize);
     #[allow(dead_code)]
     fn fzb_multi_match_list_parallel(mm: *mut c_void, c: *const c_void, threads: usize, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
     fn fzb_multi_match_list_parallel_sharded(mm: *mut c_void, sc: *const c_void, out: *mut *mut FzbMatch, out_len: *mut usize) -> c_int;
@@ -672,6 +679,24 @@ impl HipMultiMatcher {
         let mut handle = std::ptr::null_mut();
         check(unsafe { fzb_multi_matcher_create(&cfg, pats.as_ptr(), pats.len(), &mut handle) });
         Self { handle }
+    }
+
+    /// `build` with any-of groups: `group_of[i]` is the term id of pattern i; patterns with equal, adjacent ids are the alternatives of
+    /// one group, which matches when any of them does and scores their maximum.  The forms with matched positions refuse such a matcher.
+    pub fn build_groups(patterns: &[Pattern], group_of: &[u32], config: &Config) -> Self {
+        assert_eq!(patterns.len(), group_of.len(), "one term id per pattern");
+        let cfg = c_config(config, sort_code(&config.sort));
+        let pats = c_patterns(patterns);
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { fzb_multi_matcher_create_groups(&cfg, pats.as_ptr(), pats.len(), group_of.as_ptr(), &mut handle) });
+        Self { handle }
+    }
+
+    /// `set_patterns` with a grouping: skipped when the patterns and the grouping are unchanged.
+    pub fn set_pattern_groups(&mut self, patterns: &[Pattern], group_of: &[u32]) {
+        assert_eq!(patterns.len(), group_of.len(), "one term id per pattern");
+        let pats = c_patterns(patterns);
+        check(unsafe { fzb_multi_matcher_set_pattern_groups(self.handle, pats.as_ptr(), pats.len(), group_of.as_ptr()) });
     }
 
     /// `Matcher::set_patterns` (src/matcher/mod.rs:170-176): skipped when the patterns are the same.
