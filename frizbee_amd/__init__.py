@@ -139,6 +139,8 @@ SYMBOLS = [
     "fzb_match_list_top_sections_indices", "fzb_match_list_top_sections_indices_device", "fzb_multi_match_list_top_sections_indices",
     "fzb_multi_match_list_top_sections_indices_device",
     "fzb_multi_matcher_create_groups", "fzb_multi_matcher_set_pattern_groups", "fzb_parse_query_groups", "fzb_query_groups_free",
+    "fzb_multi_match_list_top_indices_groups", "fzb_multi_match_list_top_indices_groups_device", "fzb_multi_matcher_groups_positions_stride",
+    "fzb_multi_matcher_reserve_top_indices_groups",
 ]
 
 
@@ -291,6 +293,11 @@ def lib():
         l.fzb_match_list_top_indices_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                         C.POINTER(C.c_uint64)]
         l.fzb_multi_match_list_top_indices_subset.argtypes = l.fzb_match_list_top_indices_subset.argtypes
+        l.fzb_multi_match_list_top_indices_groups.argtypes = l.fzb_match_list_top_indices_subset.argtypes
+        l.fzb_multi_match_list_top_indices_groups_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                     C.c_void_p]
+        l.fzb_multi_matcher_groups_positions_stride.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+        l.fzb_multi_matcher_reserve_top_indices_groups.argtypes = l.fzb_matcher_reserve_top_indices.argtypes
         l.fzb_facets_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         l.fzb_facets_free.argtypes = [C.c_void_p]
         l.fzb_facets_free.restype = None
@@ -1052,6 +1059,35 @@ class MultiMatcher(_IterApi):
         """After `reserve(corpus)`: no `match_list_top_indices` call with this `limit` or a smaller one allocates device memory, also after
         `set_patterns` / `set_config` that add no pattern slot and keep every needle within `max_needle_bytes` bytes."""
         _check(lib().fzb_multi_matcher_reserve_top_indices(self.h, corpus.h, limit, max_needle_bytes))
+
+    def match_list_top_indices_groups(self, corpus, limit, *, subset=None, capture=None):
+        """`match_list_top_indices` for a matcher that may have any-of groups -> (list[MatchIndices], found), one fused device call with one
+        host wait.  The records are `match_list_top`'s; a record's positions are the descending union without repeats of the positions of
+        every plain non-negated pattern and of each group's CARRIER only: among the alternatives that match the haystack, the one with the
+        largest key `score << 1 | exact`, on equal keys the first in query order.  A matcher without a group takes the ungrouped path
+        (`match_list_top_indices`'s launches, allocations and bytes)."""
+        cp = corpus if isinstance(corpus, Corpus) else Corpus(corpus)
+        out, n, pos, found = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_uint64()
+        _check(lib().fzb_multi_match_list_top_indices_groups(self.h, cp.h, _h(subset), _h(capture), limit, C.byref(out), C.byref(n), C.byref(pos), C.byref(found)))
+        return _take_indices(out, n, pos), found.value
+
+    def match_list_top_indices_groups_device(self, corpus, limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity, dev_count_ptr, stream=0, *, subset=None, capture=None):
+        """`match_list_top_indices_groups` with the result left in HBM, asynchronous on `stream`: `match_list_top_indices_device`'s
+        buffers and four count words, `positions_capacity` >= min(limit, len(corpus)) x `groups_positions_stride()` uint32."""
+        _check(lib().fzb_multi_match_list_top_indices_groups_device(self.h, corpus.h, _h(subset), _h(capture), limit, dev_out_ptr, capacity, dev_positions_ptr, positions_capacity,
+                                                                    dev_count_ptr, stream))
+
+    def groups_positions_stride(self):
+        """U_g: the needle bytes of the plain non-negated patterns + per group the largest needle bytes among its alternatives (without a
+        group: the U of `match_list_top_indices_device`)."""
+        out = C.c_size_t()
+        _check(lib().fzb_multi_matcher_groups_positions_stride(self.h, C.byref(out)))
+        return out.value
+
+    def reserve_top_indices_groups(self, corpus, limit, max_needle_bytes):
+        """`reserve_top_indices`, and what the grouped forms own on top: after `reserve(corpus)` and this, no `match_list_top_indices_groups`
+        call with this `limit` or a smaller one allocates device memory, also after `set_patterns` to another grouping of the same slots."""
+        _check(lib().fzb_multi_matcher_reserve_top_indices_groups(self.h, corpus.h, limit, max_needle_bytes))
 
     def match_list_indices(self, haystacks, selection=None):
         """`Matcher::match_list_indices` over the compiled patterns (`match_one_indices_multi`, src/matcher/multi.rs:56-82); see

@@ -309,6 +309,11 @@ void fzb_launch_indices_pack(const fzb_match_rec* head, const u32* head_count, c
 struct IUnionSrc;
 void fzb_launch_multi_union(const fzb_match_rec* head, const u32* head_count, u32 max_records, const IUnionSrc* src, u32 P, const IUnionSrc* src_dev, u32* cursors, fzb_match_rec* out,
                             u32* out_count, u32* npos_u, u32* pos_u, u32 U, int grid, hipStream_t st);
+// the same step for a matcher that has an any-of group (indices_union_groups.h: GUnionSrc): slots, clear, where, merge - four launches whatever
+// the number of groups and alternatives
+struct GUnionSrc;
+void fzb_launch_gunion(const fzb_match_rec* head, const u32* head_count, u32 max_records, const GUnionSrc* src, u32 P, const GUnionSrc* src_dev, u32* scratch, u32* slots, u32 n_hay,
+                       u32* where, size_t where_words, fzb_match_rec* out, u32* out_count, u32* npos_u, u32* pos_u, u32 U, int grid, hipStream_t st);
 // kernels_multi.hip
 void fzb_launch_records_to_items(const fzb_match_rec* cand, const u32* n_ptr, u32 index_offset, u32* items, int grid, hipStream_t st);
 void fzb_launch_identity_records(fzb_match_rec* out, u32 n, u32 index_offset, u32* count_out, int grid, hipStream_t st);

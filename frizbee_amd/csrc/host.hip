@@ -2839,6 +2839,12 @@ static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and p
     mm->top_packed = nullptr;
     mm->top_cap = mm->top_pos_u_words = mm->union_src_cap = mm->union_cursor_words = mm->top_packed_cap = mm->top_dense_words = 0;
     mm->union_src_host.clear();
+    for (void* p : {(void*)mm->gunion_where, (void*)mm->gunion_src, (void*)mm->gunion_scratch})
+        if (p) (void)hipFree(p);
+    mm->gunion_where = mm->gunion_scratch = nullptr;
+    mm->gunion_src = nullptr;
+    mm->gunion_where_words = mm->gunion_src_cap = mm->gunion_scratch_words = 0;
+    mm->gunion_src_host.clear();
     fzb_sort_release(mm->sort);
     fzb_out_release(*mm);
     fzb_scope_release(mm->scope);
@@ -4379,8 +4385,76 @@ int ensure_multi_top_indices_buffers(fzb_multi_matcher* mm, size_t want, size_t 
     return fzb_grow_dev(&mm->top_dense, &mm->top_dense_words, want * U, 1);
 }
 bool same_union_src(const IUnionSrc& a, const IUnionSrc& b) { return a.rec == b.rec && a.count == b.count && a.npos == b.npos && a.pos == b.pos && a.stride == b.stride; }
+// a matcher that has an any-of group (indices_union_groups.h): what its union is made of
+struct GroupShape {
+    size_t U = 0;  // U_g: the plain non-negated patterns' strides + per group the largest stride among its alternatives
+    size_t P = 0;  // sources: plain non-negated patterns + alternatives
+    size_t A = 0;  // alternatives in groups
+};
+GroupShape multi_group_shape(const fzb_multi_matcher* mm) {
+    GroupShape g;
+    const auto& ps = mm->patterns;
+    for (size_t i = 0; i < ps.size();) {
+        size_t e = i + 1;
+        while (e < ps.size() && mm->terms.size() == ps.size() && mm->terms[e] == mm->terms[i]) e++;
+        if (!ps[i].negated) {  // (a group has no negated alternative)
+            size_t widest = 0;
+            for (size_t p = i; p < e; p++) widest = std::max<size_t>(widest, trace_stride(ps[p].m));
+            g.U += widest;
+            g.P += e - i;
+            if (e - i >= 2) g.A += e - i;
+        }
+        i = e;
+    }
+    return g;
+}
+size_t gunion_where_stride(size_t want) { return (want + 3) & ~(size_t)3; }  // (the clear stores whole 16-byte words)
+// the grouped tail's own buffers for heads of up to `want` records, A alternatives and P sources
+int ensure_gunion_buffers(fzb_multi_matcher* mm, size_t want, size_t A, size_t P) {
+    int rc;
+    if ((rc = fzb_grow_dev(&mm->gunion_where, &mm->gunion_where_words, std::max<size_t>(A * gunion_where_stride(want), 4), 16))) return rc;
+    if (P > IUNION_BY_VALUE) {
+        if (!mm->gunion_src || mm->gunion_src_cap < P) mm->gunion_src_host.clear();  // (a new array holds nothing yet)
+        if ((rc = fzb_grow_dev(&mm->gunion_src, &mm->gunion_src_cap, P)) || (rc = fzb_grow_dev(&mm->gunion_scratch, &mm->gunion_scratch_words, want * 3 * P, 1))) return rc;
+    }
+    return FZB_OK;
+}
+bool same_gunion_src(const GUnionSrc& a, const GUnionSrc& b) { return same_union_src(a.s, b.s) && a.where == b.where && a.term == b.term; }
 }  // namespace
 extern "C" {
+
+int fzb_multi_matcher_groups_positions_stride(const fzb_multi_matcher* mm, size_t* out) {
+    if (!mm || !out) return fail(FZB_ERR_INVALID, "null argument");
+    *out = mm->grouped ? multi_group_shape(mm).U : multi_union_stride(mm, nullptr);
+    return FZB_OK;
+}
+
+// every buffer of the grouped query and its sources, final before anything is launched (uploaded beyond IUNION_BY_VALUE)
+static int multi_top_indices_group_sources(fzb_multi_matcher* mm, size_t want, const GroupShape& g, std::vector<GUnionSrc>* src, hipStream_t st) {
+    int rc;
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, g.U, 0, false)) || (rc = ensure_gunion_buffers(mm, want, g.A, g.P))) return rc;
+    src->clear();
+    src->reserve(g.P);
+    auto& ps = mm->patterns;
+    size_t a = 0;
+    for (size_t i = 0; i < ps.size(); i++) {
+        if (ps[i].negated) continue;
+        fzb_matcher* m = ps[i].m;
+        if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
+        const bool alt = (i > 0 && mm->terms[i - 1] == mm->terms[i]) || (i + 1 < ps.size() && mm->terms[i + 1] == mm->terms[i]);
+        const u32* where = alt ? mm->gunion_where + (a++) * gunion_where_stride(want) : nullptr;
+        src->push_back(GUnionSrc{IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0}, where, mm->terms[i], 0});
+    }
+    if (g.P > IUNION_BY_VALUE) {
+        bool same = mm->gunion_src_host.size() == g.P;
+        for (size_t i = 0; same && i < g.P; i++) same = same_gunion_src(mm->gunion_src_host[i], (*src)[i]);
+        if (!same) {  // (a pattern, a grouping or a buffer changed since the array was written: ahead of the first launch, ordered on the stream)
+            mm->gunion_src_host = *src;
+            HIPCHK(hipMemcpyAsync(mm->gunion_src, mm->gunion_src_host.data(), g.P * sizeof(GUnionSrc), hipMemcpyHostToDevice, st));
+        }
+    }
+    return FZB_OK;
+}
 
 // The two halves every fused "head + matched positions" query of the composition shares.  Ahead of the first launch: the composition's and every
 // positive pattern's buffers for a head of up to `want` records, and the sources of the union (uploaded beyond IUNION_BY_VALUE).
@@ -4407,8 +4481,17 @@ static int multi_top_indices_sources(fzb_multi_matcher* mm, size_t want, size_t 
 }
 // Behind the head (mm->top_head, its pair in mm->top_words) and its item list (mm->top_items, the length in mm->top_words[10]; k_top_items, or
 // k_sec_items for sectioned heads): one traced pass per positive pattern, the union, the bias, the pack and four words at dev_count.
+// gt (a matcher that has an any-of group, U = U_g): the traced passes are the same - one per plain non-negated pattern and per alternative, an
+// alternative's returning only the head items it matches - and fzb_launch_gunion's four launches stand in place of k_multi_union.
+// `group_slots` serves as its haystack -> head position map: the composition has finished with it, and multi_compose_groups sized it for the
+// haystacks of the list (multi_ensure_buffers(count), also over a candidate set), not for a set's items.
+struct GroupedTail {
+    const GroupShape* shape;
+    const std::vector<GUnionSrc>* src;
+    size_t n_hay;
+};
 static int multi_top_indices_tail(fzb_multi_matcher* mm, const fzb_corpus* c, size_t want, size_t U, const std::vector<IUnionSrc>& src, fzb_match_indices* dev_out, size_t capacity,
-                                  uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream) {
+                                  uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream, const GroupedTail* gt = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     u32* const head_count = mm->top_words;
     u32* const comb_count = mm->top_words + 2;  // the combined traced pair
@@ -4421,8 +4504,14 @@ static int multi_top_indices_tail(fzb_multi_matcher* mm, const fzb_corpus* c, si
         const TraceOut tr{m->trace_pos, m->trace_npos, trace_stride(m)};
         if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
     }
-    fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)src.size(), mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U,
-                           grid, st);
+    if (gt) {
+        if (!mm->group_slots || mm->group_cap < gt->n_hay) return fail(FZB_ERR_HIP, "internal: the group slots do not cover the list");
+        fzb_launch_gunion(mm->top_head, head_count, (u32)want, gt->src->data(), (u32)gt->src->size(), mm->gunion_src, mm->gunion_scratch, mm->group_slots, (u32)gt->n_hay, mm->gunion_where,
+                          gt->shape->A * gunion_where_stride(want), mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, grid, st);
+    } else {
+        fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)src.size(), mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u,
+                               (u32)U, grid, st);
+    }
     if ((rc = apply_bias(c, mm->top_comb, comb_count, want, 0, 0, grid, st))) return rc;  // once, after the sum: as the head's records
     fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
                             dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
@@ -4446,7 +4535,9 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
     if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
     if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_indices_fused");
     size_t P = 0;
-    const size_t U = multi_union_stride(mm, &P);
+    // (a matcher that has an any-of group gets here through fzb_multi_match_list_top_indices_groups* alone: its stride is U_g)
+    const GroupShape shape = mm->grouped ? multi_group_shape(mm) : GroupShape{};
+    const size_t U = mm->grouped ? shape.U : multi_union_stride(mm, &P);
     if (positions_capacity < want * U)
         return fail(FZB_ERR_CAPACITY, "positions buffer smaller than min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(want * U));
     if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
@@ -4459,14 +4550,20 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
     // every buffer first: the sources of the union are final before anything is launched
     int rc;
     std::vector<IUnionSrc> src;
-    if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st))) return rc;
+    std::vector<GUnionSrc> group_src;
+    const GroupedTail gt{&shape, &group_src, n};
+    if (mm->grouped) {
+        if ((rc = multi_top_indices_group_sources(mm, want, shape, &group_src, st))) return rc;
+    } else if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st))) {
+        return rc;
+    }
     u32* const head_count = mm->top_words;      // (records, matches found) of the head
     u32* const n_items = mm->top_words + 10;
     // (the composition's pair in words 12-13: word 8 follows the host form's four result words, where its wait picks up a captured count)
     if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 12, st, sa))) return rc;
     const int grid = mm->num_cus * 2;
     fzb_launch_top_items(mm->top_head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
-    return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream);
+    return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, mm->grouped ? &gt : nullptr);
 }
 
 static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
@@ -4950,6 +5047,78 @@ int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_cor
     if (!in && !capture) return fzb_multi_match_list_top_indices_fused(mm, c, limit, out, out_len, out_positions, out_found);
     SubsetArgs sa{in, capture, nullptr};
     return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, &sa);
+}
+
+// ---- matched positions of the top-`limit` for a matcher that has an any-of group ---------------------------------------------------------------
+// The head is the multi top stage's, as in the fused form above.  Behind it every plain non-negated pattern AND every alternative of every
+// group runs the traced pipeline over the head's one item list, each into its own sub-matcher's trace buffers; an alternative's pass returns
+// only the head items it matches.  fzb_launch_gunion (indices_union_groups.h) then finds every alternative's row per head record, picks each
+// group's carrier - the largest key score << 1 | exact, the first in query order on equal keys - and merges the plain patterns' and the
+// carriers' positions; bias and pack follow unchanged.  Four launches in place of the ungrouped tail's one union, whatever the number of groups
+// and alternatives; nothing is read back in between.  Both kinds of matcher share multi_top_indices_device_impl and multi_top_indices_tail: a
+// matcher without a group takes them as the ungrouped entry points do, call for call.
+int fzb_multi_match_list_top_indices_groups_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices* dev_out,
+                                                   size_t capacity, uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    if (!mm || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_indices_groups_device");
+    if (rc) return rc;
+    if (mm->patterns.empty() && (in || capture)) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_indices_groups");
+    if (!in && !capture) return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
+    if (c->dev.n == 0) {
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
+    }
+    const SubsetArgs sa{in, capture, nullptr};
+    return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, &sa);
+}
+
+int fzb_multi_match_list_top_indices_groups(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
+                                            uint32_t** out_positions, uint64_t* out_found) {
+    if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
+    if (!mm->grouped) {  // the ungrouped forms, call for call
+        if (!in && !capture) return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr);
+        return fzb_multi_match_list_top_indices_subset(mm, c, in, capture, limit, out, out_len, out_positions, out_found);
+    }
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
+    int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_indices_groups");
+    if (rc) return rc;
+    const size_t n = c->dev.n;
+    const size_t want = std::min(limit, n);
+    if (n == 0) {  // (a grouped matcher has a pattern)
+        if ((rc = subset_capture_trivial(c, in, capture))) return rc;
+        if ((rc = facets_every(mm->facets, c, 0, n, "fzb_multi_match_list_top_indices_groups"))) return rc;
+        return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
+    }
+    const GroupShape g = multi_group_shape(mm);
+    if ((u64)want * g.U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x the grouped positions stride does not fit the 32-bit positions_begin");
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, g.U, 0, true))) return rc;
+    u32* const words = mm->top_words + 4;
+    const SubsetArgs sa{in, capture, capture ? mm->top_words + 8 : nullptr};
+    if ((rc = multi_top_indices_device_impl(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr,
+                                                   (in || capture) ? &sa : nullptr)))
+        return rc;
+    u32 captured = 0;
+    rc = fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * g.U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out, out_len,
+                           out_positions, out_found, capture ? &captured : nullptr);
+    if (rc) return rc;
+    subset_capture_known(capture, captured);
+    return FZB_OK;
+}
+
+// fzb_multi_matcher_reserve_top_indices, and what the grouped tail owns for any grouping of the matcher's slots: the `where` maps of as many
+// alternatives as there are slots, the sources' device array and scratch, and the group slots for the haystacks the corpus has room for.
+int fzb_multi_matcher_reserve_top_indices_groups(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, size_t max_needle_bytes) {
+    int rc = fzb_multi_matcher_reserve_top_indices(mm, c, limit, max_needle_bytes);
+    if (rc) return rc;
+    const size_t n = fzb_corpus_reserved_items(c);
+    const size_t want = std::min(limit, n);
+    if (want == 0) return FZB_OK;
+    const size_t slots = mm->patterns.size() + mm->spare.size();
+    if ((rc = multi_ensure_buffers(mm, n)) || (rc = multi_ensure_group_buffers(mm))) return rc;
+    return ensure_gunion_buffers(mm, want, slots, slots);
 }
 
 // fzb_matcher_reserve_top_indices for the composition: every sub-matcher slot (the spares too) gets the trace buffers and the traced scorer's

@@ -12,6 +12,7 @@
 #include "../../include/frizbee_hip.h"
 #include "fzb_internal.h"
 #include "indices_union.h"
+#include "indices_union_groups.h"
 #include "knobs.h"
 
 // error state of the calling thread (fzb_last_error) + the usual early return
@@ -360,6 +361,16 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     std::vector<IUnionSrc> union_src_host;
     u32* union_cursors = nullptr;
     size_t union_cursor_words = 0;
+    // fzb_multi_match_list_top_indices_groups*: the grouped tail's own buffers (indices_union_groups.h) - the alternatives' `where` maps side by
+    // side (one clear covers them), and beyond IUNION_BY_VALUE sources their array on the device (what it holds: `gunion_src_host`) and three
+    // scratch words per source and head record.  The haystack -> head position map is `group_slots`, free once the composition has finished.
+    u32* gunion_where = nullptr;
+    size_t gunion_where_words = 0;
+    GUnionSrc* gunion_src = nullptr;
+    size_t gunion_src_cap = 0;
+    std::vector<GUnionSrc> gunion_src_host;
+    u32* gunion_scratch = nullptr;
+    size_t gunion_scratch_words = 0;
     fzb_indices_rec* top_packed = nullptr;
     u32* top_dense = nullptr;
     size_t top_packed_cap = 0, top_dense_words = 0;

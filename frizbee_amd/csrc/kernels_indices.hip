@@ -15,10 +15,13 @@
 //     an atomic.
 // The multi-pattern form (fzb_multi_match_list_top_indices_device) traces every positive pattern over the one item list and puts a step
 // between those passes and the pack: k_multi_union merges the patterns' records and positions per head record (indices_union.h says how),
-// and the pack then sees one traced pass with a stride of U.
+// and the pack then sees one traced pass with a stride of U.  A matcher that has an any-of group (fzb_multi_match_list_top_indices_groups*)
+// takes the k_gunion_* launches in that place: an alternative's traced pass returns only the head items it matches, so its rows are found
+// first, and only each group's carrier contributes positions (indices_union_groups.h says how).
 #include "kernels_common.h"
 #include "indices_pack.h"
 #include "indices_union.h"
+#include "indices_union_groups.h"
 
 #define IPACK_THREADS (IPACK_TILE / IPACK_SHARE)
 static_assert(IPACK_THREADS == 256, "four waves scan a tile");
@@ -227,6 +230,118 @@ void fzb_launch_multi_union(const fzb_match_rec* head, const u32* head_count, u3
     const int g = (int)std::max<u32>(1, std::min<u32>((u32)grid, (max_records + 255) / 256));
     if (by_value) FZB_LAUNCH((k_multi_union<true>), dim3(g), dim3(256), 0, st, a);
     else FZB_LAUNCH((k_multi_union<false>), dim3(g), dim3(256), 0, st, a);
+}
+
+// ---- the union of a matcher that has an any-of group (indices_union_groups.h) --------------------------------------------------------------
+// An alternative's traced pass over the head's items returns only the items it matches, so its row of head record k has to be found:
+//   k_gunion_slots  slot[head[k].index] = k - one word per haystack of the corpus, never cleared: it is read only at the indices of traced
+//                   records, and those are head items, which this launch wrote;
+//   k_gunion_clear  all the alternatives' `where` arrays at once (16-byte stores);
+//   k_gunion_where  for traced record j of alternative a: where_a[slot[rec_a[j].index]] = j + 1 - one launch for all alternatives;
+//   k_gunion_merge  k_multi_union's step with the carrier rule: one thread per head record.
+// The same class as k_multi_union: latency-bound glue over at most `limit` records, dependent loads and no reuse.
+struct GUnionArgs {
+    const fzb_match_rec* head;
+    const u32* head_count;
+    u32 cap;
+    u32 P;                           // sources: plain positive patterns and alternatives, the sources of a term adjacent
+    GUnionSrc src[IUNION_BY_VALUE];  // P <= IUNION_BY_VALUE ..
+    const GUnionSrc* more;           // .. or all P in device memory, with 3 P scratch words per record of the head (carriers, rows, cursors)
+    u32* scratch;
+    const u32* slots;                // haystack -> head position (k_gunion_where)
+    u32 n_hay;
+    fzb_match_rec* out;
+    u32* out_count;
+    u32* npos_u;
+    u32* pos_u;
+    u32 U;
+};
+
+__global__ __launch_bounds__(256) void k_gunion_slots(const fzb_match_rec* __restrict__ head, const u32* __restrict__ head_count, u32 cap, u32* __restrict__ slots, u32 n_hay) {
+    const u32 n = min(head_count[0], cap);
+    for (u32 k = blockIdx.x * 256u + threadIdx.x; k < n; k += gridDim.x * 256u) {
+        const u32 h = head[k].index;
+        if (h < n_hay) slots[h] = k;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gunion_clear(uint4* __restrict__ where4, u32 n4) {
+    for (u32 j = blockIdx.x * 256u + threadIdx.x; j < n4; j += gridDim.x * 256u) where4[j] = make_uint4(0, 0, 0, 0);
+}
+
+// A traced record whose haystack is not the head record its slot names (cannot happen: the pass ran over the head's items) is dropped, never
+// written out of bounds: the alternative then counts as absent there.
+template <bool BY_VALUE>
+__global__ __launch_bounds__(256) void k_gunion_where(const GUnionArgs a) {
+    const GUnionSrc* const src = BY_VALUE ? a.src : a.more;
+    const u32 n = min(a.head_count[0], a.cap);
+    const u64 total = (u64)a.P * a.cap;
+    for (u64 t = (u64)blockIdx.x * 256u + threadIdx.x; t < total; t += (u64)gridDim.x * 256u) {
+        const u32 p = (u32)(t / a.cap), j = (u32)(t % a.cap);
+        u32* const where = const_cast<u32*>(src[p].where);
+        if (!where || j >= min(src[p].s.count[0], a.cap)) continue;
+        const u32 h = src[p].s.rec[j].index;
+        if (h >= a.n_hay) continue;
+        const u32 k = a.slots[h];
+        if (k < n && a.head[k].index == h) where[k] = j + 1;
+    }
+}
+
+template <bool BY_VALUE>
+__global__ __launch_bounds__(256) void k_gunion_merge(const GUnionArgs a) {
+    const u32 n = min(a.head_count[0], a.cap);
+    const GUnionSrc* const src = BY_VALUE ? a.src : a.more;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.out_count[0] = gunion_count(src, a.P, a.head_count[0]);
+        a.out_count[1] = a.head_count[1];
+    }
+    for (u32 k = blockIdx.x * 256u + threadIdx.x; k < n; k += gridDim.x * 256u) {
+        u32 own[3 * IUNION_BY_VALUE];
+        u32* const carrier = BY_VALUE ? own : a.scratch + (size_t)k * 3u * a.P;
+        u32* const row = carrier + (BY_VALUE ? IUNION_BY_VALUE : a.P);
+        u32* const cur = row + (BY_VALUE ? IUNION_BY_VALUE : a.P);
+        bool missing = false;
+        const u32 T = gunion_carriers(src, a.P, k, carrier, row, &missing);
+        const IUnionRec r = gunion_record_of(src, T, carrier, row, missing, a.head[k].index);
+        fzb_match_rec o;
+        o.index = r.index;
+        o.score = r.score;
+        o.exact = r.exact;
+        o.valid = 0;
+        a.out[k] = o;
+        a.npos_u[k] = gunion_merge(src, T, carrier, row, cur, a.pos_u + (size_t)k * a.U, a.U);
+    }
+}
+
+// src: P sources in host memory (copied into the argument block while P <= IUNION_BY_VALUE); src_dev / scratch: the same P sources and
+// max_records x 3 P words in device memory, read only beyond that.  where: the alternatives' maps, where_words of them (a multiple of four)
+// in one array.  slots: n_hay words.
+void fzb_launch_gunion(const fzb_match_rec* head, const u32* head_count, u32 max_records, const GUnionSrc* src, u32 P, const GUnionSrc* src_dev, u32* scratch, u32* slots, u32 n_hay,
+                       u32* where, size_t where_words, fzb_match_rec* out, u32* out_count, u32* npos_u, u32* pos_u, u32 U, int grid, hipStream_t st) {
+    GUnionArgs a{};
+    a.head = head;
+    a.head_count = head_count;
+    a.cap = max_records;
+    a.P = P;
+    const bool by_value = P <= IUNION_BY_VALUE;
+    for (u32 p = 0; by_value && p < P; p++) a.src[p] = src[p];
+    a.more = src_dev;
+    a.scratch = scratch;
+    a.slots = slots;
+    a.n_hay = n_hay;
+    a.out = out;
+    a.out_count = out_count;
+    a.npos_u = npos_u;
+    a.pos_u = pos_u;
+    a.U = U;
+    const auto blocks = [&](u64 work) { return (int)std::max<u64>(1, std::min<u64>((u64)grid, (work + 255) / 256)); };
+    const int g = blocks(max_records);
+    FZB_LAUNCH(k_gunion_slots, dim3(g), dim3(256), 0, st, head, head_count, max_records, slots, n_hay);
+    FZB_LAUNCH(k_gunion_clear, dim3(blocks(where_words / 4)), dim3(256), 0, st, (uint4*)where, (u32)(where_words / 4));
+    if (by_value) FZB_LAUNCH((k_gunion_where<true>), dim3(blocks((u64)P * max_records)), dim3(256), 0, st, a);
+    else FZB_LAUNCH((k_gunion_where<false>), dim3(blocks((u64)P * max_records)), dim3(256), 0, st, a);
+    if (by_value) FZB_LAUNCH((k_gunion_merge<true>), dim3(g), dim3(256), 0, st, a);
+    else FZB_LAUNCH((k_gunion_merge<false>), dim3(g), dim3(256), 0, st, a);
 }
 
 void fzb_launch_top_items(const fzb_match_rec* head, const u32* head_count, u32 cap, u32* items, u32* n_items, u32* dev_count, int grid, hipStream_t st) {

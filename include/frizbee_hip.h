@@ -750,7 +750,9 @@ int fzb_multi_match_list_parallel(fzb_multi_matcher* mm, const fzb_corpus* c, si
  * REFUSED for a matcher with a group (FZB_ERR_INVALID, the message names the entry point and says "any-of group"): every form with matched
  * positions - fzb_multi_match_list_indices, _indices_into, _top_indices, _top_indices_device, _top_indices_fused, _top_indices_subset,
  * _top_sections_indices, _top_sections_indices_device - and the multi-device forms fzb_multi_match_list_parallel_sharded, _top_sharded and
- * _parallel_rccl.  (The traced union assumes every non-negated pattern matches every head record; an alternative need not.) */
+ * _parallel_rccl.  (The traced union assumes every non-negated pattern matches every head record; an alternative need not.)  A grouped
+ * matcher gets the matched positions of its top-`limit` from fzb_multi_match_list_top_indices_groups / _groups_device below, which build the
+ * per-record presence and the carrier rule that union lacks. */
 #define FZB_GROUP_ALTS_MAX 8
 /* fzb_multi_matcher_create with a grouping: group_of[i] = the term id of pattern i; equal ids must be adjacent and make one group, an id
  * used once is a single term.  group_of == NULL is fzb_multi_matcher_create. */
@@ -767,6 +769,43 @@ int fzb_multi_matcher_set_pattern_groups(fzb_multi_matcher* mm, const fzb_patter
  * released with fzb_query_groups_free. */
 int fzb_parse_query_groups(const uint8_t* query_utf8, size_t query_len, fzb_pattern** out_patterns, uint32_t** out_group_of, size_t* out_n);
 void fzb_query_groups_free(fzb_pattern* patterns, uint32_t* group_of, size_t n);
+/* ---- ANY-OF GROUPS WITH MATCHED POSITIONS: the top-`limit` of a grouped matcher, fused on the device ---------------------------------------
+ * HEAD AND RECORDS: the head is exactly what fzb_multi_match_list_top / _top_subset return for the same matcher, corpus, subset, bias and
+ * scope; records carry (index, score, exact), `found` is theirs.
+ * THE CARRIER OF A GROUP: for a head record on haystack h and a group G, the carrier is chosen among the alternatives that match h - the
+ * alternative with the largest key score << 1 | exact, on equal keys the first in query order.  The carrier's record is the group's record
+ * (its exact flag equals the group's: the key maximum prefers a set flag at equal scores).
+ * POSITIONS of a head record: the strictly descending union without repeats (`match_one_indices_multi`, src/matcher/multi.rs:56-82) of the
+ * positions of every plain non-negated pattern and of each group's carrier ONLY.  Alternatives that match but do not carry contribute
+ * nothing; negated terms contribute nothing.
+ * STRIDE: U_g = the trace strides (needle bytes, at least 1) of the plain non-negated patterns + per group the maximum trace stride among its
+ * alternatives (fzb_multi_matcher_groups_positions_stride).  U_g replaces the U of the ungrouped forms in every capacity rule.
+ * A matcher WITHOUT a group takes the ungrouped path unchanged through these entry points: the same launches, the same allocations, a
+ * byte-identical result to fzb_multi_match_list_top_indices_fused / _device (with `in` / `capture`: _top_indices_subset); U_g is then U.
+ * A biased or scoped corpus, an attached facet sink and the `in` / `capture` candidate sets (both nullable) behave as in
+ * fzb_multi_match_list_top_indices_fused / _subset: only the top stage sees the set, the bias is added once after the sum, the capture
+ * receives what the composition accepted.  An empty pattern list, a corpus of 0 haystacks and `limit` 0 behave as in the fused form.
+ * LAUNCHES behind the head: one traced pass per plain non-negated pattern and per alternative over the head's one item list, then four
+ * launches whatever the number of groups and alternatives - the haystack -> head position map, one clear of all the alternatives' row maps,
+ * one launch that fills them, one merge (in place of the ungrouped union) -, the bias and the pack.  One host wait in the host form, none in
+ * the device form.
+ * DISAGREEMENT stays an error: a head record for which some group has no matching alternative, or whose carriers' sum differs from the head's
+ * record, and a traced pass that produced more records than the head has (a plain pattern's: another number), make the host form fail with
+ * FZB_ERR_HIP "the traced passes disagree with the multi top stage" and raise word [3] of the device form's count words.
+ * Still REFUSED for a grouped matcher: the list-order forms, the sectioned forms with positions and the multi-device forms named above. */
+/* U_g of the matcher's compiled patterns (the U of the ungrouped forms for a matcher without a group) */
+int fzb_multi_matcher_groups_positions_stride(const fzb_multi_matcher* mm, size_t* out);
+/* The device form: fzb_multi_match_list_top_indices_device's arguments and four count words at dev_count, plus the nullable candidate sets;
+ * capacity >= min(limit, haystacks), positions_capacity >= min(limit, haystacks) x U_g, else FZB_ERR_CAPACITY before anything is launched. */
+int fzb_multi_match_list_top_indices_groups_device(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices* dev_out,
+                                                   size_t capacity, uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream);
+/* The host form: one wait; the result is released with fzb_match_indices_free. */
+int fzb_multi_match_list_top_indices_groups(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out,
+                                            size_t* out_len, uint32_t** out_positions, uint64_t* out_found);
+/* fzb_multi_matcher_reserve_top_indices, and additionally what the grouped tail owns, for any grouping of the matcher's slots.  After
+ * fzb_multi_matcher_reserve(mm, c) and this call no call of the two forms above with this `limit` or a smaller one allocates device memory
+ * (needles of up to max_needle_bytes bytes, no more compiled patterns than now). */
+int fzb_multi_matcher_reserve_top_indices_groups(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, size_t max_needle_bytes);
 /* The multi-device form (see fzb_match_list_parallel_sharded): the whole AND / NOT composition runs per shard on the shard's device
  * through per-shard clones the matcher keeps (they follow set_patterns / set_config), each run numbered from its shard's first index;
  * the runs are gathered and ordered once on the root (the caller's current device).  Result = fzb_multi_match_list on the unsharded

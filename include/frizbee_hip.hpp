@@ -713,6 +713,42 @@ class Matcher {  // src/matcher/mod.rs:77-222
         if (single_) check(fzb_matcher_reserve_top_indices(single_.get(), corpus.raw(), limit, max_needle_bytes));
         else check(fzb_multi_matcher_reserve_top_indices(multi_.get(), corpus.raw(), limit, max_needle_bytes));
     }
+    // match_list_top_indices for a `from_patterns` matcher that may have any-of groups (fzb_multi_match_list_top_indices_groups): the records
+    // are match_list_top's; a record's positions are the descending union of every plain non-negated pattern's and of each group's carrier's
+    // only - the matching alternative with the largest key score << 1 | exact, the first in query order on equal keys.  Without a group: the
+    // ungrouped call.
+    std::vector<MatchIndices> match_list_top_indices_groups(const Corpus& corpus, size_t limit, size_t* found = nullptr, const Subset* in = nullptr, Subset* capture = nullptr) {
+        if (!multi_) throw Error(FZB_ERR_INVALID, "match_list_top_indices_groups: a single-needle matcher has no groups");
+        fzb_match_indices* out = nullptr;
+        uint32_t* pos = nullptr;
+        size_t n = 0;
+        uint64_t f = 0;
+        check(fzb_multi_match_list_top_indices_groups(multi_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, &out, &n, &pos, &f));
+        if (found) *found = (size_t)f;
+        std::vector<MatchIndices> v(n);
+        for (size_t i = 0; i < n; i++)
+            v[i] = MatchIndices{out[i].score, out[i].index, out[i].exact != 0, std::vector<uint32_t>(pos + out[i].positions_begin, pos + out[i].positions_begin + out[i].positions_len)};
+        fzb_match_indices_free(out, pos);
+        return v;
+    }
+    // the same left in HBM, asynchronous on `stream`: positions_capacity >= min(limit, haystacks) x groups_positions_stride()
+    void match_list_top_indices_groups_device(const Corpus& corpus, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                              uint32_t* dev_count, void* stream = nullptr, const Subset* in = nullptr, Subset* capture = nullptr) {
+        if (!multi_) throw Error(FZB_ERR_INVALID, "match_list_top_indices_groups_device: a single-needle matcher has no groups");
+        check(fzb_multi_match_list_top_indices_groups_device(multi_.get(), corpus.raw(), in ? in->raw() : nullptr, capture ? capture->raw() : nullptr, limit, dev_out, capacity,
+                                                             dev_positions, positions_capacity, dev_count, stream));
+    }
+    // U_g: the plain non-negated patterns' needle bytes + per group the largest among its alternatives
+    size_t groups_positions_stride() const {
+        if (!multi_) throw Error(FZB_ERR_INVALID, "groups_positions_stride: a single-needle matcher has no groups");
+        size_t u = 0;
+        check(fzb_multi_matcher_groups_positions_stride(multi_.get(), &u));
+        return u;
+    }
+    void reserve_top_indices_groups(const Corpus& corpus, size_t limit, size_t max_needle_bytes) {
+        if (!multi_) throw Error(FZB_ERR_INVALID, "reserve_top_indices_groups: a single-needle matcher has no groups");
+        check(fzb_multi_matcher_reserve_top_indices_groups(multi_.get(), corpus.raw(), limit, max_needle_bytes));
+    }
 
     // `match_list_indices(&haystacks)` (src/matcher/mod.rs:234-275; multi-pattern: match_one_indices_multi, multi.rs:56-82).
     // `selection`: corpus indices standing in for the haystack list (the top of a match_list result); empty optional = the whole corpus.

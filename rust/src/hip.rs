@@ -218,6 +218,12 @@ extern "C" {
     #[allow(dead_code)]
     fn fzb_multi_match_list_top_indices_subset(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
                                                out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_indices_groups(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, out: *mut *mut FzbMatchIndices,
+                                               out_len: *mut usize, out_positions: *mut *mut u32, out_found: *mut u64) -> c_int;
+    fn fzb_multi_match_list_top_indices_groups_device(mm: *mut c_void, c: *const c_void, input: *const c_void, capture: *mut c_void, limit: usize, dev_out: *mut FzbMatchIndices,
+                                                      capacity: usize, dev_positions: *mut u32, positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) -> c_int;
+    fn fzb_multi_matcher_groups_positions_stride(mm: *const c_void, out: *mut usize) -> c_int;
+    fn fzb_multi_matcher_reserve_top_indices_groups(mm: *mut c_void, c: *const c_void, limit: usize, max_needle_bytes: usize) -> c_int;
     fn fzb_match_list_top_sharded(m: *mut c_void, sc: *const c_void, limit: usize, out: *mut *mut FzbMatch, out_len: *mut usize, out_found: *mut u64) -> c_int;
     fn fzb_match_list_indices(m: *mut c_void, c: *const c_void, selection: *const u32, n_selection: usize, out: *mut *mut FzbMatchIndices, out_len: *mut usize,
                               out_positions: *mut *mut u32) -> c_int;
@@ -789,6 +795,39 @@ impl HipMultiMatcher {
     /// `set_patterns` / `set_config` that add no pattern slot and keep every needle within `max_needle_bytes` bytes.
     pub fn reserve_top_indices(&mut self, corpus: &HipCorpus, limit: usize, max_needle_bytes: usize) {
         check(unsafe { fzb_multi_matcher_reserve_top_indices(self.handle, corpus.handle, limit, max_needle_bytes) });
+    }
+
+    /// `match_list_top_indices` for a matcher that may have any-of groups: the records are `match_list_top`'s; a record's positions are
+    /// the descending union of every plain non-negated pattern's and of each group's carrier's only - the matching alternative with the
+    /// largest key `score << 1 | exact`, the first in query order on equal keys.  Without a group: the ungrouped call.
+    pub fn match_list_top_indices_groups(&mut self, corpus: &HipCorpus, limit: usize) -> (Vec<MatchIndices>, usize) {
+        let (mut out, mut n, mut pos, mut found) = (std::ptr::null_mut(), 0usize, std::ptr::null_mut(), 0u64);
+        check(unsafe {
+            fzb_multi_match_list_top_indices_groups(self.handle, corpus.handle, std::ptr::null(), std::ptr::null_mut(), limit, &mut out, &mut n, &mut pos, &mut found)
+        });
+        (take_indices(out, n, pos), found as usize)
+    }
+
+    /// The same left in device memory: `positions_capacity >= min(limit, len) x groups_positions_stride()`.  Asynchronous on `stream`.
+    ///
+    /// # Safety
+    /// The three device pointers must be valid for the capacities given, on the device the corpus lives on.
+    pub unsafe fn match_list_top_indices_groups_device(&mut self, corpus: &HipCorpus, limit: usize, dev_out: *mut c_void, capacity: usize, dev_positions: *mut u32,
+                                                       positions_capacity: usize, dev_count: *mut u32, stream: *mut c_void) {
+        check(fzb_multi_match_list_top_indices_groups_device(self.handle, corpus.handle, std::ptr::null(), std::ptr::null_mut(), limit, dev_out as *mut FzbMatchIndices, capacity,
+                                                             dev_positions, positions_capacity, dev_count, stream));
+    }
+
+    /// U_g: the plain non-negated patterns' needle bytes + per group the largest among its alternatives.
+    pub fn groups_positions_stride(&self) -> usize {
+        let mut u = 0usize;
+        check(unsafe { fzb_multi_matcher_groups_positions_stride(self.handle, &mut u) });
+        u
+    }
+
+    /// `reserve_top_indices`, and what the grouped forms own on top.
+    pub fn reserve_top_indices_groups(&mut self, corpus: &HipCorpus, limit: usize, max_needle_bytes: usize) {
+        check(unsafe { fzb_multi_matcher_reserve_top_indices_groups(self.handle, corpus.handle, limit, max_needle_bytes) });
     }
 
     /// `match_list_top` over a sharded list: every shard selects its own head, only those records reach the root.
