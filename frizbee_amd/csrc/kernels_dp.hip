@@ -139,10 +139,15 @@ __global__ __launch_bounds__(128, 2) void k2b_dp(const u8* __restrict__ bytes, c
 // 0-typo window comes from one merged flag word per needle byte and the per-lane bonuses from two small LDS tables.  No
 // queues (nothing can be wider than a chunk) and a third of the registers of the general kernel: four waves per SIMD.
 // Chosen by fzb_launch_dp when LaunchCfg::cf_ok and CorpusDev::max_len allow; otherwise k2b_dp runs.
-// SEG: the survivors come as the signature filter's SEGMENTED list (seg_list.h) instead of a dense one behind a compaction launch.  Every
-// workgroup loads the <= 2048 segment counts (16 per thread, one round trip, in flight while the bonus tables are built), scans them into an
-// exclusive prefix in LDS, takes M from the total, and load_item(j) finds j's segment by bisection of that prefix.  The output position stays
-// j, so records stay index-ordered; pipeline, priorities and dev_count are as in the dense form, whose instantiations do not change.
+// SEG: the survivors come as the signature filter's SEGMENTED list (seg_list.h) instead of a dense one behind a compaction launch; the host
+// takes this form only for 0-typo windows computed here (pipe_seg_applies), so window mode 1 is compiled in and the window words, the typo
+// table and the rejections do not exist.  A wave's FIRST item comes straight from the filter's own segment (seg_list.h, "direct"): workgroup
+// b requests seg_counts[b] together with its sixteen of the <= 2048 counts, list entry b * stride + lane of the lanes that word admits, and
+// the row as soon as the entry is there - only then are the counts scanned into the two exclusive prefixes in LDS (output positions; the
+// pool the direct round leaves) and the barriers passed, with the rows in flight.  The pool is walked grid-strided by bisection of its
+// prefix, its items prefetched during the direct item's DP.  Output positions are ranks in the whole list, so records stay index-ordered
+// and dense; dev_count, the cut at `capacity` and the priorities are as in the dense form, whose instantiations do not change.  No ordering
+// between workgroups.
 // ---------------------------------------------------------------------------------------------------------------
 #ifdef FZB_DP_TIMING
 // Debug build only (make TIMING=1 -> libfrizbee_hip_timing.so, tools/exp_dp_timing.py): per wave, the constant 100 MHz counter
@@ -162,58 +167,205 @@ extern "C" int fzb_debug_dp_timing(unsigned long long* host_out) { return (int)h
 #define FZB_TIMING_END
 #endif
 struct SegNone {};
+// One survivor of k2b_dp_short: the window [ws, we) of the haystack of L bytes held by (q0, q1) -> its record at *dst.  mid(): called half
+// way through the DP (the priority step).
+template <int SWL, bool UPPER, class Mid>
+__device__ __forceinline__ void dp_short_item(const NeedleDev& nd, const CfTables& tab, const uint4& q0, const uint4& q1, u32 L, u32 ws, u32 we, u32 index,
+                                              fzb_match_rec* __restrict__ dst, Mid mid) {
+    // ---- trim_haystack (matcher/algo.rs:332-338) --------------------------------------------------
+    const u32 sp = ws ? ws - 1 : 0;
+    const bool include_exact = sp == 0 && we == L;
+    const u32 m = we - sp;
+    u32 score = 0;
+    u32 hb[SWL / 4];
+#pragma unroll
+    for (int k = 0; k < SWL / 4; k++) hb[k] = 0;
+    if (m > 0) {
+        load_window_regs<SWL / 4>(q0, q1, sp, m, hb);
+        score = dp_single_chunk_cf_tab<SWL, UPPER, SWL / 4, Mid>(nd, sp == 0, tab, hb, mid);
+    }
+    const bool exact = exact_match<SWL / 4>(nd, include_exact, m, hb);
+    if (exact) score = (score + nd.exact_bonus) & 0xFFFF;
+    fzb_match_rec rec;
+    rec.index = index;
+    rec.score = (u16)score;
+    rec.exact = exact ? 1 : 0;
+    rec.valid = 0;
+    *dst = rec;
+}
+
+// The segmented form of k2b_dp_short (see there; the work assignment is seg_list.h's).  Called by every thread of the workgroup.
+template <int SWL, bool UPPER>
+__device__ __forceinline__ void dp_short_seg(const u8* __restrict__ bytes, const EndsAny& ends, u64 first, u32 index_offset, const NeedleDev& nd,
+                                             fzb_match_rec* __restrict__ out, u32 capacity, u32* __restrict__ dev_count, u32* __restrict__ kept_out, u32 ulen,
+                                             const SegList& seg) {
+    __shared__ CfTables tab;
+    __shared__ u32 seg_pre[FZB_SEG_MAX];   // exclusive prefix of the segment counts: output positions
+    __shared__ u32 seg_rpre[FZB_SEG_MAX];  // exclusive prefix of what the direct round leaves: the pool; entries at and beyond nseg hold its size
+    __shared__ u32 seg_wsum[4];
+    constexpr u32 NONE = 0xFFFFFFFFu;  // output position of a pipeline slot without an item (never below `capacity`)
+    const u32 b = blockIdx.x, G = gridDim.x, t = threadIdx.x;
+    // (the workgroup's size is the launch's 128, one direct item per thread: told to the compiler, which otherwise fetches it from the
+    // dispatch packet - a memory round trip of its own wherever it is first needed, behind the barriers and in front of the bonus tables)
+    const u32 wg_size = blockDim.x;
+    __builtin_assume(wg_size == FZB_SEG_DIRECT);
+    auto load_span = [&](u32 jo, u32 li, u64& s, u32& L) {
+        s = 0; L = 0;
+        if (jo != NONE) haystack_span_u(ends, ulen, first + li, s, L);
+    };
+    auto load_vecs = [&](u64 s, u32 L, uint4& q0, uint4& q1) {
+        q0 = make_uint4(0, 0, 0, 0);
+        q1 = make_uint4(0, 0, 0, 0);
+        const uint4* vp = (const uint4*)(bytes + s);
+        if (L > 0) q0 = vp[0];
+        if (SWL > 32 && L > 16) q1 = vp[1];
+    };
+    // ---- 1. the segment's own count (one word), the thread's sixteen counts, then the direct item's list entry ----------------------------
+    // The ORDER of the requests and of the waits below is what this form is for, and it is the compiler's to keep: after a compiler update,
+    // read the s_waitcnt of this prologue in the ISA again (profiles/seg_direct.txt, section 4, says what each misplaced wait cost).
+    // (the entry's address needs no prefix; the count only says which lanes hold one - lanes beyond it read nothing: the list has no room
+    // beyond the range's tiles, and a segment without survivors costs no memory access)
+    const bool own = b < seg.nseg;
+    // (a VECTOR load although the address is wave-uniform, hence the lane index the compiler cannot see through: as a scalar load it shares
+    // its counter with the kernel-argument fetches, and the first wait for one of those - in front of the bonus tables' own loads - would
+    // wait for it too, one more dependent round trip in every launch, an empty one included)
+    u32 lane_zero = t;
+    asm volatile("" : "+v"(lane_zero));
+    const u32 cb_any = seg.counts[(own ? b : 0u) + (lane_zero >> 31)];
+    u32 sc[16];
+    const uint4* c4 = (const uint4*)seg.counts;  // (the array has FZB_SEG_MAX words whatever nseg is: read without a branch, masked below)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const u32 i0 = 16u * t + 4u * k;
+        const uint4 v = c4[4 * t + k];
+        sc[4 * k] = i0 < seg.nseg ? v.x : 0u;
+        sc[4 * k + 1] = i0 + 1 < seg.nseg ? v.y : 0u;
+        sc[4 * k + 2] = i0 + 2 < seg.nseg ? v.z : 0u;
+        sc[4 * k + 3] = i0 + 3 < seg.nseg ? v.w : 0u;
+    }
+    // (the bonus tables here, beside the counts: the needle's scoring words are vector loads of their own, and a wait for a vector load is a
+    // wait for every one in front of it - behind the rows' requests it would hold the prefixes back until the rows are there)
+    cf_build_tables<UPPER>(nd, tab);
+    const bool has_c = own && t < seg_direct(cb_any, b, G);
+    u32 li_c = 0;
+    if (has_c) li_c = seg.list[(size_t)b * seg.stride + t];
+    u32 sr[16], tot = 0, rtot = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        sr[k] = seg_rest(sc[k], 16u * t + k, G);
+        tot += sc[k];
+        rtot += sr[k];
+    }
+    asm volatile("" : "+v"(tot), "+v"(rtot));  // (the counts are taken HERE, for the same reason: no wait for them behind the rows' requests)
+    // ---- 2. the direct item's row, as soon as its entry is there ------------------------------------------------------------------------
+    u32 jo_c = has_c ? 0u : NONE;  // (the position itself needs the prefix: set behind the barriers)
+    u64 s_c;
+    u32 L_c;
+    uint4 q0_c, q1_c;
+    load_span(jo_c, li_c, s_c, L_c);
+    load_vecs(s_c, L_c, q0_c, q1_c);
+    // ---- 3. both prefixes: with the rows in flight ------------------------------------------------------------------------------------
+    u32 incl = tot, rincl = rtot;
+    for (int off = 1; off < 64; off <<= 1) {
+        const u32 v = __shfl_up(incl, off), rv = __shfl_up(rincl, off);
+        if ((t & 63) >= (u32)off) { incl += v; rincl += rv; }
+    }
+    if ((t & 63) == 63) { seg_wsum[t >> 6] = incl; seg_wsum[2 + (t >> 6)] = rincl; }
+    __syncthreads();
+    const u32 M = __builtin_amdgcn_readfirstlane(seg_wsum[0] + seg_wsum[1]);  // wave-uniform: keeps the loop control on the scalar unit
+    const u32 R = __builtin_amdgcn_readfirstlane(seg_wsum[2] + seg_wsum[3]);  // the pool's size
+    {
+        u32 run = (t >= 64 ? seg_wsum[0] : 0u) + incl - tot, rrun = (t >= 64 ? seg_wsum[2] : 0u) + rincl - rtot;
+        if (R) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                seg_pre[16 * t + k] = run;
+                seg_rpre[16 * t + k] = rrun;
+                run += sc[k];
+                rrun += sr[k];
+            }
+        } else {
+            // no pool (no segment holds more than the direct round takes - a selective query, an empty launch): nothing is searched, and the
+            // one prefix anybody reads is this workgroup's own - one LDS store, by the thread that holds it, instead of thirty-two by each
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                if (16 * t + k == b) seg_pre[b] = run;
+                run += sc[k];
+            }
+        }
+    }
+    __syncthreads();
+    if (b == 0 && t == 0) {
+        *seg.total_out = M;  // counters[0]: fzb_last_counters' filter_survivors
+        if (dev_count) { dev_count[0] = M < capacity ? M : capacity; dev_count[1] = M; }
+        if (kept_out) *kept_out = M;
+    }
+    if (has_c) jo_c = seg_pre[own ? b : 0u] + t;
+    // ---- the pool: grid-strided, three-deep software pipeline over the dependent loads of one item (see k2b_dp) behind the direct item ----
+    const u32 stride = G * FZB_SEG_DIRECT, j0 = b * FZB_SEG_DIRECT + t;
+    auto load_pool = [&](u64 jp, u32& li, u32& jo) {
+        li = 0; jo = NONE;
+        if (jp < R) {
+            // (over all FZB_SEG_MAX entries - those at and beyond nseg hold the pool's size, which no jp reaches: eleven fixed steps without a loop,
+            // so that the two searches in front of the pipeline interleave and the one inside it overlaps the scoring)
+            const SegItem it = seg_pool_item(seg_pre, seg_rpre, FZB_SEG_MAX, FZB_SEG_MAX / 2, G, (u32)jp);
+            li = seg.list[(size_t)it.seg * seg.stride + it.slot];
+            jo = it.pos;
+        }
+    };
+    u32 li_n, jo_n, L_n, li_m, jo_m;
+    u64 s_n;
+    load_pool(j0, li_n, jo_n);
+    load_pool((u64)j0 + stride, li_m, jo_m);
+    load_span(jo_n, li_n, s_n, L_n);
+    // issue priority follows the wave's progress through its share (kernels_common.h, FzbProgressPrio): the direct item and its pool items
+    const u32 jw = __builtin_amdgcn_readfirstlane(j0);  // the wave's first pool item (lane 0's)
+    const u32 n_pool = jw < R ? (R - jw - 1u) / stride + 1u : 0u;
+    const u32 n_iter = (n_pool || __any((int)has_c)) ? 1u + n_pool : 0u;  // (a wave with nothing to score does not enter the loop: an empty launch ends here)
+    struct MidItem {
+        FzbProgressPrio* p;
+        __device__ __forceinline__ void operator()() const { p->k2 += 1; p->apply(); }
+    };
+    FzbProgressPrio prio{0u, 2 * n_iter};
+    u64 jp_f = (u64)j0 + 2 * (u64)stride;
+    for (u32 k = 0; k < n_iter; k++, jp_f += stride) {
+        prio.apply();
+        uint4 q0_n, q1_n;
+        load_vecs(s_n, L_n, q0_n, q1_n);
+        u64 s_m;
+        u32 L_m;
+        load_span(jo_m, li_m, s_m, L_m);
+        u32 li_f, jo_f;
+        load_pool(jp_f, li_f, jo_f);
+        if (jo_c < capacity) {
+            u32 ws, we;
+            cf_window_first_last_regs(nd, q0_c, q1_c, ws, we);
+            dp_short_item<SWL, UPPER>(nd, tab, q0_c, q1_c, L_c, ws, we, index_offset + li_c, &out[jo_c], MidItem{&prio});
+        }
+        li_c = li_n; jo_c = jo_n; s_c = s_n; L_c = L_n; q0_c = q0_n; q1_c = q1_n;
+        li_n = li_m; jo_n = jo_m; s_n = s_m; L_n = L_m;
+        li_m = li_f; jo_m = jo_f;
+        prio.k2 = (prio.k2 | 1u) + 1;  // next item
+    }
+}
+
 template <int SWL, bool UPPER, bool SEG = false>
 __global__ __launch_bounds__(128, 4) void k2b_dp_short(const u8* __restrict__ bytes, const EndsAny ends, u64 first, u32 index_offset,
                                                     const u32* __restrict__ items, const u32* __restrict__ win, const u32* __restrict__ n_items_ptr,
                                                     const NeedleDev nd, int wmode, fzb_match_rec* __restrict__ out, u32 capacity, u32* __restrict__ dev_count,
                                                     RejectOut rej, u32* __restrict__ kept_out, u32 ulen, std::conditional_t<SEG, SegList, SegNone> seg) {
     FZB_TIMING_BEGIN
+    if constexpr (SEG) {  // (the rest of this function is the dense form)
+        dp_short_seg<SWL, UPPER>(bytes, ends, first, index_offset, nd, out, capacity, dev_count, kept_out, ulen, seg);
+        FZB_TIMING_END
+        return;
+    }
     __shared__ CfTables tab;
     __shared__ u8 fl[256];
-    __shared__ u32 seg_pre[SEG ? FZB_SEG_MAX : 1u];  // exclusive prefix of the segment counts; entries at and beyond nseg hold the total
-    __shared__ u32 seg_wsum[2];
-    u32 sc[16];  // SEG: the thread's sixteen counts
-    if constexpr (SEG) {
-        const uint4* c4 = (const uint4*)seg.counts;  // (the array has FZB_SEG_MAX words whatever nseg is)
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const u32 i0 = 16u * threadIdx.x + 4u * k;
-            const uint4 v = i0 < seg.nseg ? c4[4 * threadIdx.x + k] : make_uint4(0, 0, 0, 0);
-            sc[4 * k] = v.x;
-            sc[4 * k + 1] = i0 + 1 < seg.nseg ? v.y : 0u;
-            sc[4 * k + 2] = i0 + 2 < seg.nseg ? v.z : 0u;
-            sc[4 * k + 3] = i0 + 3 < seg.nseg ? v.w : 0u;
-        }
-    }
     cf_build_tables<UPPER>(nd, tab);
     if (wmode == 3) cf_build_typo_table(nd, fl);
-    u32 seg_incl = 0, seg_tot = 0;
-    if constexpr (SEG) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) seg_tot += sc[k];
-        seg_incl = seg_tot;
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 v = __shfl_up(seg_incl, off);
-            if ((threadIdx.x & 63) >= (u32)off) seg_incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) seg_wsum[threadIdx.x >> 6] = seg_incl;
-    }
     __syncthreads();
-    u32 M_;
-    if constexpr (SEG) {
-        u32 run = (threadIdx.x >= 64 ? seg_wsum[0] : 0u) + seg_incl - seg_tot;
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            seg_pre[16 * threadIdx.x + k] = run;
-            run += sc[k];
-        }
-        M_ = seg_wsum[0] + seg_wsum[1];
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) *seg.total_out = M_;  // counters[0]: fzb_last_counters' filter_survivors
-    } else {
-        M_ = *n_items_ptr;
-    }
-    const u32 M = __builtin_amdgcn_readfirstlane(M_);  // wave-uniform: keeps the loop control on the scalar unit
+    const u32 M = __builtin_amdgcn_readfirstlane(*n_items_ptr);  // wave-uniform: keeps the loop control on the scalar unit
     // wmode 3 (typos): survivors that the decide pass rejected (rare) are skipped and the records behind them move up
     const u32 nrej = wmode == 3 ? __builtin_amdgcn_readfirstlane(*rej.count) : 0u;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -227,14 +379,7 @@ __global__ __launch_bounds__(128, 4) void k2b_dp_short(const u8* __restrict__ by
     auto load_item = [&](u64 j, u32& li, u32& ws, u32& we) {
         li = 0; ws = 0; we = 0;
         if (j < M) {
-            if constexpr (SEG) {  // the last segment whose prefix is <= j holds survivor j (empty segments share their successor's prefix)
-                // (over all FZB_SEG_MAX entries - those at and beyond nseg hold the total, which no j reaches: eleven fixed steps without a loop,
-                // so that the three searches in front of the pipeline interleave and the one inside it overlaps the scoring)
-                const u32 sg = seg_find(seg_pre, FZB_SEG_MAX, FZB_SEG_MAX / 2, (u32)j);
-                li = seg.list[(size_t)sg * seg.stride + ((u32)j - seg_pre[sg])];
-            } else {
-                li = items ? items[j] : (u32)j;
-            }
+            li = items ? items[j] : (u32)j;
             if (wmode == 0) { const uint2 w = *(const uint2*)(win + 2 * j); ws = w.x; we = w.y; }
         }
     };
@@ -291,26 +436,7 @@ __global__ __launch_bounds__(128, 4) void k2b_dp_short(const u8* __restrict__ by
             if (wmode == 2) { ws = 0; we = L; }
             else if (wmode == 1) cf_window_first_last_regs(nd, q0_c, q1_c, ws, we);
             else if (wmode == 3) cf_window_typos_regs(fl, q0_c, q1_c, L, ws, we);
-            // ---- trim_haystack (matcher/algo.rs:332-338) --------------------------------------------------
-            const u32 sp = ws ? ws - 1 : 0;
-            const bool include_exact = sp == 0 && we == L;
-            const u32 m = we - sp;
-            u32 score = 0;
-            u32 hb[SWL / 4];
-#pragma unroll
-            for (int k = 0; k < SWL / 4; k++) hb[k] = 0;
-            if (m > 0) {
-                load_window_regs<SWL / 4>(q0_c, q1_c, sp, m, hb);
-                score = dp_single_chunk_cf_tab<SWL, UPPER, SWL / 4, MidItem>(nd, sp == 0, tab, hb, MidItem{&prio});
-            }
-            const bool exact = exact_match<SWL / 4>(nd, include_exact, m, hb);
-            if (exact) score = (score + nd.exact_bonus) & 0xFFFF;
-            fzb_match_rec rec;
-            rec.index = index_offset + li_c;
-            rec.score = (u16)score;
-            rec.exact = exact ? 1 : 0;
-            rec.valid = 0;
-            out[jo] = rec;
+            dp_short_item<SWL, UPPER>(nd, tab, q0_c, q1_c, L, ws, we, index_offset + li_c, &out[jo], MidItem{&prio});
         }
         li_c = li_n; ws_c = ws_n; we_c = we_n; s_c = s_n; L_c = L_n; q0_c = q0_n; q1_c = q1_n;
         li_n = li_m; ws_n = ws_m; we_n = we_m; s_n = s_m; L_n = L_m;
@@ -1067,7 +1193,8 @@ void fzb_launch_dp(const CorpusDev& c, u64 first, u32 index_offset, const u32* i
         const RejectOut rj = rejects ? *rejects : RejectOut{};
         u32* kept_out = rejects ? &counters[1] : nullptr;
         // every haystack fits half a chunk (and the two prefetched vectors): the short-haystack kernel
-#define FZB_K2S(SWL, U, SEG, SA)                                                                                                        \
+        static_assert(FZB_SEG_DIRECT == 128, "dp_short_seg takes one direct item per thread and tells the compiler its workgroup has FZB_SEG_DIRECT threads: the launch below must have as many");
+#define FZB_K2S(SWL, U, SEG, SA)                                                                                                     \
     do {                                                                                                                                \
         static int per_cu = 0;                                                                                                          \
         if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k2b_dp_short<SWL, U, SEG>, 128, 0) != hipSuccess || per_cu < 1)) per_cu = 4; \
