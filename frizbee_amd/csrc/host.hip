@@ -37,6 +37,17 @@ namespace {
 
 thread_local std::string g_err;
 inline int fail(int code, const std::string& msg) { return fzb_fail(code, msg); }
+// the three refusals many entry points share.  `items` haystacks numbered from index_offset pass the u32 index space; an output / positions
+// buffer of `capacity` entries is smaller than the `want` the bound (`of`: "min(limit, haystacks)", ..) asks for
+int refuse_index_overflow(u64 items, u64 index_offset = 0) {
+    return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(items) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+}
+int refuse_small_output(const char* of, size_t capacity, size_t want) {
+    return fail(FZB_ERR_CAPACITY, std::string("output buffer smaller than ") + of + ": " + std::to_string(capacity) + " < " + std::to_string(want));
+}
+int refuse_small_positions(const char* of, size_t capacity, size_t want) {
+    return fail(FZB_ERR_CAPACITY, std::string("positions buffer smaller than ") + of + " x needle bytes: " + std::to_string(capacity) + " < " + std::to_string(want));
+}
 
 // ---- UTF-8 / case helpers ---------------------------------------------------------------------------
 bool decode_utf8(const u8* s, size_t n, std::vector<u32>& out) {
@@ -334,7 +345,7 @@ void fzb_scope_release(ScopeScratch& s) {
 }
 int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_records) {
     if (int rc = fzb_grow_dev(&s.words, &s.words_cap, fzb_sections_scratch_words(n_records), 16)) return rc;
-    return stage_records ? fzb_grow_dev(&s.stage, &s.stage_words, 32 + 2 * stage_records, 16) : FZB_OK;
+    return stage_records ? fzb_grow_dev(&s.stage, &s.stage_words, SEC_STAGE_RECORDS + 2 * stage_records, 16) : FZB_OK;
 }
 int fzb_sections_ensure_slabs(SectionsScratch& s, size_t slab_records) { return fzb_grow_dev(&s.slabs, &s.slabs_words, SECTIONS_SLAB_WORDS + 2 * slab_records, 16); }
 void fzb_sections_release(SectionsScratch& s) {
@@ -342,6 +353,22 @@ void fzb_sections_release(SectionsScratch& s) {
     if (s.stage) (void)hipFree(s.stage);
     if (s.slabs) (void)hipFree(s.slabs);
     s = SectionsScratch{};
+}
+int fzb_top_ensure(TopStaging& t, size_t want, size_t position_words, bool staging) {
+    int rc;
+    if (!t.head || !t.tiles || t.cap < want) {
+        t.cap = 0;
+        if ((rc = fzb_dev_renew(&t.head, want + 16)) || (rc = fzb_dev_renew(&t.tiles, fzb_indices_pack_tile_words(want)))) return rc;
+        t.cap = want;
+    }
+    if (!staging) return FZB_OK;
+    if ((rc = fzb_grow_dev(&t.packed, &t.packed_cap, want, 1))) return rc;
+    return fzb_grow_dev(&t.dense, &t.dense_words, position_words, 1);
+}
+void fzb_top_release(TopStaging& t) {
+    for (void* p : {(void*)t.head, (void*)t.tiles, (void*)t.packed, (void*)t.dense})
+        if (p) (void)hipFree(p);
+    t = TopStaging{};
 }
 void fzb_out_release(OutStaging& o) {
     if (o.out_dev) (void)hipFree(o.out_dev);
@@ -356,8 +383,8 @@ static void release_state(MatcherState& s) {
     fzb_out_release(s);
     fzb_scope_release(s.scope);
     fzb_sections_release(s.sections);
-    for (void* p : {(void*)s.top_words, (void*)s.trace_sel, (void*)s.trace_pos, (void*)s.trace_npos, (void*)s.top_head, (void*)s.top_traced, (void*)s.top_idx_words, (void*)s.top_tiles,
-                    (void*)s.top_packed, (void*)s.top_dense, s.long_blob_dev, (void*)s.long_scratch})
+    fzb_top_release(s.top);
+    for (void* p : {(void*)s.top_words, (void*)s.trace_sel, (void*)s.trace_pos, (void*)s.trace_npos, (void*)s.top_traced, (void*)s.top_idx_words, s.long_blob_dev, (void*)s.long_scratch})
         if (p) (void)hipFree(p);
     for (auto& tr : s.evring)
         for (auto& e : tr)
@@ -1077,7 +1104,7 @@ extern "C" {
 int fzb_corpus_from_device(const void* dev_bytes, const void* dev_ends, int ends_are_u64, size_t n, uint64_t total_bytes, fzb_corpus** out) {
     if (!out || (n && (!dev_bytes || !dev_ends))) return fail(FZB_ERR_INVALID, "null argument");
     if (((uintptr_t)dev_bytes & 15) != 0) return fail(FZB_ERR_INVALID, "dev_bytes must be 16-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     auto c = new fzb_corpus();
     c->dev.bytes = (const u8*)dev_bytes;
     c->dev.ends = dev_ends;
@@ -1282,7 +1309,7 @@ int fzb_out_ensure(OutStaging& o, size_t count) {  // device-side result of the 
     o.out_cap = 0;
     if (int rc = fzb_dev_renew(&o.out_dev, count + 16)) return rc;
     o.out_cap = count;
-    if (!o.count_dev) HIPCHK(fzb_dev_alloc((void**)&o.count_dev, 64));
+    if (!o.count_dev) HIPCHK(fzb_dev_alloc((void**)&o.count_dev, OUT_WORDS * sizeof(u32)));
     return FZB_OK;
 }
 
@@ -1488,7 +1515,7 @@ static int prompt_top_stage(fzb_matcher* m, const fzb_corpus* c, const fzb_subse
     bool reversed, by_score, one_pass;
     prompt_order_flags(m, c, &reversed, &by_score, &one_pass);
     Workspace& w = m->ws;
-    u32* const raw_count = m->count_dev + 4;  // the producer's pair (records written, visible haystacks)
+    u32* const raw_count = m->count_dev + OUT_RAW;  // the producer's pair (records written, visible haystacks)
     if ((rc = prompt_records(m, c, in, 0, n, 0, w.sort.tmp, n, raw_count, st))) return rc;
     const u32 ntiles_cap = (u32)(w.sort.cap / 2048 + 2);
     const int grid = m->lc.num_cus * 2;
@@ -2099,8 +2126,7 @@ static int run_pipeline(fzb_matcher* m, const fzb_corpus* c, size_t first, size_
     // an item list may repeat haystacks, so only the contiguous form bounds `count` by the corpus
     if (first > c->dev.n || (!items_in && count > c->dev.n - first)) return fail(FZB_ERR_INVALID, "range outside the corpus");
     // guard_against_haystack_overflow (src/matcher/mod.rs:438-446)
-    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
-        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull) return refuse_index_overflow((u64)count + index_offset, index_offset);
     if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list / fzb_match_list_into");
     hipStream_t st = (hipStream_t)stream;
     int rc = fzb_bind_device(m);
@@ -2159,8 +2185,8 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (rc) return rc;
     if (m->empty) {  // the empty prompt (prompt_records): flag words, the sort's buffers (the selection's input) and the staging - with or without a scope or a bias
         if ((rc = fzb_scope_ensure_flags(m->scope, n)) || (rc = fzb_ensure_out_staging(m, n)) || (rc = ensure_sort_buffers(m, n))) return rc;
-        if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, 32, hipHostMallocDefault));
-        if (!m->fetch.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch.count_host, 32, hipHostMallocDefault));
+        if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));
+        if (!m->fetch.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));
         return FZB_OK;
     }
     rc = ensure_workspace(m, n);
@@ -2174,7 +2200,7 @@ int fzb_matcher_reserve(fzb_matcher* m, const fzb_corpus* c) {
     if (!m->long_needle && !m->literal_mode && m->nd.unicode && m->lc.bias_ok && !no_wide && m->nd.max_typos < 0 && (rc = ensure_aux_stream(m))) return rc;  // whole-haystack windows: the wide ones on the second stream
     if ((rc = fzb_ensure_out_staging(m, n))) return rc;
     if ((rc = ensure_sort_buffers(m, n))) return rc;
-    if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, 32, hipHostMallocDefault));  // (a top query's pinned count words)
+    if (!m->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&m->fetch_top.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));  // (a top query's pinned count words)
     return FZB_OK;
 }
 
@@ -2394,7 +2420,7 @@ hipError_t fzb_stream_wait(hipStream_t st) {
 }
 // (dev_words: eight u32 in device memory, all copied to h.count_host; the record count is word `n_word`)
 int fzb_fetch_records(FetchHint& h, const void* dev_records, const u32* dev_words, int n_word, size_t capacity, hipStream_t st, fzb_match** out, size_t* out_len) {
-    if (!h.count_host) HIPCHK(hipHostMalloc((void**)&h.count_host, 32, hipHostMallocDefault));
+    if (!h.count_host) HIPCHK(hipHostMalloc((void**)&h.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));
     // the guess: the previous result's size and a little more (every speculated record that does not exist is copied for nothing - a
     // quarter more cost 19 us on a 4 MB result, more than the synchronisation it saves); the buffer has room for half as many again, so a
     // result that outgrew the guess usually only needs its remainder copied
@@ -2402,7 +2428,7 @@ int fzb_fetch_records(FetchHint& h, const void* dev_records, const u32* dev_word
     size_t room = std::min(capacity, guess + guess / 2);
     fzb_match* r = (fzb_match*)pinned_pool().get(std::max<size_t>(room, 1) * sizeof(fzb_match));
     if (!r) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
-    hipError_t e = hipMemcpyAsync(h.count_host, dev_words, 32, hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(h.count_host, dev_words, OUT_FETCH_WORDS * sizeof(u32), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && guess) e = hipMemcpyAsync(r, dev_records, guess * sizeof(fzb_match), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = fzb_stream_wait(st);
     const size_t n = e == hipSuccess ? (size_t)h.count_host[n_word] : 0;
@@ -2442,8 +2468,7 @@ extern "C" {
 int fzb_match_list_into(fzb_matcher* m, const fzb_corpus* c, size_t first, size_t count, uint32_t index_offset, fzb_match** out, size_t* out_len) {
     if (!m || !c || !out || !out_len) return fail(FZB_ERR_INVALID, "null argument");
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
-    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
-        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull) return refuse_index_overflow((u64)count + index_offset, index_offset);
     *out = nullptr;
     *out_len = 0;
     if (prompt_on_device(m, c, nullptr, count)) return prompt_list_host(m, c, nullptr, first, count, index_offset, false, out, out_len);  // the empty prompt, index order
@@ -2517,8 +2542,7 @@ namespace {
 int check_selection(const fzb_corpus* c, const uint32_t* selection, size_t n_selection, size_t& count, uint32_t index_offset = 0) {
     count = selection ? n_selection : (size_t)c->dev.n;
     if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)  // guard_against_haystack_overflow(haystacks.len(), 0), mod.rs:235
-        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " +
-                                       std::to_string(index_offset) + ")");
+        return refuse_index_overflow((u64)count + index_offset, index_offset);
     for (size_t i = 0; i < n_selection; i++)
         if (selection[i] >= c->dev.n) return fail(FZB_ERR_INVALID, "selection entry outside the corpus");
     return FZB_OK;
@@ -2830,14 +2854,13 @@ static void multi_free_group_buffers(fzb_multi_matcher* mm) {
 }
 static void multi_release(fzb_multi_matcher* mm) {  // every device buffer and pinned word the composition itself owns
     multi_free_buffers(mm);
-    for (void* p : {(void*)mm->top_head, (void*)mm->top_comb, (void*)mm->top_items, (void*)mm->top_npos_u, (void*)mm->top_tiles, (void*)mm->top_words, (void*)mm->top_pos_u,
-                    (void*)mm->union_src, (void*)mm->union_cursors, (void*)mm->top_packed, (void*)mm->top_dense})
+    fzb_top_release(mm->top);
+    for (void* p : {(void*)mm->top_comb, (void*)mm->top_items, (void*)mm->top_npos_u, (void*)mm->top_words, (void*)mm->top_pos_u, (void*)mm->union_src, (void*)mm->union_cursors})
         if (p) (void)hipFree(p);
-    mm->top_head = mm->top_comb = nullptr;
-    mm->top_items = mm->top_npos_u = mm->top_tiles = mm->top_words = mm->top_pos_u = mm->union_cursors = mm->top_dense = nullptr;
+    mm->top_comb = nullptr;
+    mm->top_items = mm->top_npos_u = mm->top_words = mm->top_pos_u = mm->union_cursors = nullptr;
     mm->union_src = nullptr;
-    mm->top_packed = nullptr;
-    mm->top_cap = mm->top_pos_u_words = mm->union_src_cap = mm->union_cursor_words = mm->top_packed_cap = mm->top_dense_words = 0;
+    mm->top_rec_cap = mm->top_pos_u_words = mm->union_src_cap = mm->union_cursor_words = 0;
     mm->union_src_host.clear();
     for (void* p : {(void*)mm->gunion_where, (void*)mm->gunion_src, (void*)mm->gunion_scratch})
         if (p) (void)hipFree(p);
@@ -2859,7 +2882,7 @@ static int multi_ensure_buffers(fzb_multi_matcher* mm, size_t count) {
     const size_t cap = count + count / 8 + 4096;
     HIPCHK(dev_alloc((void**)&mm->cand[0], (cap + 16) * sizeof(fzb_match_rec)));
     HIPCHK(dev_alloc((void**)&mm->cand[1], (cap + 16) * sizeof(fzb_match_rec)));
-    HIPCHK(dev_alloc((void**)&mm->counts, 64));
+    HIPCHK(dev_alloc((void**)&mm->counts, MCOUNT_SLOTS * MCOUNT_SLOT_WORDS * sizeof(u32)));
     HIPCHK(dev_alloc((void**)&mm->items, cap * 4));
     HIPCHK(dev_alloc((void**)&mm->bitmap, (cap / 64 + 17) * 8));
     HIPCHK(dev_alloc((void**)&mm->tile_counts, (((cap + FZB_TILE - 1) / FZB_TILE + 5) & ~(size_t)3) * 4));  // (as the workspace's: a multiple of four entries)
@@ -3132,8 +3155,8 @@ int fzb_multi_matcher_reserve(fzb_multi_matcher* mm, const fzb_corpus* c) {
     if ((rc = multi_ensure_buffers(mm, n)) || (rc = fzb_out_ensure(*mm, n)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;
     if (mm->grouped && (rc = multi_ensure_group_buffers(mm))) return rc;
     if ((c->tags.data || mm->facets) && n && (rc = fzb_scope_ensure(mm->scope, n))) return rc;  // (a corpus that carries tags, or a facet sink: the composition's records ahead of the drop / the count)
-    if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, 32, hipHostMallocDefault));
-    if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, 32, hipHostMallocDefault));
+    if (!mm->fetch.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));
+    if (!mm->fetch_top.count_host) HIPCHK(hipHostMalloc((void**)&mm->fetch_top.count_host, OUT_FETCH_WORDS * sizeof(u32), hipHostMallocDefault));
     return FZB_OK;
 }
 
@@ -3198,7 +3221,7 @@ static int multi_compose_groups(fzb_multi_matcher* mm, const fzb_corpus* c, size
     for (size_t t = 0; t < terms.size(); t++)
         if (!ps[terms[t].b].negated) { base = t; break; }  // (a group has no negated alternative; a grouped matcher has a non-negated term)
     const u32 n_max = (u32)count;
-    u32* const hit_count = &mm->counts[4 * 3];
+    u32* const hit_count = fzb_multi_count(mm, MCOUNT_ALTERNATIVE);
     int cur = 0;
     // the group `t` over the candidates cand[cur] (cand_in == nullptr: as the base term) -> cand[dst]
     auto run_group = [&](const Term& t, const fzb_match_rec* cand_in, const u32* n_ptr, const u32* slot_items, u32 n_bound, int dst) -> int {
@@ -3211,44 +3234,44 @@ static int multi_compose_groups(fzb_multi_matcher* mm, const fzb_corpus* c, size
             fzb_launch_anyof_accumulate(mm->group_hits, hit_count, (u32)std::min<size_t>(mm->group_cap, 0xFFFFFFFFu), mm->group_slots, n_ptr, n_max, n_bound, index_offset, slot_items, cand_in,
                                         cus * 4, st);
         }
-        fzb_launch_anyof_keep(mm->group_slots, n_ptr, n_max, n_bound, index_offset, slot_items, cand_in, mm->bitmap, mm->tile_counts, mm->cand[dst], &mm->counts[4 * dst], cus * 2, st);
+        fzb_launch_anyof_keep(mm->group_slots, n_ptr, n_max, n_bound, index_offset, slot_items, cand_in, mm->bitmap, mm->tile_counts, mm->cand[dst], fzb_multi_count(mm, dst), cus * 2, st);
         return FZB_OK;
     };
     const Term& bt = terms[base];
     if (bt.e - bt.b >= 2) {
         const u32 n_bound = subset_items(sa) ? (u32)std::min<u64>(subset_hint(sa), count) : n_max;
         if ((rc = run_group(bt, nullptr, subset_count(sa), subset_items(sa), n_bound, 0))) return rc;
-    } else if ((rc = run_pipeline(ps[bt.b].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], st, nullptr,
+    } else if ((rc = run_pipeline(ps[bt.b].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, fzb_multi_count(mm, 0), st, nullptr,
                                   subset_hint(sa)))) {
         return rc;
     }
     for (size_t ti = 0; ti < terms.size(); ti++) {
         if (ti == base) continue;
         const Term& t = terms[ti];
-        fzb_launch_records_to_items(mm->cand[cur], &mm->counts[4 * cur], index_offset, mm->items, cus * 2, st);
+        fzb_launch_records_to_items(mm->cand[cur], fzb_multi_count(mm, cur), index_offset, mm->items, cus * 2, st);
         const int oth = cur ^ 1;
         if (t.e - t.b >= 2) {
-            if ((rc = run_group(t, mm->cand[cur], &mm->counts[4 * cur], nullptr, n_max, oth))) return rc;
+            if ((rc = run_group(t, mm->cand[cur], fzb_multi_count(mm, cur), nullptr, n_max, oth))) return rc;
         } else if (!ps[t.b].negated) {
-            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)mm->cand[oth], mm->cap, &mm->counts[4 * oth], st))) return rc;
-            fzb_launch_join_add(mm->cand[oth], &mm->counts[4 * oth], mm->cand[cur], &mm->counts[4 * cur], cus * 2, st);
+            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, fzb_multi_count(mm, cur), (fzb_match*)mm->cand[oth], mm->cap, fzb_multi_count(mm, oth), st))) return rc;
+            fzb_launch_join_add(mm->cand[oth], fzb_multi_count(mm, oth), mm->cand[cur], fzb_multi_count(mm, cur), cus * 2, st);
         } else {
             fzb_match_rec* hits = mm->cand[oth];  // (as multi_compose_device: read by the flag pass, then overwritten by the compaction)
-            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)hits, mm->cap, &mm->counts[4 * 2], st))) return rc;
-            fzb_launch_remove_hits(mm->cand[cur], &mm->counts[4 * cur], hits, &mm->counts[4 * 2], mm->bitmap, mm->tile_counts, mm->cand[oth], &mm->counts[4 * oth], cus * 2, st);
+            if ((rc = run_pipeline(ps[t.b].m, c, first, count, index_offset, mm->items, fzb_multi_count(mm, cur), (fzb_match*)hits, mm->cap, fzb_multi_count(mm, MCOUNT_NEGATED), st))) return rc;
+            fzb_launch_remove_hits(mm->cand[cur], fzb_multi_count(mm, cur), hits, fzb_multi_count(mm, MCOUNT_NEGATED), mm->bitmap, mm->tile_counts, mm->cand[oth], fzb_multi_count(mm, oth), cus * 2, st);
         }
         cur = oth;
     }
     if (sa && sa->capture && captured && g_debug_fused_capture) {
         fzb_subset* cp = sa->capture;
-        fzb_launch_copy_capture_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
+        fzb_launch_copy_capture_records(mm->cand[cur], fzb_multi_count(mm, cur), (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
                                         cp->count_dev, sa->mirror, cus * 2, st);
         HIPCHK(hipGetLastError());
         subset_captured(cp, c);
         *captured = true;
         return FZB_OK;
     }
-    fzb_launch_copy_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
+    fzb_launch_copy_records(mm->cand[cur], fzb_multi_count(mm, cur), (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
@@ -3261,8 +3284,7 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
                                 uint32_t* dev_count, void* stream, const SubsetArgs* sa = nullptr, bool* captured = nullptr) {
     if (!mm || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
-    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
-        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull) return refuse_index_overflow((u64)count + index_offset, index_offset);
     hipStream_t st = (hipStream_t)stream;
     if (!mm->num_cus) HIPCHK((hipError_t)fzb_effective_cus(&mm->num_cus));
     const int cus = mm->num_cus;
@@ -3293,44 +3315,44 @@ static int multi_compose_device(fzb_multi_matcher* mm, const fzb_corpus* c, size
     int cur = 0;  // cand[cur] / counts[cur] = the candidates
     int rc;
     if (base != ps.size()) {
-        rc = run_pipeline(ps[base].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, &mm->counts[4 * 0], stream, nullptr, subset_hint(sa));
+        rc = run_pipeline(ps[base].m, c, first, count, index_offset, subset_items(sa), subset_count(sa), (fzb_match*)mm->cand[0], mm->cap, fzb_multi_count(mm, 0), stream, nullptr, subset_hint(sa));
         if (rc) return rc;
     } else if (subset_items(sa)) {  // all patterns negated over a candidate set: every haystack of the set is a candidate
-        fzb_launch_items_records(mm->cand[0], subset_items(sa), subset_count(sa), (u32)std::min<size_t>(mm->cap, count), (u32)std::min<u64>(subset_hint(sa), count), index_offset, &mm->counts[4 * 0],
+        fzb_launch_items_records(mm->cand[0], subset_items(sa), subset_count(sa), (u32)std::min<size_t>(mm->cap, count), (u32)std::min<u64>(subset_hint(sa), count), index_offset, fzb_multi_count(mm, 0),
                                  cus * 2, st);
     } else {
-        fzb_launch_identity_records(mm->cand[0], (u32)count, index_offset, &mm->counts[4 * 0], cus * 2, st);  // all patterns negated: every haystack is a candidate
+        fzb_launch_identity_records(mm->cand[0], (u32)count, index_offset, fzb_multi_count(mm, 0), cus * 2, st);  // all patterns negated: every haystack is a candidate
     }
     for (size_t pi = 0; pi < ps.size(); pi++) {
         if (pi == base) continue;
         // (the reference skips the remaining patterns once no candidate is left; with the count on the device the kernels just find nothing to do)
-        fzb_launch_records_to_items(mm->cand[cur], &mm->counts[4 * cur], index_offset, mm->items, cus * 2, st);
+        fzb_launch_records_to_items(mm->cand[cur], fzb_multi_count(mm, cur), index_offset, mm->items, cus * 2, st);
         const int oth = cur ^ 1;
         if (!ps[pi].negated) {
-            rc = run_pipeline(ps[pi].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)mm->cand[oth], mm->cap, &mm->counts[4 * oth], stream);
+            rc = run_pipeline(ps[pi].m, c, first, count, index_offset, mm->items, fzb_multi_count(mm, cur), (fzb_match*)mm->cand[oth], mm->cap, fzb_multi_count(mm, oth), stream);
             if (rc) return rc;
-            fzb_launch_join_add(mm->cand[oth], &mm->counts[4 * oth], mm->cand[cur], &mm->counts[4 * cur], cus * 2, st);
+            fzb_launch_join_add(mm->cand[oth], fzb_multi_count(mm, oth), mm->cand[cur], fzb_multi_count(mm, cur), cus * 2, st);
             cur = oth;
         } else {
             // the negated pattern's hits land in the other slot; k_flag_absent reads them, then k_compact_records (next in stream
             // order) overwrites that same slot with the candidates that were not hit
             fzb_match_rec* hits = mm->cand[oth];
-            rc = run_pipeline(ps[pi].m, c, first, count, index_offset, mm->items, &mm->counts[4 * cur], (fzb_match*)hits, mm->cap, &mm->counts[4 * 2], stream);
+            rc = run_pipeline(ps[pi].m, c, first, count, index_offset, mm->items, fzb_multi_count(mm, cur), (fzb_match*)hits, mm->cap, fzb_multi_count(mm, MCOUNT_NEGATED), stream);
             if (rc) return rc;
-            fzb_launch_remove_hits(mm->cand[cur], &mm->counts[4 * cur], hits, &mm->counts[4 * 2], mm->bitmap, mm->tile_counts, mm->cand[oth], &mm->counts[4 * oth], cus * 2, st);
+            fzb_launch_remove_hits(mm->cand[cur], fzb_multi_count(mm, cur), hits, fzb_multi_count(mm, MCOUNT_NEGATED), mm->bitmap, mm->tile_counts, mm->cand[oth], fzb_multi_count(mm, oth), cus * 2, st);
             cur = oth;
         }
     }
     if (sa && sa->capture && captured && g_debug_fused_capture) {
         fzb_subset* cp = sa->capture;
-        fzb_launch_copy_capture_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
+        fzb_launch_copy_capture_records(mm->cand[cur], fzb_multi_count(mm, cur), (fzb_match_rec*)dev_out, cap32, dev_count, index_offset, cp->idx, (u32)std::min<size_t>(cp->cap, 0xFFFFFFFFu),
                                         cp->count_dev, sa->mirror, cus * 2, st);
         HIPCHK(hipGetLastError());
         subset_captured(cp, c);
         *captured = true;
         return FZB_OK;
     }
-    fzb_launch_copy_records(mm->cand[cur], &mm->counts[4 * cur], (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
+    fzb_launch_copy_records(mm->cand[cur], fzb_multi_count(mm, cur), (fzb_match_rec*)dev_out, cap32, dev_count, cus * 2, st);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
@@ -3508,7 +3530,7 @@ int fzb_fetch_top(FetchHint& h, const void* dev_records, const u32* dev_words, s
     if (max_records <= FZB_TOP_COPY_WHOLE) h.last = max_records;
     int rc = fzb_fetch_records(h, dev_records, dev_words, 0, max_records, st, out, out_len);
     if (rc) return rc;
-    if (out_found) *out_found = h.count_host[1];
+    if (out_found) *out_found = h.count_host[PAIR_FOUND];
     return FZB_OK;
 }
 // CompiledPatterns::Empty: every haystack matches with score 0, reversed for the *Desc strategies, never sorted (mod.rs:215-220, 381-384)
@@ -3540,7 +3562,7 @@ static int top_produce(fzb_matcher* m, const fzb_corpus* c, size_t n, void* stre
     if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
     fzb_order_flags(m, fzb_corpus_bias_hi(c), reversed, by_score, one_pass);
     Workspace& w = m->ws;
-    u32* const raw_count = m->count_dev + 4;  // the pipeline's pair (records written, matches found)
+    u32* const raw_count = m->count_dev + OUT_RAW;  // the pipeline's pair (records written, matches found)
     *raw_count_out = raw_count;
     if (fzb_corpus_scoped(c)) {  // the selection sees the visible haystacks' records only: `found` counts those, the head holds none that is hidden
         if ((rc = fzb_scope_ensure(m->scope, n)) || (rc = run_pipeline(m, c, 0, n, 0, subset_items(sa), subset_count(sa), (fzb_match*)m->scope.recs, n, m->scope.words, stream, nullptr, subset_hint(sa)))) return rc;
@@ -3558,8 +3580,8 @@ static int top_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fz
     if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (capacity < want) return refuse_small_output("min(limit, haystacks)", capacity, want);
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top");
     if (int rc_ = facets_check(m->facets, c, "fzb_match_list_top_device")) return rc_;
     hipStream_t st = (hipStream_t)stream;
@@ -3600,6 +3622,12 @@ int fzb_match_list_top(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_ma
 }
 
 }  // extern "C"
+// the ordering flags of the composition: a matcher without a pattern scores 0 everywhere, so only a bias makes its scores an order
+static void multi_order_flags(const fzb_multi_matcher* mm, const fzb_corpus* c, bool* reversed, bool* by_score) {
+    const int sort = mm->config.sort;
+    *reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
+    *by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+}
 // The top stage of a `from_patterns` matcher on `st`: the composition over the n haystacks into the sort's second buffer (its pair in
 // raw_count), the selection of the best `want` and their ordering into `head` (room for `want` records; its pair - records, matches found -
 // in head_count).  Nothing is read back.
@@ -3609,9 +3637,8 @@ static int multi_top_stage(fzb_multi_matcher* mm, const fzb_corpus* c, size_t n,
     int rc;
     if ((rc = fzb_sort_ensure(mm->sort, n))) return rc;
     if ((rc = multi_match_list_device_impl(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st, sa))) return rc;
-    const int sort = mm->config.sort;
-    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    bool reversed, by_score;
+    multi_order_flags(mm, c, &reversed, &by_score);
     const u32 ntiles_cap = (u32)(mm->sort.cap / 2048 + 2);
     const int grid = mm->num_cus * 2;
     // (summed scores can pass 255: both selection levels, both radix passes - as fzb_multi_match_list orders)
@@ -3635,13 +3662,13 @@ static int multi_match_list_top_impl(fzb_multi_matcher* mm, const fzb_corpus* c,
     if (n == 0) return facets_none(mm->facets, nullptr);
     const size_t want = std::min(limit, n);
     int rc;
-    if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + 4, nullptr, sa))) return rc;
+    if ((rc = fzb_out_ensure(*mm, want)) || (rc = multi_top_stage(mm, c, n, want, mm->out_dev, mm->count_dev, mm->count_dev + OUT_RAW, nullptr, sa))) return rc;
     return fzb_fetch_top(mm->fetch_top, mm->out_dev, mm->count_dev, want, nullptr, out, out_len, out_found);
 }
 
 // ---- top-`limit` with matched positions: one fused device call ------------------------------------------------------------------
 // The reference has no such call: the caller truncates what `Matcher::match_list_indices` returns (src/matcher/mod.rs:234-275).  Here the top
-// stage leaves its sorted head in HBM (m->top_head), k_top_items makes it the item list of a traced second pass (run_pipeline's item form
+// stage leaves its sorted head in HBM (m->top.head), k_top_items makes it the item list of a traced second pass (run_pipeline's item form
 // with a TraceOut: records in head order into m->top_traced - neither the head nor the caller's output -, strided positions into the
 // matched-indices scratch), and the pack kernels (kernels_indices.hip) write the caller's records and dense positions while checking that
 // the two passes agree (the accept decision and the scores of match_list and match_list_indices are the same code in the reference:
@@ -3656,16 +3683,9 @@ namespace {
 int ensure_top_indices_buffers(fzb_matcher* m, size_t want, size_t stride, bool staging) {
     int rc = ensure_trace_buffers(m, want, want * stride);
     if (rc) return rc;
-    if (!m->top_idx_words) HIPCHK(dev_alloc((void**)&m->top_idx_words, 64));
-    if (!m->top_head || !m->top_traced || !m->top_tiles || m->top_cap < want) {
-        m->top_cap = 0;
-        if ((rc = fzb_dev_renew(&m->top_head, want + 16)) || (rc = fzb_dev_renew(&m->top_traced, want + 16)) || (rc = fzb_dev_renew(&m->top_tiles, fzb_indices_pack_tile_words(want))))
-            return rc;
-        m->top_cap = want;
-    }
-    if (!staging) return FZB_OK;
-    if ((rc = fzb_grow_dev(&m->top_packed, &m->top_packed_cap, want, 1))) return rc;
-    return fzb_grow_dev(&m->top_dense, &m->top_dense_words, want * stride, 1);
+    if (!m->top_idx_words) HIPCHK(dev_alloc((void**)&m->top_idx_words, TOPIDX_WORDS * sizeof(u32)));
+    if ((rc = fzb_grow_dev(&m->top_traced, &m->top_traced_cap, want, 16))) return rc;
+    return fzb_top_ensure(m->top, want, want * stride, staging);
 }
 u32 trace_stride(const fzb_matcher* m) { return (u32)std::max(1, m->nd.nbytes); }  // position dwords per record: as indices_in_list_order
 // the traced scorer's matrices for heads of up to `want` records and needles of up to `stride` bytes: one (rows + 1) x TRACE_W slab per wave
@@ -3725,39 +3745,34 @@ int empty_top_indices(const fzb_corpus* c, size_t n, int sort, size_t limit, fzb
     return hand_over_indices(recs.data(), want, nullptr, 0, out, out_len, out_positions);
 }
 
-// The result of a fused query on the null stream -> the caller, with ONE wait for the four words (`words`), the records (`packed`) and the
-// packed positions (`dense`): a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind the words, filled or not (fzb_fetch_top's
+// The result of a fused query on the null stream -> the caller, with ONE wait for the count words (w), the records (t.packed) and the
+// packed positions (t.dense): a head of up to FZB_TOP_COPY_WHOLE records is copied whole behind the words, filled or not (fzb_fetch_top's
 // rule), and so are its positions while they are no more than the records would be at that bound (256 KB); beyond, the copy takes the
 // previous result's size (*last_records, *last_positions) and a little more, and a result that outgrew it costs a second wait.
 // want / max_pos: the most records / positions the result can have.  `disagree`: what a raised inconsistency word means.
-// The sectioned form (SectionWords): `words` are sw->n words, the pack's four at sw->pack; all of them are copied and handed back in sw->host.
-struct SectionWords {
-    size_t n, pack;
-    u32 host[SECTIONS_SLAB_WORDS];
-};
-int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32* dense, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions, const char* disagree,
-                      fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* fifth_word = nullptr,  // fifth_word: words[4] is copied and returned too
-                      SectionWords* sw = nullptr) {
+// HostWords: the count words of a host form - `n` words at `dev` come back in the one copy, into `host`; the pack's PACK_WORDS sit at word
+// `pack` of them and the captured count, where the form captures, at word `capture`.
+struct HostWords { u32* dev; size_t n, pack, capture; u32 host[SEC_SLAB_FETCH] = {}; };
+int fetch_top_indices(HostWords& w, TopStaging& t, size_t want, size_t max_pos, const char* disagree, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
     auto guess = [](size_t last, size_t most) { return last ? std::min(most, last + last / 64 + 64) : (size_t)0; };
-    const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(*last_records, want);
-    const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(*last_positions, max_pos);
-    const size_t front = sw ? (sw->n * 4 + 31) / 32 * 32 : 32;  // the words' room in front of the records
+    const size_t grec = want <= FZB_TOP_COPY_WHOLE ? want : guess(t.last_records, want);
+    const size_t gpos = max_pos <= (size_t)FZB_TOP_COPY_WHOLE * 4 ? max_pos : guess(t.last_positions, max_pos);
+    const size_t front = (w.n * 4 + 31) / 32 * 32;  // the words' room in front of the records
     u8* stage = (u8*)fzb_pinned_get(front + grec * sizeof(fzb_match_indices) + gpos * 4);
     if (!stage) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
-    const u32* const hw = (const u32*)stage + (sw ? sw->pack : 0);
+    const u32* const hw = (const u32*)stage + w.pack;
     const fzb_match_indices* const hrec = (const fzb_match_indices*)(stage + front);
     const u32* const hpos = (const u32*)(stage + front + grec * sizeof(fzb_match_indices));
-    hipError_t e = hipMemcpyAsync(stage, words, sw ? sw->n * 4 : fifth_word ? 20 : 16, hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
-    if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
+    hipError_t e = hipMemcpyAsync(stage, w.dev, w.n * 4, hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && grec) e = hipMemcpyAsync((void*)hrec, t.packed, grec * sizeof(fzb_match_indices), hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess && gpos) e = hipMemcpyAsync((void*)hpos, t.dense, gpos * 4, hipMemcpyDeviceToHost, nullptr);
     if (e == hipSuccess) e = fzb_stream_wait(nullptr);
     if (e != hipSuccess) {
         fzb_pinned_put(stage);
         return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
     }
     const size_t nrec = std::min<size_t>(hw[0], want), npos = std::min<size_t>(hw[2], max_pos), found = hw[1];
-    if (fifth_word) *fifth_word = hw[4];
-    if (sw) memcpy(sw->host, stage, sw->n * 4);
+    memcpy(w.host, stage, w.n * 4);
     if (hw[3]) {
         const u32 why = hw[3];
         fzb_pinned_put(stage);
@@ -3772,8 +3787,8 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
         u32* p = r ? (u32*)realloc(*out_positions, std::max<size_t>(npos, 1) * 4) : nullptr;
         if (p) *out_positions = p;
         e = (r && p) ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess && nrec > grec) e = hipMemcpy(r + grec, (const fzb_match_indices*)packed + grec, (nrec - grec) * sizeof(fzb_match_indices), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && npos > gpos) e = hipMemcpy(p + gpos, dense + gpos, (npos - gpos) * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && nrec > grec) e = hipMemcpy(r + grec, (const fzb_match_indices*)t.packed + grec, (nrec - grec) * sizeof(fzb_match_indices), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && npos > gpos) e = hipMemcpy(p + gpos, t.dense + gpos, (npos - gpos) * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
             fzb_match_indices_free(*out, *out_positions);
             *out = nullptr;
@@ -3783,22 +3798,50 @@ int fetch_top_indices(const u32* words, const fzb_indices_rec* packed, const u32
         }
         *out_len = nrec;
     }
-    *last_records = nrec;
-    *last_positions = npos;
+    t.last_records = nrec;
+    t.last_positions = npos;
     if (out_found) *out_found = found;
     return FZB_OK;
+}
+// after a host form's wait: the captured count came back in `word`
+void subset_capture_known(fzb_subset* capture, u32 word) {
+    if (!capture) return;
+    capture->count = word;
+    capture->known = true;
+}
+// What the host forms with matched positions share behind their own checks and trivial branches, on the null stream: the packed staging for a
+// head of up to `want` records and max_pos positions, the form's device impl - impl(PackedOut): the staging as the _device form's output, the
+// count words, and `mirror` = where a capturing form's count lands -, the one wait, and the captured count made known.  The owner's buffers
+// (w.dev among them) exist before the call.
+struct PackedOut { fzb_match_indices* recs; size_t cap; u32* pos; size_t pos_cap; u32 *words, *mirror; };
+template <typename Impl>
+int top_indices_host(TopStaging& t, HostWords& w, size_t want, size_t max_pos, fzb_subset* capture, const char* disagree, Impl&& impl, fzb_match_indices** out, size_t* out_len,
+                     uint32_t** out_positions, uint64_t* out_found) {
+    int rc;
+    if ((rc = fzb_top_ensure(t, want, max_pos, true))) return rc;
+    if ((rc = impl(PackedOut{(fzb_match_indices*)t.packed, t.packed_cap, t.dense, t.dense_words, w.dev, capture ? w.dev + w.capture : nullptr}))) return rc;
+    if ((rc = fetch_top_indices(w, t, want, max_pos, disagree, out, out_len, out_positions, out_found))) return rc;
+    subset_capture_known(capture, w.host[w.capture]);
+    return FZB_OK;
+}
+// the out-parameters of the host forms with matched positions, cleared ahead of everything that can fail
+void clear_indices_out(fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    *out = nullptr;
+    *out_len = 0;
+    *out_positions = nullptr;
+    if (out_found) *out_found = 0;
 }
 }  // namespace
 extern "C" {
 
-// The tail of every fused "head + matched positions" query of a single matcher: m->top_head holds a head of up to `want` records in the caller's
+// The tail of every fused "head + matched positions" query of a single matcher: m->top.head holds a head of up to `want` records in the caller's
 // order, m->top_idx_words its pair, m->trace_sel / the word behind it the head's item list (k_top_items; k_sec_items for sectioned heads).
 // From there: the traced pass over the items, the bias on the traced records, the pack into the caller's buffers and four words at dev_count.
 static int top_indices_tail(fzb_matcher* m, const fzb_corpus* c, size_t want, u32 stride, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
                             uint32_t* dev_count, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    u32* const head_count = m->top_idx_words;
-    u32* const traced_count = m->top_idx_words + 2;  // the traced pass' pair
+    u32* const head_count = m->top_idx_words + TOPIDX_HEAD;
+    u32* const traced_count = m->top_idx_words + TOPIDX_TRACED;  // the traced pass' pair
     u32* const n_items = m->trace_sel + m->trace_cap;
     const int grid = m->lc.num_cus * 2;
     int rc;
@@ -3807,67 +3850,68 @@ static int top_indices_tail(fzb_matcher* m, const fzb_corpus* c, size_t want, u3
     if ((rc = run_pipeline(m, c, 0, want, 0, m->trace_sel, n_items, (fzb_match*)m->top_traced, want, traced_count, stream, &tr))) return rc;
     // (the head's scores are biased: the traced records get the same pass, so the pack holds them to the head on the scores the caller sees)
     if ((rc = apply_bias(c, m->top_traced, traced_count, want, 0, 0, grid, st))) return rc;
-    fzb_launch_indices_pack(m->top_head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
-                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top_tiles, (u32)want, grid, st);
+    fzb_launch_indices_pack(m->top.head, head_count, m->top_traced, traced_count, m->trace_npos, m->trace_pos, stride, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, m->top.tiles, (u32)want, grid, st);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
 
-static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
-                                   uint32_t* dev_count, void* stream, const SubsetArgs* sa);
-int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
-                                      uint32_t* dev_count, void* stream) {
-    return top_indices_device_impl(m, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
-}
 // (sa: the top stage runs over the candidate set and captures; the traced pass runs over the head's item list as before)
 static int top_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
                                    uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!m || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if (capacity < want) return refuse_small_output("min(limit, haystacks)", capacity, want);
     if (m->empty) return fail(FZB_ERR_INVALID, "empty needle: handled on the host by fzb_match_list_top_indices");
     const u32 stride = trace_stride(m);
-    if (positions_capacity < want * (size_t)stride)
-        return fail(FZB_ERR_CAPACITY, "positions buffer smaller than min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(want * (size_t)stride));
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (positions_capacity < want * (size_t)stride) return refuse_small_positions("min(limit, haystacks)", positions_capacity, want * (size_t)stride);
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     if ((u64)want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
+        HIPCHK(hipMemsetAsync(dev_count, 0, PACK_WORDS * sizeof(u32), st));
         return facets_none(m->facets, st);
     }
     int rc;
     if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false))) return rc;
-    u32* const head_count = m->top_idx_words;        // (records, matches found) of the head
+    u32* const head_count = m->top_idx_words + TOPIDX_HEAD;  // (records, matches found) of the head
     u32* const n_items = m->trace_sel + m->trace_cap;
-    if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->top_head, want, head_count, stream, sa))) return rc;
+    if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->top.head, want, head_count, stream, sa))) return rc;
     const int grid = m->lc.num_cus * 2;
-    fzb_launch_top_items(m->top_head, head_count, (u32)want, m->trace_sel, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
+    fzb_launch_top_items(m->top.head, head_count, (u32)want, m->trace_sel, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
     return top_indices_tail(m, c, want, stride, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream);
+}
+int fzb_match_list_top_indices_device(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions, size_t positions_capacity,
+                                      uint32_t* dev_count, void* stream) {
+    return top_indices_device_impl(m, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
+}
+// what both host forms of the single matcher do behind their trivial branches (a needle, a corpus that is not empty): in / capture as the
+// _subset form got them, null from the plain form, whose device call sees no SubsetArgs at all
+static int top_indices_host_query(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
+                                  uint32_t** out_positions, uint64_t* out_found) {
+    const size_t want = std::min(limit, (size_t)c->dev.n), stride = trace_stride(m);
+    int rc;
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false))) return rc;
+    HostWords w{m->top_idx_words + TOPIDX_RESULT, PACK_WORDS + (capture ? 1 : 0), 0, TOPIDX_CAPTURE - TOPIDX_RESULT};
+    auto impl = [&](const PackedOut& o) {
+        const SubsetArgs sa{in, capture, o.mirror};
+        return top_indices_device_impl(m, c, limit, o.recs, o.cap, o.pos, o.pos_cap, o.words, nullptr, (in || capture) ? &sa : nullptr);
+    };
+    return top_indices_host(m->top, w, want, want * stride, capture, "the traced pass disagrees with the top stage", impl, out, out_len, out_positions, out_found);
 }
 
 int fzb_match_list_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
     if (!m || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     const size_t n = c->dev.n;
-    const size_t want = std::min(limit, n);
     if (prompt_on_device(m, c, nullptr, n)) return prompt_top_indices_host(m, c, nullptr, limit, out, out_len, out_positions, out_found);
     if (m->empty || n == 0) {
         if (int rc_ = facets_every(m->facets, c, 0, n, "fzb_match_list_top_indices")) return rc_;
     }
     if (m->empty) return empty_top_indices(c, n, m->config.sort, limit, out, out_len, out_positions, out_found);
     if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
-    const size_t stride = trace_stride(m);
-    int rc;
-    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
-    u32* const words = m->top_idx_words + 4;
-    if ((rc = fzb_match_list_top_indices_device(m, c, limit, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense, m->top_dense_words, words, nullptr))) return rc;
-    return fetch_top_indices(words, m->top_packed, m->top_dense, want, want * stride, &m->top_last_records, &m->top_last_positions, "the traced pass disagrees with the top stage", out, out_len,
-                             out_positions, out_found);
+    return top_indices_host_query(m, c, nullptr, nullptr, limit, out, out_len, out_positions, out_found);
 }
 
 // Sizes what fzb_matcher_reserve leaves to the first matched-indices query - item list, position counts, strided positions, the traced
@@ -3878,7 +3922,7 @@ int fzb_matcher_reserve_top_indices(fzb_matcher* m, const fzb_corpus* c, size_t 
     const size_t n = fzb_corpus_reserved_items(c);
     const size_t want = std::min(limit, n);
     if (want == 0) return FZB_OK;
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     const size_t stride = std::max<size_t>(std::max<size_t>(max_needle_bytes, 1), m->empty ? 1 : trace_stride(m));
     if ((u64)want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
     int rc = fzb_bind_device(m);
@@ -4013,12 +4057,6 @@ int hand_over_matches(const std::vector<fzb_match>& recs, fzb_match** out, size_
     *out_len = recs.size();
     return FZB_OK;
 }
-// after a host form's wait: the captured count came back in `word`
-void subset_capture_known(fzb_subset* capture, u32 word) {
-    if (!capture) return;
-    capture->count = word;
-    capture->known = true;
-}
 }  // namespace
 extern "C" {
 
@@ -4086,7 +4124,7 @@ int fzb_subset_from_scope(fzb_subset* s, const fzb_corpus* c, uint16_t require, 
     if (s->corpus != c) return fail(FZB_ERR_INVALID, "fzb_subset_from_scope: the subset belongs to another corpus");
     int rc = subset_begin(s, "fzb_subset_from_scope");
     if (rc) return rc;
-    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return refuse_index_overflow(c->dev.n);
     if ((rc = subset_room(s, c->dev.n))) return rc;
     fzb_launch_subset_from_scope(c->tags.data, (u32)c->dev.n, require, exclude, s->bitmap, s->tiles, s->idx, s->count_dev, (int)fzb_grid_cap(~0ull, 2), nullptr);  // (512 on 256 CUs)
     HIPCHK(hipGetLastError());
@@ -4190,10 +4228,10 @@ int fzb_match_list_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
         return prompt_list_host(m, c, in, 0, n, 0, true, out, out_len);
     }
     if ((rc = fzb_ensure_out_staging(m, n))) return rc;
-    SubsetArgs sa{in, capture, capture ? m->count_dev + 6 : nullptr};
+    SubsetArgs sa{in, capture, capture ? m->count_dev + OUT_CAPTURE : nullptr};
     if ((rc = sorted_range_impl(m, c, 0, n, 0, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr, &sa))) return rc;
     if ((rc = fetch_records(m->fetch, m->out_dev, m->count_dev, m->out_cap, out, out_len))) return rc;
-    subset_capture_known(capture, m->fetch.count_host[6]);
+    subset_capture_known(capture, m->fetch.count_host[OUT_CAPTURE]);
     return FZB_OK;
 }
 
@@ -4224,20 +4262,17 @@ int fzb_match_list_top_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_sub
     }
     const size_t want = std::min(limit, n);
     if ((rc = fzb_ensure_out_staging(m, want))) return rc;
-    SubsetArgs sa{in, capture, capture ? m->count_dev + 6 : nullptr};
+    SubsetArgs sa{in, capture, capture ? m->count_dev + OUT_CAPTURE : nullptr};
     if ((rc = top_device_impl(m, c, limit, (fzb_match*)m->out_dev, m->out_cap, m->count_dev, nullptr, &sa))) return rc;
     if ((rc = fzb_fetch_top(m->fetch_top, m->out_dev, m->count_dev, want, nullptr, out, out_len, out_found))) return rc;
-    subset_capture_known(capture, m->fetch_top.count_host[6]);
+    subset_capture_known(capture, m->fetch_top.count_host[OUT_CAPTURE]);
     return FZB_OK;
 }
 
 int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
                                       uint32_t** out_positions, uint64_t* out_found) {
     if (!m || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     int rc = subset_check(c, in, capture, "fzb_match_list_top_indices_subset");
     if (rc) return rc;
     const size_t n = c->dev.n;
@@ -4247,18 +4282,7 @@ int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const
         if (n == 0) return hand_over_indices(nullptr, 0, nullptr, 0, out, out_len, out_positions);
         return prompt_top_indices_host(m, c, in, limit, out, out_len, out_positions, out_found);
     }
-    const size_t want = std::min(limit, n);
-    const size_t stride = trace_stride(m);
-    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true))) return rc;
-    u32* const words = m->top_idx_words + 4;
-    SubsetArgs sa{in, capture, capture ? m->top_idx_words + 8 : nullptr};
-    if ((rc = top_indices_device_impl(m, c, limit, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense, m->top_dense_words, words, nullptr, &sa))) return rc;
-    u32 captured = 0;
-    rc = fetch_top_indices(words, m->top_packed, m->top_dense, want, want * stride, &m->top_last_records, &m->top_last_positions, "the traced pass disagrees with the top stage", out, out_len,
-                           out_positions, out_found, capture ? &captured : nullptr);
-    if (rc) return rc;
-    subset_capture_known(capture, captured);
-    return FZB_OK;
+    return top_indices_host_query(m, c, in, capture, limit, out, out_len, out_positions, out_found);
 }
 
 // ---- the empty prompt's _device forms: NEW entry points - the existing _device forms keep refusing an empty needle ---------------------
@@ -4266,7 +4290,7 @@ int fzb_match_list_top_indices_subset(fzb_matcher* m, const fzb_corpus* c, const
 static int prompt_device_check(const fzb_matcher* m, const fzb_corpus* c, const fzb_subset* in, const void* dev_out, size_t capacity, const uint32_t* dev_count, const char* call) {
     if (!m || !c || !dev_count || (!dev_out && capacity)) return fail(FZB_ERR_INVALID, "null argument");
     if (!m->empty) return fail(FZB_ERR_INVALID, std::string(call) + ": the matcher's needle is not empty; this call is the empty needle's form of the _device queries");
-    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return refuse_index_overflow(c->dev.n);
     return subset_check(c, in, nullptr, call);
 }
 
@@ -4275,8 +4299,7 @@ int fzb_prompt_list_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset
     int rc = prompt_device_check(m, c, in, dev_out, capacity, dev_count, "fzb_prompt_list_device");
     if (rc) return rc;
     if (first > c->dev.n || count > c->dev.n - first) return fail(FZB_ERR_INVALID, "range outside the corpus");
-    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull)
-        return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string((u64)count + index_offset) + " > 4294967295 (index offset: " + std::to_string(index_offset) + ")");
+    if ((u64)count + (u64)index_offset > 0xFFFFFFFFull) return refuse_index_overflow((u64)count + index_offset, index_offset);
     if (in && (first != 0 || count != c->dev.n)) return fail(FZB_ERR_INVALID, "fzb_prompt_list_device: a candidate set is queried over the whole corpus (first = 0, count = its length)");
     hipStream_t st = (hipStream_t)stream;
     if (count == 0) {
@@ -4292,7 +4315,7 @@ int fzb_prompt_top_device(fzb_matcher* m, const fzb_corpus* c, const fzb_subset*
     if (rc) return rc;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if (capacity < want) return refuse_small_output("min(limit, haystacks)", capacity, want);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, st));
@@ -4311,10 +4334,7 @@ int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c,
     if (int rc_ = fzb_refuse_biased(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_scoped(c, "fzb_multi_match_list_top_indices", "fzb_multi_match_list_top_indices_fused")) return rc_;
     if (int rc_ = fzb_refuse_facets(mm ? mm->facets : nullptr, "fzb_multi_match_list_top_indices")) return rc_;
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     fzb_match* head = nullptr;
     size_t nhead = 0;
     uint64_t found = 0;
@@ -4344,7 +4364,7 @@ int fzb_multi_match_list_top_indices(fzb_multi_matcher* mm, const fzb_corpus* c,
 }
 
 // ---- the `from_patterns` form fused on the device --------------------------------------------------------------------------------
-// The multi top stage leaves its sorted head in HBM (mm->top_head), k_top_items makes it ONE item list, every positive pattern's sub-matcher
+// The multi top stage leaves its sorted head in HBM (mm->top.head), k_top_items makes it ONE item list, every positive pattern's sub-matcher
 // runs the traced pipeline over that list into its own trace buffers (records in head order: every pattern accepts every haystack of the
 // head, which is what the composition selected), k_multi_union puts the patterns' records and positions together per head record
 // (indices_union.h: match_one_indices_multi, src/matcher/multi.rs:56-82) and the pack kernels write the caller's result while holding the
@@ -4367,22 +4387,18 @@ size_t multi_union_stride(const fzb_multi_matcher* mm, size_t* positive) {
 // the composition's own buffers of a fused query: a head of up to `want` records, unions of U dwords, P sources; staging: the host form's too
 int ensure_multi_top_indices_buffers(fzb_multi_matcher* mm, size_t want, size_t U, size_t P, bool staging) {
     int rc;
-    if (!mm->top_words) HIPCHK(dev_alloc((void**)&mm->top_words, 64));
-    if (!mm->top_head || !mm->top_comb || !mm->top_items || !mm->top_npos_u || !mm->top_tiles || mm->top_cap < want) {
-        mm->top_cap = 0;
-        if ((rc = fzb_dev_renew(&mm->top_head, want + 16)) || (rc = fzb_dev_renew(&mm->top_comb, want + 16)) || (rc = fzb_dev_renew(&mm->top_items, want + 4)) ||
-            (rc = fzb_dev_renew(&mm->top_npos_u, want + 4)) || (rc = fzb_dev_renew(&mm->top_tiles, fzb_indices_pack_tile_words(want))))
-            return rc;
-        mm->top_cap = want;
+    if (!mm->top_words) HIPCHK(dev_alloc((void**)&mm->top_words, MTOP_WORDS * sizeof(u32)));
+    if (!mm->top_comb || !mm->top_items || !mm->top_npos_u || mm->top_rec_cap < want) {
+        mm->top_rec_cap = 0;
+        if ((rc = fzb_dev_renew(&mm->top_comb, want + 16)) || (rc = fzb_dev_renew(&mm->top_items, want + 4)) || (rc = fzb_dev_renew(&mm->top_npos_u, want + 4))) return rc;
+        mm->top_rec_cap = want;
     }
     if ((rc = fzb_grow_dev(&mm->top_pos_u, &mm->top_pos_u_words, want * U, 1))) return rc;
     if (P > IUNION_BY_VALUE) {
         if (!mm->union_src || mm->union_src_cap < P) mm->union_src_host.clear();  // (a new array holds nothing yet)
         if ((rc = fzb_grow_dev(&mm->union_src, &mm->union_src_cap, P)) || (rc = fzb_grow_dev(&mm->union_cursors, &mm->union_cursor_words, want * P, 1))) return rc;
     }
-    if (!staging) return FZB_OK;
-    if ((rc = fzb_grow_dev(&mm->top_packed, &mm->top_packed_cap, want, 1))) return rc;
-    return fzb_grow_dev(&mm->top_dense, &mm->top_dense_words, want * U, 1);
+    return fzb_top_ensure(mm->top, want, want * U, staging);
 }
 bool same_union_src(const IUnionSrc& a, const IUnionSrc& b) { return a.rec == b.rec && a.count == b.count && a.npos == b.npos && a.pos == b.pos && a.stride == b.stride; }
 // a matcher that has an any-of group (indices_union_groups.h): what its union is made of
@@ -4443,7 +4459,7 @@ static int multi_top_indices_group_sources(fzb_multi_matcher* mm, size_t want, c
         if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
         const bool alt = (i > 0 && mm->terms[i - 1] == mm->terms[i]) || (i + 1 < ps.size() && mm->terms[i + 1] == mm->terms[i]);
         const u32* where = alt ? mm->gunion_where + (a++) * gunion_where_stride(want) : nullptr;
-        src->push_back(GUnionSrc{IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0}, where, mm->terms[i], 0});
+        src->push_back(GUnionSrc{IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + TOPIDX_TRACED, m->trace_npos, m->trace_pos, trace_stride(m), 0}, where, mm->terms[i], 0});
     }
     if (g.P > IUNION_BY_VALUE) {
         bool same = mm->gunion_src_host.size() == g.P;
@@ -4467,7 +4483,7 @@ static int multi_top_indices_sources(fzb_multi_matcher* mm, size_t want, size_t 
         if (p.negated) continue;
         fzb_matcher* m = p.m;
         if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, trace_stride(m), false))) return rc;
-        src->push_back(IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + 2, m->trace_npos, m->trace_pos, trace_stride(m), 0});
+        src->push_back(IUnionSrc{(const IUnionRec*)m->top_traced, m->top_idx_words + TOPIDX_TRACED, m->trace_npos, m->trace_pos, trace_stride(m), 0});
     }
     if (P > IUNION_BY_VALUE) {
         bool same = mm->union_src_host.size() == P;
@@ -4479,7 +4495,7 @@ static int multi_top_indices_sources(fzb_multi_matcher* mm, size_t want, size_t 
     }
     return FZB_OK;
 }
-// Behind the head (mm->top_head, its pair in mm->top_words) and its item list (mm->top_items, the length in mm->top_words[10]; k_top_items, or
+// Behind the head (mm->top.head, its pair in mm->top_words) and its item list (mm->top_items, the length at word MTOP_N_ITEMS of them; k_top_items, or
 // k_sec_items for sectioned heads): one traced pass per positive pattern, the union, the bias, the pack and four words at dev_count.
 // gt (a matcher that has an any-of group, U = U_g): the traced passes are the same - one per plain non-negated pattern and per alternative, an
 // alternative's returning only the head items it matches - and fzb_launch_gunion's four launches stand in place of k_multi_union.
@@ -4493,58 +4509,50 @@ struct GroupedTail {
 static int multi_top_indices_tail(fzb_multi_matcher* mm, const fzb_corpus* c, size_t want, size_t U, const std::vector<IUnionSrc>& src, fzb_match_indices* dev_out, size_t capacity,
                                   uint32_t* dev_positions, size_t positions_capacity, uint32_t* dev_count, void* stream, const GroupedTail* gt = nullptr) {
     hipStream_t st = (hipStream_t)stream;
-    u32* const head_count = mm->top_words;
-    u32* const comb_count = mm->top_words + 2;  // the combined traced pair
-    u32* const n_items = mm->top_words + 10;
+    u32* const head_count = mm->top_words + MTOP_HEAD;
+    u32* const comb_count = mm->top_words + MTOP_COMBINED;  // the combined traced pair
+    u32* const n_items = mm->top_words + MTOP_N_ITEMS;
     const int grid = mm->num_cus * 2;
     int rc;
     for (auto& p : mm->patterns) {
         if (p.negated) continue;
         fzb_matcher* m = p.m;
         const TraceOut tr{m->trace_pos, m->trace_npos, trace_stride(m)};
-        if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + 2, stream, &tr))) return rc;
+        if ((rc = run_pipeline(m, c, 0, want, 0, mm->top_items, n_items, (fzb_match*)m->top_traced, want, m->top_idx_words + TOPIDX_TRACED, stream, &tr))) return rc;
     }
     if (gt) {
         if (!mm->group_slots || mm->group_cap < gt->n_hay) return fail(FZB_ERR_HIP, "internal: the group slots do not cover the list");
-        fzb_launch_gunion(mm->top_head, head_count, (u32)want, gt->src->data(), (u32)gt->src->size(), mm->gunion_src, mm->gunion_scratch, mm->group_slots, (u32)gt->n_hay, mm->gunion_where,
+        fzb_launch_gunion(mm->top.head, head_count, (u32)want, gt->src->data(), (u32)gt->src->size(), mm->gunion_src, mm->gunion_scratch, mm->group_slots, (u32)gt->n_hay, mm->gunion_where,
                           gt->shape->A * gunion_where_stride(want), mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, grid, st);
     } else {
-        fzb_launch_multi_union(mm->top_head, head_count, (u32)want, src.data(), (u32)src.size(), mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u,
+        fzb_launch_multi_union(mm->top.head, head_count, (u32)want, src.data(), (u32)src.size(), mm->union_src, mm->union_cursors, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u,
                                (u32)U, grid, st);
     }
     if ((rc = apply_bias(c, mm->top_comb, comb_count, want, 0, 0, grid, st))) return rc;  // once, after the sum: as the head's records
-    fzb_launch_indices_pack(mm->top_head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
-                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top_tiles, (u32)want, grid, st);
+    fzb_launch_indices_pack(mm->top.head, head_count, mm->top_comb, comb_count, mm->top_npos_u, mm->top_pos_u, (u32)U, (fzb_indices_rec*)dev_out, (u32)std::min<size_t>(capacity, 0xFFFFFFFFu),
+                            dev_positions, (u32)std::min<size_t>(positions_capacity, 0xFFFFFFFFu), dev_count, mm->top.tiles, (u32)want, grid, st);
     HIPCHK(hipGetLastError());
     return FZB_OK;
 }
 
-static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
-                                         size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa);
-int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
-                                            size_t positions_capacity, uint32_t* dev_count, void* stream) {
-    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_device")) return rc_;
-    return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
-}
 // (sa: only the top stage sees the candidate set and captures; the traced passes run over the head's item list as before)
 static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
                                          size_t positions_capacity, uint32_t* dev_count, void* stream, const SubsetArgs* sa) {
     if (!mm || !c || !dev_count || (!dev_out && capacity) || (!dev_positions && positions_capacity)) return fail(FZB_ERR_INVALID, "null argument");
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
+    if (capacity < want) return refuse_small_output("min(limit, haystacks)", capacity, want);
     if (mm->patterns.empty()) return fail(FZB_ERR_INVALID, "no pattern: handled on the host by fzb_multi_match_list_top_indices_fused");
     size_t P = 0;
     // (a matcher that has an any-of group gets here through fzb_multi_match_list_top_indices_groups* alone: its stride is U_g)
     const GroupShape shape = mm->grouped ? multi_group_shape(mm) : GroupShape{};
     const size_t U = mm->grouped ? shape.U : multi_union_stride(mm, &P);
-    if (positions_capacity < want * U)
-        return fail(FZB_ERR_CAPACITY, "positions buffer smaller than min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(want * U));
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (positions_capacity < want * U) return refuse_small_positions("min(limit, haystacks)", positions_capacity, want * U);
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     if ((u64)want * U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        HIPCHK(hipMemsetAsync(dev_count, 0, 16, st));
+        HIPCHK(hipMemsetAsync(dev_count, 0, PACK_WORDS * sizeof(u32), st));
         return facets_none(mm->facets, st);
     }
     // every buffer first: the sources of the union are final before anything is launched
@@ -4557,29 +4565,38 @@ static int multi_top_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus
     } else if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st))) {
         return rc;
     }
-    u32* const head_count = mm->top_words;      // (records, matches found) of the head
-    u32* const n_items = mm->top_words + 10;
-    // (the composition's pair in words 12-13: word 8 follows the host form's four result words, where its wait picks up a captured count)
-    if ((rc = multi_top_stage(mm, c, n, want, mm->top_head, head_count, mm->top_words + 12, st, sa))) return rc;
+    u32* const head_count = mm->top_words + MTOP_HEAD;  // (records, matches found) of the head
+    u32* const n_items = mm->top_words + MTOP_N_ITEMS;
+    // (the composition's pair at MTOP_RAW: MTOP_CAPTURE follows the host form's result words, where its wait picks up a captured count)
+    if ((rc = multi_top_stage(mm, c, n, want, mm->top.head, head_count, mm->top_words + MTOP_RAW, st, sa))) return rc;
     const int grid = mm->num_cus * 2;
-    fzb_launch_top_items(mm->top_head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
+    fzb_launch_top_items(mm->top.head, head_count, (u32)want, mm->top_items, n_items, dev_count, (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, (want + 255) / 256)), st);
     return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, mm->grouped ? &gt : nullptr);
 }
-
-static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
-                                        const SubsetArgs* sa);
-int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
-    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_fused")) return rc_;
-    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr);
+int fzb_multi_match_list_top_indices_device(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices* dev_out, size_t capacity, uint32_t* dev_positions,
+                                            size_t positions_capacity, uint32_t* dev_count, void* stream) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_device")) return rc_;
+    return multi_top_indices_device_impl(mm, c, limit, dev_out, capacity, dev_positions, positions_capacity, dev_count, stream, nullptr);
 }
-// (sa: `in` and `capture` as the caller gave them; the mirror word is set here.  A no-pattern matcher never gets here with a subset.)
+// what the composition's host forms - fused, over a candidate set, with any-of groups - do behind their trivial branches (a pattern, a corpus
+// that is not empty), for unions of U dwords from P sources: in / capture as the caller gave them, and no SubsetArgs at all without either
+static int multi_top_indices_host_query(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, size_t U, size_t P, fzb_match_indices** out,
+                                        size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    const size_t want = std::min(limit, (size_t)c->dev.n);
+    if (int rc = ensure_multi_top_indices_buffers(mm, want, U, P, false)) return rc;
+    HostWords w{mm->top_words + MTOP_RESULT, PACK_WORDS + (capture ? 1 : 0), 0, MTOP_CAPTURE - MTOP_RESULT};
+    auto impl = [&](const PackedOut& o) {
+        const SubsetArgs sa{in, capture, o.mirror};
+        return multi_top_indices_device_impl(mm, c, limit, o.recs, o.cap, o.pos, o.pos_cap, o.words, nullptr, (in || capture) ? &sa : nullptr);
+    };
+    return top_indices_host(mm->top, w, want, want * U, capture, "the traced passes disagree with the multi top stage", impl, out, out_len, out_positions, out_found);
+}
+
+// (in / capture: as the _subset form got them, null from the fused form.  A no-pattern matcher never gets here with a subset.)
 static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found,
-                                        const SubsetArgs* sa) {
+                                        const fzb_subset* in, fzb_subset* capture) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
     if (mm->patterns.empty() || n == 0) {
@@ -4590,19 +4607,11 @@ static int multi_top_indices_fused_impl(fzb_multi_matcher* mm, const fzb_corpus*
     size_t P = 0;
     const size_t U = multi_union_stride(mm, &P);
     if ((u64)want * U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
-    int rc;
-    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, true))) return rc;
-    u32* const words = mm->top_words + 4;
-    fzb_subset* const capture = sa ? sa->capture : nullptr;
-    const SubsetArgs with_mirror{sa ? sa->in : nullptr, capture, capture ? mm->top_words + 8 : nullptr};
-    if ((rc = multi_top_indices_device_impl(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr, sa ? &with_mirror : nullptr)))
-        return rc;
-    u32 captured = 0;
-    rc = fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out, out_len,
-                           out_positions, out_found, capture ? &captured : nullptr);
-    if (rc) return rc;
-    subset_capture_known(capture, captured);
-    return FZB_OK;
+    return multi_top_indices_host_query(mm, c, in, capture, limit, U, P, out, out_len, out_positions, out_found);
+}
+int fzb_multi_match_list_top_indices_fused(fzb_multi_matcher* mm, const fzb_corpus* c, size_t limit, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_fused")) return rc_;
+    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr, nullptr);
 }
 
 // ---- candidate sets on the `from_patterns` forms -----------------------------------------------------------------------------------------
@@ -4622,9 +4631,9 @@ int fzb_multi_match_list_subset(fzb_multi_matcher* mm, const fzb_corpus* c, cons
     }
     if (!in && !capture) return fzb_multi_match_list(mm, c, out, out_len);
     if ((rc = fzb_out_ensure(*mm, c->dev.n))) return rc;
-    SubsetArgs sa{in, capture, capture ? mm->count_dev + 6 : nullptr};
+    SubsetArgs sa{in, capture, capture ? mm->count_dev + OUT_CAPTURE : nullptr};
     if ((rc = multi_match_list_impl(mm, c, out, out_len, &sa))) return rc;
-    subset_capture_known(capture, mm->fetch.count_host[6]);
+    subset_capture_known(capture, mm->fetch.count_host[OUT_CAPTURE]);
     return FZB_OK;
 }
 
@@ -4642,9 +4651,9 @@ int fzb_multi_match_list_top_subset(fzb_multi_matcher* mm, const fzb_corpus* c, 
     }
     if (!in && !capture) return fzb_multi_match_list_top(mm, c, limit, out, out_len, out_found);
     if ((rc = fzb_out_ensure(*mm, std::min(limit, (size_t)c->dev.n)))) return rc;
-    SubsetArgs sa{in, capture, capture ? mm->count_dev + 6 : nullptr};
+    SubsetArgs sa{in, capture, capture ? mm->count_dev + OUT_CAPTURE : nullptr};
     if ((rc = multi_match_list_top_impl(mm, c, limit, out, out_len, out_found, &sa))) return rc;
-    subset_capture_known(capture, mm->fetch_top.count_host[6]);
+    subset_capture_known(capture, mm->fetch_top.count_host[OUT_CAPTURE]);
     return FZB_OK;
 }
 
@@ -4656,8 +4665,8 @@ int fzb_multi_match_list_top_subset_device(fzb_multi_matcher* mm, const fzb_corp
     if (rc) return rc;
     const size_t n = c->dev.n;
     const size_t want = std::min(limit, n);
-    if (capacity < want) return fail(FZB_ERR_CAPACITY, "output buffer smaller than min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(want));
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if (capacity < want) return refuse_small_output("min(limit, haystacks)", capacity, want);
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     if (n == 0) {
         if ((rc = subset_capture_trivial(c, in, capture))) return rc;
         HIPCHK(hipMemsetAsync(dev_count, 0, 8, (hipStream_t)stream));
@@ -4665,7 +4674,7 @@ int fzb_multi_match_list_top_subset_device(fzb_multi_matcher* mm, const fzb_corp
     }
     if ((rc = fzb_out_ensure(*mm, 0))) return rc;  // (the composition's pair lives next to the staging's count words)
     SubsetArgs sa{in, capture, nullptr};
-    return multi_top_stage(mm, c, n, want, (fzb_match_rec*)dev_out, dev_count, mm->count_dev + 4, (hipStream_t)stream, &sa);
+    return multi_top_stage(mm, c, n, want, (fzb_match_rec*)dev_out, dev_count, mm->count_dev + OUT_RAW, (hipStream_t)stream, &sa);
 }
 
 // ---- sectioned top-`limit`: the best matches per tag section, one device call (sections.h, kernels_sections.hip) ---------------------------
@@ -4682,7 +4691,7 @@ int sections_check(const void* m, const fzb_corpus* c, const fzb_section* sectio
     if (!m || !c || (!sections && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
     if (n_sections > FZB_SECTIONS_MAX) return fail(FZB_ERR_INVALID, std::string(call) + ": " + std::to_string(n_sections) + " sections; at most FZB_SECTIONS_MAX = 8 in one call");
     if (limit > FZB_SECTION_LIMIT_MAX) return fail(FZB_ERR_INVALID, std::string(call) + ": limit " + std::to_string(limit) + " is above FZB_SECTION_LIMIT_MAX = 1024");
-    if ((u64)c->dev.n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(c->dev.n) + " > 4294967295 (index offset: 0)");
+    if ((u64)c->dev.n > 0xFFFFFFFFull) return refuse_index_overflow(c->dev.n);
     *ss = sections_set{};
     ss->n = (u32)n_sections;
     for (size_t s = 0; s < n_sections; s++) {
@@ -4690,6 +4699,13 @@ int sections_check(const void* m, const fzb_corpus* c, const fzb_section* sectio
         ss->exclude[s] = sections[s].exclude;
     }
     return subset_check(c, in, capture, call);
+}
+// the per-section out-parameters of the host forms, cleared ahead of everything that can fail
+void sections_clear_out(size_t n_sections, size_t* out_len, uint64_t* out_found) {
+    for (size_t s = 0; s < n_sections; s++) {
+        out_len[s] = 0;
+        if (out_found) out_found[s] = 0;
+    }
 }
 // an empty corpus: S empty heads
 int sections_nothing(const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, fzb_facets* f, size_t n_sections, u32* dev_counts, hipStream_t st) {
@@ -4717,7 +4733,7 @@ int single_sections_stage(fzb_matcher* m, const fzb_corpus* c, const sections_se
         if ((rc = fzb_bind_device(m)) || (rc = fzb_ensure_sort_buffers(m, n))) return rc;
         if (!m->count_dev && (rc = fzb_ensure_out_staging(m, 0))) return rc;
         prompt_order_flags(m, c, &reversed, &by_score, &one_pass);
-        raw_count = m->count_dev + 4;
+        raw_count = m->count_dev + OUT_RAW;
         if ((rc = prompt_records(m, c, sa->in, 0, n, 0, m->ws.sort.tmp, n, raw_count, st))) return rc;
     } else if ((rc = top_produce(m, c, n, st, sa, &raw_count, &reversed, &by_score, &one_pass))) {
         return rc;
@@ -4737,18 +4753,17 @@ int multi_sections_stage(fzb_multi_matcher* mm, const fzb_corpus* c, const secti
         args.capture = nullptr;
     }
     if ((rc = fzb_out_ensure(*mm, 0)) || (rc = fzb_sort_ensure(mm->sort, n))) return rc;  // (the composition's pair lives next to the staging's count words)
-    u32* const raw_count = mm->count_dev + 4;
+    u32* const raw_count = mm->count_dev + OUT_RAW;
     if ((rc = multi_match_list_device_impl(mm, c, 0, n, 0, (fzb_match*)mm->sort.tmp, n, raw_count, st, &args))) return rc;
-    const int sort = mm->config.sort;
-    const bool reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;
-    const bool by_score = (!mm->patterns.empty() || fzb_corpus_bias(c)) && (sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC);
+    bool reversed, by_score;
+    multi_order_flags(mm, c, &reversed, &by_score);
     if (ss.n == 0) return FZB_OK;
     return sections_stage(mm->sections, c, mm->sort.tmp, raw_count, n, ss, limit, by_score, reversed, false, dev_out, dev_counts, mm->num_cus * 2, st);
 }
-// The host forms' result: the stage block - 32 words (the 2S counts, [16] = the captured count), then S slabs of `limit` records - in ONE
-// copy and one wait on the null stream; the heads are moved together in the pinned block that is handed over.
+// The host forms' result: the stage block - SEC_STAGE_RECORDS words (the 2S counts, the captured count), then S slabs of `limit` records - in
+// ONE copy and one wait on the null stream; the heads are moved together in the pinned block that is handed over.
 int sections_fetch(const SectionsScratch& sc, size_t S, size_t limit, fzb_match** out, size_t* out_len, uint64_t* out_found, u32* captured) {
-    const size_t bytes = 32 * sizeof(u32) + S * limit * sizeof(fzb_match);
+    const size_t bytes = SEC_STAGE_RECORDS * sizeof(u32) + S * limit * sizeof(fzb_match);
     uint8_t* r = (uint8_t*)pinned_pool().get(bytes);
     if (!r) return fail(FZB_ERR_HIP, "hipHostMalloc failed for the result list");
     hipError_t e = hipMemcpyAsync(r, sc.stage, bytes, hipMemcpyDeviceToHost, nullptr);
@@ -4757,17 +4772,17 @@ int sections_fetch(const SectionsScratch& sc, size_t S, size_t limit, fzb_match*
         pinned_pool().put(r);
         return fail(FZB_ERR_HIP, std::string("device to host: ") + hipGetErrorString(e));
     }
-    u32 words[32];
+    u32 words[SEC_STAGE_RECORDS];  // (the words in front of the records)
     memcpy(words, r, sizeof(words));
     size_t total = 0;
     for (size_t s = 0; s < S; s++) {  // (head s moves towards the front: its destination ends before any later slab begins)
-        const size_t kept = std::min<size_t>(words[2 * s], limit);
+        const size_t kept = std::min<size_t>(words[SEC_STAGE_COUNTS + 2 * s], limit);
         memmove(r + total * sizeof(fzb_match), r + sizeof(words) + s * limit * sizeof(fzb_match), kept * sizeof(fzb_match));
         out_len[s] = kept;
-        if (out_found) out_found[s] = words[2 * s + 1];
+        if (out_found) out_found[s] = words[SEC_STAGE_COUNTS + 2 * s + 1];
         total += kept;
     }
-    *captured = words[16];
+    *captured = words[SEC_STAGE_CAPTURE];
     *out = (fzb_match*)r;
     return FZB_OK;
 }
@@ -4779,8 +4794,7 @@ int fzb_match_list_top_sections_device(fzb_matcher* m, const fzb_corpus* c, cons
     sections_set ss;
     if ((!dev_counts && n_sections) || (!dev_out && n_sections && limit)) return fail(FZB_ERR_INVALID, "null argument");
     if (int rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections_device", &ss)) return rc;
-    if (capacity < n_sections * limit)
-        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * limit: " + std::to_string(capacity) + " < " + std::to_string(n_sections * limit));
+    if (capacity < n_sections * limit) return refuse_small_output("n_sections * limit", capacity, n_sections * limit);
     SubsetArgs sa{in, capture, nullptr};
     return single_sections_stage(m, c, ss, limit, &sa, (fzb_match_rec*)dev_out, dev_counts, (hipStream_t)stream);
 }
@@ -4791,15 +4805,12 @@ int fzb_match_list_top_sections(fzb_matcher* m, const fzb_corpus* c, const fzb_s
     if (!out || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     if (int rc = sections_check(m, c, sections, n_sections, limit, in, capture, "fzb_match_list_top_sections", &ss)) return rc;
-    for (size_t s = 0; s < n_sections; s++) {
-        out_len[s] = 0;
-        if (out_found) out_found[s] = 0;
-    }
+    sections_clear_out(n_sections, out_len, out_found);
     int rc;
     if ((rc = fzb_bind_device(m)) || (rc = fzb_sections_ensure(m->sections, c->dev.n, n_sections * limit + 1))) return rc;
     u32* const words = m->sections.stage;
-    SubsetArgs sa{in, capture, capture ? words + 16 : nullptr};
-    if ((rc = single_sections_stage(m, c, ss, limit, &sa, (fzb_match_rec*)(words + 32), words, nullptr))) return rc;
+    SubsetArgs sa{in, capture, capture ? words + SEC_STAGE_CAPTURE : nullptr};
+    if ((rc = single_sections_stage(m, c, ss, limit, &sa, (fzb_match_rec*)(words + SEC_STAGE_RECORDS), words + SEC_STAGE_COUNTS, nullptr))) return rc;
     if (n_sections == 0 || c->dev.n == 0) return FZB_OK;
     u32 captured = 0;
     if ((rc = sections_fetch(m->sections, n_sections, limit, out, out_len, out_found, &captured))) return rc;
@@ -4812,8 +4823,7 @@ int fzb_multi_match_list_top_sections_device(fzb_multi_matcher* mm, const fzb_co
     sections_set ss;
     if ((!dev_counts && n_sections) || (!dev_out && n_sections && limit)) return fail(FZB_ERR_INVALID, "null argument");
     if (int rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections_device", &ss)) return rc;
-    if (capacity < n_sections * limit)
-        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * limit: " + std::to_string(capacity) + " < " + std::to_string(n_sections * limit));
+    if (capacity < n_sections * limit) return refuse_small_output("n_sections * limit", capacity, n_sections * limit);
     SubsetArgs sa{in, capture, nullptr};
     return multi_sections_stage(mm, c, ss, limit, &sa, (fzb_match_rec*)dev_out, dev_counts, (hipStream_t)stream);
 }
@@ -4824,16 +4834,13 @@ int fzb_multi_match_list_top_sections(fzb_multi_matcher* mm, const fzb_corpus* c
     if (!out || (!out_len && n_sections)) return fail(FZB_ERR_INVALID, "null argument");
     *out = nullptr;
     if (int rc = sections_check(mm, c, sections, n_sections, limit, in, capture, "fzb_multi_match_list_top_sections", &ss)) return rc;
-    for (size_t s = 0; s < n_sections; s++) {
-        out_len[s] = 0;
-        if (out_found) out_found[s] = 0;
-    }
+    sections_clear_out(n_sections, out_len, out_found);
     int rc;
     if ((rc = fzb_sections_ensure(mm->sections, c->dev.n, n_sections * limit + 1))) return rc;
     u32* const words = mm->sections.stage;
     const bool captures = capture && !mm->patterns.empty();
-    SubsetArgs sa{in, capture, captures ? words + 16 : nullptr};
-    if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, (fzb_match_rec*)(words + 32), words, nullptr))) return rc;
+    SubsetArgs sa{in, capture, captures ? words + SEC_STAGE_CAPTURE : nullptr};
+    if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, (fzb_match_rec*)(words + SEC_STAGE_RECORDS), words + SEC_STAGE_COUNTS, nullptr))) return rc;
     if (n_sections == 0 || c->dev.n == 0) return FZB_OK;
     u32 captured = 0;
     if ((rc = sections_fetch(mm->sections, n_sections, limit, out, out_len, out_found, &captured))) return rc;
@@ -4851,11 +4858,8 @@ namespace {
 // what the _device forms check behind sections_check; *want = the records the dense head has room for
 int sections_indices_room(size_t n_sections, size_t limit, size_t n, size_t stride, size_t capacity, size_t positions_capacity, size_t* want) {
     *want = n_sections * std::min(limit, n);
-    if (capacity < *want)
-        return fail(FZB_ERR_CAPACITY, "output buffer smaller than n_sections * min(limit, haystacks): " + std::to_string(capacity) + " < " + std::to_string(*want));
-    if (positions_capacity < *want * stride)
-        return fail(FZB_ERR_CAPACITY,
-                    "positions buffer smaller than n_sections * min(limit, haystacks) x needle bytes: " + std::to_string(positions_capacity) + " < " + std::to_string(*want * stride));
+    if (capacity < *want) return refuse_small_output("n_sections * min(limit, haystacks)", capacity, *want);
+    if (positions_capacity < *want * stride) return refuse_small_positions("n_sections * min(limit, haystacks)", positions_capacity, *want * stride);
     if ((u64)*want * stride > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "n_sections * min(limit, haystacks) x needle bytes does not fit the 32-bit positions_begin");
     return FZB_OK;
 }
@@ -4870,19 +4874,18 @@ int sections_indices_plain(fzb_match* head, size_t n_sections, const size_t* out
     size_t len = 0;
     return hand_over_indices(recs.data(), total, nullptr, 0, out, &len, out_positions);
 }
-// the host forms' one wait: the 2S + 4 words (and the captured count at word 24), the dense head, the dense positions
-int sections_indices_fetch(SectionsScratch& sc, const fzb_indices_rec* packed, const u32* dense, size_t S, size_t want, size_t max_pos, size_t* last_records, size_t* last_positions,
-                           const char* disagree, fzb_match_indices** out, size_t* out_len, uint32_t** out_positions, uint64_t* out_found, u32* captured) {
-    SectionWords sw{};
-    sw.n = 32;
-    sw.pack = 2 * S;
+// the sectioned host forms' tail (top_indices_host): their one wait brings the 2S + PACK_WORDS result words and the captured count, the dense
+// head and the dense positions; the sections' counts are handed out from the words
+template <typename Impl>
+int sections_indices_host(TopStaging& t, SectionsScratch& sc, size_t S, size_t want, size_t max_pos, fzb_subset* capture, const char* disagree, Impl&& impl, fzb_match_indices** out,
+                          size_t* out_len, uint32_t** out_positions, uint64_t* out_found) {
+    HostWords w{sc.slabs + SEC_SLAB_RESULT, SEC_SLAB_FETCH, 2 * S, SEC_SLAB_CAPTURE - SEC_SLAB_RESULT};
     size_t total = 0;
-    if (int rc = fetch_top_indices(sc.slabs + 16, packed, dense, want, max_pos, last_records, last_positions, disagree, out, &total, out_positions, nullptr, nullptr, &sw)) return rc;
+    if (int rc = top_indices_host(t, w, want, max_pos, capture, disagree, impl, out, &total, out_positions, nullptr)) return rc;
     for (size_t s = 0; s < S; s++) {
-        out_len[s] = sw.host[2 * s];
-        if (out_found) out_found[s] = sw.host[2 * s + 1];
+        out_len[s] = w.host[2 * s];
+        if (out_found) out_found[s] = w.host[2 * s + 1];
     }
-    *captured = sw.host[24];
     return FZB_OK;
 }
 }  // namespace
@@ -4904,14 +4907,14 @@ static int sections_indices_device_impl(fzb_matcher* m, const fzb_corpus* c, con
     SubsetArgs sa{in, capture, mirror};
     if (n == 0 || n_sections == 0) {  // nothing to select: the sectioned call's side effects (capture, facets), 2S + 4 zero words
         if ((rc = single_sections_stage(m, c, ss, limit, &sa, nullptr, dev_counts, st))) return rc;
-        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, 16, st));
+        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, PACK_WORDS * sizeof(u32), st));
         return FZB_OK;
     }
     if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false)) || (rc = fzb_sections_ensure_slabs(m->sections, n_sections * limit))) return rc;
-    u32* const slab_counts = m->sections.slabs;
+    u32* const slab_counts = m->sections.slabs + SEC_SLAB_COUNTS;
     fzb_match_rec* const slabs = (fzb_match_rec*)(m->sections.slabs + SECTIONS_SLAB_WORDS);
     if ((rc = single_sections_stage(m, c, ss, limit, &sa, slabs, slab_counts, st))) return rc;
-    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, m->top_head, m->top_idx_words, m->trace_sel, m->trace_sel + m->trace_cap, dev_counts,
+    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, m->top.head, m->top_idx_words + TOPIDX_HEAD, m->trace_sel, m->trace_sel + m->trace_cap, dev_counts,
                               m->lc.num_cus * 2, st);
     return top_indices_tail(m, c, want, stride, dev_out, capacity, dev_positions, positions_capacity, dev_counts + 2 * n_sections, stream);
 }
@@ -4936,22 +4939,11 @@ int fzb_match_list_top_sections_indices(fzb_matcher* m, const fzb_corpus* c, con
         if ((rc = fzb_match_list_top_sections(m, c, sections, n_sections, limit, in, capture, &head, out_len, out_found))) return rc;
         return sections_indices_plain(head, n_sections, out_len, out, out_positions);
     }
-    for (size_t s = 0; s < n_sections; s++) {
-        out_len[s] = 0;
-        if (out_found) out_found[s] = 0;
-    }
+    sections_clear_out(n_sections, out_len, out_found);
     const size_t stride = trace_stride(m), want = n_sections * std::min(limit, n);
-    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, true)) || (rc = fzb_sections_ensure_slabs(m->sections, n_sections * limit))) return rc;
-    u32* const words = m->sections.slabs + 16;
-    if ((rc = sections_indices_device_impl(m, c, sections, n_sections, limit, in, capture, capture ? words + 24 : nullptr, (fzb_match_indices*)m->top_packed, m->top_packed_cap, m->top_dense,
-                                           m->top_dense_words, words, nullptr)))
-        return rc;
-    u32 captured = 0;
-    if ((rc = sections_indices_fetch(m->sections, m->top_packed, m->top_dense, n_sections, want, want * stride, &m->top_last_records, &m->top_last_positions,
-                                     "the traced pass disagrees with the sectioned stage", out, out_len, out_positions, out_found, &captured)))
-        return rc;
-    subset_capture_known(capture, captured);
-    return FZB_OK;
+    if ((rc = fzb_bind_device(m)) || (rc = ensure_top_indices_buffers(m, want, stride, false)) || (rc = fzb_sections_ensure_slabs(m->sections, n_sections * limit))) return rc;
+    auto impl = [&](const PackedOut& o) { return sections_indices_device_impl(m, c, sections, n_sections, limit, in, capture, o.mirror, o.recs, o.cap, o.pos, o.pos_cap, o.words, nullptr); };
+    return sections_indices_host(m->top, m->sections, n_sections, want, want * stride, capture, "the traced pass disagrees with the sectioned stage", impl, out, out_len, out_positions, out_found);
 }
 
 static int multi_sections_indices_device_impl(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_section* sections, size_t n_sections, size_t limit, const fzb_subset* in,
@@ -4971,16 +4963,17 @@ static int multi_sections_indices_device_impl(fzb_multi_matcher* mm, const fzb_c
     SubsetArgs sa{in, capture, mirror};
     if (n == 0 || n_sections == 0) {
         if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, nullptr, dev_counts, st))) return rc;
-        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, 16, st));
+        HIPCHK(hipMemsetAsync(dev_counts + 2 * n_sections, 0, PACK_WORDS * sizeof(u32), st));
         return FZB_OK;
     }
     // every buffer first: the sources of the union are final before anything is launched
     std::vector<IUnionSrc> src;
     if ((rc = multi_top_indices_sources(mm, want, U, P, &src, st)) || (rc = fzb_sections_ensure_slabs(mm->sections, n_sections * limit))) return rc;
-    u32* const slab_counts = mm->sections.slabs;
+    u32* const slab_counts = mm->sections.slabs + SEC_SLAB_COUNTS;
     fzb_match_rec* const slabs = (fzb_match_rec*)(mm->sections.slabs + SECTIONS_SLAB_WORDS);
     if ((rc = multi_sections_stage(mm, c, ss, limit, &sa, slabs, slab_counts, st))) return rc;
-    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, mm->top_head, mm->top_words, mm->top_items, mm->top_words + 10, dev_counts, mm->num_cus * 2, st);
+    fzb_launch_sections_items(slabs, slab_counts, (u32)n_sections, (u32)limit, (u32)want, mm->top.head, mm->top_words + MTOP_HEAD, mm->top_items, mm->top_words + MTOP_N_ITEMS, dev_counts,
+                              mm->num_cus * 2, st);
     return multi_top_indices_tail(mm, c, want, U, src, dev_out, capacity, dev_positions, positions_capacity, dev_counts + 2 * n_sections, stream);
 }
 
@@ -5005,33 +4998,20 @@ int fzb_multi_match_list_top_sections_indices(fzb_multi_matcher* mm, const fzb_c
         if ((rc = fzb_multi_match_list_top_sections(mm, c, sections, n_sections, limit, in, capture, &head, out_len, out_found))) return rc;
         return sections_indices_plain(head, n_sections, out_len, out, out_positions);
     }
-    for (size_t s = 0; s < n_sections; s++) {
-        out_len[s] = 0;
-        if (out_found) out_found[s] = 0;
-    }
+    sections_clear_out(n_sections, out_len, out_found);
     size_t P = 0;
     const size_t U = multi_union_stride(mm, &P), want = n_sections * std::min(limit, n);
-    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, true)) || (rc = fzb_sections_ensure_slabs(mm->sections, n_sections * limit))) return rc;
-    u32* const words = mm->sections.slabs + 16;
-    if ((rc = multi_sections_indices_device_impl(mm, c, sections, n_sections, limit, in, capture, capture ? words + 24 : nullptr, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap,
-                                                 mm->top_dense, mm->top_dense_words, words, nullptr)))
-        return rc;
-    u32 captured = 0;
-    if ((rc = sections_indices_fetch(mm->sections, mm->top_packed, mm->top_dense, n_sections, want, want * U, &mm->top_last_records, &mm->top_last_positions,
-                                     "the traced passes disagree with the sectioned multi stage", out, out_len, out_positions, out_found, &captured)))
-        return rc;
-    subset_capture_known(capture, captured);
-    return FZB_OK;
+    if ((rc = ensure_multi_top_indices_buffers(mm, want, U, P, false)) || (rc = fzb_sections_ensure_slabs(mm->sections, n_sections * limit))) return rc;
+    auto impl = [&](const PackedOut& o) { return multi_sections_indices_device_impl(mm, c, sections, n_sections, limit, in, capture, o.mirror, o.recs, o.cap, o.pos, o.pos_cap, o.words, nullptr); };
+    return sections_indices_host(mm->top, mm->sections, n_sections, want, want * U, capture, "the traced passes disagree with the sectioned multi stage", impl, out, out_len, out_positions,
+                                 out_found);
 }
 
 int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_corpus* c, const fzb_subset* in, fzb_subset* capture, size_t limit, fzb_match_indices** out, size_t* out_len,
                                             uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
     if (int rc_ = fzb_refuse_groups(mm, "fzb_multi_match_list_top_indices_subset")) return rc_;
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_indices_subset");
     if (rc) return rc;
     if (mm->patterns.empty() || c->dev.n == 0) {
@@ -5045,8 +5025,7 @@ int fzb_multi_match_list_top_indices_subset(fzb_multi_matcher* mm, const fzb_cor
         return hand_over_indices(recs.data(), recs.size(), nullptr, 0, out, out_len, out_positions);
     }
     if (!in && !capture) return fzb_multi_match_list_top_indices_fused(mm, c, limit, out, out_len, out_positions, out_found);
-    SubsetArgs sa{in, capture, nullptr};
-    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, &sa);
+    return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, in, capture);
 }
 
 // ---- matched positions of the top-`limit` for a matcher that has an any-of group ---------------------------------------------------------------
@@ -5076,13 +5055,10 @@ int fzb_multi_match_list_top_indices_groups(fzb_multi_matcher* mm, const fzb_cor
                                             uint32_t** out_positions, uint64_t* out_found) {
     if (!mm || !c || !out || !out_len || !out_positions) return fail(FZB_ERR_INVALID, "null argument");
     if (!mm->grouped) {  // the ungrouped forms, call for call
-        if (!in && !capture) return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr);
+        if (!in && !capture) return multi_top_indices_fused_impl(mm, c, limit, out, out_len, out_positions, out_found, nullptr, nullptr);
         return fzb_multi_match_list_top_indices_subset(mm, c, in, capture, limit, out, out_len, out_positions, out_found);
     }
-    *out = nullptr;
-    *out_len = 0;
-    *out_positions = nullptr;
-    if (out_found) *out_found = 0;
+    clear_indices_out(out, out_len, out_positions, out_found);
     int rc = subset_check(c, in, capture, "fzb_multi_match_list_top_indices_groups");
     if (rc) return rc;
     const size_t n = c->dev.n;
@@ -5094,18 +5070,7 @@ int fzb_multi_match_list_top_indices_groups(fzb_multi_matcher* mm, const fzb_cor
     }
     const GroupShape g = multi_group_shape(mm);
     if ((u64)want * g.U > 0xFFFFFFFFull) return fail(FZB_ERR_CAPACITY, "min(limit, haystacks) x the grouped positions stride does not fit the 32-bit positions_begin");
-    if ((rc = ensure_multi_top_indices_buffers(mm, want, g.U, 0, true))) return rc;
-    u32* const words = mm->top_words + 4;
-    const SubsetArgs sa{in, capture, capture ? mm->top_words + 8 : nullptr};
-    if ((rc = multi_top_indices_device_impl(mm, c, limit, (fzb_match_indices*)mm->top_packed, mm->top_packed_cap, mm->top_dense, mm->top_dense_words, words, nullptr,
-                                                   (in || capture) ? &sa : nullptr)))
-        return rc;
-    u32 captured = 0;
-    rc = fetch_top_indices(words, mm->top_packed, mm->top_dense, want, want * g.U, &mm->top_last_records, &mm->top_last_positions, "the traced passes disagree with the multi top stage", out, out_len,
-                           out_positions, out_found, capture ? &captured : nullptr);
-    if (rc) return rc;
-    subset_capture_known(capture, captured);
-    return FZB_OK;
+    return multi_top_indices_host_query(mm, c, in, capture, limit, g.U, 0, out, out_len, out_positions, out_found);
 }
 
 // fzb_multi_matcher_reserve_top_indices, and what the grouped tail owns for any grouping of the matcher's slots: the `where` maps of as many
@@ -5129,7 +5094,7 @@ int fzb_multi_matcher_reserve_top_indices(fzb_multi_matcher* mm, const fzb_corpu
     const size_t n = fzb_corpus_reserved_items(c);
     const size_t want = std::min(limit, n);
     if (want == 0) return FZB_OK;
-    if ((u64)n > 0xFFFFFFFFull) return fail(FZB_ERR_PANIC, "too many items in haystack, will overflow the u32 index: " + std::to_string(n) + " > 4294967295 (index offset: 0)");
+    if ((u64)n > 0xFFFFFFFFull) return refuse_index_overflow(n);
     std::vector<fzb_matcher*> slots;
     for (auto& p : mm->patterns) slots.push_back(p.m);
     slots.insert(slots.end(), mm->spare.begin(), mm->spare.end());

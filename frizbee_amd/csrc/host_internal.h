@@ -161,9 +161,18 @@ void fzb_sort_release(SortBuffers& s);
 // what the synchronous entry points remember between two results (fetch_records, host.hip)
 struct FetchHint {
     size_t last = 0;            // records of the previous result: the next one's records are copied speculatively, behind the count
-    u32* count_host = nullptr;  // page-locked landing place of the two counters
+    u32* count_host = nullptr;  // page-locked landing place of the counters: OUT_FETCH_WORDS words (below)
 };
-// staging of the synchronous entry points, of either matcher type: the device-side result and what the copies to the host remember
+// staging of the synchronous entry points, of either matcher type: the device-side result and what the copies to the host remember.
+// Every count pair of the library is (records written, matches found).
+constexpr size_t PAIR_RECORDS = 0, PAIR_FOUND = 1;
+// count_dev's words: the result pair, the producer's raw pair (pipeline / composition / a shard's selection) and the capture mirror - the
+// first OUT_FETCH_WORDS are what fzb_fetch_records copies into FetchHint::count_host.  The sharded root (host_shard.hip) alternates its
+// running totals between two blocks at 0 and OUT_SHARD_BLOCK, keeps the sticky "a run was truncated" word at OUT_SHARD_TRUNCATED and its
+// top-`limit` result pair at OUT_SHARD_RESULT, which fzb_fetch_top copies from.
+constexpr size_t OUT_RESULT = 0, OUT_SHARD_TRUNCATED = 2, OUT_RAW = 4, OUT_SHARD_BLOCK = 4, OUT_CAPTURE = 6, OUT_FETCH_WORDS = 8, OUT_SHARD_RESULT = 8, OUT_WORDS = 16;
+static_assert(OUT_RAW + 2 <= OUT_CAPTURE && OUT_CAPTURE < OUT_FETCH_WORDS, "the capture mirror comes back with the fetched words, behind the raw pair");
+static_assert(OUT_SHARD_TRUNCATED < OUT_FETCH_WORDS && OUT_SHARD_RESULT + OUT_FETCH_WORDS <= OUT_WORDS, "every fetch stays inside count_dev");
 struct OutStaging {
     fzb_match_rec* out_dev = nullptr;
     size_t out_cap = 0;
@@ -194,11 +203,17 @@ int fzb_scope_ensure_flags(ScopeScratch& s, size_t count);  // bitmap / tiles / 
 void fzb_scope_release(ScopeScratch& s);
 
 // The buffers of the sectioned top-`limit` queries (sections.h; host.hip), of either matcher type: `words` = the stage's scratch (bins, cuts,
-// tile rows: fzb_sections_scratch_words), `stage` = the host forms' device-side result - 16 count words, then n_sections * limit records, so
-// that one copy brings both back; `slabs` = the form with matched positions: SECTIONS_SLAB_WORDS words (the stage's 2S count words at 0, the host
-// form's 2S + 4 result words at 16 and its captured count at 40), then the n_sections * limit slab records that k_sec_items makes one dense
-// head.  Grown through fzb_grow_dev on the first sectioned query, released with the matcher.
-#define SECTIONS_SLAB_WORDS 48
+// tile rows: fzb_sections_scratch_words), `stage` = the host forms' device-side result - the 2S count words, the captured count, then from
+// SEC_STAGE_RECORDS the n_sections * limit records, so that one copy brings all back; `slabs` = the form with matched positions: the stage's 2S
+// count words, the host form's 2S + PACK_WORDS result words (its one copy takes SEC_SLAB_FETCH words from there) and its captured count, then
+// from SECTIONS_SLAB_WORDS the n_sections * limit slab records that k_sec_items makes one dense head.  Grown through fzb_grow_dev on the first
+// sectioned query, released with the matcher.
+constexpr size_t PACK_WORDS = 4;  // what the pack kernels leave at dev_count: records, matches found, positions, "the passes disagree"
+constexpr size_t SEC_STAGE_COUNTS = 0, SEC_STAGE_CAPTURE = 16, SEC_STAGE_RECORDS = 32;
+constexpr size_t SEC_SLAB_COUNTS = 0, SEC_SLAB_RESULT = 16, SEC_SLAB_CAPTURE = 40, SEC_SLAB_FETCH = 32, SECTIONS_SLAB_WORDS = 48;
+static_assert(SEC_STAGE_COUNTS + 2 * FZB_SECTIONS_MAX == SEC_STAGE_CAPTURE && SEC_STAGE_CAPTURE < SEC_STAGE_RECORDS, "the stage's counts end where its capture word begins");
+static_assert(SEC_SLAB_COUNTS + 2 * FZB_SECTIONS_MAX <= SEC_SLAB_RESULT && SEC_SLAB_RESULT + 2 * FZB_SECTIONS_MAX + PACK_WORDS <= SEC_SLAB_CAPTURE, "the slabs' result words end before the capture");
+static_assert(SEC_SLAB_CAPTURE < SEC_SLAB_RESULT + SEC_SLAB_FETCH && SEC_SLAB_RESULT + SEC_SLAB_FETCH <= SECTIONS_SLAB_WORDS, "one copy brings the result words and the capture back");
 struct SectionsScratch {
     u32* words = nullptr;
     size_t words_cap = 0;
@@ -210,6 +225,21 @@ struct SectionsScratch {
 int fzb_sections_ensure(SectionsScratch& s, size_t n_records, size_t stage_records);  // host.hip
 int fzb_sections_ensure_slabs(SectionsScratch& s, size_t slab_records);
 void fzb_sections_release(SectionsScratch& s);
+
+// "Head, pack, host copy" of the top-`limit` queries with matched positions (host.hip), of either matcher type: the top stage's sorted head and
+// the pack's tile sums, for heads of up to `cap` records; the host forms' packed staging (records, dense positions) and what their previous
+// result held (the guess of the next copy).  An owner's own per-record arrays beside the head have a capacity of their own.
+struct TopStaging {
+    fzb_match_rec* head = nullptr;
+    u32* tiles = nullptr;
+    size_t cap = 0;
+    fzb_indices_rec* packed = nullptr;
+    u32* dense = nullptr;
+    size_t packed_cap = 0, dense_words = 0;
+    size_t last_records = 0, last_positions = 0;
+};
+int fzb_top_ensure(TopStaging& t, size_t want, size_t position_words, bool staging);  // host.hip; staging: the host forms' packed result too
+void fzb_top_release(TopStaging& t);
 
 // A matcher is two things (struct fzb_matcher below).  CompiledNeedle: what (config, needle) compile to, on the host alone - compile_needle
 // (host.hip) computes all of it and makes no HIP call.  fzb_matcher_set_pattern / _set_config replace it as a whole.
@@ -252,6 +282,9 @@ struct CompiledNeedle {
 // MatcherState: what a session has accumulated on the device - buffers, streams, events, pinned words, the multi-device form's clones and
 // workers.  It survives a needle or config change untouched (but for the few resets rebuild_matcher names); release_state (host.hip) is the
 // one place that frees what it owns.  A matcher that gains a buffer adds it here and there.
+// the words of MatcherState::top_idx_words
+constexpr size_t TOPIDX_HEAD = 0, TOPIDX_TRACED = 2, TOPIDX_RESULT = 4, TOPIDX_CAPTURE = 8, TOPIDX_WORDS = 16;
+static_assert(TOPIDX_CAPTURE == TOPIDX_RESULT + PACK_WORDS && TOPIDX_CAPTURE < TOPIDX_WORDS, "the capture mirror is the word right behind the result words");
 struct MatcherState : OutStaging {
     Workspace ws{};
     int device = -1;
@@ -269,18 +302,13 @@ struct MatcherState : OutStaging {
     u32* trace_pos = nullptr;
     u32* trace_npos = nullptr;
     size_t trace_cap = 0, trace_pos_words = 0;
-    // fzb_match_list_top_indices*: the top stage's sorted head, the traced second pass' records, the count words of both passes
-    // ([0..1] head pair, [2..3] traced pair, [4..7] the host form's four result words), the pack's tile sums - for `top_cap` records; the
-    // host form's packed staging (records, dense positions) and what its previous result held (the guess of the next copy)
-    fzb_match_rec* top_head = nullptr;
+    // fzb_match_list_top_indices*: the head, pack and host copy (TopStaging), the traced second pass' records and the
+    // count words of both passes: the head pair, the traced pair, the host form's PACK_WORDS result words and, right behind them so that one
+    // copy of PACK_WORDS + 1 words brings it along, the capture mirror
+    TopStaging top;
     fzb_match_rec* top_traced = nullptr;
+    size_t top_traced_cap = 0;
     u32* top_idx_words = nullptr;
-    u32* top_tiles = nullptr;
-    size_t top_cap = 0;
-    fzb_indices_rec* top_packed = nullptr;
-    u32* top_dense = nullptr;
-    size_t top_packed_cap = 0, top_dense_words = 0;
-    size_t top_last_records = 0, top_last_positions = 0;
     // a long needle's arrays on the device (the copy of CompiledNeedle::long_blob_host: dropped with the needle it belongs to) and the global
     // scratch of its kernels (N-typo path state, per-row previous-chunk vectors, traced cells)
     void* long_blob_dev = nullptr;
@@ -312,6 +340,10 @@ struct MatcherState : OutStaging {
 struct fzb_matcher : CompiledNeedle, MatcherState {};
 
 // ---- multi-pattern composition (src/matcher/multi.rs; host.hip) ----------------------------------------------------------
+// the slots of fzb_multi_matcher::counts (slot k < 2 belongs to cand[k]; fzb_multi_count below) and the words of fzb_multi_matcher::top_words
+constexpr size_t MCOUNT_NEGATED = 2, MCOUNT_ALTERNATIVE = 3, MCOUNT_SLOTS = 4, MCOUNT_SLOT_WORDS = 4;
+constexpr size_t MTOP_HEAD = 0, MTOP_COMBINED = 2, MTOP_RESULT = 4, MTOP_CAPTURE = 8, MTOP_N_ITEMS = 10, MTOP_RAW = 12, MTOP_WORDS = 16;
+static_assert(MTOP_CAPTURE == MTOP_RESULT + PACK_WORDS && MTOP_CAPTURE < MTOP_N_ITEMS && MTOP_RAW + 2 <= MTOP_WORDS, "the capture mirror is the word right behind the result words");
 struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entry points)
     fzb_config config{};
     struct Compiled { bool negated; fzb_matcher* m; };
@@ -335,25 +367,26 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     // and the bitmap / per-tile counts of the negation's compaction
     size_t cap = 0;
     fzb_match_rec* cand[2] = {nullptr, nullptr};
-    u32* counts = nullptr;  // [0],[4] = lengths of cand[0], cand[1]; [8] = hits of a negated pattern, [12] = hits of a group's alternative (each slot: count, untruncated total)
+    // `counts`: one slot of MCOUNT_SLOT_WORDS words per list (count, untruncated total) - the lengths of cand[0] and cand[1], the hits of a
+    // negated pattern, the hits of a group's alternative (fzb_multi_count)
+    u32* counts = nullptr;
     u32* items = nullptr;
     u64* bitmap = nullptr;
     u32* tile_counts = nullptr;
     SortBuffers sort{};  // ordering of the synchronous entry points
-    // fzb_multi_match_list_top_indices_device / _fused: for heads of up to `top_cap` records - the multi top stage's sorted head, the item
-    // list every positive pattern traces (one list, shared), the combined records and union lengths k_multi_union writes, the pack's tile
-    // sums; `top_words`: [0..1] head pair, [2..3] combined pair, [4..7] the host form's four result words, [8..9] the composition's pair,
-    // [10] the item list's length.  `top_pos_u`: the strided unions (U per record).  Beyond IUNION_BY_VALUE positive patterns the union
-    // kernel reads its sources from `union_src` (what it holds: `union_src_host`; written again only when a pattern or a buffer changed,
-    // ahead of the query's first launch) and keeps its cursors in `union_cursors`.  Then the host form's packed staging and what its
-    // previous result held, as MatcherState's.
-    fzb_match_rec* top_head = nullptr;
+    // fzb_multi_match_list_top_indices_device / _fused: the head, pack and host copy (TopStaging) and, for heads of up to `top_rec_cap` records, the
+    // item list every positive pattern traces (one list, shared), the combined records and union lengths k_multi_union writes.  `top_words`:
+    // the head pair, the combined pair, the host form's PACK_WORDS result words, the capture mirror right behind them (one copy of
+    // PACK_WORDS + 1 words brings it along), the item list's length and the composition's raw pair.  `top_pos_u`: the strided unions (U per
+    // record).  Beyond IUNION_BY_VALUE positive patterns the union kernel reads its sources from `union_src` (what it holds:
+    // `union_src_host`; written again only when a pattern or a buffer changed, ahead of the query's first launch) and keeps its cursors in
+    // `union_cursors`.
+    TopStaging top;
     fzb_match_rec* top_comb = nullptr;
     u32* top_items = nullptr;
     u32* top_npos_u = nullptr;
-    u32* top_tiles = nullptr;
+    size_t top_rec_cap = 0;  // of top_comb / top_items / top_npos_u
     u32* top_words = nullptr;
-    size_t top_cap = 0;
     u32* top_pos_u = nullptr;
     size_t top_pos_u_words = 0;
     IUnionSrc* union_src = nullptr;
@@ -371,10 +404,6 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     std::vector<GUnionSrc> gunion_src_host;
     u32* gunion_scratch = nullptr;
     size_t gunion_scratch_words = 0;
-    fzb_indices_rec* top_packed = nullptr;
-    u32* top_dense = nullptr;
-    size_t top_packed_cap = 0, top_dense_words = 0;
-    size_t top_last_records = 0, top_last_positions = 0;
     // multi-device forms (host_shard.hip, host_rccl.hip): `order` = an empty-needle matcher that holds the root's ordering, staging and
     // gather state (merge_runs_on_device and the sharded driver take it like any matcher); `shard_clones[g]` composes shard g's run on
     // shard_devices[g] (-1 = not used yet) and writes it into the staging of order->shard_clones[g]
@@ -385,6 +414,7 @@ struct fzb_multi_matcher : OutStaging {  // (the staging of its synchronous entr
     std::vector<fzb_multi_matcher*> shard_clones;
     std::vector<int> shard_devices;
 };
+inline u32* fzb_multi_count(const fzb_multi_matcher* mm, size_t slot) { return mm->counts + MCOUNT_SLOT_WORDS * slot; }
 
 
 // pooled page-locked host buffers (result lists, upload staging): get() returns nullptr on failure; put() returns false for a pointer

@@ -147,8 +147,8 @@ static int merge_runs_on_device(fzb_matcher* m, const void* const* dev_runs, con
     if ((rc = fzb_ensure_out_staging(m, cap))) return rc;
     OrderPlan plan;
     if ((rc = fzb_order_begin(m, cap, m->out_dev, &plan, 0))) return rc;
-    // count_dev: two blocks of four words, alternating between batches of FZB_MAX_RUNS runs - [0] records written so far, [1] matches
-    // found, [2] "a run was truncated by its producer" (sticky: every batch writes into the same word)
+    // count_dev: two blocks (at 0 and OUT_SHARD_BLOCK) that alternate between batches of FZB_MAX_RUNS runs, each the pair (records written so
+    // far, matches found), and the word OUT_SHARD_TRUNCATED: "a run was truncated by its producer" (sticky: every batch writes into it)
     u32* words = m->count_dev;  // (every word read below is assigned by the concatenation launches: no clearing fill in the stream)
     const u32* base = nullptr;
     u32* tot = words;
@@ -160,9 +160,9 @@ static int merge_runs_on_device(fzb_matcher* m, const void* const* dev_runs, con
             rs.count[k] = dev_counts[g0 + (size_t)k];
             rs.cap[k] = (u32)run_caps[g0 + (size_t)k];
         }
-        fzb_launch_concat_runs(rs, base, tot, plan.in, (u32)cap, m->lc.num_cus * 2, words + 2, st);
+        fzb_launch_concat_runs(rs, base, tot, plan.in, (u32)cap, m->lc.num_cus * 2, words + OUT_SHARD_TRUNCATED, st);
         base = tot;
-        tot = tot == words ? words + 4 : words;
+        tot = tot == words ? words + OUT_SHARD_BLOCK : words;
     }
     HIPCHK(hipGetLastError());
     if ((rc = fzb_order_finish(m, plan, m->out_dev, base, st))) return rc;
@@ -171,7 +171,7 @@ static int merge_runs_on_device(fzb_matcher* m, const void* const* dev_runs, con
     fzb_match* r = nullptr;
     size_t n = 0;
     if ((rc = fzb_fetch_records(m->fetch, final_dev, words, (int)(base - words), cap, st, &r, &n))) return rc;
-    if (m->fetch.count_host[2]) {
+    if (m->fetch.count_host[OUT_SHARD_TRUNCATED]) {
         fzb_matches_free(r);
         return fzb_fail(FZB_ERR_CAPACITY, "a shard's run was truncated by its producer (more matches than its buffer holds): nothing merged");
     }
@@ -471,7 +471,7 @@ int fzb_sharded_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const ShardR
         if (!count) return FZB_OK;
         HIPCHK(hipMemcpyAsync(cm->shard_count_host, cm->count_dev, 8, hipMemcpyDeviceToHost, cm->shard_stream));
         HIPCHK(hipStreamSynchronize(cm->shard_stream));
-        const u32 cnt = cm->shard_count_host[0];
+        const u32 cnt = cm->shard_count_host[PAIR_RECORDS];
         counts[g].store((int64_t)cnt, std::memory_order_release);
         if (!cnt) return FZB_OK;
         size_t at = 0;
@@ -577,7 +577,7 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
         if ((rc_ = fzb_ensure_sort_buffers(cm, count))) return rc_;
         const size_t keep = slot[g + 1] - slot[g];
         fzb_match_rec* const sel = cm->ws.sort.tmp;
-        u32* const sel_count = cm->count_dev + 4;
+        u32* const sel_count = cm->count_dev + OUT_RAW;
         HIPCHK(fzb_launch_topk_select(cm->out_dev, cm->count_dev, (u32)count, (u32)keep, by_score, reversed, one_pass, sel, (u32)keep, sel_count, cm->ws.sort.hist,
                                       (u32)(cm->ws.sort.cap / 2048 + 2), cm->lc.num_cus * 2, st));
         if (copy_forced || sc->device[g] != root) {  // the slot and its count pair travel to the root
@@ -603,7 +603,7 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
                                               : "copy (selected slots and their count pairs copied to the root, no count read back)");
     if ((rc = shard_join(m, recorded))) return drained(rc);
     hipStream_t st = m->shard_stream;
-    u32* words = m->count_dev;  // two alternating pairs (records, matches found) for the batches of FZB_MAX_RUNS runs; the result pair at [8]
+    u32* words = m->count_dev;  // the two alternating blocks of merge_runs_on_device (a pair each); the result pair at OUT_SHARD_RESULT, clear of both
     const u32* base = nullptr;
     u32* tot = words;
     for (size_t g0 = 0; g0 < ns; g0 += FZB_MAX_RUNS) {
@@ -613,24 +613,24 @@ int fzb_sharded_top_query(fzb_matcher* m, const fzb_sharded_corpus* sc, const Sh
             const size_t g = g0 + (size_t)k;
             const bool local = !copy_forced && sc->device[g] == root;
             rs.run[k] = local ? m->shard_clones[g]->ws.sort.tmp : m->out_dev + slot[g];
-            rs.count[k] = local ? m->shard_clones[g]->count_dev + 4 : m->top_words + 2 * g;
+            rs.count[k] = local ? m->shard_clones[g]->count_dev + OUT_RAW : m->top_words + 2 * g;
             rs.cap[k] = (u32)(slot[g + 1] - slot[g]);
         }
         fzb_launch_topk_concat(rs, base, tot, m->ws.sort.tmp, (u32)cap, m->lc.num_cus * 2, st);
         base = tot;
-        tot = tot == words ? words + 4 : words;
+        tot = tot == words ? words + OUT_SHARD_BLOCK : words;
     }
     const size_t want = std::min(limit, cap);
     const u32 ntiles_cap = (u32)(m->ws.sort.cap / 2048 + 2);
-    hipError_t e_sel = fzb_launch_topk_select(m->ws.sort.tmp, base, (u32)cap, (u32)want, by_score, reversed, one_pass, m->out_dev, (u32)want, words + 8, m->ws.sort.hist, ntiles_cap,
+    hipError_t e_sel = fzb_launch_topk_select(m->ws.sort.tmp, base, (u32)cap, (u32)want, by_score, reversed, one_pass, m->out_dev, (u32)want, words + OUT_SHARD_RESULT, m->ws.sort.hist, ntiles_cap,
                                               m->lc.num_cus * 2, st);
     if (e_sel != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_sel)));
-    fzb_launch_sort(m->out_dev, m->ws.sort.tmp, words + 8, m->ws.sort.hist, ntiles_cap, reversed, by_score, m->lc.num_cus * 2, st, one_pass ? 1 : 2);
+    fzb_launch_sort(m->out_dev, m->ws.sort.tmp, words + OUT_SHARD_RESULT, m->ws.sort.hist, ntiles_cap, reversed, by_score, m->lc.num_cus * 2, st, one_pass ? 1 : 2);
     {
         hipError_t e_ = hipGetLastError();
         if (e_ != hipSuccess) return drained(fzb_fail(FZB_ERR_HIP, std::string("top selection: ") + hipGetErrorString(e_)));
     }
-    rc = fzb_fetch_top(m->fetch_top, m->out_dev, words + 8, want, st, out, out_len, out_found);
+    rc = fzb_fetch_top(m->fetch_top, m->out_dev, words + OUT_SHARD_RESULT, want, st, out, out_len, out_found);
     return rc ? drained(rc) : FZB_OK;
 }
 
