@@ -6,7 +6,28 @@
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ us2 as_us2(u32 x) { return __builtin_bit_cast(us2, x); }
 __device__ __forceinline__ u32 as_u32(us2 x) { return __builtin_bit_cast(u32, x); }
-__device__ __forceinline__ u32 p_add(u32 a, u32 b) { return as_u32(as_us2(a) + as_us2(b)); }
+#ifdef FZB_HOST_SHIM
+// Precondition meter of the host build (tests/kernel_host only; the device branches below are untouched): what p_max3_s was given and whether a
+// p_add wrapped a 16-bit lane.  Atomics: the four-lane harness runs a host thread per quad lane.  tests/kernel_host/dp_host.cpp resets and reads it.
+inline std::atomic<u32> fzb_meter_max3_hi{0};                  // the largest 16-bit operand of any p_max3_s call
+inline std::atomic<unsigned long long> fzb_meter_max3_bad{0};  // calls with an operand >= 0x7C00 (where v_pk_maximum3_f16 stops being an integer maximum)
+inline std::atomic<unsigned long long> fzb_meter_add_wrap{0};  // p_add calls in which a lane's sum passed 0xFFFF
+inline void fzb_meter_max3(u32 a, u32 b, u32 s) {
+    const u32 hi = std::max(std::max(std::max(a & 0xFFFF, a >> 16), std::max(b & 0xFFFF, b >> 16)), std::max(s & 0xFFFF, s >> 16));
+    u32 seen = fzb_meter_max3_hi.load(std::memory_order_relaxed);
+    while (hi > seen && !fzb_meter_max3_hi.compare_exchange_weak(seen, hi, std::memory_order_relaxed)) {}
+    if (hi >= 0x7C00) fzb_meter_max3_bad.fetch_add(1, std::memory_order_relaxed);
+}
+inline void fzb_meter_add(u32 a, u32 b) {
+    if ((((a & 0xFFFF) + (b & 0xFFFF)) | ((a >> 16) + (b >> 16))) >> 16) fzb_meter_add_wrap.fetch_add(1, std::memory_order_relaxed);
+}
+#endif
+__device__ __forceinline__ u32 p_add(u32 a, u32 b) {
+#ifdef FZB_HOST_SHIM
+    fzb_meter_add(a, b);
+#endif
+    return as_u32(as_us2(a) + as_us2(b));
+}
 __device__ __forceinline__ u32 p_sub(u32 a, u32 b) { return as_u32(as_us2(a) - as_us2(b)); }
 __device__ __forceinline__ u32 p_subs(u32 a, u32 b) { return as_u32(__builtin_elementwise_sub_sat(as_us2(a), as_us2(b))); }
 __device__ __forceinline__ u32 p_max(u32 a, u32 b) { return as_u32(__builtin_elementwise_max(as_us2(a), as_us2(b))); }
@@ -17,6 +38,7 @@ __device__ __forceinline__ u32 p_max(u32 a, u32 b) { return as_u32(__builtin_ele
 // (LaunchCfg::cf_ok / cfm_ok: biased scores stay below 0x7C00).
 __device__ __forceinline__ u32 p_max3_s(u32 a, u32 b, u32 s) {
 #ifdef FZB_HOST_SHIM
+    fzb_meter_max3(a, b, s);
     return p_max(p_max(a, b), s);
 #else
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)

@@ -129,6 +129,15 @@ size_t max_matrix_score(const fzb_scoring& s, size_t needle_len) {
     size_t max_per_char = (size_t)s.match_score + (size_t)max_per_char_bonus(s);
     return max_per_char * needle_len + (size_t)max_one_time_bonus(s) + (size_t)s.prefix_bonus;
 }
+// What a matrix cell can REALLY reach: every row earns at most match + the larger of the delimiter / capitalisation bonus + the case bonus, the
+// first one the prefix bonus.  max_matrix_score is the reference's guard, kept for what must agree with the reference (the score class, the
+// overflow guard); it amortises the per-letter bonus over two rows or a gap, and a needle such as "/aA/aA" beats that - delimiter, lowercase
+// behind it, capital behind the lowercase: two rows of every three earn the bonus with no gap (default scoring, 6 rows: 124 against 122).  Every
+// gate that picks an arithmetic form or a pass count from "no value exceeds ..." takes this ceiling (tests/test_form_gates_host.py searches it).
+size_t score_ceiling(const fzb_scoring& s, size_t needle_len) {
+    const size_t per_char = (size_t)s.match_score + (size_t)std::max(s.delimiter_bonus, s.capitalization_bonus) + (size_t)s.matching_case_bonus;
+    return per_char * needle_len + (size_t)s.prefix_bonus;
+}
 bool fits_in_u8(size_t needle_len, const fzb_scoring& s) {
     size_t max_constant = std::max<size_t>({(size_t)s.match_score + (size_t)s.mismatch_penalty, s.gap_open_penalty, s.gap_extend_penalty,
                                             s.matching_case_bonus, s.capitalization_bonus, s.delimiter_bonus, s.prefix_bonus});
@@ -502,11 +511,11 @@ static void build_long_needle(CompiledNeedle* m, const uint8_t* needle_utf8, siz
     lc.window_mode = (k < 0 || k >= m->rows) ? 2 : 0;
     lc.pad_ok = lc.cf_ok = lc.cfm_ok = 0;
     // (the biased gap scan of dp_multi_chunk, as for short needles below: the largest biased value stays inside 16 bits)
-    lc.bias_ok = max_matrix_score(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 <= 0xFFFF;
+    lc.bias_ok = score_ceiling(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 <= 0xFFFF;
     // dp_cfm.h's arithmetic for the four-lanes-per-window scorer (k2d_dp_long_quad; set_scorer_forms' condition with this needle's rows in the
     // bias: lanes up to 3/2 chunks + rows + 1 of gap_extend)
     lc.cfm_ok = !m->unicode && m->rows <= FZB_LONG_LDS_ROWS && 2 * (u32)sc.gap_extend_penalty <= (u32)sc.mismatch_penalty &&
-                max_matrix_score(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + (137 + (size_t)m->rows) * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;
+                score_ceiling(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + (137 + (size_t)m->rows) * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;
     m->long_upper = false;
     if (!m->unicode)
         for (size_t i = 0; i < nb; i++) m->long_upper = m->long_upper || (blob[m->long_off_c + i] >= 'A' && blob[m->long_off_c + i] <= 'Z');
@@ -854,13 +863,13 @@ static void set_scorer_forms(CompiledNeedle* m, const uint8_t* needle_utf8, size
     for (size_t i = 0; i < needle_len; i++)
         if (needle_utf8[i] == 0) lc.pad_ok = 0;
     // biased gap propagation needs max cell value + lanes*gex (+ headroom) to stay below 2^16
-    lc.bias_ok = max_matrix_score(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 <= 0xFFFF;
+    lc.bias_ok = score_ceiling(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 <= 0xFFFF;
     // dp_cf.h / dp_cfm.h: every biased value stays below 0x7C00, so that the cell's three-way maximum can be v_pk_maximum3_f16 (exact on
     // non-negative finite binary16 patterns: dp_body.h, p_max3_s); scorings beyond that - needle rows worth thousands of points - take the first forms
     lc.cfm_ok = 2 * (u32)sc.gap_extend_penalty <= (u32)sc.mismatch_penalty &&
-                max_matrix_score(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 200 * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;  // lanes up to 3/2 chunks + rows of bias
+                score_ceiling(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 200 * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;  // lanes up to 3/2 chunks + rows of bias
     lc.cf_ok = lc.pad_ok && 2 * (u32)sc.gap_extend_penalty <= (u32)sc.mismatch_penalty &&
-               max_matrix_score(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;
+               score_ceiling(sc, (size_t)m->rows) + (size_t)sc.mismatch_penalty + 130 * (size_t)sc.gap_extend_penalty + 64 < 0x7C00;
     lc.cfu_ok = lc.bias_ok && 2 * (u32)sc.gap_extend_penalty <= (u32)sc.mismatch_penalty && !fzb_knobs().no_dp_cfu;  // (knob: the unicode scorer's first form)
 }
 
@@ -2331,9 +2340,9 @@ void fzb_order_flags(const fzb_matcher* m, u32 bias_hi, bool* reversed, bool* by
     const int sort = m->config.sort;
     *reversed = sort == FZB_SORT_INDEX_DESC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;          // src/matcher/mod.rs:215-217
     *by_score = sort == FZB_SORT_SCORE_THEN_INDEX_ASC || sort == FZB_SORT_SCORE_THEN_INDEX_DESC;  // :218-220
-    // one radix pass is enough when no score can reach 256 (Scoring::guard's bound on the matrix + the exact-match bonus added after it)
+    // one radix pass is enough when no score can reach 256 (score_ceiling: what the matrix can really hold, + the exact-match bonus added after it)
     // - nor, on a biased corpus, the largest positive bias on top of it (score_bias.h)
-    *one_pass = !m->sum_scores && !m->literal_mode && sbias_one_pass(max_matrix_score(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus, bias_hi);
+    *one_pass = !m->sum_scores && !m->literal_mode && sbias_one_pass(score_ceiling(m->config.scoring, (size_t)m->rows) + (size_t)m->config.scoring.exact_match_bonus, bias_hi);
 }
 int fzb_order_begin(fzb_matcher* m, size_t cap, fzb_match_rec* dev_out, OrderPlan* p, u32 bias_hi) {
     fzb_order_flags(m, bias_hi, &p->reversed, &p->by_score, &p->one_pass);

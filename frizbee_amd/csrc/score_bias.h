@@ -33,7 +33,7 @@ FZB_SBIAS_FN uint32_t sbias_clamp_add(uint32_t score, int32_t bias) {
     return v < 0 ? 0u : v > 65535 ? 65535u : (uint32_t)v;
 }
 
-// score_bound = the largest unbiased score (max_matrix_score + exact_match_bonus), bias_hi = the upper bound of the largest positive bias
+// score_bound = the largest unbiased score (score_ceiling + exact_match_bonus), bias_hi = the upper bound of the largest positive bias
 FZB_SBIAS_FN bool sbias_one_pass(uint64_t score_bound, uint32_t bias_hi) { return score_bound + (uint64_t)bias_hi < 256; }
 
 // haystack i survives the removal: bit i of the pass' bitmap (32-bit words, bit i & 31 of word i >> 5) marks a removed haystack

@@ -178,6 +178,19 @@ static int run_quad(const ND& nd, bool upper, const u8* hay, u32 m, int include_
 }
 
 extern "C" {
+// dp_body.h's precondition meter (host build only): reset, and read {largest 16-bit operand p_max3_s was given, p_max3_s calls with an operand
+// >= 0x7C00, p_add calls in which a lane wrapped}
+void kh_meter_reset() {
+    fzb_meter_max3_hi.store(0);
+    fzb_meter_max3_bad.store(0);
+    fzb_meter_add_wrap.store(0);
+}
+void kh_meter_read(unsigned long long* out) {
+    out[0] = fzb_meter_max3_hi.load();
+    out[1] = fzb_meter_max3_bad.load();
+    out[2] = fzb_meter_add_wrap.load();
+}
+
 // form: 0 = dp_single_chunk biased, 1 = literal (unbiased) scan, 2 = its padded-half form, 3 = dp_single_chunk_cf with `real` dwords,
 // 4 = dp_single_chunk_cf_tab (LDS-table set-up, swl/4 dwords).
 // Returns the score of `hay[0..m)` as ONE chunk of `swl` lanes (no exact bonus), or < 0 on a bad argument.

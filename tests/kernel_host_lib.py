@@ -44,7 +44,23 @@ def lib():
         _lib.kh_dp_quad.argtypes = _lib.kh_dp_multi.argtypes + [C.c_int]
         _lib.kh_window_typos.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint32)]
         _lib.kh_dp_batch.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.kh_meter_reset.restype = None
+        _lib.kh_meter_read.restype = None
+        _lib.kh_meter_read.argtypes = [C.POINTER(C.c_ulonglong)]
     return _lib
+
+
+def meter_reset():
+    """clears dp_body.h's precondition meter (host build only)"""
+    lib().kh_meter_reset()
+
+
+def meter_read():
+    """(largest 16-bit operand p_max3_s was given, p_max3_s calls with an operand >= 0x7C00, p_add calls in which a 16-bit lane wrapped) since
+    the last meter_reset()"""
+    out = (C.c_ulonglong * 3)()
+    lib().kh_meter_read(out)
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def dp_single(needle, hay, scoring, case_sensitive=False, include_prefix=True, swl=64, form=3, real=16):

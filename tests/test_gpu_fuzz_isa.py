@@ -22,7 +22,7 @@ SCORINGS = [
     (DEFAULT, "default: cf_ok, cfm_ok, u8 class for short needles"),
     ([12, 6, 5, 3, 12, 4, 4, 8, 4], "2 * gap_extend = mismatch: the cf_ok boundary, inside"),
     ([12, 6, 5, 4, 12, 4, 4, 8, 4], "2 * gap_extend > mismatch: dp_body.h first form (biased), dp_multi first form"),
-    ([12, 900, 450, 400, 12, 4, 4, 8, 4], "130 * gex fits, 200 * gex does not: cf_ok but not cfm_ok"),
+    ([12, 900, 450, 400, 12, 4, 4, 8, 4], "130 * gex = 52 000 is beyond 0x7C00 but inside 16 bits: neither cf_ok nor cfm_ok; bias_ok and cfu_ok (k2b_dp and dp_multi first forms, biased scan)"),
     ([12, 1100, 600, 500, 12, 4, 4, 8, 4], "130 * gex does not fit 16 bits: bias_ok false, literal gap scan"),
     ([1, 1, 1, 0, 0, 0, 0, 0, 0], "minimal: zero gap_extend, u8 class for every needle"),
     ([40, 13, 17, 2, 30, 11, 9, 21, 10], "heavy bonuses: u16 class already for short needles"),
