@@ -115,7 +115,7 @@ SYMBOLS = [
     "fzb_parse_query", "fzb_patterns_free", "fzb_match_list_indices", "fzb_match_indices_free", "fzb_multi_match_list_indices",
     "fzb_match_list_indices_into", "fzb_multi_match_list_into", "fzb_multi_match_list_indices_into",
     "fzb_device_count", "fzb_shard_ranges", "fzb_corpus_upload_sharded", "fzb_sharded_corpus_free", "fzb_sharded_corpus_len", "fzb_sharded_corpus_shards",
-    "fzb_sharded_corpus_shard", "fzb_match_list_parallel_sharded", "fzb_debug_lcs_dfa_accepts", "fzb_debug_cdfa_state",
+    "fzb_sharded_corpus_shard", "fzb_match_list_parallel_sharded", "fzb_debug_lcs_dfa_accepts", "fzb_debug_cdfa_state", "fzb_debug_kmp_dfa_accepts",
     "fzb_merge_shard_runs", "fzb_corpus_build_view", "fzb_debug_reload_knobs", "fzb_matcher_shard_report",
     "fzb_rccl_unique_id", "fzb_shard_comm_create", "fzb_shard_comm_free", "fzb_shard_comm_rank", "fzb_shard_comm_world", "fzb_match_list_parallel_rccl",
     "fzb_shard_comm_last_exchange",
@@ -216,6 +216,7 @@ def lib():
         l.fzb_shard_comm_last_exchange.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.fzb_debug_lcs_dfa_accepts.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
         l.fzb_debug_cdfa_state.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32)]
+        l.fzb_debug_kmp_dfa_accepts.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_size_t]
         l.fzb_multi_matcher_set_patterns.argtypes = [C.c_void_p, C.POINTER(_CPattern), C.c_size_t]
         l.fzb_multi_matcher_set_config.argtypes = [C.c_void_p, C.POINTER(_CConfig)]
         l.fzb_multi_matcher_reserve.argtypes = [C.c_void_p, C.c_void_p]

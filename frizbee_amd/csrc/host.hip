@@ -5294,6 +5294,18 @@ int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len,
     return st >= acc ? 1 : 0;
 }
 
+// Test hook (host only): the Knuth-Morris-Pratt byte table of a literal Substring matcher on the ASCII path (build_filter_tables) run over
+// one haystack and then over `fill` bytes of what the streaming kernels read behind its end (zero fill; the dead byte where the needle
+// holds a NUL and the kernels sanitise): 1 / 0 = accepts / rejects, -1 if the matcher has no such table.
+int fzb_debug_kmp_dfa_accepts(const fzb_matcher* m, const uint8_t* bytes, size_t len, size_t fill) {
+    if (!m || m->empty || m->long_needle || m->unicode || m->literal_mode != FZB_MATCH_SUBSTRING || (!bytes && len)) return -1;
+    if (m->dfa.size() != (size_t)(m->rows + 1) * 256) return -1;
+    const u8 behind = m->lc.pad_ok ? (u8)0 : (u8)m->lc.dead_byte;
+    u32 st = 0;
+    for (size_t i = 0; i < len + fill; i++) st = m->dfa[(size_t)st * 256 + (i < len ? bytes[i] : behind)];
+    return st == (u32)m->rows ? 1 : 0;
+}
+
 int fzb_last_counters(fzb_matcher* m, uint32_t out[4]) {
     if (!m || !out) return fail(FZB_ERR_INVALID, "null argument");
     if (m->ws.counters) {

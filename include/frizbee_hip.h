@@ -965,6 +965,12 @@ int fzb_debug_lcs_dfa_accepts(const fzb_matcher* m, const uint8_t* bytes, size_t
  * classes; the ragged filter's table) run over one haystack: 1 / 0 = accepts / rejects, -1 if the matcher has none; out_kg[0] = K, [1] = G */
 int fzb_debug_cdfa_state(const fzb_matcher* m, const uint8_t* bytes, size_t len, int32_t* out_kg);
 
+/* test hook, host only: the BYTE table of a literal Substring matcher on the ASCII path (the needle's Knuth-Morris-Pratt automaton, what
+ * the streaming filter runs byte by byte where the matcher has no class-composite table) run over one haystack and then over `fill` bytes
+ * of what the kernels read behind a haystack's end (zero, or the dead byte for a needle that holds a NUL): 1 / 0 = accepts / rejects, -1 if
+ * the matcher has no such table (another mode, the unicode path, a needle beyond 63 bytes) */
+int fzb_debug_kmp_dfa_accepts(const fzb_matcher* m, const uint8_t* bytes, size_t len, size_t fill);
+
 /* test hook, host only: the needle's letter signature (*out_mask, optional; 0 when not eligible) and whether the signature form of the
  * streaming filter may decide for this matcher (*out_eligible, optional: fuzzy matching, max_typos = 0, an ASCII needle without a NUL byte) */
 int fzb_debug_needle_signature(const fzb_matcher* m, uint32_t* out_mask, int* out_eligible);

@@ -1,7 +1,8 @@
 """The ragged streaming filter over the interleaved filter view (k1_cdfa_view<SAN, G, NV>) and what follows it on a ragged list (classifier,
 class launches, multi-chunk tail classes) against the oracle: every vector-count class of the view (longest haystack 33..64 / ..128 / ..256
 bytes), both composition widths of the class-composite automaton (4 bytes per lookup for short needles, 2 for needles with many classes),
-every automaton the filter runs (subsequence, LCS for typos, unicode), a needle with a NUL byte (bytes behind a haystack's end must be
+the automata that never step back (subsequence, LCS for typos, unicode - the Knuth-Morris-Pratt automaton of a literal Substring needle,
+the one that falls back on a mismatch, goes through the same kernels in tests/test_gpu_literal_forms.py), a needle with a NUL byte (bytes behind a haystack's end must be
 sanitised), lists that end inside a tile and inside a 64-haystack group, empty haystacks, and lists too small for a tile."""
 import random
 

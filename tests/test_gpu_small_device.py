@@ -344,6 +344,45 @@ def test_the_four_literal_modes(cus):
                 assert_top(fm.match_list_top(cp, len(want) // 2), want, len(want) // 2, (mode, sort))
 
 
+LONG_LITERAL = ("aab" * 22)[:65]  # periodic, beyond the by-value needle: the literal kernels with the needle's arrays in device memory
+
+
+def long_literal_list():
+    """N ragged haystacks of up to 256 bytes around the 65-byte needle (tests/lit_forms_lib.py: glued prefixes, near-misses, overlapping
+    occurrences); three in twenty are made the needle itself, three start with it and three end with it, so that every mode keeps thousands"""
+    from lit_forms_lib import make_list
+    rng = np.random.default_rng(65)
+    nb = LONG_LITERAL.encode()
+    hs = make_list("aab*65", "v256", n_rows=N, seed=2)
+    for i in np.flatnonzero(rng.random(N) < 0.6).tolist():
+        k, body = i % 4, hs[i][: 256 - len(nb)]
+        own = nb.upper() if i % 3 == 0 else nb  # (a lowercase needle under smart case: found in either case, scored differently)
+        hs[i] = (own, own + body, body + own, hs[i])[k]
+    return hs
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_the_four_literal_modes_over_a_needle_beyond_64_bytes(cus):
+    """k_literal_filter / k_literal_score in their long-needle form (NeedleLongDev): more than two trips of both grid-stride loops at one compute unit"""
+    if "long_literal" not in Lists._made:
+        Lists._made["long_literal"] = long_literal_list()
+    hs = Lists.get("long_literal")
+    with device_of(cus):
+        cp = F.Corpus(hs)
+        for mode in ("Exact", "Prefix", "Suffix", "Substring"):
+            for sort in ("ScoreThenIndexAsc", "IndexDesc"):
+                fm, om = single(LONG_LITERAL, sort=sort, matching=mode)
+                F.launch_grids()
+                got = fm.match_list(cp)
+                grids = F.launch_grids()
+                want = Lists.want("long_literal", LONG_LITERAL, sort, matching=mode)
+                same(got, want, (mode, sort))
+                assert N >= 4097 and len(want) >= 2049, (mode, len(want))
+                assert not any(k.startswith("k1_") for k in grids), sorted(grids)  # no streaming automaton for such a needle
+                prove(cus, grids, dict(n=N, surv=len(want), match=len(want)), ("k_literal_filter", "k_compact1", "k_literal_score"), ("long needle", mode, sort))
+                assert_top(fm.match_list_top(cp, len(want) // 2), want, len(want) // 2, ("long needle", mode, sort))
+
+
 @pytest.mark.parametrize("cus", CUS)
 def test_a_parsed_multi_pattern_query_with_and_and_not(cus):
     hs = Lists.get("uniform32")
